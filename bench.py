@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- person-crops/sec of the ProbPose top-down inference hot path on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--precision f16x3|bf16|f32] [--no-graph] [--in-flight 2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--precision f16x3|bf16|f32] [--no-graph] [--in-flight 2] [--dump-outputs DIR]
 
 One process per GPU. The driver launches N>1 as
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...`;
@@ -97,6 +97,8 @@ def parse(argv=None):
                     help="steps in flight (StepPipeline slots: own HIP stream, workspace and graph each); 1 = strictly one batch "
                          "at a time on one stream")
     ap.add_argument("--stub", action="store_true", help="tests only: fake engine on CPU + gloo (no GPU needed)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (float32/float64, rank 0)")
     return ap.parse_args(argv)
 
 
@@ -700,6 +702,28 @@ def timed_run(eng, crops, gather, flip, steps, warmup, use_graph, dist_mod, dev,
     return dt, snap
 
 
+DUMP_MAX_BYTES = 64 << 20
+# batch axis of each array timed_run snapshots: keypoints (B, K, 2), scores (B, K), scalars (4, B, K), records (world, B, K, 7)
+DUMP_BATCH_AXIS = {"keypoints": 0, "scores": 0, "scalars": 1, "records": 1}
+
+
+def dump_outputs(out_dir, snap):
+    """Writes timed_run's snapshot of the last timed step as ``out_dir/<name>.npy``: float64 stays float64, the rest is
+    float32. Over DUMP_MAX_BYTES in all, a fixed seeded sample of crops (the same indices in every array) is kept."""
+    arrs = {k: np.asarray(a) for k, a in snap.items()}
+    arrs = {k: a.astype(np.float64 if a.dtype == np.float64 else np.float32) for k, a in arrs.items()}
+    B = arrs["keypoints"].shape[0]
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_MAX_BYTES:
+        keep = max(1, B * DUMP_MAX_BYTES // total)
+        idx = np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+        arrs = {k: np.take(a, idx, axis=DUMP_BATCH_AXIS[k]) for k, a in arrs.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    return sorted(arrs)
+
+
 def reduce_times(dt, dist_mod, dev, world, local_dev_index):
     """max over ranks (the job's step time) + every rank's own seconds and device index."""
     if dist_mod is None:
@@ -963,6 +987,8 @@ def main(argv=None):
     gather = ResultGather(B, eng.K, dev, world)  # fixed-layout result record, pinned host copy, RCCL all_gather
     depth = max(1, args.in_flight)
     dt_rank, snap = timed_run(eng, crops, gather, flip, args.steps, args.warmup, use_graph, dist, dev, depth, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, snap)
     dt, rank_secs, rank_devs = reduce_times(dt_rank, dist, dev, world, local_rank)
     # The shader clock of that loop, from a SECOND pass of the same loop with the probe beside it - never from the timed pass itself:
     # the probe's sleeping wavefront holds a few registers of one SIMD, and a workgroup of the 256-register layer kernel (one per CU,

@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
@@ -44,3 +46,25 @@ def test_gpus_beyond_the_node_is_refused(lib_built):
     r = subprocess.run([sys.executable, BENCH, "--gpus", "64", "--steps", "1", "--warmup", "0"], env=_env(), cwd=ROOT,
                        capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "refusing" in r.stderr
+
+
+def test_dump_outputs_writes_the_last_timed_step(lib_built, tmp_path):
+    """--dump-outputs DIR: the last timed step's outputs as float32/float64 .npy, the same from run to run."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, BENCH, "--stub", "--steps", "4", "--warmup", "1", "--batch", "6", "--dump-outputs", str(d)],
+                           env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 4 and line["ms_per_step"] > 0
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["keypoints.npy", "records.npy", "scalars.npy", "scores.npy"], files
+        dumps.append({f[:-4]: np.load(d / f) for f in files})
+    a, b = dumps
+    assert a["keypoints"].shape == (6, 17, 2) and a["records"].shape == (1, 6, 17, 7)
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64), (f, a[f].dtype)
+        assert np.array_equal(a[f], b[f]), f
+    assert np.array_equal(a["keypoints"][:, 0, 0], np.arange(6)), "the stub's keypoints encode the crop index"
+    assert sum(p.stat().st_size for p in (tmp_path / "run0").iterdir()) <= 64 << 20
