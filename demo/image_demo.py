@@ -1,7 +1,9 @@
-"""Counterpart of the reference's ``demo/image_demo.py`` (:12-100) without the visualizer: pose estimation of the people
-in one image - the whole image as one box, or ``--bboxes x0,y0,x1,y1;...`` - printed / saved as JSON.
+"""Counterpart of the reference's ``demo/image_demo.py`` (:12-100): pose estimation of the people in one image - the whole
+image as one box, or ``--bboxes x0,y0,x1,y1;...`` - printed / saved as JSON; ``--out-img`` also draws the result on the GPU
+(probpose_code_amd.visualization), with ``--draw-heatmap`` the probability areas under it.
 
     python demo/image_demo.py IMG configs/td-pm_ProbPose-small_mi355x_coco-256x192.py CHECKPOINT --out-file out.json
+    python demo/image_demo.py IMG CONFIG CHECKPOINT --draw-heatmap --out-img out.png
 
 CHECKPOINT may be "synthetic" (seeded random weights: plumbing check, BASELINE config 1)."""
 import json
@@ -24,13 +26,23 @@ def main():
     ap.add_argument("--bboxes", default=None, help="x0,y0,x1,y1;x0,y0,x1,y1;... (default: the whole image)")
     ap.add_argument("--precision", default=None, choices=[None, "f16x3", "bf16", "f32"],
                     help="overrides model.precision of the config (default there: f16x3, the mode within 1e-3 of the fp32 reference)")
+    ap.add_argument("--out-img", default=None, help="draw the predictions into this image file (PNG / JPEG by its extension)")
+    ap.add_argument("--draw-heatmap", action="store_true", help="with --out-img: the probability areas of the keypoints under the poses")
+    ap.add_argument("--kpt-thr", type=float, default=0.3, help="visibility threshold of the keypoints drawn")
+    ap.add_argument("--radius", type=int, default=3, help="keypoint radius for visualization")
+    ap.add_argument("--thickness", type=int, default=1, help="link thickness for visualization")
+    ap.add_argument("--alpha", type=float, default=0.8, help="opacity of the keypoints")
     args = ap.parse_args()
+    if args.draw_heatmap and not args.out_img:
+        ap.error("--draw-heatmap draws into --out-img")
 
     from probpose_code_amd import apis, synthetic
     from probpose_code_amd.structures import merge_data_samples
 
     ckpt = dict(state_dict=synthetic.synthetic_state_dict("small", seed=0, logit_scale=2.0)) if args.checkpoint == "synthetic" else args.checkpoint
     opts = {"model.precision": args.precision} if args.precision else None
+    if args.draw_heatmap:
+        opts = dict(opts or {}, **{"model.test_cfg.output_heatmaps": True})
     model = apis.init_model(args.config, ckpt, device=args.device, cfg_options=opts)
     boxes = None
     if args.bboxes:
@@ -45,6 +57,14 @@ def main():
         open(args.out_file, "w").write(text)
     else:
         print(text)
+    if args.out_img:
+        from probpose_code_amd.apis import load_image_bgr
+        from probpose_code_amd.visualization import PoseLocalVisualizer
+
+        vis = PoseLocalVisualizer(radius=args.radius, line_width=args.thickness, alpha=args.alpha, device=args.device)
+        vis.set_dataset_meta(model.dataset_meta)
+        vis.add_datasample("result", load_image_bgr(args.img)[:, :, ::-1], results, draw_heatmap=args.draw_heatmap, kpt_thr=args.kpt_thr,
+                           out_file=args.out_img)
 
 
 if __name__ == "__main__":

@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-/* 4 (round 6): the numeric domain of PP_PREC_F16X3 stated and guarded (below); power-of-two WEIGHT SCALES: + pp_gemm_ws, pp_linear_ln_folded_ws,
+/* 4 (round 6): + pp_parea_scratch_bytes, pp_parea_thresholds, pp_parea_compose, pp_draw_poses, pp_resize_bilinear_u8 (the --draw-heatmap
+ *    picture, csrc/pp_render.hip; added later under the same version: purely additive); the numeric domain of PP_PREC_F16X3 stated and guarded (below); power-of-two WEIGHT SCALES: + pp_gemm_ws, pp_linear_ln_folded_ws,
  *    pp_qkv_attention_split_ws, pp_gemm_residual_layernorm_ws, pp_ffn_split_residual_layernorm_ws, pp_proj_ffn_split_residual_layernorm_ws (the unsuffixed entry points = scale 1);
  *    CHANGED signatures: pp_qkv_attention_split_folded (centered rows, no column sums, + w_inv_scale), pp_proj_ffn_split_folded (+ residual_stats,
  *    + three weight scales; the rows it leaves are centered); pp_probmap_decode_flags writes NaN results for a map with a non-finite logit;
@@ -666,6 +667,28 @@ int pp_exmap_accumulate(const int* dt_match, const unsigned char* dt_ignore, con
  * bilinear arithmetic restated from its source; cv2 is not available in the build image: parity unpinned. */
 int pp_warp_affine_u8(const void* img_hwc, int img_h, int img_w, int channels, const double* inverse_maps, void* crops_chw,
                       int n, int out_h, int out_w, void* stream);
+
+/* The --draw-heatmap picture (mmpose/visualization/local_visualizer.py:215-343, 520-585, 796-865), csrc/pp_render.hip; the
+ * drawing rules are stated there. K <= 22 (the reference's colour table); maps (K, H, W) < 2^29 values per map.
+ * pp_parea_thresholds: per keypoint the probability-area threshold thr (K) float32 - the largest value v of maps[k] with
+ * mass{x >= v} >= 0.75 * total, fp64 masses - and draw (K) int32 = 0 when a value is negative or non-finite or total < 0.75
+ * (:560-568). Deterministic radix select, no sort; scratch: pp_parea_scratch_bytes(K, H, W) bytes (< 0: error). */
+long long pp_parea_scratch_bytes(int K, int H, int W);
+int pp_parea_thresholds(const float* maps, int K, int H, int W, void* scratch, float* thr, int* draw, void* stream);
+/* The heatmap panel canvas_rgb (canvas_h, canvas_w, 3) uint8: image_rgb (img_h, img_w, 3) uint8 placed at (pad_left, pad_top)
+ * inside an (80, 80, 80) border, the areas maps[k] > thr[k] of every drawn keypoint blended 0.7 / 0.3 with its colour and
+ * outlined (:570-583), then 1-px green rectangles boxes (n_boxes, 4) int32 x1, y1, x2, y2 in canvas pixels (:844-858). */
+int pp_parea_compose(const void* image_rgb, int img_h, int img_w, int pad_left, int pad_top, const float* maps, int K,
+                     const float* thr, const int* draw, const int* boxes, int n_boxes, void* canvas_rgb, int canvas_h,
+                     int canvas_w, void* stream);
+/* The pose panel out_rgb (img_h, img_w, 3) uint8 from image_rgb: per instance its box (boxes (n, 4) int32 or NULL), its links
+ * (skeleton (n_links, 2) int32, link_rgb (n_links, 3) uint8) and its points (keypoints (n, K, 2) float32, visible (n, K) float32,
+ * kpt_rgb (K, 3) uint8) - _draw_instances_kpts + _draw_instances_bbox (:215-343) with integer rules of our own. */
+int pp_draw_poses(const void* image_rgb, int img_h, int img_w, const float* keypoints, const float* visible, const int* boxes,
+                  int n, int K, const int* skeleton, const void* link_rgb, const void* kpt_rgb, int n_links, double kpt_thr,
+                  float radius, float thickness, float alpha, void* out_rgb, void* stream);
+/* cv2.resize(src, (dst_w, dst_h), INTER_LINEAR) of an RGB uint8 image, restated in fp32 (half-pixel centres, edge clamp). */
+int pp_resize_bilinear_u8(const void* src_rgb, int src_h, int src_w, void* dst_rgb, int dst_h, int dst_w, void* stream);
 
 #ifdef __cplusplus
 }

@@ -150,6 +150,12 @@ SIGNATURES = {
     "pp_winograd_scratch_bytes": (c_longlong, [c_int] * 4),
     "pp_conv3x3_winograd_maxpool_relu": (c_int, [_P] * 5 + [c_int] * 8 + [_P]),
     "pp_tower_final": (c_int, [_P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
+    "pp_parea_scratch_bytes": (c_longlong, [c_int, c_int, c_int]),
+    "pp_parea_thresholds": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "pp_parea_compose": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, c_int, _P, c_int, c_int, _P]),
+    "pp_draw_poses": (
+        c_int, [_P, c_int, c_int, _P, _P, _P, c_int, c_int, _P, _P, _P, c_int, c_double, c_float, c_float, c_float, _P, _P]),
+    "pp_resize_bilinear_u8": (c_int, [_P, c_int, c_int, _P, c_int, c_int, _P]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

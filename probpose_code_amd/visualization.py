@@ -1,0 +1,259 @@
+"""The ``--draw-heatmap`` picture of the reference demo on the device (mmpose/visualization/local_visualizer.py:215-343,
+520-585, 796-865): the pose panel - boxes, skeleton links and keypoints on the image - and under it the presence-probability
+area of every keypoint on the padded canvas that shows keypoints outside the image.
+
+All drawing runs in ``csrc/pp_render.hip`` (the rules are stated there); the host uploads the instances and copies the
+finished image back once. The drawing rules differ from the reference where the reference is not reproducible:
+  * the reference draws links and points through matplotlib (anti-aliased); here a pixel takes a link's colour when its
+    distance to the segment between the two int positions is at most max(thickness, 1) / 2, and a keypoint's colour
+    (blended by ``alpha``) when its distance to the keypoint is at most ``radius`` - fp32 formulas in pp_render.hip;
+  * the outline of a probability area is every mask pixel with a 4-neighbour outside the mask or the canvas. cv2 draws the
+    RETR_EXTERNAL contours with LINE_4 instead: it leaves the rims of holes un-outlined and its diagonal steps can put an
+    outline pixel one pixel outside the mask;
+  * the panel resize is bilinear with half-pixel centres in fp32 (cv2.resize uses fixed-point weights).
+cv2 and matplotlib are not available to pin the difference.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+
+PAREA_MAX_KEYPOINTS = 22  # colours of the reference's probability-area table (local_visualizer.py:523-547)
+
+# configs/_base_/datasets/coco.py: skeleton_info (as keypoint indices), its link colours, keypoint_info colours (RGB)
+COCO_SKELETON = ((15, 13), (13, 11), (16, 14), (14, 12), (11, 12), (5, 11), (6, 12), (5, 6), (5, 7), (6, 8), (7, 9), (8, 10),
+                 (1, 2), (0, 1), (0, 2), (1, 3), (2, 4), (3, 5), (4, 6))
+_GREEN, _ORANGE, _BLUE = (0, 255, 0), (255, 128, 0), (51, 153, 255)
+COCO_LINK_COLORS = (_GREEN, _GREEN, _ORANGE, _ORANGE, _BLUE, _BLUE, _BLUE, _BLUE, _GREEN, _ORANGE, _GREEN, _ORANGE, _BLUE, _BLUE,
+                    _BLUE, _BLUE, _BLUE, _BLUE, _BLUE)
+COCO_KEYPOINT_COLORS = (_BLUE,) * 5 + (_GREEN, _ORANGE) * 6
+
+_INT_LIMIT = 2 ** 30  # box corners are clipped to this before the int conversion (the kernels compare ints only)
+
+
+def _stream(device):
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def _as_device_image(image_rgb, device):
+    t = torch.as_tensor(np.ascontiguousarray(image_rgb)) if isinstance(image_rgb, np.ndarray) else image_rgb
+    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
+        raise ValueError(f"expected an (H, W, 3) uint8 RGB image, got {tuple(t.shape)} {t.dtype}")
+    return t.to(device).contiguous()
+
+
+def _output(out, shape, device):
+    """``out`` as given - checked to be a dense uint8 tensor of ``shape`` on ``device``, the kernels write all of it - or a new one."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != torch.uint8 or out.device != device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape {tuple(shape)} on {device}, got {tuple(out.shape)} "
+                         f"{out.dtype} on {out.device}")
+    return out
+
+
+def _check_device(device):
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("the visualizer draws on the GPU only (no CPU fallback)")
+    return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def int_boxes(boxes) -> np.ndarray:
+    """(n, 4) x1, y1, x2, y2 -> int32 corners as ``int()`` gives them (truncation toward zero) after clipping to +-2^30; a box
+    with a non-finite corner is dropped."""
+    b = np.asarray(boxes, np.float64).reshape(-1, 4)
+    b = b[np.isfinite(b).all(axis=1)]
+    return np.clip(b, -_INT_LIMIT, _INT_LIMIT).astype(np.int64).astype(np.int32)
+
+
+def aspect_boxes(boxes, image_pad) -> np.ndarray:
+    """The rectangles of the heatmap panel (local_visualizer.py:844-858): every box shifted by the (left, top) pad, grown to
+    3:4 and padded 1.25 (fix_bbox_aspect_ratio), corners truncated to int. Returns int32 (n, 4)."""
+    from .transforms import fix_bbox_aspect_ratio_xyxy
+
+    b = np.array(boxes, np.float32).reshape(-1, 4)
+    pad = np.asarray(image_pad).reshape(4)
+    b[:, :2] += pad[:2]
+    b[:, 2:] += pad[:2]
+    return int_boxes(fix_bbox_aspect_ratio_xyxy(b, aspect_ratio=3 / 4, padding=1.25))
+
+
+def probability_area_thresholds(maps):
+    """Per keypoint the threshold of its probability area and whether it is drawn (pp_parea_thresholds): for a (K, H, W)
+    float32 device tensor, thr[k] = the largest value v of maps[k] whose superlevel set {x >= v} holds at least 0.75 of the
+    map's fp64 mass, and draw[k] = 0 when the map has a negative or non-finite value or a mass below 0.75 (:560-568). The
+    area is ``maps[k] > thr[k]``. Returns (thr float32 (K,), draw int32 (K,)) device tensors."""
+    device = _check_device(maps.device)
+    maps = maps.to(torch.float32).contiguous()
+    K, H, W = maps.shape
+    n = int(_lib.lib.pp_parea_scratch_bytes(K, H, W))
+    if n < 0:
+        raise _lib.ProbPoseLibraryError("pp_parea_scratch_bytes", _lib.lib.pp_status_string(n).decode(), _lib.last_error())
+    scratch = torch.empty(n, dtype=torch.uint8, device=device)
+    thr = torch.empty(K, dtype=torch.float32, device=device)
+    draw = torch.empty(K, dtype=torch.int32, device=device)
+    _lib.call("pp_parea_thresholds", maps.data_ptr(), K, H, W, scratch.data_ptr(), thr.data_ptr(), draw.data_ptr(), _stream(device))
+    return thr, draw
+
+
+def render_probability_areas(posterior, image_rgb, image_pad, boxes=None, out=None):
+    """The heatmap panel (local_visualizer.py:520-585, 844-858) as an (Hp, Wp, 3) uint8 device tensor: ``image_rgb`` (H, W, 3)
+    inside an (80, 80, 80) border of ``image_pad`` = [left, top, right, bottom], the probability area of every keypoint of
+    ``posterior`` (K <= 22, Hp, Wp) blended over it in the reference's colours and outlined, then the aspect-fixed
+    rectangles of ``boxes`` (n, 4) xyxy in image coordinates, or none."""
+    device = _check_device(posterior.device)
+    posterior = posterior.to(torch.float32).contiguous()
+    K, Hp, Wp = posterior.shape
+    img = _as_device_image(image_rgb, device)
+    H, W = img.shape[:2]
+    pad = [int(v) for v in np.asarray(image_pad).reshape(4)]
+    if (Hp, Wp) != (H + pad[1] + pad[3], W + pad[0] + pad[2]):
+        raise ValueError(f"maps {(Hp, Wp)} are not the image {(H, W)} padded by {pad}")
+    thr, draw = probability_area_thresholds(posterior)
+    rects = aspect_boxes(boxes, pad) if boxes is not None else np.zeros((0, 4), np.int32)
+    rects_d = torch.from_numpy(np.ascontiguousarray(rects)).to(device)
+    out = _output(out, (Hp, Wp, 3), device)
+    _lib.call("pp_parea_compose", img.data_ptr(), H, W, pad[0], pad[1], posterior.data_ptr(), K, thr.data_ptr(), draw.data_ptr(),
+              rects_d.data_ptr() if len(rects) else None, len(rects), _lib.ptr(out), Hp, Wp, _stream(device))
+    return out
+
+
+def draw_poses(image_rgb, keypoints, keypoints_visible, bboxes=None, skeleton=COCO_SKELETON, link_colors=COCO_LINK_COLORS,
+               keypoint_colors=COCO_KEYPOINT_COLORS, kpt_thr=0.3, radius=3.0, thickness=1.0, alpha=0.8, out=None,
+               device="cuda:0"):
+    """The pose panel (_draw_instances_kpts + _draw_instances_bbox, local_visualizer.py:215-343) as an (H, W, 3) uint8 device
+    tensor: per instance its box (int corners, 1-px green), its links (skipped as in :285-297), its points (drawn when
+    ``keypoints_visible >= kpt_thr``). ``keypoints`` (n, K, 2), ``keypoints_visible`` (n, K), ``bboxes`` (n, 4) xyxy or None."""
+    device = _check_device(image_rgb.device if isinstance(image_rgb, torch.Tensor) else device)
+    img = _as_device_image(image_rgb, device)
+    H, W = img.shape[:2]
+    K = len(keypoint_colors)
+    kp = np.ascontiguousarray(np.asarray(keypoints, np.float32).reshape(-1, K, 2))
+    n = len(kp)
+    vis = np.ascontiguousarray(np.asarray(keypoints_visible, np.float32).reshape(n, K))
+    sk = np.ascontiguousarray(np.asarray(skeleton, np.int32).reshape(-1, 2))
+    L = len(sk)
+    if L and (sk.min() < 0 or sk.max() >= K):
+        raise ValueError(f"skeleton links name keypoints outside 0..{K - 1}")
+    lc = np.ascontiguousarray(np.asarray(link_colors, np.uint8).reshape(L, 3))
+    kc = np.ascontiguousarray(np.asarray(keypoint_colors, np.uint8).reshape(K, 3))
+    boxes = None
+    if bboxes is not None:
+        b = np.asarray(bboxes, np.float64).reshape(n, 4)
+        ib = int_boxes(b)
+        if len(ib) != n:  # keep the rows aligned with the instances: a non-finite box is drawn nowhere
+            ib = np.full((n, 4), -_INT_LIMIT, np.int32)
+            ok = np.isfinite(b).all(axis=1)
+            ib[ok] = int_boxes(b[ok])
+        boxes = torch.from_numpy(ib).to(device)
+    dev = {name: torch.from_numpy(a).to(device) for name, a in (("kp", kp), ("vis", vis), ("sk", sk), ("lc", lc), ("kc", kc))}
+    out = _output(out, (H, W, 3), device)
+    _lib.call("pp_draw_poses", img.data_ptr(), H, W, dev["kp"].data_ptr(), dev["vis"].data_ptr(), _lib.ptr(boxes), n, K,
+              dev["sk"].data_ptr() if L else None, dev["lc"].data_ptr() if L else None, dev["kc"].data_ptr(), L, float(kpt_thr),
+              float(radius), float(thickness), float(alpha), _lib.ptr(out), _stream(device))
+    return out
+
+
+def resize_rgb(src, size_hw, out=None):
+    """cv2.resize(src, (W, H), INTER_LINEAR) of an (h, w, 3) uint8 device tensor (fp32 bilinear, half-pixel centres)."""
+    device = _check_device(src.device)
+    H, W = int(size_hw[0]), int(size_hw[1])
+    if src.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 3 or not src.is_contiguous():
+        raise ValueError(f"expected a contiguous (h, w, 3) uint8 tensor, got {tuple(src.shape)} {src.dtype}")
+    out = _output(out, (H, W, 3), device)
+    _lib.call("pp_resize_bilinear_u8", _lib.ptr(src), src.shape[0], src.shape[1], _lib.ptr(out), H, W, _stream(device))
+    return out
+
+
+class PoseLocalVisualizer:
+    """mmpose/visualization/local_visualizer.py:PoseLocalVisualizer for what ProbPose's demo draws: predictions in the
+    "mmpose" skeleton style, their boxes, and (``draw_heatmap``) the probability areas of the posterior maps on the padded
+    canvas, stacked under the pose panel. Everything is drawn on the GPU; ``add_datasample`` copies the image back once."""
+
+    def __init__(self, name="visualizer", radius=3, line_width=1, alpha=0.8, device="cuda:0"):
+        self.name = name
+        self.radius = radius
+        self.line_width = line_width
+        self.alpha = alpha
+        self.device = _check_device(device)
+        self.skeleton, self.link_color, self.kpt_color = COCO_SKELETON, COCO_LINK_COLORS, COCO_KEYPOINT_COLORS
+        self._image = None
+
+    def set_dataset_meta(self, dataset_meta, skeleton_style="mmpose"):
+        """Skeleton, link colours and keypoint colours from ``dataset_meta`` (keys ``skeleton_links``,
+        ``skeleton_link_colors``, ``keypoint_colors``); the COCO ones where a key is absent."""
+        if skeleton_style != "mmpose":
+            raise NotImplementedError(f"skeleton_style={skeleton_style!r}: only the 'mmpose' style is drawn (ProbPose's demo uses it)")
+        meta = dataset_meta or {}
+        self.dataset_meta = meta
+        self.skeleton = meta.get("skeleton_links", COCO_SKELETON)
+        self.link_color = meta.get("skeleton_link_colors", COCO_LINK_COLORS)
+        self.kpt_color = meta.get("keypoint_colors", COCO_KEYPOINT_COLORS)
+
+    def get_image(self):
+        return self._image
+
+    def draw_instance_heatmap(self, posterior, image_rgb, image_pad, boxes=None, draw_type="p_area"):
+        """_draw_instance_heatmap (:480-585) for the reference's probability-area drawing; returns the (Hp, Wp, 3) device
+        panel."""
+        if draw_type in ("featmap", "contours"):
+            raise NotImplementedError(f"draw_type={draw_type!r}: only ProbPose's 'p_area' drawing is implemented")
+        if draw_type != "p_area":
+            raise ValueError(f"unknown draw_type {draw_type!r}")
+        return render_probability_areas(posterior, image_rgb, image_pad, boxes)
+
+    def add_datasample(self, name, image, data_sample, draw_gt=False, draw_bbox=True, draw_heatmap=False, kpt_thr=0.3,
+                       out_file=None, show_kpt_idx=False, skeleton_style="mmpose", show=False, wait_time=0, step=0):
+        """Draw the predictions of one merged sample on ``image`` ((H, W, 3) uint8 RGB, host array or device tensor). Returns
+        the (H, W, 3) pose panel, or with ``draw_heatmap`` (and heatmaps in ``pred_fields``) the (2H, W, 3) stack of the pose
+        panel over the probability areas resized to (H, W) (:796-865); ``out_file`` is written with Pillow."""
+        if draw_gt:
+            raise NotImplementedError("draw_gt: ground-truth drawing is outside ProbPose's demo")
+        if show_kpt_idx:
+            raise NotImplementedError("show_kpt_idx: keypoint index text is not drawn")
+        if skeleton_style != "mmpose":
+            raise NotImplementedError(f"skeleton_style={skeleton_style!r}: only the 'mmpose' style is drawn")
+        if show:
+            raise NotImplementedError("show: no window system; use out_file or get_image()")
+        from .structures import _image_padding, posterior_heatmaps
+
+        img = _as_device_image(image, self.device)
+        H, W = img.shape[:2]
+        pi = data_sample.pred_instances if "pred_instances" in data_sample else None
+        with_heatmap = bool(draw_heatmap) and pi is not None and "pred_fields" in data_sample and "heatmaps" in data_sample.pred_fields
+        out = torch.empty((2 * H if with_heatmap else H, W, 3), dtype=torch.uint8, device=self.device)
+        top = out[:H]
+        if pi is not None and "keypoints" in pi:
+            kpts = pi.get("transformed_keypoints", pi.keypoints)
+            vis = pi.keypoints_visible if "keypoints_visible" in pi else np.ones(np.asarray(kpts).shape[:-1], np.float32)
+            boxes = pi.bboxes if draw_bbox and "bboxes" in pi else None
+            draw_poses(img, kpts, vis, boxes, self.skeleton, self.link_color, self.kpt_color, kpt_thr, self.radius, self.line_width,
+                       self.alpha, out=top)
+        else:
+            top.copy_(img)
+        if with_heatmap:
+            if "keypoints_probs" not in pi:
+                raise ValueError("draw_heatmap needs pred_instances.keypoints_probs (the presence probabilities of ProbPose)")
+            meta = data_sample.metainfo
+            pad = meta.get("image_pad")
+            if pad is None:
+                pad = _image_padding(np.asarray(meta["input_center"]).reshape(-1, 2), np.asarray(meta["input_scale"]).reshape(-1, 2),
+                                     meta["ori_shape"])
+            posterior = posterior_heatmaps(data_sample.pred_fields.heatmaps, pi.keypoints_probs, device=self.device)
+            boxes = None
+            if draw_bbox:
+                src = data_sample.gt_instances if "gt_instances" in data_sample and "bboxes" in data_sample.gt_instances else pi
+                boxes = src.bboxes if "bboxes" in src else None
+            panel = render_probability_areas(posterior, img, pad, boxes)
+            resize_rgb(panel, (H, W), out=out[H:])
+        self._image = out.cpu().numpy()
+        if out_file is not None:
+            from PIL import Image
+
+            Image.fromarray(self._image).save(out_file)
+        return self._image
+
+
+__all__ = ["PoseLocalVisualizer", "probability_area_thresholds", "render_probability_areas", "draw_poses", "resize_rgb", "aspect_boxes",
+           "int_boxes", "COCO_SKELETON", "COCO_LINK_COLORS", "COCO_KEYPOINT_COLORS", "PAREA_MAX_KEYPOINTS"]
