@@ -1121,3 +1121,19 @@ def test_proj_ffn_split_folded_vs_plain_launch(M):
         L.call("pp_proj_ffn_split_folded", ad.data_ptr(), wpp.data_ptr(), dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), rs4.data_ptr(),
                packed.data_ptr(), dev[3].data_ptr(), dev[4].data_ptr(), rs.data_ptr(), SPLIT, None, 1, None, None, None, eps, rs3.data_ptr(), rst4.data_ptr(),
                M, E, F_, 1.0, 1.0, 1.0, None)
+
+
+@gpu
+@pytest.mark.parametrize("fuzzer,verdict", [("fuzz_layer.py", "LAYER FUZZ OK"), ("fuzz_head.py", "HEAD FUZZ OK")])
+def test_shape_fuzz_of_the_layer_and_head_kernels(fuzzer, verdict):
+    """tests/fuzz_layer.py / tests/fuzz_head.py for a few seconds: the ViT-layer kernels (fused qkv + attention in its three forms, the fused
+    projection + FFN launches, pp_linear_ln_folded, pp_gemm_residual_layernorm, pp_attention) and the head kernels (deconvolution + 1x1 head,
+    Winograd and split-K tower stages, fused conv + pool, tower_final) over random shapes on both sides of every dispatch threshold and four value
+    classes, against fp64; outputs between canaries, inputs unchanged, repeat launches bit-identical."""
+    import os
+    import subprocess
+    import sys
+
+    here = os.path.dirname(os.path.abspath(__file__))
+    r = subprocess.run([sys.executable, os.path.join(here, fuzzer), "10"], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and verdict in r.stdout, (r.stdout[-1500:], r.stderr[-800:])
