@@ -35,7 +35,7 @@ BF16, F32, F16X3 = 0, 1, 2  # PP_PREC_*
 SPLIT = 2                   # PP_OUT_SPLIT
 EPS = 1e-6
 CAN = 2048                  # canary elements on each side of every guarded buffer
-PATTERN = {torch.float32: 0x7FC0DEAD, torch.bfloat16: 0x7FAD}  # NaN payloads no kernel writes
+PATTERN = {torch.float32: 0x7FC0DEAD, torch.bfloat16: 0x7FAD, torch.float64: 0x7FF8DEAD0BADF00D}  # NaN payloads no kernel writes
 MASSIVE = (250.0, -120.0, 60.0)  # synthetic.TRAINED_MASSIVE: residual-stream values of the massive-activation channels
 MEM_CAP = 2 << 30
 # base tolerances (rtol = atol) of the fixed-shape tests, per kernel output (tests/test_split_fp16.py, tests/test_kernels_gpu.py)
@@ -117,7 +117,7 @@ class Guard:
 
     def out(self, name, shape, dtype=torch.float32, init=None, must_write=True):
         n = int(np.prod(shape))
-        idt = torch.int32 if dtype == torch.float32 else torch.int16
+        idt = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.float64: torch.int64}[dtype]
         full = torch.full((n + 2 * CAN,), PATTERN[dtype], dtype=idt, device="cuda")
         view = full[CAN:CAN + n].view(dtype).view(*shape)
         init = init.to(device="cuda", dtype=dtype).reshape(shape).clone() if init is not None else None
@@ -155,6 +155,19 @@ class Guard:
 
 def bits_equal(a, b):
     return all(torch.equal(x.reshape(-1).view(torch.uint8), y.reshape(-1).view(torch.uint8)) for x, y in zip(a, b))
+
+
+def run_twice(guard, go):
+    """launch, check buffers, snapshot; rearm, launch again: the same bits."""
+    go()
+    faults = guard.faults()
+    first = guard.snapshot()
+    guard.rearm()
+    go()
+    if not bits_equal(first, guard.snapshot()):
+        faults.append("repeat launch differs")
+    faults += [f for f in guard.faults() if f not in faults]
+    return faults, first
 
 
 def sample_rows(M, block, rng, extra=0):
@@ -231,18 +244,6 @@ def _main(seconds):
                 raise Refused(str(exc)) from None
             raise
         torch.cuda.synchronize()
-
-    def run_twice(guard, go):
-        """launch, check buffers, snapshot; rearm, launch again: the same bits."""
-        go()
-        faults = guard.faults()
-        first = guard.snapshot()
-        guard.rearm()
-        go()
-        if not bits_equal(first, guard.snapshot()):
-            faults.append("repeat launch differs")
-        faults += [f for f in guard.faults() if f not in faults]
-        return faults, first
 
     # ------------------------------------------------------------------------------------------------- fused qkv + attention
     def case_qkv(form, rng, g):
@@ -705,8 +706,9 @@ def _main(seconds):
     return run_entries(entries, seconds, 70000, "LAYER", L)
 
 
-def run_entries(entries, seconds, seed0, label, L):
-    """Round robin over the entry points until the time is up; prints the per-entry-point table and the verdict. Returns the exit status."""
+def run_entries(entries, seconds, seed0, label, L, summary=None):
+    """Round robin over the entry points until the time is up; prints the per-entry-point table (then `summary()`, when given) and the verdict.
+    Returns the exit status."""
     stats = {name: dict(cases=0, refused=0, worst=0.0, bad=0) for name, _ in entries}
     t_end = time.time() + seconds
     seed = 0
@@ -734,6 +736,8 @@ def run_entries(entries, seconds, seed0, label, L):
     print(f"{'entry point':44s} {'cases':>6s} {'refused':>8s} {'worst err/tol':>14s}")
     for n, s in stats.items():
         print(f"{n:44s} {s['cases']:6d} {s['refused']:8d} {s['worst']:14.3g}")
+    if summary is not None:
+        summary()
     print(f"{sum(s['cases'] for s in stats.values())} cases in {seconds:.0f} s, {bad} mismatches" + (f"; no accepted case: {', '.join(idle)}" if idle else ""))
     print(f"{label} FUZZ", "FAILED" if (bad or idle) else "OK")
     return 1 if (bad or idle) else 0

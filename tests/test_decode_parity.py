@@ -260,3 +260,15 @@ def test_differential_fuzz_against_the_oracle():
     here = os.path.dirname(os.path.abspath(__file__))
     r = subprocess.run([sys.executable, os.path.join(here, "fuzz_decode.py"), "10"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "DECODE FUZZ OK" in r.stdout, (r.stdout[-800:], r.stderr[-800:])
+
+
+def test_logits_decode_fuzz_against_fp64():
+    """tests/fuzz_decode_logits.py for a few seconds: the fused x / T -> Sparsemax -> normalize -> flip merge -> decode of every logits entry point
+    and flag combination against an exact fp64 Sparsemax and the oracle's decode - value classes on both sides of 1 024 candidates, ties, heavy
+    tails, non-finite poison, map sizes across the NV buckets - with canaries, repeat launches and the exact equalities the kernel claims."""
+    import subprocess
+    import sys
+
+    here = os.path.dirname(os.path.abspath(__file__))
+    r = subprocess.run([sys.executable, os.path.join(here, "fuzz_decode_logits.py"), "10"], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "DECODE LOGITS FUZZ OK" in r.stdout, (r.stdout[-1500:], r.stderr[-800:])
