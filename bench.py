@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- person-crops/sec of the ProbPose top-down inference hot path on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--precision f16x3|bf16|f32] [--no-graph] [--in-flight 2] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--precision f16x3|bf16|f32] [--no-graph] [--in-flight 2] [--dump-outputs DIR] [--full]
 
 One process per GPU. The driver launches N>1 as
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...`;
@@ -18,14 +18,17 @@ Sparsemax, 4 scalar towers, flip average) -> ProbMap decode -> result tensors co
 Steps are submitted through probpose_code_amd.pipeline.StepPipeline: by default TWO steps are in flight (each slot its own
 HIP stream, workspace, captured graph and pinned record buffer), so the low-occupancy tail of one batch shares the chip with
 the head of the next; each step is the complete launch sequence and delivers its own record; all K have completed at the
-closing synchronize. `one_step_in_flight` in the JSON line is the same engine strictly one batch at a time.
+closing synchronize. `one_step_in_flight` in the --full line is the same engine strictly one batch at a time.
 
-Rank 0 prints ONE JSON line:
-  * `value` etc. for --precision. The default is `f16x3` (split-fp16 operands, three fp16 MFMAs per product): the fastest
-    mode whose keypoints / probabilities are within the path's 1e-3 tolerance of the fp32 reference - the headline is the
-    number the tolerance allows, not the fastest arithmetic the chip has;
-  * `roofline` for that mode's dominant kernel -- its launches timed live with HIP events on the launch stream in an
-    instrumented pass of the same step;
+Rank 0 prints ONE JSON line with `value` etc. for --precision. The default is `f16x3` (split-fp16 operands, three fp16 MFMAs
+per product): the fastest mode whose keypoints / probabilities are within the path's 1e-3 tolerance of the fp32 reference -
+the headline is the number the tolerance allows, not the fastest arithmetic the chip has. A plain run does only what that
+headline needs: set-up, W warm-up steps, K timed steps, --dump-outputs, the line. With `--full` the line also carries the
+records below, each measured after the timed steps in runs of its own (the --no-* options skip single ones):
+  * `clock`: the shader clock of a second pass of the timed loop with a probe beside it, and the device's power / clock limits;
+  * `one_step_in_flight` and `host_input`: the same engine one batch at a time, and with the crops in pinned host memory;
+  * `kernel_ms_per_step` and `roofline` for that mode's dominant kernel -- its launches timed live with HIP events on the launch stream in an
+    instrumented pass of the same step; `roofline_targets` for the attention and decode kernels of BASELINE's `north_star`;
   * `parity_vs_oracle`: the outputs of the LAST TIMED STEP (the hipGraph replay that was measured, not a separate
     eager run) against the CPU oracle on the same crops;
   * `throughput_mode`: the same bench (timing, roofline, parity of the replayed output) in bf16 - 3x the rate, 0.3 - 0.45 px
@@ -33,7 +36,8 @@ Rank 0 prints ONE JSON line:
   * `config4`: a bounded run of BASELINE config 4 (ProbPose-base = ViT-B 12 x 768, 384x288 crops, bs 32, flip test) in both
     modes, with its dominant kernel's roofline and its parity against the oracle on a few crops;
   * `cpu_baseline`: the oracle (torch-CPU model + per-sample scipy decode loop, as the reference runs) timed on this
-    box's host cores on a bounded sample.
+    box's host cores on a bounded sample;
+  * `drop_in` and `small_batch`: `model.test_step` / `test_step_stream` timed, and the latency of B = 1, 2, 4, 8.
 
 `--stub` (tests only): a fake engine on CPU tensors with the gloo backend -- exercises the launcher / sharding /
 gather / reduction plumbing of this file where there is no GPU (tests/test_bench_launcher.py).
@@ -79,6 +83,10 @@ def parse(argv=None):
     ap.add_argument("--batch", type=int, default=64, help="crops per GPU per step")
     ap.add_argument("--precision", default=PARITY_PRECISION, choices=sorted(PEAK_TFLOPS))
     ap.add_argument("--no-graph", action="store_true", help="launch kernel by kernel instead of replaying the HIP graph")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure every record beyond the headline (clock, one step in flight, host input, "
+                         "rooflines, the other precision, cpu_baseline and parity, drop_in, small_batch, config4); the --no-* options "
+                         "below skip single ones")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-second-mode", "--no-parity-mode", dest="no_second_mode", action="store_true",
@@ -990,12 +998,13 @@ def main(argv=None):
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, snap)
     dt, rank_secs, rank_devs = reduce_times(dt_rank, dist, dev, world, local_rank)
+    # --full only from here to the JSON line: the measurements beyond the headline, in passes of their own after the timed steps.
     # The shader clock of that loop, from a SECOND pass of the same loop with the probe beside it - never from the timed pass itself:
     # the probe's sleeping wavefront holds a few registers of one SIMD, and a workgroup of the 256-register layer kernel (one per CU,
     # all 256 CUs) then cannot be placed on that CU until the probe has left (seen in the rocprofv3 trace: some launches of
     # proj_ffn_split at twice their duration while the probe ran)
     clock, dt_probe = None, None
-    if not args.stub and not args.no_clock_probe:
+    if args.full and not args.stub and not args.no_clock_probe:
         probe = ClockProbe(dev)
         kp = min(args.steps, 30)
         dtp_rank, _ = timed_run(eng, crops, gather, flip, kp, min(args.warmup, 3), use_graph, dist, dev, depth, world, probe=probe)
@@ -1004,24 +1013,24 @@ def main(argv=None):
     # the PCIe-inclusive rate: every step's crops start in pinned HOST memory (never `value`: the boundary hands over device
     # buffers); the host-to-device copy rides on a copy stream under the kernels in flight (pipeline.StepPipeline.submit)
     dth = None
-    if depth > 1 and not args.stub:
+    if args.full and depth > 1 and not args.stub:
         kh, wh = min(args.steps, 20), min(args.warmup, 5)
         dth_rank, _ = timed_run(eng, crops_cpu.pin_memory(), gather, flip, kh, wh, use_graph, dist, dev, depth, world)
         dth = reduce_times(dth_rank, dist, dev, world, local_rank)[0] / kh
     # the same engine strictly one batch at a time (one stream, one graph replay after the other): the latency figure
     dt1 = None
-    if depth > 1:
+    if args.full and depth > 1:
         k1, w1 = min(args.steps, 20), min(args.warmup, 5)
         dt1_rank, _ = timed_run(eng, crops, gather, flip, k1, w1, use_graph, dist, dev, 1, world)
         dt1 = reduce_times(dt1_rank, dist, dev, world, local_rank)[0] / k1
-    prof = instrumented_pass(eng, crops, flip) if not args.stub else None
+    prof = instrumented_pass(eng, crops, flip) if args.full and not args.stub else None
 
     # ---- the same bench in the other precision: bf16 (`throughput_mode`) beside the f16x3 headline; `parity_mode` (f16x3) when
     # the bench was asked for another precision (every rank takes part: barriers inside)
     pm = None
     second = THROUGHPUT_PRECISION if args.precision == PARITY_PRECISION else PARITY_PRECISION
     second_key = "throughput_mode" if second == THROUGHPUT_PRECISION else "parity_mode"
-    if not args.stub and not args.no_second_mode:
+    if args.full and not args.stub and not args.no_second_mode:
         eng_p = make_engine(second)
         k_p, w_p = min(args.steps, 20), min(args.warmup, 5)
         dt_p_rank, snap_p = timed_run(eng_p, crops, gather, flip, k_p, w_p, use_graph, dist, dev, depth, world)
@@ -1076,8 +1085,7 @@ def main(argv=None):
         if args.stub:
             rec = snap["records"]  # (world, B, K, 7): x of crop i on rank r is r * 1000 + i
             line["stub_gather_ok"] = bool(all(rec[r, i, 0, 0] == r * 1000 + i for r in range(world) for i in (0, B - 1)))
-            print(json.dumps(line))
-        else:
+        elif args.full:
             # the clock the timed loop ran at on this box (rank 0's GPU) and the limits it ran under: the box-to-box spread of
             # `value` is clock spread, `value / shader_clock_MHz` is the box-independent figure
             line["clock"] = dict(clock or {}, **device_limits(local_rank))
@@ -1145,7 +1153,7 @@ def main(argv=None):
                     line["small_batch"] = {"error": repr(exc)[:300]}
             if world == 1 and not args.no_config4:
                 line["config4"] = config4_record(dev, args)
-            print(json.dumps(line))
+        print(json.dumps(line))
     if distributed:
         dist.barrier()
         dist.destroy_process_group()

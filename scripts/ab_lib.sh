@@ -4,7 +4,7 @@ libs=$1; reps=${2:-2}; extra=${3:-}
 root=${GRAFT_REPO_ROOT:-/root/repo}
 for i in $(seq $reps); do for v in $libs; do
   cp $root/scripts/micro/build/lib_$v.so $root/probpose_code_amd/libprobpose_mi355x.so
-  python $root/bench.py --no-config4 --no-drop-in --no-cpu-baseline --no-second-mode --steps 60 $extra 2>/dev/null > /tmp/ab.json
+  python $root/bench.py --full --no-config4 --no-drop-in --no-cpu-baseline --no-second-mode --steps 60 $extra 2>/dev/null > /tmp/ab.json
   python3 - "$v" <<'PY'
 import json, sys
 d = json.load(open("/tmp/ab.json"))

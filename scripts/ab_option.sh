@@ -3,7 +3,7 @@
 opt=$1; vals=$2; reps=${3:-2}
 root=${GRAFT_REPO_ROOT:-/root/repo}
 for i in $(seq $reps); do for v in $vals; do
-  env PP_OPT_$opt=$v python $root/bench.py --no-config4 --no-drop-in --no-cpu-baseline --no-second-mode --steps 60 2>/dev/null > /tmp/ab.json
+  env PP_OPT_$opt=$v python $root/bench.py --full --no-config4 --no-drop-in --no-cpu-baseline --no-second-mode --steps 60 2>/dev/null > /tmp/ab.json
   python3 - "$opt" "$v" <<'PY'
 import json, sys
 d = json.load(open("/tmp/ab.json"))

@@ -1,7 +1,8 @@
+root=$(cd "$(dirname "$0")/../.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 for v in 0 1; do
-  PP_OPT_PSPLIT_DECONV_WEIGHT_MAJOR=$v python $GRAFT_REPO_ROOT/bench.py --no-config4 --no-drop-in --no-cpu-baseline --no-second-mode --no-parity --steps 40 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().split(chr(10))[-1]); k=d['kernel_ms_per_step']; print('weight_major=$v', round(d['value']), 'deconv_head', k['deconv_head'], 'deconv', k['deconv'])"
-  rm -rf /tmp/pf_$v; PP_OPT_PSPLIT_DECONV_WEIGHT_MAJOR=$v rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/pf_$v -- python $GRAFT_REPO_ROOT/bench.py --no-graph --steps 3 --warmup 1 --no-bs512-decode --no-cpu-baseline --no-parity --no-parity-mode --no-config4 --no-drop-in --no-clock-probe > /dev/null 2>&1
+  PP_OPT_PSPLIT_DECONV_WEIGHT_MAJOR=$v python $root/bench.py --full --no-config4 --no-drop-in --no-cpu-baseline --no-second-mode --no-parity --steps 40 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().split(chr(10))[-1]); k=d['kernel_ms_per_step']; print('weight_major=$v', round(d['value']), 'deconv_head', k['deconv_head'], 'deconv', k['deconv'])"
+  rm -rf /tmp/pf_$v; PP_OPT_PSPLIT_DECONV_WEIGHT_MAJOR=$v rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/pf_$v -- python $root/bench.py --full --no-graph --steps 3 --warmup 1 --no-bs512-decode --no-cpu-baseline --no-parity --no-parity-mode --no-config4 --no-drop-in --no-clock-probe > /dev/null 2>&1
   python3 - $v <<'PY'
 import csv, glob, sys, collections
 acc = collections.defaultdict(list)

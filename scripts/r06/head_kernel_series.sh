@@ -4,7 +4,7 @@
 root=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_series
-rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_series -- python $root/bench.py --in-flight ${1:-1} --steps 24 --warmup 5 --no-cpu-baseline --no-parity --no-parity-mode --no-config4 --no-drop-in --no-small-batch --no-bs512-decode > /tmp/series_bench.json 2> /tmp/series.log
+rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_series -- python $root/bench.py --full --in-flight ${1:-1} --steps 24 --warmup 5 --no-cpu-baseline --no-parity --no-parity-mode --no-config4 --no-drop-in --no-small-batch --no-bs512-decode > /tmp/series_bench.json 2> /tmp/series.log
 python3 - <<'PY'
 import csv, glob
 f = glob.glob("/tmp/prof_series/**/*kernel_trace.csv", recursive=True)[0]

@@ -34,6 +34,25 @@ def test_gpus2_spawns_two_ranks_itself(lib_built):
     assert d["max_rank_ms_per_step"] >= 1e3 * 5 * 3 / max(d["rank_crops_per_s"]) / 3 - 1e-9
 
 
+def test_records_beyond_the_headline_need_full(lib_built):
+    """A plain run times its steps and prints the headline; the passes after them (here the one-step-in-flight run, the
+    only one the stub engine takes part in) run with --full alone, on every rank."""
+    lines = {}
+    for extra in ([], ["--full"]):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--stub", "--steps", "3", "--warmup", "1", "--batch", "5"] + extra,
+                           env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1, "rank 0 prints exactly one JSON line"
+        lines[bool(extra)] = json.loads(out[0])
+    for d in lines.values():
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["stub_gather_ok"] is True
+    assert "one_step_in_flight" not in lines[False]
+    assert lines[True]["one_step_in_flight"]["ms_per_step"] > 0
+
+
 def test_world_size_mismatch_is_refused(lib_built):
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--stub", "--steps", "1", "--warmup", "0"],
                        env=_env(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"), cwd=ROOT, capture_output=True, text=True, timeout=120)
