@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-/* 4 (round 6): + pp_parea_scratch_bytes, pp_parea_thresholds, pp_parea_compose, pp_draw_poses, pp_resize_bilinear_u8 (the --draw-heatmap
+/* 4 (round 6): + pp_warp_affine_u8_batch (additive); + pp_parea_scratch_bytes, pp_parea_thresholds, pp_parea_compose, pp_draw_poses, pp_resize_bilinear_u8 (the --draw-heatmap
  *    picture, csrc/pp_render.hip; added later under the same version: purely additive); the numeric domain of PP_PREC_F16X3 stated and guarded (below); power-of-two WEIGHT SCALES: + pp_gemm_ws, pp_linear_ln_folded_ws,
  *    pp_qkv_attention_split_ws, pp_gemm_residual_layernorm_ws, pp_ffn_split_residual_layernorm_ws, pp_proj_ffn_split_residual_layernorm_ws (the unsuffixed entry points = scale 1);
  *    CHANGED signatures: pp_qkv_attention_split_folded (centered rows, no column sums, + w_inv_scale), pp_proj_ffn_split_folded (+ residual_stats,
@@ -668,6 +668,14 @@ int pp_exmap_accumulate(const int* dt_match, const unsigned char* dt_ignore, con
  * bilinear arithmetic restated from its source; cv2 is not available in the build image: parity unpinned. */
 int pp_warp_affine_u8(const void* img_hwc, int img_h, int img_w, int channels, const double* inverse_maps, void* crops_chw,
                       int n, int out_h, int out_w, void* stream);
+/* The same crops cut from many images in one launch (the batches of a test loop): crop i is cut from image crop_image[i]
+ * (n int32 on the device) with inverse_maps[i]; image j is the HWC uint8 buffer images[j] (a device table of device
+ * pointers) of image_hw[2 j] rows and image_hw[2 j + 1] columns (int32 on the device); every image has `channels` channels.
+ * max_img_h / max_img_w bound the sides in the table (checked here: below 32768, as pp_warp_affine_u8). Bytes equal to
+ * pp_warp_affine_u8 on each image alone. */
+int pp_warp_affine_u8_batch(const void* const* images, const int* image_hw, int channels, const int* crop_image,
+                            const double* inverse_maps, int max_img_h, int max_img_w, void* crops_chw, int n, int out_h,
+                            int out_w, void* stream);
 
 /* The --draw-heatmap picture (mmpose/visualization/local_visualizer.py:215-343, 520-585, 796-865), csrc/pp_render.hip; the
  * drawing rules are stated there. K <= 22 (the reference's colour table); maps (K, H, W) < 2^29 values per map.

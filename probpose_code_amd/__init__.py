@@ -19,7 +19,8 @@ from .pose_estimators import (  # noqa: F401
     VisionTransformer,
     build_pose_estimator,
 )
-from .registry import KEYPOINT_CODECS, MODELS, TRANSFORMS  # noqa: F401
+from .registry import DATASETS, EVALUATORS, KEYPOINT_CODECS, MODELS, TRANSFORMS  # noqa: F401
+from . import datasets, runner  # noqa: F401,E402  (register CocoDataset / CombinedDataset / MultiDatasetEvaluator)
 from .structures import InstanceData, PixelData, PoseDataSample  # noqa: F401
 
 __version__ = "0.1.0"

@@ -126,6 +126,7 @@ SIGNATURES = {
     "pp_conv3x3_splitk": (c_int, [c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_int, _P]),
     "pp_sum_maxpool_relu_nhwc": (c_int, [_P, c_int, c_longlong, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "pp_warp_affine_u8": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_int, c_int, _P]),
+    "pp_warp_affine_u8_batch": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, _P, c_int, c_int, c_int, _P]),
     "pp_extended_oks": (
         c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_double, c_double, c_int, c_int, _P, _P]),
     "pp_pack_records": (c_int, [_P, _P, _P, _P, c_int, _P]),

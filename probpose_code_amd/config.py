@@ -1,7 +1,7 @@
 """Minimal loader for MMPose-style python config files (reference: mmengine ``Config`` [3P], used at
 ``mmpose/apis/inference.py:88-93`` and ``tools/test.py:115``). Only what the inference path needs:
 ``Config.fromfile`` (python files, ``_base_`` inheritance with dict merge and ``_delete_``),
-attribute/item access, ``merge_from_dict`` with dotted keys (``--cfg-options``), ``custom_imports``.
+attribute/item access, ``merge_from_dict`` with dotted keys and list indices (``--cfg-options``), ``custom_imports``.
 When mmengine is importable its own ``Config`` is used instead."""
 import importlib
 import os
@@ -42,6 +42,11 @@ except Exception:  # noqa: BLE001
                 out[k] = {kk: vv for kk, vv in v.items() if kk != "_delete_"} if isinstance(v, dict) else v
         return out
 
+    def _list_index(seq, key: str, full_key: str) -> int:
+        if not key.lstrip("-").isdigit() or not -len(seq) <= int(key) < len(seq):
+            raise KeyError(f"{full_key!r}: {key!r} does not index a list of {len(seq)} items")
+        return int(key)
+
     def _exec_file(path: str) -> Dict[str, Any]:
         ns: Dict[str, Any] = {"__file__": path}
         with open(path) as f:
@@ -78,12 +83,17 @@ except Exception:  # noqa: BLE001
             return cfg
 
         def merge_from_dict(self, options: dict) -> None:
+            """Dotted keys; a key that is an integer indexes into a list met on the way, as mmengine's ``--cfg-options`` do
+            (``test_dataloader.dataset.datasets.0.data_root=...``)."""
             for full_key, v in options.items():
                 d = self._cfg_dict
                 keys = full_key.split(".")
                 for k in keys[:-1]:
-                    d = d.setdefault(k, ConfigDict())
-                d[keys[-1]] = _wrap(v)
+                    d = d[_list_index(d, k, full_key)] if isinstance(d, (list, tuple)) else d.setdefault(k, ConfigDict())
+                if isinstance(d, list):
+                    d[_list_index(d, keys[-1], full_key)] = _wrap(v)
+                else:
+                    d[keys[-1]] = _wrap(v)
 
         def get(self, key, default=None):
             return self._cfg_dict.get(key, default)

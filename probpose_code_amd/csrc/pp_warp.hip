@@ -9,7 +9,8 @@
 //   * X = (round((M1 y + M2) 1024) + 16 + round(M0 x 1024)) >> 5  - coordinates with 5 fractional bits;
 //   * the four taps are weighted with 15-bit integer weights (32 - fx)(32 - fy) 32, ..., taps outside the image read
 //     the border value 0, result = (sum + 16384) >> 15.
-// One thread per output pixel (all three channels): HBM-bound on the 3 x 48 KiB each crop writes.
+// One thread per output pixel (all three channels): HBM-bound on the 3 x 48 KiB each crop writes. pp_warp_affine_u8 cuts
+// the crops of one image, pp_warp_affine_u8_batch those of many images (a device table of image pointers) in one launch.
 #include "pp_common.h"
 
 #include <cstdint>
@@ -21,12 +22,10 @@ __device__ __forceinline__ int round_to_int(double v) {  // saturate_cast<int>(d
     return v >= 2147483647.0 ? 2147483647 : (v <= -2147483648.0 ? (int)0x80000000 : (int)v);
 }
 
-__global__ __launch_bounds__(256) void warp_affine_kernel(const uint8_t* __restrict__ img, int ih, int iw, int ic,
-                                                          const double* __restrict__ inv, uint8_t* __restrict__ out,
-                                                          int n, int oh, int ow) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
-    if (x >= ow) return;
-    const double* M = inv + 6 * b;
+// One output pixel (x, y) of one crop, all channels: the fixed-point arithmetic of both warp kernels. img: (ih, iw, ic)
+// HWC; M: the crop's inverse map; out: the crop's (ic, oh, ow) CHW plane. 64-bit offsets into the image.
+__device__ __forceinline__ void warp_pixel_u8(const uint8_t* __restrict__ img, int ih, int iw, int ic, const double* __restrict__ M,
+                                              uint8_t* __restrict__ out, int oh, int ow, int x, int y) {
     const int X0 = round_to_int((M[1] * y + M[2]) * 1024.0) + 16, Y0 = round_to_int((M[4] * y + M[5]) * 1024.0) + 16;
     const int X = (X0 + round_to_int(M[0] * x * 1024.0)) >> 5, Y = (Y0 + round_to_int(M[3] * x * 1024.0)) >> 5;
     int sx = X >> 5, sy = Y >> 5;
@@ -36,13 +35,35 @@ __global__ __launch_bounds__(256) void warp_affine_kernel(const uint8_t* __restr
     const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
     const bool x0in = sx >= 0 && sx < iw, x1in = sx + 1 >= 0 && sx + 1 < iw;
     const bool y0in = sy >= 0 && sy < ih, y1in = sy + 1 >= 0 && sy + 1 < ih;
+    const ptrdiff_t row = (ptrdiff_t)iw * ic;
     for (int c = 0; c < ic; ++c) {
-        const uint8_t* s = img + ((size_t)sy * iw + sx) * ic + c;
+        const uint8_t* s = img + ((ptrdiff_t)sy * iw + sx) * ic + c;
         const int v00 = (x0in && y0in) ? s[0] : 0, v01 = (x1in && y0in) ? s[ic] : 0;
-        const int v10 = (x0in && y1in) ? s[(size_t)iw * ic] : 0, v11 = (x1in && y1in) ? s[(size_t)iw * ic + ic] : 0;
+        const int v10 = (x0in && y1in) ? s[row] : 0, v11 = (x1in && y1in) ? s[row + ic] : 0;
         const int v = (v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + (1 << 14)) >> 15;
-        out[(((size_t)b * ic + c) * oh + y) * ow + x] = (uint8_t)(v > 255 ? 255 : v);
+        out[((size_t)c * oh + y) * ow + x] = (uint8_t)(v > 255 ? 255 : v);
     }
+}
+
+__global__ __launch_bounds__(256) void warp_affine_kernel(const uint8_t* __restrict__ img, int ih, int iw, int ic,
+                                                          const double* __restrict__ inv, uint8_t* __restrict__ out,
+                                                          int n, int oh, int ow) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
+    if (x >= ow) return;
+    warp_pixel_u8(img, ih, iw, ic, inv + 6 * b, out + (size_t)b * ic * oh * ow, oh, ow, x, y);
+}
+
+// The crops of many source images in one launch: crop b reads image crop_image[b], whose base address is images[i] and
+// whose sides are image_hw[2 i], image_hw[2 i + 1] (every image has `ic` channels).
+__global__ __launch_bounds__(256) void warp_affine_batch_kernel(const uint8_t* const* __restrict__ images,
+                                                                const int* __restrict__ image_hw, int ic,
+                                                                const int* __restrict__ crop_image,
+                                                                const double* __restrict__ inv, uint8_t* __restrict__ out,
+                                                                int oh, int ow) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
+    if (x >= ow) return;
+    const int i = crop_image[b];
+    warp_pixel_u8(images[i], image_hw[2 * i], image_hw[2 * i + 1], ic, inv + 6 * b, out + (size_t)b * ic * oh * ow, oh, ow, x, y);
 }
 
 // Heatmaps of the persons of one image back on the image (revert_heatmap, mmpose/structures/utils.py:146-175: float32
@@ -161,6 +182,24 @@ extern "C" int pp_warp_affine_u8(const void* img_hwc, int img_h, int img_w, int 
     hipLaunchKernelGGL(warp_affine_kernel, dim3((out_w + 255) / 256, out_h, n), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const uint8_t*>(img_hwc), img_h, img_w, channels,
                        inverse_maps, reinterpret_cast<uint8_t*>(crops_chw), n, out_h, out_w);
+    PP_LAUNCH_CHECK();
+    return PP_OK;
+}
+
+extern "C" int pp_warp_affine_u8_batch(const void* const* images, const int* image_hw, int channels, const int* crop_image,
+                                       const double* inverse_maps, int max_img_h, int max_img_w, void* crops_chw, int n, int out_h,
+                                       int out_w, void* stream) {
+    using namespace pp;
+    if (n == 0) return PP_OK;
+    PP_REQUIRE(images && image_hw && crop_image && inverse_maps && crops_chw, PP_ERR_INVALID_ARG,
+               "pp_warp_affine_u8_batch: NULL argument");
+    PP_REQUIRE(n > 0 && max_img_h > 0 && max_img_w > 0 && out_h > 0 && out_w > 0 && channels > 0 && channels <= 4,
+               PP_ERR_INVALID_ARG, "pp_warp_affine_u8_batch: bad shape");
+    PP_REQUIRE(max_img_h < 32768 && max_img_w < 32768 && out_h <= 65535 && n <= 65535, PP_ERR_UNSUPPORTED,
+               "pp_warp_affine_u8_batch: image sides must be below 32768 (16-bit source coordinates, as in cv2)");
+    hipLaunchKernelGGL(warp_affine_batch_kernel, dim3((out_w + 255) / 256, out_h, n), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const uint8_t* const*>(images), image_hw, channels,
+                       crop_image, inverse_maps, reinterpret_cast<uint8_t*>(crops_chw), out_h, out_w);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }

@@ -119,6 +119,11 @@ else:
     KEYPOINT_CODECS = Registry("KEYPOINT_CODECS")
     TRANSFORMS = Registry("transform")  # mmpose/registry.py:36: the val pipeline's LoadImage / GetBBoxCenterScale / TopdownAffine / PackPoseInputs
 
+# The test loop's datasets (datasets.py) and evaluators (runner.py) are this package's own classes, not mmengine BaseDataset /
+# Evaluator subclasses: they live in registries of their own, under the reference's names, with or without a real MMPose.
+DATASETS = Registry("dataset")      # mmpose/registry.py:41
+EVALUATORS = Registry("evaluator")  # mmpose/registry.py:97
+
 # Under a real MMPose, registering under the reference's own names needs force=True.
 OVERRIDE_REFERENCE_NAMES = (not USING_MMENGINE) or os.environ.get("PROBPOSE_MI355X_OVERRIDE", "0") == "1"
 

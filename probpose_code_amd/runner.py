@@ -1,0 +1,232 @@
+"""The test loop of ``tools/test.py CONFIG CHECKPOINT`` (mmengine ``Runner.test()`` [3P] over the config's ``test_dataloader``
+and ``test_evaluator``): the person instances of a dataset in batches, the model, one metric per dataset.
+
+``test_dataset`` keeps every stage busy at once:
+  * decode: the distinct images of the next batches are decoded on a thread pool (``apis.load_image_bgr``), at least two
+    batches ahead; an image is dropped once its last instance has been batched;
+  * crops: the val pipeline through ``Compose.batched`` - box arithmetic on the host, ONE ``pp_warp_affine_u8_batch`` launch
+    for the batch, its images uploaded with one copy - on a producer stream, under the model step of the batch before;
+  * model: ``test_step_stream`` (full batches replay the captured graph, a partial last batch runs kernel by kernel);
+  * metric: ``MultiDatasetEvaluator`` routes every sample to the metric of its ``dataset_name``.
+"""
+from concurrent.futures import ThreadPoolExecutor
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence
+
+import numpy as np
+import torch
+
+from .registry import DATASETS, EVALUATORS
+
+MAX_WORKERS = 16  # a job's share of a GPU machine's CPUs; never sized from os.cpu_count()
+
+
+class Batch(NamedTuple):
+    """One batch of the plan: dataset ``indices`` (consecutive), the distinct ``images`` it reads (keys, in order of first
+    use) and ``crop_image[i]`` = the position in ``images`` of instance ``indices[i]``."""
+
+    indices: List[int]
+    images: List[str]
+    crop_image: List[int]
+
+
+def plan_batches(image_keys: Sequence[str], batch_size: int) -> List[Batch]:
+    """Instances in dataset order, ``batch_size`` per batch, the last one partial (DefaultSampler(shuffle=False,
+    round_up=False), drop_last=False). ``image_keys[i]``: the source image of instance i."""
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    plan = []
+    for lo in range(0, len(image_keys), batch_size):
+        idx = list(range(lo, min(lo + batch_size, len(image_keys))))
+        slot: Dict[str, int] = {}
+        crop_image = [slot.setdefault(image_keys[i], len(slot)) for i in idx]
+        plan.append(Batch(idx, list(slot), crop_image))
+    return plan
+
+
+def last_use(plan: Sequence[Batch]) -> Dict[str, int]:
+    """image key -> the last batch that reads it (its decoded pixels are released after that batch is built)."""
+    out: Dict[str, int] = {}
+    for k, b in enumerate(plan):
+        for key in b.images:
+            out[key] = k
+    return out
+
+
+def sample_to_dict(ds) -> dict:
+    """PoseDataSample -> the dict ``BaseDataElement.to_dict()`` gives the metric: metainfo keys, ``pred_instances`` and
+    ``gt_instances`` as dicts of their fields; a one-element ``category_id`` array as an int."""
+    if hasattr(ds, "to_dict"):
+        d = ds.to_dict()
+    else:
+        d = dict(ds.metainfo)
+        for name in ("pred_instances", "gt_instances"):
+            if hasattr(ds, name):
+                d[name] = dict(getattr(ds, name).all_items())
+    if isinstance(d.get("category_id"), np.ndarray) and d["category_id"].size == 1:
+        d["category_id"] = int(d["category_id"])  # the dataset keeps np.array(ann["category_id"]); the metric hashes it
+    return d
+
+
+def _coco_gt(ann_file: str) -> list:
+    from .datasets import COCO
+
+    coco = COCO(ann_file)
+    return coco.loadAnns(coco.getAnnIds(imgIds=coco.getImgIds()))
+
+
+def build_metric(cfg, ann_file: Optional[str] = None, device: str = "cuda"):
+    """A ``CocoMetric`` config -> ``evaluation.CocoMetric``: ``ann_file`` loaded through the COCO index (its annotation list is
+    the ground truth; when the config has none, the paired dataset's file, as the reference's CocoMetric takes it from the
+    MessageHub, coco_metric.py:196-216), every other key passed on unchanged."""
+    from .evaluation import CocoMetric
+
+    if not isinstance(cfg, dict):
+        return cfg  # a metric object already
+    cfg = dict(cfg)
+    kind = cfg.pop("type", "CocoMetric")
+    if kind not in ("CocoMetric", "mmpose.CocoMetric"):
+        raise NotImplementedError(f"metric type {kind!r}: only CocoMetric is implemented")
+    for k in ("outfile_prefix", "format_only", "collect_device", "pred_converter", "gt_converter"):
+        if cfg.get(k):
+            raise NotImplementedError(f"CocoMetric({k}=...) is not supported")
+        cfg.pop(k, None)
+    path = cfg.pop("ann_file", None) or ann_file
+    if path is None:
+        raise ValueError("CocoMetric needs an ann_file (in its config or from its dataset)")
+    cfg.setdefault("device", device)
+    return CocoMetric(_coco_gt(path), **cfg)
+
+
+@EVALUATORS.register_module(name="MultiDatasetEvaluator", force=True)
+class MultiDatasetEvaluator:
+    """mmpose/evaluation/evaluators/mutli_dataset_evaluator.py: metric i belongs to dataset config i and is keyed by that
+    dataset class's ``dataset_name``; ``process`` routes every sample to the metric of its ``dataset_name``; ``evaluate``
+    merges the metrics' (prefixed) results into one dict. ``ann_files``: dataset_name -> annotation file, for metrics
+    whose config names none."""
+
+    def __init__(self, metrics: Sequence, datasets: Sequence[dict], ann_files: Optional[Dict[str, str]] = None, device: str = "cuda"):
+        assert len(metrics) == len(datasets), "the argument datasets should have same length as metrics"
+        self.metrics_dict = {}
+        for dcfg, mcfg in zip(datasets, metrics):
+            cls = DATASETS.get(dcfg["type"]) if isinstance(dcfg["type"], str) else dcfg["type"]
+            if cls is None:
+                raise KeyError(f"{dcfg['type']} is not in the dataset registry")
+            name = cls.DATASET_NAME
+            self.metrics_dict[name] = build_metric(mcfg, (ann_files or {}).get(name), device)
+
+    @property
+    def metrics(self):
+        return list(self.metrics_dict.values())
+
+    def process(self, data_samples: Sequence, data_batch: Optional[dict] = None) -> None:
+        routed: Dict[str, list] = {}
+        for s in data_samples:
+            s = s if isinstance(s, dict) else sample_to_dict(s)
+            name = s.get("dataset_name")
+            if name not in self.metrics_dict:
+                raise KeyError(f"sample of dataset {name!r}: no metric for it (metrics: {list(self.metrics_dict)})")
+            routed.setdefault(name, []).append(s)
+        for name, metric in self.metrics_dict.items():
+            if name in routed:
+                metric.process(None, routed[name])
+
+    def evaluate(self) -> dict:
+        out = {}
+        for metric in self.metrics_dict.values():
+            res = metric.compute_metrics()
+            dup = set(out) & set(res)
+            if dup:
+                raise ValueError(f"metrics of two datasets give the same key(s) {sorted(dup)}: set a distinct `prefix` per metric")
+            out.update(res)
+        return out
+
+
+def build_evaluator(cfg, dataset=None, device: str = "cuda"):
+    """``cfg.test_evaluator`` -> an evaluator; ``dataset`` (the built test dataset) supplies the annotation files of metrics
+    that name none. A single metric config is a one-dataset evaluator."""
+    subsets = getattr(dataset, "datasets", [dataset] if dataset is not None else [])
+    ann_files = {type(d).DATASET_NAME: d.ann_file for d in subsets if hasattr(d, "ann_file")}
+    cfg = dict(cfg)
+    kind = cfg.pop("type", "MultiDatasetEvaluator")
+    if kind in ("CocoMetric", "mmpose.CocoMetric"):
+        if dataset is None or len(subsets) != 1:
+            raise ValueError("a single CocoMetric evaluates a single dataset")
+        return EVALUATORS.build(dict(type="MultiDatasetEvaluator", metrics=[dict(cfg, type=kind)],
+                                     datasets=[dict(type=type(subsets[0]).__name__)]), ann_files=ann_files, device=device)
+    return EVALUATORS.build(dict(cfg, type=kind), ann_files=ann_files, device=device)
+
+
+def _pipeline_of(model, dataset):
+    from . import apis
+    from .transforms import TopdownAffine
+
+    pipe = getattr(dataset, "pipeline", None)
+    if pipe is None or not pipe.transforms:
+        return apis._val_pipeline(model)
+    dev = str(next(model.parameters()).device)
+    for t in pipe.transforms:
+        if isinstance(t, TopdownAffine) and t.device is None:
+            t.device = dev
+    return pipe
+
+
+def test_dataset(model, dataset, evaluator=None, batch_size: int = 64, workers: int = 8, depth: int = 2,
+                 sink: Optional[Callable[[list], None]] = None) -> dict:
+    """Run ``model`` over every instance of ``dataset`` (``get_data_info(i)``, i in order) and return the evaluator's metrics
+    (``{}`` without one). ``sink``, when given, receives every batch's list of PoseDataSample, in order."""
+    from .apis import load_image_bgr
+    from .transforms import pseudo_collate
+
+    n = len(dataset)
+    infos = [dataset.get_data_info(i) for i in range(n)]
+    plan = plan_batches([d["img_path"] for d in infos], batch_size)
+    last = last_use(plan)
+    pipeline = _pipeline_of(model, dataset)
+    device = next(model.parameters()).device
+    ahead = max(2, depth)
+    pool = ThreadPoolExecutor(max_workers=max(1, min(MAX_WORKERS, int(workers))))
+    decoded: Dict[str, object] = {}  # image key -> future of its pixels
+    submitted = 0  # batches whose images have been queued for decoding
+
+    def queue_until(k):
+        nonlocal submitted
+        while submitted < min(k, len(plan)):
+            for key in plan[submitted].images:
+                if key not in decoded:
+                    decoded[key] = pool.submit(load_image_bgr, key)
+            submitted += 1
+
+    producer = torch.cuda.Stream(device=device)
+
+    def batches():
+        for k, b in enumerate(plan):
+            queue_until(k + 1 + ahead)
+            pixels = [decoded[key].result() for key in b.images]
+            data_list = []
+            for i, j in zip(b.indices, b.crop_image):
+                d = dict(infos[i])
+                d["img"] = pixels[j]  # the instances of an image share its array: one upload per batch, one table entry
+                data_list.append(d)
+            for key in b.images:
+                if last[key] == k:
+                    del decoded[key]
+            with torch.cuda.stream(producer):
+                packed = pipeline.batched(data_list)
+            consumer = torch.cuda.current_stream(device)
+            consumer.wait_stream(producer)
+            for p in packed:
+                if isinstance(p["inputs"], torch.Tensor) and p["inputs"].is_cuda:
+                    p["inputs"].record_stream(consumer)
+            if packed:
+                yield pseudo_collate(packed)
+
+    try:
+        with torch.no_grad():
+            for samples in model.test_step_stream(batches(), depth=depth, max_batch=batch_size):
+                if sink is not None:
+                    sink(samples)
+                if evaluator is not None:
+                    evaluator.process(samples)
+    finally:
+        pool.shutdown(wait=True, cancel_futures=True)
+    return evaluator.evaluate() if evaluator is not None else {}

@@ -186,3 +186,46 @@ def whole_image_bbox_meta(batch: int, img_size=(256, 192), padding: float = 1.25
     center = np.tile(np.array([W / 2, H / 2], np.float32), (batch, 1))
     scale = np.tile(np.array([W * padding, H * padding], np.float32), (batch, 1))
     return center, scale
+
+
+def synthetic_coco_dataset(root: str, n_images: int, seed: int = 0, image_size=(640, 480), fmt: str = "png",
+                           persons=(1, 8), invalid_image: bool = True, id_base: int = 0) -> int:
+    """A seeded COCO-format keypoint set under ``root``: ``root/val2017/*.{png,jpg}`` (written by PIL) and
+    ``root/annotations/person_keypoints_val2017.json``, ``persons`` boxes per image (some partly outside the image), 17
+    keypoints each with random visibilities; the first image's instances are all crowd (invalid) when ``invalid_image``.
+    Returns the number of valid instances. PNG decodes exactly on every decoder; JPEG is what a real set holds."""
+    import json
+    import os
+
+    import numpy as np
+    from PIL import Image
+
+    rng = np.random.default_rng(seed)
+    W, H = image_size
+    os.makedirs(os.path.join(root, "val2017"), exist_ok=True)
+    os.makedirs(os.path.join(root, "annotations"), exist_ok=True)
+    yy, xx = np.mgrid[0:H, 0:W]
+    images, anns, valid = [], [], 0
+    for k in range(n_images):
+        img_id = id_base + 1000 + 7 * k
+        name = f"{img_id:012d}.{fmt}"
+        base = (np.sin(xx / rng.uniform(8, 40) + rng.uniform(0, 6)) + np.cos(yy / rng.uniform(8, 40))) * 60 + 128
+        img = np.clip(base[..., None] + rng.normal(0, 12, (H, W, 3)) + rng.uniform(-40, 40, 3), 0, 255).astype(np.uint8)
+        Image.fromarray(img).save(os.path.join(root, "val2017", name), **({"quality": 90} if fmt == "jpg" else {}))
+        images.append(dict(id=img_id, file_name=name, width=W, height=H))
+        for p in range(int(rng.integers(persons[0], persons[1] + 1))):
+            w, h = rng.uniform(20, W * 0.6), rng.uniform(40, H * 0.9)
+            x, y = rng.uniform(-0.2 * w, W - 0.8 * w), rng.uniform(-0.2 * h, H - 0.8 * h)
+            v = rng.choice([0, 1, 2], 17, p=[0.2, 0.2, 0.6])
+            kx, ky = rng.uniform(x, x + w, 17), rng.uniform(y, y + h, 17)
+            kp = np.stack([np.where(v > 0, np.round(kx, 2), 0), np.where(v > 0, np.round(ky, 2), 0), v], 1)
+            crowd = int(invalid_image and k == 0)
+            nk = int((v > 0).sum())
+            anns.append(dict(id=id_base * 100 + len(anns) + 1, image_id=img_id, category_id=1, iscrowd=crowd, num_keypoints=nk,
+                             bbox=[round(float(x), 2), round(float(y), 2), round(float(w), 2), round(float(h), 2)],
+                             area=round(float(w * h * 0.55), 2), keypoints=[float(t) if i % 3 < 2 else int(t) for i, t in enumerate(kp.flatten())]))
+            valid += int(not crowd and nk > 0)
+    doc = dict(images=images, annotations=anns, categories=[dict(id=1, name="person", supercategory="person")])
+    with open(os.path.join(root, "annotations", "person_keypoints_val2017.json"), "w") as f:
+        json.dump(doc, f)
+    return valid

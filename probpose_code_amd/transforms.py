@@ -2,8 +2,8 @@
 ``LoadImage`` -> ``GetBBoxCenterScale`` -> ``TopdownAffine`` -> ``PackPoseInputs``, registered in ``TRANSFORMS`` under the
 reference's names and composed from ``cfg.test_dataloader.dataset.pipeline`` as the reference does
 (mmpose/apis/inference.py:159). The box arithmetic is host numpy exactly as in the reference (it is a handful of scalars per
-person); the image warp runs on the device (``pp_warp_affine_u8``), one launch for all boxes of an image when the pipeline
-is applied to a list (``Compose.batched``).
+person); the image warp runs on the device (``pp_warp_affine_u8``), one launch for all boxes of a list when the pipeline
+is applied to one (``Compose.batched`` -> ``pp_warp_affine_u8_batch``, the boxes may come from many images).
 """
 import math
 import warnings
@@ -125,6 +125,97 @@ def warp_affine_crops(img: torch.Tensor, mats: np.ndarray, input_size: Tuple[int
     _lib.call("pp_warp_affine_u8", img.data_ptr(), img.shape[0], img.shape[1], img.shape[2], inv.data_ptr(), out.data_ptr(), n, h, w,
               torch.cuda.current_stream(img.device).cuda_stream)
     return out
+
+
+class BatchStaging:
+    """The reused pinned host buffer behind ``warp_affine_crops_batch``: the tables and the host images of one batch are
+    packed into it and go to the device in ONE host-to-device copy. An event recorded after the copy guards it: the next
+    batch waits for that copy before it writes into the buffer (a copy in flight still reads it)."""
+
+    def __init__(self):
+        self.buf: Optional[torch.Tensor] = None
+        self.ev: Optional[torch.cuda.Event] = None
+
+    def acquire(self, nbytes: int) -> np.ndarray:
+        if self.ev is not None:
+            self.ev.synchronize()
+        if self.buf is None or self.buf.numel() < nbytes:
+            self.buf = torch.empty(1 << max(20, (nbytes - 1).bit_length()), dtype=torch.uint8, pin_memory=True)
+        return self.buf.numpy()
+
+    def upload(self, dev: torch.Tensor, nbytes: int) -> None:
+        stream = torch.cuda.current_stream(dev.device)
+        dev[:nbytes].copy_(self.buf[:nbytes], non_blocking=True)
+        if self.ev is None:
+            self.ev = torch.cuda.Event()
+        self.ev.record(stream)
+
+
+def _align(v: int, a: int = 256) -> int:
+    return (v + a - 1) // a * a
+
+
+def warp_affine_crops_batch(images: Sequence, crop_image: Sequence[int], mats: np.ndarray, input_size: Tuple[int, int],
+                            device=None, staging: Optional[BatchStaging] = None):
+    """Crops of many source images in ONE ``pp_warp_affine_u8_batch`` launch. images: (H, W, C) uint8 BGR images, host
+    arrays / tensors or device tensors, all with the same C; crop_image[i]: the image of crop i; mats: (n, 2, 3) forward warp
+    matrices. Device images are read in place; host images are packed with the tables into the pinned buffer of
+    ``staging`` and uploaded with one copy on the current stream. Returns ((n, C, h, w) uint8 crops on the device, the images
+    as (H, W, C) device tensors - the host ones as views of the uploaded block)."""
+    w, h = int(input_size[0]), int(input_size[1])
+    n, m = len(crop_image), len(images)
+    if staging is None:
+        staging = BatchStaging()
+    dev_device = next((im.device for im in images if isinstance(im, torch.Tensor) and im.is_cuda), None)
+    dev_device = torch.device(dev_device if dev_device is not None else (device or "cuda"))
+    if dev_device.type != "cuda":
+        raise RuntimeError("probpose_code_amd.transforms.warp_affine_crops_batch runs on the GPU only (no CPU fallback)")
+    chans = set()
+    for im in images:
+        dt = im.dtype if isinstance(im, torch.Tensor) else np.asarray(im).dtype
+        if dt not in (torch.uint8, np.uint8) or len(im.shape) != 3:
+            raise TypeError(f"the crop warp takes (H, W, C) uint8 images, got {tuple(im.shape)} {dt}")
+        if isinstance(im, torch.Tensor) and im.is_cuda and im.device != dev_device:
+            raise ValueError(f"images of one batch must share a device: {im.device} and {dev_device}")
+        chans.add(int(im.shape[2]))
+    if len(chans) > 1:
+        raise ValueError(f"images of one batch must have the same number of channels, got {sorted(chans)}")
+    C = chans.pop() if chans else 3
+    # the block: inverse maps (n, 6) f64 | image pointers (m) i64 | sides (m, 2) i32 | crop -> image (n) i32 | host images
+    o_ptr = 48 * n
+    o_hw = o_ptr + 8 * m
+    o_crop = o_hw + 8 * m
+    off, offsets = _align(o_crop + 4 * n), []
+    for im in images:
+        host = not (isinstance(im, torch.Tensor) and im.is_cuda)
+        offsets.append(off if host else None)
+        if host:
+            off = _align(off + int(np.prod(im.shape)))
+    total = off
+    dev = torch.empty(total, dtype=torch.uint8, device=dev_device)
+    blk = staging.acquire(total)
+    blk[:o_ptr].view(np.float64)[:] = np.stack([invert_affine(mm) for mm in mats]).reshape(-1) if n else []
+    ptrs, hw = blk[o_ptr:o_hw].view(np.int64), blk[o_hw:o_crop].view(np.int32)
+    dev_images = []
+    for j, im in enumerate(images):
+        H, W = int(im.shape[0]), int(im.shape[1])
+        if offsets[j] is None:
+            t = im.contiguous()
+        else:
+            a = im.numpy() if isinstance(im, torch.Tensor) else np.asarray(im)
+            blk[offsets[j]:offsets[j] + a.size].reshape(a.shape)[...] = a
+            t = dev[offsets[j]:offsets[j] + a.size].view(a.shape)
+        ptrs[j], hw[2 * j], hw[2 * j + 1] = t.data_ptr(), H, W
+        dev_images.append(t)
+    blk[o_crop:o_crop + 4 * n].view(np.int32)[:] = np.asarray(crop_image, np.int32)
+    staging.upload(dev, total)
+    out = torch.empty((n, C, h, w), dtype=torch.uint8, device=dev_device)
+    max_h = max((int(im.shape[0]) for im in images), default=1)
+    max_w = max((int(im.shape[1]) for im in images), default=1)
+    base = dev.data_ptr()
+    _lib.call("pp_warp_affine_u8_batch", base + o_ptr, base + o_hw, C, base + o_crop, base, max_h, max_w, out.data_ptr(), n, h, w,
+              torch.cuda.current_stream(dev_device).cuda_stream)
+    return out, dev_images
 
 
 # ------------------------------------------------------------------------------------------------- registered transforms
@@ -273,6 +364,7 @@ class TopdownAffine(BaseTransform):
         assert len(input_size) == 2 and all(isinstance(v, int) for v in input_size), f"Invalid input_size {input_size}"
         self.input_size, self.use_udp, self.input_padding = tuple(input_size), use_udp, input_padding
         self.with_bbox_mask, self.device = with_bbox_mask, device
+        self._staging: Optional[BatchStaging] = None  # the pinned upload buffer of transform_batch, made at first use
 
     _fix_aspect_ratio = staticmethod(fix_aspect_ratio)
 
@@ -338,22 +430,28 @@ class TopdownAffine(BaseTransform):
         return results
 
     def transform_batch(self, results_list: List[Dict]) -> List[Dict]:
-        """The same for a list of samples, ONE warp launch per distinct source image (the persons of a frame)."""
+        """The same for a list of samples: ONE warp launch for all boxes, whatever the number of source images (the persons
+        of a frame, or the instances of a test batch spread over many images): ``warp_affine_crops_batch``."""
+        if not results_list:
+            return results_list
         mats, boxes = [], []
         for r in results_list:
             boxes.append(r.get("bbox_xyxy_wrt_input", r.get("bbox")))
             mats.append(np.asarray(self.prepare(r), np.float64))
-        cache: dict = {}
-        groups: Dict[int, List[int]] = {}
-        for i, r in enumerate(results_list):
-            groups.setdefault(id(r["img"]), []).append(i)
-        for idx in groups.values():
-            img_t = self._device_image(results_list[idx[0]]["img"], cache)
-            crops = warp_affine_crops(img_t, np.stack([mats[i] for i in idx]), self.input_size)
-            for k, i in enumerate(idx):
-                if self.with_bbox_mask:
-                    self._bbox_mask(results_list[i], img_t, mats[i], boxes[i])
-                results_list[i]["img"] = crops[k]
+        slot: Dict[int, int] = {}
+        images, crop_image = [], []
+        for r in results_list:
+            i = slot.setdefault(id(r["img"]), len(images))
+            if i == len(images):
+                images.append(r["img"])
+            crop_image.append(i)
+        if self._staging is None:
+            self._staging = BatchStaging()
+        crops, dev_images = warp_affine_crops_batch(images, crop_image, np.stack(mats), self.input_size, self.device, self._staging)
+        for k, r in enumerate(results_list):
+            if self.with_bbox_mask:
+                self._bbox_mask(r, dev_images[crop_image[k]], mats[k], boxes[k])
+            r["img"] = crops[k]
         return results_list
 
     def __repr__(self) -> str:
@@ -402,7 +500,7 @@ class PackPoseInputs(BaseTransform):
 class Compose:
     """mmengine.dataset.Compose [3P]: a list of transforms (config dicts built through ``TRANSFORMS``, or callables) applied in
     order; a transform returning ``None`` ends the chain. ``batched`` applies the chain to a list of samples and lets
-    ``TopdownAffine`` warp all boxes that share a source image in one launch."""
+    ``TopdownAffine`` warp all their boxes in one launch."""
 
     def __init__(self, transforms):
         self.transforms = []

@@ -1,0 +1,103 @@
+"""Throughput of dataset evaluation (runner.test_dataset) on a seeded synthetic COCO-format set: a few hundred 640x480 JPEGs
+written by PIL into a temp directory, 1-8 boxes per image, synthetic weights. One rate per run of its own:
+
+    end_to_end      test_dataset without the metric (decode + crops + model)
+    end_to_end_eval test_dataset with the two-metric evaluator of the CropCOCO / COCO config
+    decode_only     the decode of every image on the same number of threads
+    model_only      test_step_stream on pre-made crops, batches of --batch-size
+    per_image_loop  apis.inference_topdown, one image (all its boxes) per call
+
+    python scripts/bench_dataset_eval.py --images 300 --step end_to_end    (default: all steps, one JSON line each)"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+CONFIG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "configs",
+                      "td-pm_ProbPose-small_mi355x_cropcoco-coco-val-256x192.py")
+STEPS = ("end_to_end", "end_to_end_eval", "decode_only", "model_only", "per_image_loop")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=300, help="images in all, half in each of the two datasets")
+    ap.add_argument("--batch-size", type=int, default=64)
+    ap.add_argument("--workers", type=int, default=8)
+    ap.add_argument("--step", choices=STEPS, action="append")
+    ap.add_argument("--data", default=None, help="reuse / keep the generated set in this directory")
+    args = ap.parse_args()
+
+    import torch
+
+    from probpose_code_amd import apis, runner, synthetic
+    from probpose_code_amd.config import Config
+    from probpose_code_amd.datasets import build_dataset
+
+    tmp = args.data or tempfile.mkdtemp(prefix="pp_bench_ds_")
+    roots = [os.path.join(tmp, "cropcoco") + "/", os.path.join(tmp, "coco") + "/"]
+    for i, r in enumerate(roots):
+        if not os.path.exists(os.path.join(r, "annotations", "person_keypoints_val2017.json")):
+            synthetic.synthetic_coco_dataset(r, args.images // 2, seed=100 + i, fmt="jpg", invalid_image=False, id_base=i + 1)
+    cfg = Config.fromfile(CONFIG)
+    cfg.merge_from_dict({f"test_dataloader.dataset.datasets.{i}.data_root": r for i, r in enumerate(roots)})
+    model = apis.init_model(cfg, dict(state_dict=synthetic.synthetic_state_dict("small", seed=0, logit_scale=2.0)), device="cuda:0")
+    dataset = build_dataset(cfg.test_dataloader.dataset)
+    n = len(dataset)
+    infos = [dataset.get_data_info(i) for i in range(n)]
+    paths = list(dict.fromkeys(d["img_path"] for d in infos))
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    for step in args.step or STEPS:
+        if step in ("end_to_end", "end_to_end_eval"):
+            runner.test_dataset(model, dataset, None, args.batch_size, args.workers)  # warm-up: graph capture, pinned buffers
+            ev = runner.build_evaluator(cfg.test_evaluator, dataset) if step == "end_to_end_eval" else None
+            dt = timed(lambda: runner.test_dataset(model, dataset, ev, args.batch_size, args.workers))
+        elif step == "decode_only":
+            with ThreadPoolExecutor(max_workers=min(16, args.workers)) as pool:
+                dt = timed(lambda: list(pool.map(apis.load_image_bgr, paths)))
+        elif step == "model_only":
+            g = torch.Generator().manual_seed(0)
+            crops = torch.randint(0, 256, (args.batch_size, 3, 256, 192), dtype=torch.uint8, generator=g).cuda()
+            from probpose_code_amd.apis import pack_crops
+
+            c = np.tile(np.array([[96.0, 128.0]], np.float32), (args.batch_size, 1))
+            s = np.tile(np.array([[192.0, 256.0]], np.float32), (args.batch_size, 1))
+            nb = (n + args.batch_size - 1) // args.batch_size
+
+            def run():
+                with torch.no_grad():
+                    for _ in model.test_step_stream((pack_crops(crops, c, s, model.dataset_meta) for _ in range(nb)), depth=2,
+                                                    max_batch=args.batch_size):
+                        pass
+
+            run()
+            dt = timed(run)
+        else:
+            per_img = {}
+            for d in infos:
+                per_img.setdefault(d["img_path"], []).append(d["bbox"][0])
+
+            def loop():
+                for p, boxes in per_img.items():
+                    apis.inference_topdown(model, apis.load_image_bgr(p), np.stack(boxes))
+
+            loop()
+            dt = timed(loop)
+        print(json.dumps(dict(step=step, instances=n, images=len(paths), seconds=round(dt, 4), instances_per_s=round(n / dt, 1),
+                              batch_size=args.batch_size, workers=args.workers)), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,78 @@
+"""Counterpart of the reference's ``tools/test.py CONFIG CHECKPOINT``: evaluate a config's test set end to end - the
+``test_dataloader`` (COCO-style datasets on ground-truth boxes) through the model, the ``test_evaluator`` over the results
+(probpose_code_amd.runner.test_dataset) - and print the metrics.
+
+    python tools/test.py configs/td-pm_ProbPose-small_mi355x_cropcoco-coco-val-256x192.py CHECKPOINT \
+        --cfg-options test_dataloader.dataset.datasets.0.data_root=/data/CropCOCO/ \
+                      test_dataloader.dataset.datasets.1.data_root=/data/coco/ --out metrics.json
+
+CHECKPOINT may be "synthetic" (seeded random weights: a plumbing check, as in demo/image_demo.py)."""
+import ast
+import json
+import os
+import sys
+import time
+from argparse import ArgumentParser
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def parse_cfg_options(items):
+    """``key=value`` pairs (mmengine's DictAction): values read as Python literals where they parse as one (numbers, booleans,
+    lists, tuples, None), as strings otherwise."""
+    opts = {}
+    for it in items or []:
+        if "=" not in it:
+            raise ValueError(f"--cfg-options takes key=value pairs, got {it!r}")
+        k, v = it.split("=", 1)
+        try:
+            opts[k] = ast.literal_eval(v)
+        except (ValueError, SyntaxError):
+            opts[k] = {"true": True, "false": False, "none": None}.get(v.lower(), v)
+    return opts
+
+
+def main(argv=None):
+    ap = ArgumentParser(description="Evaluate a config's test set (COCO-style datasets, ground-truth boxes)")
+    ap.add_argument("config")
+    ap.add_argument("checkpoint", help='a checkpoint file, or "synthetic" for seeded random weights')
+    ap.add_argument("--cfg-options", nargs="+", default=None, metavar="KEY=VALUE",
+                    help="override config keys; integer parts index lists, e.g. test_dataloader.dataset.datasets.0.data_root=DIR")
+    ap.add_argument("--out", default=None, help="write the metrics as JSON to this file")
+    ap.add_argument("--batch-size", type=int, default=None, help="instances per step (default: test_dataloader.batch_size, else 64)")
+    ap.add_argument("--workers", type=int, default=8, help="image decoding threads (at most 16)")
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--precision", default=None, choices=[None, "f16x3", "bf16", "f32"],
+                    help="overrides model.precision of the config (default there: f16x3)")
+    args = ap.parse_args(argv)
+
+    from probpose_code_amd import apis, runner, synthetic
+    from probpose_code_amd.config import Config
+    from probpose_code_amd.datasets import build_dataset
+
+    cfg = Config.fromfile(args.config)
+    opts = parse_cfg_options(args.cfg_options)
+    if args.precision:
+        opts["model.precision"] = args.precision
+    if opts:
+        cfg.merge_from_dict(opts)
+    ckpt = dict(state_dict=synthetic.synthetic_state_dict("small", seed=0, logit_scale=2.0)) if args.checkpoint == "synthetic" else args.checkpoint
+    model = apis.init_model(cfg, ckpt, device=args.device)
+    loader = cfg["test_dataloader"]
+    dataset = build_dataset(loader["dataset"])
+    evaluator = runner.build_evaluator(cfg["test_evaluator"], dataset, device=args.device)
+    batch_size = args.batch_size or int(loader.get("batch_size", 64))
+    t0 = time.perf_counter()
+    metrics = runner.test_dataset(model, dataset, evaluator, batch_size=batch_size, workers=args.workers)
+    dt = time.perf_counter() - t0
+    for k, v in metrics.items():
+        print(f"{k}: {v:.4f}")
+    print(f"{len(dataset)} instances in {dt:.2f} s ({len(dataset) / dt:.1f} instances/s)", file=sys.stderr)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(metrics, f, indent=1)
+    return metrics
+
+
+if __name__ == "__main__":
+    main()
