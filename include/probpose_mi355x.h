@@ -47,6 +47,11 @@ extern "C" {
  *              maps) and - since the LayerNorm fold - the residual rows themselves (centered per row in the ViT-S chain, raw in ViT-B's
  *              pp_linear_ln_folded plan). Beyond it hi = inf, the product NaN: it reaches the heatmap logits as NaN / inf, pp_probmap_decode_flags
  *              then writes NaN keypoints / scores (never "pixel 0 with a score"), and the host mirror raises FloatingPointError.
+ *              The same holds in the four scalar towers (features, every stage's pooled output): their pooling max and ReLU keep a NaN
+ *              (pp_maxpool_relu_nhwc, pp_sum_maxpool_relu_nhwc, the pooled epilogues of pp_conv3x3_winograd_maxpool_relu and
+ *              pp_conv3x3_maxpool_relu, pp_tower_final's error tower), so an overflowing tower yields NaN scalars for its crops - never a
+ *              window pooled to a clean 0 - and the record check of the host mirror raises. (PP_PREC_BF16 has fp32's range; its halo-pooled
+ *              epilogue keeps a NaN too, its ReLU epilogues of pp_conv_gemm do not.)
  *   precision  hi + lo has 22 significant bits while lo is a NORMAL fp16 number: |x| >= 2^-3. Below that lo is subnormal and the pair is exact
  *              to an ABSOLUTE 2^-25 only (no bits at all below 2^-25). Harmless for activations next to O(1) neighbours, fatal for weights,
  *              which are small numbers throughout (trained ViT weights ~ 0.02: 17 bits; rows of 1e-3: 13 bits - measured, tests/

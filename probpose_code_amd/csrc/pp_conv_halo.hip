@@ -23,6 +23,7 @@
 //     bf16 epilogue staged through the activation buffer that was just consumed and stored as whole rows.
 #include "pp_common.h"
 #include "pp_gemm.h"
+#include "pp_split.h"
 #include <cstdlib>
 
 namespace pp {
@@ -326,17 +327,17 @@ __global__ __launch_bounds__(THREADS, 2) void conv3_halo_kernel(const GemmParams
                 const int c8 = tid_e & 31, pr = tid_e >> 5;  // 8-byte piece of the 256-byte row, pooled pixel
                 if (img * IMG_PIX < p.M) {
                     const int yo = pr >> 2, xo = pr & 3;
-                    float mx[4] = {0.f, 0.f, 0.f, 0.f};  // ReLU folded into the start value
+                    float mx[4] = {0.f, 0.f, 0.f, 0.f};  // ReLU folded into the start value (a NaN is kept: pp_split.h, max_keep_nan)
 #pragma unroll
                     for (int i = 0; i < PH; ++i)
 #pragma unroll
                         for (int j = 0; j < PWD; ++j) {
                             const int ml = (yo * PH + i) * IW + xo * PWD + j;
                             const uint2 raw = *reinterpret_cast<const uint2*>(cst + ml * ROWB + (((c8 >> 1) ^ (ml & 7)) << 4) + (c8 & 1) * 8);
-                            mx[0] = fmaxf(mx[0], __builtin_bit_cast(float, raw.x << 16));
-                            mx[1] = fmaxf(mx[1], __builtin_bit_cast(float, raw.x & 0xffff0000u));
-                            mx[2] = fmaxf(mx[2], __builtin_bit_cast(float, raw.y << 16));
-                            mx[3] = fmaxf(mx[3], __builtin_bit_cast(float, raw.y & 0xffff0000u));
+                            mx[0] = max_keep_nan(mx[0], __builtin_bit_cast(float, raw.x << 16));
+                            mx[1] = max_keep_nan(mx[1], __builtin_bit_cast(float, raw.x & 0xffff0000u));
+                            mx[2] = max_keep_nan(mx[2], __builtin_bit_cast(float, raw.y << 16));
+                            mx[3] = max_keep_nan(mx[3], __builtin_bit_cast(float, raw.y & 0xffff0000u));
                         }
                     uint2 o;
                     o.x = (__builtin_bit_cast(unsigned, mx[0]) >> 16) | (__builtin_bit_cast(unsigned, mx[1]) & 0xffff0000u);

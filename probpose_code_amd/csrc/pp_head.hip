@@ -24,7 +24,8 @@ __device__ __forceinline__ void store4(__bf16* base, size_t idx, f32x4 v) {
 }
 __device__ __forceinline__ void store4(SplitH* base, size_t idx, f32x4 v) { split_store4(base, idx, v); }
 
-// MaxPool2d(kernel = stride = (ph, pw), no padding, floor) followed by ReLU on NHWC tensors.
+// MaxPool2d(kernel = stride = (ph, pw), no padding, floor) followed by ReLU on NHWC tensors; a NaN in a window gives a NaN (torch's
+// MaxPool2d + ReLU; pp_split.h, max_keep_nan).
 // in  [N, H, W, C] -> out [N, H/ph, W/pw, C]; one thread per 4 output channels.
 template <typename TI, typename TO>
 __global__ __launch_bounds__(256) void maxpool_relu_kernel(const TI* __restrict__ in, TO* __restrict__ out, int N,
@@ -43,10 +44,10 @@ __global__ __launch_bounds__(256) void maxpool_relu_kernel(const TI* __restrict_
         for (int j = 0; j < pw; ++j) {
             const f32x4 v = load4(in, (((size_t)n * H + yo * ph + i) * W + xo * pw + j) * C + c);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) m[q] = fmaxf(m[q], v[q]);
+            for (int q = 0; q < 4; ++q) m[q] = max_keep_nan(m[q], v[q]);
         }
 #pragma unroll
-    for (int q = 0; q < 4; ++q) m[q] = fmaxf(m[q], 0.f);
+    for (int q = 0; q < 4; ++q) m[q] = relu_keep_nan(m[q]);
     store4(out, (((size_t)n * Ho + yo) * Wo + xo) * C + c, m);
 }
 
@@ -85,11 +86,11 @@ __global__ __launch_bounds__(256) void sum_maxpool_relu_kernel(const float* __re
                 for (int sp = 1; sp < nsplit; ++sp) v += *reinterpret_cast<const f32x4*>(src + sp * split_stride);
             }
 #pragma unroll
-            for (int q = 0; q < 4; ++q) m[q] = fmaxf(m[q], v[q]);
+            for (int q = 0; q < 4; ++q) m[q] = max_keep_nan(m[q], v[q]);
         }
     const f32x4 b = bias ? *reinterpret_cast<const f32x4*>(bias + (size_t)(n / images_per_group) * C + c) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int q = 0; q < 4; ++q) m[q] = fmaxf(m[q] + b[q], 0.f);  // max(x) + b == max(x + b): the bias is per channel
+    for (int q = 0; q < 4; ++q) m[q] = relu_keep_nan(m[q] + b[q]);  // max(x) + b == max(x + b): the bias is per channel
     store4(out, (((size_t)n * Ho + yo) * Wo + xo) * C + c, m);
 }
 
@@ -123,7 +124,7 @@ __global__ __launch_bounds__(256) void tower_final_kernel(const TI* __restrict__
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
         acc += bias[t * K + kk];
-        res += (t == 3) ? fmaxf(acc, 0.f) : 1.0f / (1.0f + expf(-acc));
+        res += (t == 3) ? relu_keep_nan(acc) : 1.0f / (1.0f + expf(-acc));
     }
     if (passes == 2) res *= 0.5f;
     if (t == 3) res = res / err_div;

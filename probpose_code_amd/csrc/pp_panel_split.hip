@@ -489,14 +489,14 @@ __global__ __launch_bounds__(THREADS, 2) void panel_split_kernel(const GemmParam
                             const f32x4 a1 = *reinterpret_cast<const f32x4*>(cst + ml * ROWB + (((2 * cl + 1) ^ (ml & 7)) << 4));
 #pragma unroll
                             for (int i = 0; i < 4; ++i) {
-                                v0[i] = fmaxf(v0[i], a0[i]);
-                                v1[i] = fmaxf(v1[i], a1[i]);
+                                v0[i] = max_keep_nan(v0[i], a0[i]);  // (NaN kept: pp_split.h)
+                                v1[i] = max_keep_nan(v1[i], a1[i]);
                             }
                         }
                     f16x8 hv, lv;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        const float b0 = fmaxf(v0[i], 0.f), b1 = fmaxf(v1[i], 0.f);
+                        const float b0 = relu_keep_nan(v0[i]), b1 = relu_keep_nan(v1[i]);
                         hv[i] = split_hi(b0);
                         lv[i] = split_lo(b0, hv[i]);
                         hv[4 + i] = split_hi(b1);

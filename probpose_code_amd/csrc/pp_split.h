@@ -130,6 +130,15 @@ __device__ __forceinline__ float relu_keep_nan(float x) {
     return x != x ? x : r;
 }
 
+// The max of a pooling window that keeps a NaN, for the same reason: the scalar towers pool after every convolution, and a window max that starts
+// at -inf and skips NaN ends at -inf (all NaN) or at its finite members, which the ReLU then turns into plausible numbers - the tower would score
+// an out-of-range crop as if nothing had happened. Once either operand is NaN the result is NaN (torch's MaxPool2d); one compare and one select
+// more per value, in memory-bound pooling and epilogues only.
+__device__ __forceinline__ float max_keep_nan(float m, float x) {
+    const float r = fmaxf(m, x);
+    return __builtin_isunordered(m, x) ? m + x : r;
+}
+
 // GELU(x) = 0.5 x (1 + erf(x / sqrt 2)) for the parity mode's epilogues. libdevice erff costs ~57 VALU instructions per
 // element - 55 us of a 166 us fc1 launch at bs 64 (scripts/bench_split_gemm.py). This form is Abramowitz & Stegun 7.1.26,
 //     erfc(z) = t (a1 + t (a2 + t (a3 + t (a4 + t a5)))) exp(-z^2),  t = 1 / (1 + p z),  z >= 0,  |error| <= 1.5e-7,

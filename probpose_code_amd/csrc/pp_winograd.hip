@@ -339,14 +339,14 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_pool_kernel(const Params p) {
                     const f32x4 v0 = *reinterpret_cast<const f32x4*>(s), v1 = *reinterpret_cast<const f32x4*>(s + 4);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        m0[q] = fmaxf(m0[q], v0[q]);
-                        m1[q] = fmaxf(m1[q], v1[q]);
+                        m0[q] = max_keep_nan(m0[q], v0[q]);  // (NaN kept: pp_split.h)
+                        m1[q] = max_keep_nan(m1[q], v1[q]);
                     }
                 }
             f16x8 hv, lv;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {  // max(x) + b == max(x + b): the bias is per channel
-                const float r0 = fmaxf(m0[q] + bv0[q], 0.f), r1 = fmaxf(m1[q] + bv1[q], 0.f);
+                const float r0 = relu_keep_nan(m0[q] + bv0[q]), r1 = relu_keep_nan(m1[q] + bv1[q]);
                 hv[q] = split_hi(r0);
                 lv[q] = split_lo(r0, hv[q]);
                 hv[4 + q] = split_hi(r1);

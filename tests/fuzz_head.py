@@ -79,6 +79,54 @@ def tower_final64(feat, w, bias, flip_indices, B, passes, err_div):
     return a if passes == 1 else (a[:, :B] + a[:, B:][:, :, flip_indices]) * 0.5
 
 
+# ----------------------------------------------------------------------------------------------------- non-finite poison (imported by tests/fuzz_conv.py)
+# The NaN contract of the towers (include/probpose_mi355x.h, numeric domain): a value out of range must come out as NaN / inf, never be pooled
+# away. Poisoned inputs hold a few +inf, -inf or canonical NaN elements (never the canary payloads). What a case then asserts:
+#   * every output whose fp64 reference is non-finite is non-finite;
+#   * an output may be non-finite where the reference is finite only inside the poison's REACH: the outputs whose receptive field holds a
+#     poisoned input (a split-fp16 operand of +-inf is hi = inf, lo = NaN, so the kernel's product is NaN where fp64 has +-inf, which a max
+#     may discard). For a 3x3 convolution the reach is the 3x3 neighbourhood of the poisoned pixels; for the Winograd F(2x2, 3x3) form it is
+#     every 2 x 2 output tile whose 4 x 4 input tile holds one (the input transform mixes the whole tile); pooling then takes the windows
+#     that hold a reached output;
+#   * every output finite on both sides meets the normal tolerance.
+def poison_(x, g, n):
+    """In place: n random elements of x set to +inf, -inf and canonical NaN in turn."""
+    for i in range(n):
+        idx = tuple(int(torch.randint(0, d, (1,), generator=g)) for d in x.shape)
+        x[idx] = (math.inf, -math.inf, math.nan)[i % 3]
+    return x
+
+
+def bad_pixels(x):
+    """(B, H, W, C) NHWC -> (B, H, W) bool: pixels with a non-finite channel."""
+    return ~torch.isfinite(x.double()).all(dim=-1)
+
+
+def conv_reach(bad, ph=1, pw=1, winograd=False):
+    """bad (B, H, W) -> (B, 1, H // ph, W // pw) bool: pooled 3x3-convolution outputs a poisoned pixel can reach (ph = pw = 1: no pooling)."""
+    i = bad.double()[:, None]
+    if winograd:  # output tile (ty, tx) reads input rows 2 ty - 1 .. 2 ty + 2 (and the columns alike)
+        H, W = bad.shape[1:]
+        t = F.max_pool2d(F.pad(i, (1, 1, 1, 1)), 4, 2)[:, :, :H // 2, :W // 2]
+        r = t.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
+    else:
+        r = F.max_pool2d(i, 3, 1, 1)
+    B, _, H, W = r.shape
+    r = r[:, :, :H // ph * ph, :W // pw * pw].reshape(B, 1, H // ph, ph, W // pw, pw).amax(dim=(3, 5))
+    return r > 0
+
+
+def poison_ratio(got, ref, reach, rtol, atol):
+    """error / tolerance of a poisoned case (inf when a non-finite reference came out finite, or a non-finite output lies outside the reach)."""
+    got, ref = got.double(), ref.double()
+    fg, fr = torch.isfinite(got), torch.isfinite(ref)
+    reach = reach.expand_as(got)
+    if bool((~fr & fg).any()) or bool((~fg & ~reach).any()):
+        return math.inf
+    both = fg & fr
+    return error_ratio(got[both], ref[both], rtol, atol)
+
+
 def _main(seconds):
     from probpose_code_amd import _lib as L
     from probpose_code_amd.weights import from_split, pack_head_split, to_split, winograd_weights
@@ -158,6 +206,10 @@ def _main(seconds):
         order = int(rng.choice([-1, 0]))
         gd = torch.Generator(device="cuda").manual_seed(int(rng.integers(1 << 30)))
         x = torch.randn(B, H, W, C, generator=gd, device="cuda")
+        poisoned = rng.random() < 0.25
+        if poisoned:  # first and last image: both are in the sample the reference is computed on
+            for i in {0, B - 1}:
+                poison_(x[i], g, int(rng.integers(1, 4)))
         w = cpu_rand(G, C, C, 3, 3, g=g, scale=1 / math.sqrt(9 * C))
         b = cpu_rand(G, C, g=g, scale=0.3)
         guard = Guard()
@@ -178,7 +230,11 @@ def _main(seconds):
         xi = x[imgs].permute(0, 3, 1, 2).cpu().double()
         ref = torch.stack([pool_relu64(conv3x3_64(xi, w[k][ch].double(), b[k][ch].double()), 4, 3) for k in range(G)])
         got = unsp(snap[1])[:, imgs][..., ch].permute(0, 1, 4, 2, 3)
-        return faults, error_ratio(got, ref, TOL["winograd"], TOL["winograd"]), f"B {B} {H}x{W} C {C} G {G} wino_order {'default' if order else 0}"
+        if poisoned:
+            ratio = poison_ratio(got, ref, conv_reach(bad_pixels(x[imgs].cpu()), 4, 3, winograd=True)[None], TOL["winograd"], TOL["winograd"])
+        else:
+            ratio = error_ratio(got, ref, TOL["winograd"], TOL["winograd"])
+        return faults, ratio, f"B {B} {H}x{W} C {C} G {G} wino_order {'default' if order else 0} poison {poisoned}"
 
     # ------------------------------------------------------------------------------------------------- split-K tower stages
     def case_splitk(rng, g):
@@ -194,6 +250,11 @@ def _main(seconds):
         gd = torch.Generator(device="cuda").manual_seed(int(rng.integers(1 << 30)))
         x = torch.randn(G, B, H, W, C, generator=gd, device="cuda")
         shared = rng.random() < 0.5  # the four towers on one input (stride 0) or each on its own
+        poisoned = rng.random() < 0.25
+        if poisoned:
+            for k in range(G):
+                for i in {0, B - 1}:
+                    poison_(x[k, i], g, int(rng.integers(1, 3)))
         w = cpu_rand(G, C, C, 3, 3, g=g, scale=1 / math.sqrt(9 * C))
         b = cpu_rand(G, C, g=g)
         guard = Guard()
@@ -217,14 +278,19 @@ def _main(seconds):
         imgs, ch = pick(B, rng, 2), torch.from_numpy(rng.choice(C, 64, replace=False))
         ratio = 0.0
         for k in range(G):
-            xi = (x[0] if shared else x[k])[imgs].permute(0, 3, 1, 2).cpu().double()
+            xk = (x[0] if shared else x[k])[imgs].cpu()
+            xi = xk.permute(0, 3, 1, 2).double()
             conv = conv3x3_64(xi, w[k][ch].double())
             psum = snap[0][:, k][:, imgs][..., ch].cpu().double().sum(0).permute(0, 3, 1, 2)
-            ratio = max(ratio, error_ratio(psum, conv, TOL["splitk"], TOL["splitk"]))
             pref = pool_relu64(conv + b[k][ch].double().view(1, -1, 1, 1), 2, 2)
             pg = unsp(snap[1].view(G, B, H // 2, W // 2, C)[k][imgs])[..., ch].permute(0, 3, 1, 2)
-            ratio = max(ratio, error_ratio(pg, pref, TOL["splitk"], TOL["splitk"]))
-        return faults, ratio, f"B {B} {H}x{W} C {C} slices {ks} (library {lib_s}) ksplit_channels {chans} shared {shared}"
+            if poisoned:
+                bad = bad_pixels(xk)
+                ratio = max(ratio, poison_ratio(psum, conv, conv_reach(bad), TOL["splitk"], TOL["splitk"]),
+                            poison_ratio(pg, pref, conv_reach(bad, 2, 2), TOL["splitk"], TOL["splitk"]))
+            else:
+                ratio = max(ratio, error_ratio(psum, conv, TOL["splitk"], TOL["splitk"]), error_ratio(pg, pref, TOL["splitk"], TOL["splitk"]))
+        return faults, ratio, f"B {B} {H}x{W} C {C} slices {ks} (library {lib_s}) ksplit_channels {chans} shared {shared} poison {poisoned}"
 
     # ------------------------------------------------------------------------------------------------- fused conv + pool, implicit GEMM
     def case_conv_pool(rng, g):
@@ -233,6 +299,10 @@ def _main(seconds):
         fused = int(rng.integers(0, 2))
         gd = torch.Generator(device="cuda").manual_seed(int(rng.integers(1 << 30)))
         x = torch.randn(B, H, W, C, generator=gd, device="cuda")
+        poisoned = rng.random() < 0.25
+        if poisoned:
+            for i in {0, B - 1}:
+                poison_(x[i], g, int(rng.integers(1, 4)))
         w = cpu_rand(G, C, C, 3, 3, g=g, scale=1 / math.sqrt(9 * C))
         b = cpu_rand(G, C, g=g)
         guard = Guard()
@@ -253,7 +323,11 @@ def _main(seconds):
         xi = x[imgs].permute(0, 3, 1, 2).cpu().double()
         ref = torch.stack([pool_relu64(conv3x3_64(xi, w[k][ch].double(), b[k][ch].double()), 4, 3) for k in range(G)])
         got = unsp(snap[0])[:, imgs][..., ch].permute(0, 1, 4, 2, 3)
-        return faults, error_ratio(got, ref, TOL["conv_pool"], TOL["conv_pool"]), f"B {B} conv_pool_split {fused}"
+        if poisoned:
+            ratio = poison_ratio(got, ref, conv_reach(bad_pixels(x[imgs].cpu()), 4, 3)[None], TOL["conv_pool"], TOL["conv_pool"])
+        else:
+            ratio = error_ratio(got, ref, TOL["conv_pool"], TOL["conv_pool"])
+        return faults, ratio, f"B {B} conv_pool_split {fused} poison {poisoned}"
 
     # ------------------------------------------------------------------------------------------------- last tower layer + flip average
     def case_tower_final(rng, g):
@@ -264,6 +338,9 @@ def _main(seconds):
         K = int(rng.integers(1, 40))
         err_div = float(rng.choice([1.0, 2.0, 7.3, 100.0]))
         feat = cpu_rand(4, passes * B, C, g=g)
+        poisoned = rng.random() < 0.25
+        if poisoned:
+            poison_(feat, g, int(rng.integers(1, 6)))
         w = cpu_rand(4, K, C, g=g, scale=1 / math.sqrt(C))
         bias = cpu_rand(4, K, g=g, scale=0.3)
         fi = torch.randperm(K, generator=g)
@@ -283,8 +360,15 @@ def _main(seconds):
                    passes, C, K, err_div, None)
         faults, snap = run_twice(guard, go)
         ref = tower_final64(fq, w.double(), bias.double(), fi, B, passes, err_div)
-        fac = magnitude_factor(fq.reshape(-1, C))
-        return faults, error_ratio(snap[0].cpu(), ref, TOL["tower_final"] * fac, TOL["tower_final_atol"] * fac), f"fmt {fmt} passes {passes} B {B} C {C} K {K} err_div {err_div}"
+        if poisoned:  # a feature row with a non-finite element reaches every keypoint of its (tower, crop); the flip pass's row the same crop
+            bad = ~torch.isfinite(fq).all(dim=-1)
+            reach = (bad[:, :B] | bad[:, B:]) if passes == 2 else bad
+            fac = magnitude_factor(fq.nan_to_num(0.0, 0.0, 0.0).reshape(-1, C))
+            ratio = poison_ratio(snap[0].cpu(), ref, reach[..., None], TOL["tower_final"] * fac, TOL["tower_final_atol"] * fac)
+        else:
+            fac = magnitude_factor(fq.reshape(-1, C))
+            ratio = error_ratio(snap[0].cpu(), ref, TOL["tower_final"] * fac, TOL["tower_final_atol"] * fac)
+        return faults, ratio, f"fmt {fmt} passes {passes} B {B} C {C} K {K} err_div {err_div} poison {poisoned}"
 
     entries = [
         ("pp_deconv_head_split", case_deconv_head),

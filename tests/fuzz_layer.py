@@ -707,8 +707,8 @@ def _main(seconds):
 
 
 def run_entries(entries, seconds, seed0, label, L, summary=None):
-    """Round robin over the entry points until the time is up; prints the per-entry-point table (then `summary()`, when given) and the verdict.
-    Returns the exit status."""
+    """Round robin over the entry points until the time is up; prints the per-entry-point table (then `summary()`, when given: a non-empty list it
+    returns names failures of its own) and the verdict. Returns the exit status."""
     stats = {name: dict(cases=0, refused=0, worst=0.0, bad=0) for name, _ in entries}
     t_end = time.time() + seconds
     seed = 0
@@ -736,11 +736,11 @@ def run_entries(entries, seconds, seed0, label, L, summary=None):
     print(f"{'entry point':44s} {'cases':>6s} {'refused':>8s} {'worst err/tol':>14s}")
     for n, s in stats.items():
         print(f"{n:44s} {s['cases']:6d} {s['refused']:8d} {s['worst']:14.3g}")
-    if summary is not None:
-        summary()
-    print(f"{sum(s['cases'] for s in stats.values())} cases in {seconds:.0f} s, {bad} mismatches" + (f"; no accepted case: {', '.join(idle)}" if idle else ""))
-    print(f"{label} FUZZ", "FAILED" if (bad or idle) else "OK")
-    return 1 if (bad or idle) else 0
+    extra = (summary() or []) if summary is not None else []
+    print(f"{sum(s['cases'] for s in stats.values())} cases in {seconds:.0f} s, {bad} mismatches" + (f"; no accepted case: {', '.join(idle)}" if idle else "")
+          + (f"; {len(extra)} summary failures" if extra else ""))
+    print(f"{label} FUZZ", "FAILED" if (bad or idle or extra) else "OK")
+    return 1 if (bad or idle or extra) else 0
 
 
 def main():

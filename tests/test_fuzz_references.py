@@ -1,7 +1,9 @@
-"""The fp64 references and tolerances of tests/fuzz_layer.py and tests/fuzz_head.py, on the CPU: (a) every reference agrees with an independent
-torch form of the same operation in fp64; (b) the fuzzers' tolerances reject two simulated faulty kernels - one that drops the low halves of the
-split operands (fp16 operands), one with bf16 operands - while the split format's own rounding passes. Emulated in fp64, no GPU needed: a kernel
-that silently lost precision would fail the fuzzers."""
+"""The fp64 references and tolerances of tests/fuzz_layer.py, tests/fuzz_head.py and tests/fuzz_conv.py, on the CPU: (a) every reference agrees
+with an independent torch form of the same operation in fp64; (b) the fuzzers' tolerances reject two simulated faulty kernels - one that drops the
+low halves of the split operands (fp16 operands), one with bf16 operands - while the split format's own rounding passes; (c) the convolution
+fuzzer's checks reject a gather that reads the neighbouring image instead of the zero pad, swapped deconvolution phases, one wrong border tap
+under the bf16-output bound, and a pooling max that drops NaN. Emulated in fp64, no GPU needed: a kernel that silently lost precision would fail
+the fuzzers."""
 import math
 import os
 import sys
@@ -171,3 +173,117 @@ def test_tolerances_reject_lost_precision_head_convolutions():
     wf, bf = _rand(17, 256, seed=66, scale=4 / math.sqrt(256)), _rand(17, seed=67)
     ref = FH.deconv_head64(xd, wd, bd, wf, bf)
     _check(_verdicts(lambda rd: (FH.deconv_head64(rd(xd), rd(wd), bd, rd(wf), bf), ref), FH.TOL["deconv_head"]))
+
+
+# ------------------------------------------------------------------------------------------------- tests/fuzz_conv.py: references and rejections
+import fuzz_conv as FC  # noqa: E402
+
+
+def test_conv_references_vs_torch():
+    B, Cin, Cout, H, W = 2, 16, 24, 5, 3
+    x = _rand(B, Cin, H, W, seed=70)
+    w, b = _rand(Cin, Cout, 4, 4, seed=71, scale=0.2), _rand(Cout, seed=72)
+    torch.testing.assert_close(FC.deconv64(x, w, b), F.conv_transpose2d(x, w, b, stride=2, padding=1), rtol=1e-12, atol=1e-12)
+    w3 = _rand(Cout, Cin, 3, 3, seed=73, scale=0.2)
+    for act, fn in ((FC.ACT_NONE, lambda y: y), (FC.ACT_RELU, F.relu), (FC.ACT_GELU, F.gelu)):
+        torch.testing.assert_close(FC.act64(FH.conv3x3_64(x, w3, b), act), fn(F.conv2d(x, w3, b, padding=1)), rtol=1e-12, atol=1e-12)
+    y = _rand(3, 4, 7, 5, seed=74)
+    for ph, pw in ((2, 2), (3, 2), (7, 5), (4, 3), (1, 1)):
+        torch.testing.assert_close(FC.pool_relu_floor64(y, ph, pw), F.relu(F.max_pool2d(y, (ph, pw))), rtol=0, atol=0)
+    y[1, 2, 3, 1] = math.nan  # a NaN in a window pools to NaN (torch's MaxPool2d), and ReLU keeps it
+    assert math.isnan(FC.pool_relu_floor64(y, 2, 2)[1, 2, 1, 0].item())
+
+
+def test_im2col_and_layernorm_references_vs_torch():
+    from oracle import model_ref as M
+
+    g = torch.Generator().manual_seed(75)
+    img = torch.randint(0, 256, (2, 3, 37, 21), generator=g, dtype=torch.uint8)
+    mean, std = [123.675, 116.28, 103.53], [58.395, 57.12, 57.375]
+    for pad in range(4):
+        for passes in (1, 2):
+            for bgr in (True, False):
+                x = M.preprocess(img, mean, std, bgr_to_rgb=bgr).double()
+                x = torch.cat([x, x.flip(-1)]) if passes == 2 else x
+                Hp, Wp = (37 + 2 * pad - 16) // 16 + 1, (21 + 2 * pad - 16) // 16 + 1
+                want = F.unfold(F.pad(x, (pad,) * 4)[:, :, :Hp * 16, :Wp * 16], 16, stride=16).transpose(1, 2).reshape(-1, 768)
+                torch.testing.assert_close(FC.im2col64(img, mean, std, pad, passes, bgr), want, rtol=1e-6, atol=1e-6)
+    x = _rand(9, 1024, seed=76) * 4 + 3
+    g_, b_ = 1 + 0.1 * _rand(1024, seed=77), _rand(1024, seed=78)
+    torch.testing.assert_close(FL.layernorm64(x, g_, b_), F.layer_norm(x, (1024,), g_, b_, FL.EPS), rtol=1e-12, atol=1e-12)
+    assert FC.ulp32(torch.tensor([1.0], dtype=torch.float64)).item() == 2.0 ** -23
+
+
+def test_conv_fuzz_rejects_neighbour_image_reads():
+    """A 3x3 gather that reads the neighbouring image instead of the zero pad (the batch stacked as one tall image): the border impulses make it
+    fail every tolerance of the fuzzer by far, while the correct convolution passes."""
+    B, C, H, W = 3, 64, 6, 4
+    x = FC.border_impulses(B, H, W, C, torch.Generator().manual_seed(79)).double().permute(0, 3, 1, 2)
+    w, b = _rand(C, C, 3, 3, seed=80, scale=1 / math.sqrt(9 * C)), _rand(C, seed=81, scale=0.3)
+    ref = FH.conv3x3_64(x, w, b)
+    tall = FH.conv3x3_64(x.permute(1, 0, 2, 3).reshape(1, C, B * H, W), w, b).reshape(C, B, H, W).permute(1, 0, 2, 3)
+    assert FC.bf16_out_ratio(ref.float().bfloat16().double(), ref) <= 1.0
+    assert FC.bf16_out_ratio(tall, ref) > 20 and FL.error_ratio(tall, ref, FC.F32_TOL, FC.F32_TOL) > 1e3
+    assert FL.error_ratio(tall, ref, FH.TOL["conv_pool"] * 8, FH.TOL["conv_pool"] * 8) > 1e3  # the f16x3 tolerance at the class's magnitude
+
+
+def test_conv_fuzz_rejects_swapped_deconv_phases_and_lost_precision():
+    B, Cin, Cout, H, W = 1, 128, 64, 4, 3
+    x, w = _rand(B, Cin, H, W, seed=82), _rand(Cin, Cout, 4, 4, seed=83, scale=1 / math.sqrt(4 * Cin))
+    ref = FC.deconv64(x, w)
+    bad = ref.clone()
+    bad[:, :, 0::2, 1::2], bad[:, :, 1::2, 0::2] = ref[:, :, 1::2, 0::2], ref[:, :, 0::2, 1::2]
+    assert FL.error_ratio(bad, ref, FC.BF16_F32OUT_TOL, FC.BF16_F32OUT_TOL) > 10
+    # f16x3 with fp16 operands (low halves lost) and the fp32 path with bf16 operands: rejected; the split rounding passes
+    v = _verdicts(lambda rd: (FC.deconv64(rd(x), rd(w)), ref), FH.TOL["deconv_head"])
+    _check(v)
+    xc, wc = _rand(B, Cin, H, W, seed=84), _rand(Cout, Cin, 3, 3, seed=85, scale=1 / math.sqrt(9 * Cin))
+    refc = FH.conv3x3_64(xc, wc)
+    assert FL.error_ratio(FH.conv3x3_64(xc.float().double(), wc.float().double()), refc, FC.F32_TOL, FC.F32_TOL) <= 1.0
+    assert FL.error_ratio(FH.conv3x3_64(xc.bfloat16().double(), wc.bfloat16().double()), refc, FC.F32_TOL, FC.F32_TOL) > 1.0
+
+
+def test_conv_fuzz_bf16_output_bound_rejects_one_wrong_tap():
+    """One product of one border pixel read from the neighbouring image instead of the zero pad: about 1 / sqrt(9 * 384) = 0.017 at unit
+    activations. The flat 2e-2 of the fixed-shape tests lets it through; 2^-8 |ref| + 2e-3 on the bf16-rounded reference does not."""
+    C = 384
+    x = _rand(1, C, 4, 4, seed=86).bfloat16().double()
+    w = _rand(C, C, 3, 3, seed=87, scale=1 / math.sqrt(9 * C)).bfloat16().double()
+    ref = FH.conv3x3_64(x, w)
+    co = int(ref[0, :, 0, 0].abs().argmin())
+    c = int((w[co, :, 0, 1].abs() - 1 / math.sqrt(9 * C)).abs().argmin())  # a typical weight of the tap that leaves the image at (0, 0)
+    bad = ref.clone()
+    bad[0, co, 0, 0] += 1.0 * w[co, c, 0, 1]  # the neighbour's pixel (value 1) where the pad's 0 belongs
+    got = bad.float().bfloat16().double()
+    assert FL.error_ratio(got, ref, 2e-2, 2e-2) <= 1.0  # what the fixed tests say
+    assert FC.bf16_out_ratio(ref.float().bfloat16().double(), ref) <= 1.0
+    assert FC.bf16_out_ratio(got, ref) > 1.0, FC.bf16_out_ratio(got, ref)
+
+
+def test_poison_check_rejects_a_nan_dropping_max():
+    """The poison contract: a max that skips NaN (v_max_f32 / torch.fmax: the other operand) turns a window of NaN into -inf and ReLU into 0 -
+    rejected; the NaN-keeping max passes, and so does a NaN the split format adds inside the reach."""
+    B, C, H, W = 2, 32, 8, 6
+    x = _rand(B, H, W, C, seed=88)
+    g = torch.Generator().manual_seed(89)
+    FH.poison_(x[0], g, 3)
+    w = _rand(C, C, 3, 3, seed=90, scale=1 / math.sqrt(9 * C))
+    conv = FH.conv3x3_64(x.permute(0, 3, 1, 2), w)
+    ref = FC.pool_relu_floor64(conv, 4, 3)
+    reach = FH.conv_reach(FH.bad_pixels(x), 4, 3)
+    assert not bool(torch.isfinite(ref).all())
+    assert FH.poison_ratio(ref, ref, reach, 1e-5, 1e-5) <= 1.0
+    inside = ref.clone()
+    inside[reach.expand_as(ref)] = math.nan  # every reached output NaN: allowed
+    assert FH.poison_ratio(inside, ref, reach, 1e-5, 1e-5) <= 1.0
+    c = conv.reshape(B, C, 2, 4, 2, 3).permute(0, 1, 2, 4, 3, 5).reshape(B, C, 2, 2, 12)
+    m = torch.full(c.shape[:-1], -math.inf, dtype=torch.float64)
+    for i in range(12):
+        m = torch.fmax(m, c[..., i])
+    dropped = torch.fmax(m, torch.zeros_like(m))
+    assert FH.poison_ratio(dropped, ref, reach, 1e-5, 1e-5) == math.inf
+    outside = ref.clone()
+    outside[~reach.expand_as(ref)] = math.nan
+    assert FH.poison_ratio(outside, ref, reach, 1e-5, 1e-5) == math.inf
+    wino = FH.conv_reach(FH.bad_pixels(x), 4, 3, winograd=True)
+    assert bool((wino | ~reach).all()), "the Winograd reach holds the direct convolution's"

@@ -662,3 +662,16 @@ def test_shape_fuzz_of_pp_gemm():
     here = os.path.dirname(os.path.abspath(__file__))
     r = subprocess.run([sys.executable, os.path.join(here, "fuzz_gemm.py"), "10"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "GEMM FUZZ OK" in r.stdout, (r.stdout[-800:], r.stderr[-800:])
+
+
+def test_shape_fuzz_of_convolutions_and_pooling():
+    """tests/fuzz_conv.py for a few seconds: pp_conv_gemm (3x3 and deconvolution, three precisions, the four kernels behind it), split-K + sum-pool,
+    the bf16 fused conv + pool and deconvolution + head, pooling, im2col and LayerNorm against fp64, outputs between canaries, the NaN contract of
+    the pooling entries."""
+    import os
+    import subprocess
+    import sys
+
+    here = os.path.dirname(os.path.abspath(__file__))
+    r = subprocess.run([sys.executable, os.path.join(here, "fuzz_conv.py"), "10"], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "CONV FUZZ OK" in r.stdout, (r.stdout[-1500:], r.stderr[-800:])

@@ -335,6 +335,40 @@ def test_overflowing_activations_raise_instead_of_decoding_index_zero():
 
 
 @gpu
+def test_overflowing_tower_raises_instead_of_pooling_nan_to_zero():
+    """Only a scalar tower leaves the domain: one channel of the probability tower's first convolution has a bias of 3e5, so its stage-0 output
+    is beyond 65504 and stage 1's split products are NaN. The pooling max and ReLU of every later stage must carry that NaN on (a plain fmaxf
+    returns the other operand and would turn a window of NaN into a clean 0, the crop then scoring a plausible, wrong probability): the affected
+    tower's scalars come out NaN, the other three towers and the keypoints stay finite, and `test_step` raises. Both tower schedules: the
+    headline's (Winograd stage 0, split-K later stages) at 20 crops, the small-batch plan's at 3."""
+    from probpose_code_amd import ProbPoseEngine, apis
+    from probpose_code_amd import synthetic as S
+
+    torch.set_num_threads(min(16, os.cpu_count()))
+    clean = S.synthetic_state_dict("small", seed=0, logit_scale=2.0)
+    sd = {k: v.clone() for k, v in clean.items()}
+    sd["head.probability_layers.0.bias"][5] = 3.0e5
+    for B in (20, 3):
+        crops = S.synthetic_crops(B, seed=7)
+        out = ProbPoseEngine(sd, 12, precision="f16x3").forward(crops.cuda(), True, S.COCO_FLIP_INDICES)
+        ref = ProbPoseEngine(clean, 12, precision="f16x3").forward(crops.cuda(), True, S.COCO_FLIP_INDICES)
+        torch.cuda.synchronize()
+        sc, sc_ref = out["scalars"].cpu(), ref["scalars"].cpu()
+        print(f"[trained-stats] tower bias of 3e5, B {B}: probability tower {int(torch.isnan(sc[0]).sum())} NaN of {sc[0].numel()}, "
+              f"largest finite |prob| deviation {float((sc[0] - sc_ref[0]).nan_to_num(0.0).abs().max()):.3g}")
+        assert torch.isnan(sc[0]).all(), "the overflowing tower's NaN was pooled away into finite scores"
+        assert torch.isfinite(sc[1:]).all() and torch.equal(sc[1:], sc_ref[1:]), "a tower that stays in the domain changed"
+        assert torch.isfinite(out["keypoints"]).all() and torch.equal(out["keypoints"].cpu(), ref["keypoints"].cpu())
+    cfg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "configs", "td-pm_ProbPose-small_mi355x_coco-256x192.py")
+    model = apis.init_model(cfg, {"state_dict": sd}, device="cuda:0")
+    B = 20
+    center, scale = S.whole_image_bbox_meta(B)
+    batch = apis.pack_crops(S.synthetic_crops(B, seed=7), center, scale, model.dataset_meta)
+    with pytest.raises(FloatingPointError, match="numeric domain"):
+        model.test_step(batch)
+
+
+@gpu
 def test_domain_report_names_the_limit():
     """`domain_report`: the one-off diagnostic for a new checkpoint - the trained-like weights are inside the domain, a residual channel of 3e5 is not,
     a row offset of 400 standard deviations asks for the unfolded plan."""
