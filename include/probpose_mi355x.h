@@ -440,7 +440,7 @@ int pp_conv3x3_maxpool_relu(int prec, const void* act_nhwc, const void* weight, 
  * i.e. pp_attention followed by pp_proj_mlp_residual_layernorm with neither the attention output nor anything between
  * the two residual adds leaving the CU. qkv_in (M, 3E) bf16 row-major [q | k | v] as the qkv Linear emits it; rows
  * [s * seq_len, (s + 1) * seq_len) are sequence s. Built for E = 384, heads * 32 = E, seq_len = 192 (256x192 input);
- * other shapes take the separate entry points. qkv_out must not alias qkv_in. */
+ * other shapes take the separate entry points. qkv_out must not alias qkv_in; scale must be positive and finite. */
 int pp_vit_layer(const void* qkv_in, int seq_len, int heads, float scale, const void* wp, const float* bp,
                  const float* residual, const float* gamma2, const float* beta2, const void* w1, const float* b1,
                  const void* w2, const float* b2, float* x_out, const float* gamma, const float* beta, float eps,

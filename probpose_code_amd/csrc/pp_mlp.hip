@@ -23,7 +23,7 @@
 //   * the 96 x 384 output accumulators start from residual + b2 and end in the LayerNorm epilogue (row statistics in
 //     registers, one LDS exchange between the column quarters).
 // LDS: 72 KiB h + 24 KiB G + 64 KiB ring = 160 KiB, the whole CU.
-// GELU uses a clamped odd polynomial for erf (|error| < 1.8e-4, a factor 60 under bf16 resolution): libdevice erff costs
+// GELU uses a clamped odd polynomial for erf (|error| < 1.8e-4 + 1e-6 |x|, a factor 60 under bf16 resolution): libdevice erff costs
 // as many VALU cycles as the MFMAs of the whole block.
 #include "pp_common.h"
 
@@ -100,9 +100,10 @@ __device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, f32x4 c) {
 }
 
 // GELU(x) = 0.5 x (1 + erf(x / sqrt 2)) = x (0.5 + t W(t^2)), t = clamp(x, -4.2, 4.2), where t W(t^2) is a degree-15 odd
-// minimax polynomial for 0.5 erf(t / sqrt 2), constrained to reach exactly 0.5 at |t| = 4.2 so that the function
-// saturates to x and to 0 outside. Absolute error < 1.8e-4 for every x, relative error < 6.2e-5 for x > 0.05 - a factor
-// 60 under bf16 resolution, which is what the result is rounded to. Twelve plain fp32 instructions and no
+// minimax polynomial for 0.5 erf(t / sqrt 2), constrained to reach 0.5 at |t| = 4.2 so that the function saturates to x
+// and to 0 outside (in fp32 it reaches 0.5 + 8e-7: x (1 + 8e-7) and -8e-7 x out there). Absolute error < 1.8e-4 + 1e-6 |x|
+// (tests/test_mlp_references.py), relative error < 6.2e-5 for x > 0.05 - a factor 60 under bf16 resolution, which is what
+// the result is rounded to. Twelve plain fp32 instructions and no
 // transcendental. Plain (unpacked) on purpose - this file is built with -fno-slp-vectorize: the GELU of the previous
 // chunk is issued between the MFMAs of the current one, and beside MFMAs a v_pk_fma_f32 costs about 22 cycles more
 // than the two v_fma_f32 it replaces.
@@ -1083,6 +1084,9 @@ extern "C" int pp_vit_layer(const void* qkv_in, int seq_len, int heads, float sc
     const bool qkv = wqkv != nullptr;
     PP_REQUIRE(qkv ? (bqkv && qkv_out) : (h_out != nullptr), PP_ERR_INVALID_ARG, "pp_vit_layer: needs h_out, or wqkv + bqkv + qkv_out");
     PP_REQUIRE(qkv_out != qkv_in, PP_ERR_INVALID_ARG, "pp_vit_layer: qkv_out must not alias qkv_in (other workgroups still read it)");
+    // the softmax takes the row maximum of the RAW logits and scales it afterwards (mb = max * scale log2 e): that is the maximum of
+    // the scaled logits only for a positive scale
+    PP_REQUIRE(scale > 0.0f && __builtin_isfinite(scale), PP_ERR_INVALID_ARG, "pp_vit_layer: scale must be positive and finite");
     PP_REQUIRE(E == mlp::E && heads * 32 == E && seq_len == 192, PP_ERR_UNSUPPORTED,
                "pp_vit_layer: built for ViT-S at 256x192 (embed dim 384, 12 heads x 32, 192 tokens)");
     PP_REQUIRE(M > 0 && M % seq_len == 0 && F > 0 && F % mlp::CHUNK == 0, PP_ERR_UNSUPPORTED,

@@ -675,3 +675,15 @@ def test_shape_fuzz_of_convolutions_and_pooling():
     here = os.path.dirname(os.path.abspath(__file__))
     r = subprocess.run([sys.executable, os.path.join(here, "fuzz_conv.py"), "10"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "CONV FUZZ OK" in r.stdout, (r.stdout[-1500:], r.stderr[-800:])
+
+
+def test_shape_fuzz_of_the_bf16_layer_kernel():
+    """tests/fuzz_mlp.py for a few seconds: the five instantiations of the fused bf16 ViT-layer kernel (pp_mlp.hip) on grids across the rotation
+    and remap thresholds, ragged M, F from one chunk up, poison and refusals, against fp64 under a derived bf16 error bound, outputs between canaries."""
+    import os
+    import subprocess
+    import sys
+
+    here = os.path.dirname(os.path.abspath(__file__))
+    r = subprocess.run([sys.executable, os.path.join(here, "fuzz_mlp.py"), "10"], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "MLP FUZZ OK" in r.stdout, (r.stdout[-1500:], r.stderr[-800:])
