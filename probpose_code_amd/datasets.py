@@ -9,6 +9,7 @@ slice of the ``xtcocotools.COCO`` index [3P] those methods call. Not built (``No
 """
 import copy
 import json
+import os
 import os.path as osp
 from collections import defaultdict
 from typing import Dict, List, Optional, Sequence
@@ -65,6 +66,9 @@ class COCO:
         if annotation_file is not None:
             with open(annotation_file) as f:
                 self.dataset = json.load(f)
+        self.createIndex()
+
+    def createIndex(self) -> None:
         self.anns, self.imgs, self.cats = {}, {}, {}
         self.imgToAnns: Dict[int, list] = defaultdict(list)
         for ann in self.dataset.get("annotations", []):
@@ -99,6 +103,36 @@ class COCO:
 
     def loadCats(self, ids=()) -> List[dict]:
         return [self.cats[i] for i in self._list(ids)]
+
+    def loadRes(self, res) -> "COCO":
+        """Keypoint results -> an index over this set's images whose annotations are the results: the keypoint branch of
+        ``xtcocotools.coco.COCO.loadRes`` [3P]. ``res``: a results file (``CocoMetric``'s ``{prefix}.keypoints.json``) or a
+        list of result dicts. Every result gets ``id`` = its position + 1 and ``area`` / ``bbox`` from the extent of its
+        keypoints (a ``bbox`` it carries is replaced); the categories are this set's. The caller's dicts are left as they
+        are (xtcocotools writes into them). Refused: results on an image outside this set (AssertionError, as
+        xtcocotools), an empty list (ValueError; xtcocotools fails with an IndexError), results without keypoints
+        (NotImplementedError)."""
+        if isinstance(res, (str, bytes, os.PathLike)):
+            with open(res) as f:
+                res = json.load(f)
+        assert isinstance(res, list), "results in not an array of objects"
+        if not res:
+            raise ValueError("COCO.loadRes: no results (an empty result list)")
+        img_ids = set(self.imgs)
+        assert all(r["image_id"] in img_ids for r in res), "Results do not correspond to current coco set"
+        anns = []
+        for i, r in enumerate(res):
+            if "keypoints" not in r:
+                raise NotImplementedError(f"COCO.loadRes: result {i} has no keypoints (only keypoint results are supported)")
+            kp = np.asarray(r["keypoints"], np.float64)
+            x, y = kp[0::3], kp[1::3]
+            x0, x1, y0, y1 = float(x.min()), float(x.max()), float(y.min()), float(y.max())
+            anns.append(dict(r, id=i + 1, area=(x1 - x0) * (y1 - y0), bbox=[x0, y0, x1 - x0, y1 - y0]))
+        out = COCO()
+        out.dataset = dict(images=list(self.dataset.get("images", [])), categories=copy.deepcopy(self.dataset.get("categories", [])),
+                           annotations=anns)
+        out.createIndex()
+        return out
 
 
 class BaseCocoStyleDataset:

@@ -6,6 +6,8 @@ most ``maxDets`` = 20), launches ``pp_extended_oks`` and returns the (levels, de
 on the device. The matching / accumulation that follows in the reference (``evaluateImg``, ``accumulate``) consumes
 exactly this tensor.
 """
+import json
+import os
 from typing import Optional, Sequence
 
 import numpy as np
@@ -453,6 +455,17 @@ def soft_oks_nms(kpts_db, thr, max_dets=20, sigmas=None, vis_thr=None, score_per
     return np.array(keep, dtype=np.intp)
 
 
+def _json_default(obj):
+    """mmengine's json handler ``set_default`` [3P]: numpy arrays as lists, numpy scalars as Python numbers."""
+    if isinstance(obj, (set, range)):
+        return list(obj)
+    if isinstance(obj, np.ndarray):
+        return obj.tolist()
+    if isinstance(obj, np.generic):
+        return obj.item()
+    raise TypeError(f"{type(obj)} is unsupported for json dump")
+
+
 def instance_score(bbox_score, keypoint_scores, keypoint_probs, score_mode="bbox_keypoint", score_thresh_type="score",
                    keypoint_score_thr=0.2):
     """Detection score of one instance (coco_metric.py:549-572)."""
@@ -464,8 +477,10 @@ def instance_score(bbox_score, keypoint_scores, keypoint_probs, score_mode="bbox
     if score_mode == "bbox_rle":
         return float(bbox_score + np.mean(keypoint_scores) + np.max(keypoint_scores))
     gate = keypoint_scores if score_thresh_type == "score" else np.asarray(keypoint_probs)
-    sel = gate > keypoint_score_thr
-    mean_kpt = float(np.sum(keypoint_scores[sel])) / int(sel.sum()) if sel.any() else 0
+    sel = keypoint_scores[gate > keypoint_score_thr]
+    # the reference's running sum, left to right in the scores' own dtype and divided in it (np.sum would pair the terms):
+    # the score is the reference's to the last bit, as the results file needs
+    mean_kpt = np.cumsum(sel)[-1] / len(sel) if len(sel) else 0
     return bbox_score * mean_kpt
 
 
@@ -489,17 +504,27 @@ class CocoMetric:
     "_NoBrd"). ``prob_thr`` (the presence-probability threshold Ex-OKS binarises with): the reference takes the
     accuracy-maximising threshold of its classification analysis (coco_metric.py:981-1003); here it is
     ``best_threshold`` over the instances that have a ground truth of the same (image, id), or the value passed in.
-    Not provided: the json dumps, converters, and the analysis printouts (calibration, OKS-to-IoU, vector fields)."""
+    ``outfile_prefix``: the kept instances are also written to ``{outfile_prefix}.keypoints.json`` (``results2json``),
+    which ``datasets.COCO.loadRes`` reads back; ``format_only``: write that file and return ``{}`` - no ground truth
+    needed, the evaluator is not run. Not provided: the ground truth built from the samples (``gt_to_coco_json``),
+    converters, and the analysis printouts (calibration, OKS-to-IoU, vector fields)."""
 
-    def __init__(self, gt_annotations, use_area=True, iou_type="keypoints", score_mode="bbox_keypoint", score_thresh_type="score",
+    def __init__(self, gt_annotations=None, use_area=True, iou_type="keypoints", score_mode="bbox_keypoint", score_thresh_type="score",
                  keypoint_score_thr=0.2, nms_mode="oks_nms", nms_thr=0.9, prefix=None, extended=(False,), match_by_bbox=(False,),
-                 ignore_border_points=(False,), ignore_stats=(), padding=1.25, prob_thr=None, sigmas=None, device="cuda"):
+                 ignore_border_points=(False,), ignore_stats=(), padding=1.25, prob_thr=None, sigmas=None, device="cuda",
+                 outfile_prefix=None, format_only=False):
         if score_mode not in ("bbox", "bbox_keypoint", "bbox_rle", "keypoint"):
             raise ValueError(f"`score_mode` should be one of 'bbox', 'bbox_keypoint', 'bbox_rle', but got {score_mode}")
         if score_thresh_type not in ("score", "prob"):
             raise ValueError("'score_thresh_type' should be one of 'score' or 'prob'")
         if nms_mode not in ("oks_nms", "soft_oks_nms", "none"):
             raise ValueError("`nms_mode` should be one of 'oks_nms', 'soft_oks_nms', " f"'none', but got {nms_mode}")
+        if format_only:  # coco_metric.py:156-162
+            assert outfile_prefix is not None, ("`outfile_prefix` can not be None when `format_only` is True, otherwise the result "
+                                                "file will be saved to a temp directory which will be cleaned up in the end.")
+        elif gt_annotations is None:
+            raise ValueError("CocoMetric needs the ground truth (annotation dicts or a COCO index) unless format_only=True")
+        self.format_only, self.outfile_prefix = format_only, outfile_prefix
         extended, match_by_bbox, ignore_border_points = list(extended), list(match_by_bbox), list(ignore_border_points)
         n = max(len(extended), len(match_by_bbox))
         if len(extended) == 1 and n > 1:
@@ -533,8 +558,10 @@ class CocoMetric:
             pred = dict(id=s["id"], img_id=s["img_id"], category_id=s.get("category_id", 1), keypoints=kp, keypoint_scores=sc,
                         keypoints_visible=np.asarray(pi.get("keypoints_visible", sc)), keypoint_probs=np.asarray(pi.get("keypoints_probs", sc)))
             if "bboxes" in pi:
-                b = np.asarray(pi["bboxes"], np.float64).reshape(-1, 4)
-                pred["bbox"] = np.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], 1)  # bbox_xyxy2xywh
+                b = np.array(pi["bboxes"]).reshape(-1, 4)  # bbox_xyxy2xywh, in the boxes' dtype (the results file shows it)
+                b[:, 2] = b[:, 2] - b[:, 0]
+                b[:, 3] = b[:, 3] - b[:, 1]
+                pred["bbox"] = b
             gi = s.get("gt_instances", {})
             if "bbox_scores" in pi:
                 pred["bbox_scores"] = np.asarray(pi["bbox_scores"])
@@ -581,20 +608,56 @@ class CocoMetric:
             return self.gt.loadAnns(self.gt.getAnnIds(imgIds=self.gt.getImgIds()))
         return list(self.gt)
 
+    def results2json(self, valid, outfile_prefix=None):
+        """results2json (coco_metric.py:630-669): one entry per kept instance, images in ``valid`` order - ``image_id``,
+        ``category_id``, ``keypoints`` (K x 3 flat, the third value the presence probability), ``score``, ``bbox`` (xywh)
+        when the instance has one, ``visibility``. With a prefix, written to ``{outfile_prefix}.keypoints.json`` as
+        mmengine's ``dump(..., sort_keys=True, indent=4)`` writes it. Returns the entries."""
+        K = len(self.sigmas)
+        out = []
+        for persons in valid.values():
+            kps = np.array([p["keypoints"] for p in persons]).reshape(-1, K * 3)
+            for p, kp in zip(persons, kps):
+                r = dict(image_id=p["img_id"], category_id=p["category_id"], keypoints=kp.tolist(), score=float(p["score"]))
+                if "bbox" in p:
+                    r["bbox"] = p["bbox"].tolist()
+                if "keypoints_visible" in p:
+                    r["visibility"] = p["keypoints_visible"].tolist()
+                out.append(r)
+        if outfile_prefix is not None:
+            path = f"{outfile_prefix}.keypoints.json"
+            if os.path.dirname(path):
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+            with open(path, "w", encoding="utf-8") as f:
+                f.write(json.dumps(out, sort_keys=True, indent=4, default=_json_default))
+        return out
+
+    def _gt_index(self, results):
+        """The ground truth as a ``datasets.COCO`` index, whose ``loadRes`` reads the results. A plain annotation list names no
+        image set: its images are those of its annotations and of the results."""
+        from .datasets import COCO
+
+        if isinstance(self.gt, COCO):
+            return self.gt
+        gts = self._gt_list()
+        if hasattr(self.gt, "getImgIds"):
+            img_ids = self.gt.getImgIds()
+        else:
+            img_ids = dict.fromkeys([g["image_id"] for g in gts] + [r["image_id"] for r in results])
+        coco = COCO()
+        coco.dataset = dict(images=[dict(id=i) for i in img_ids], annotations=gts,
+                            categories=[dict(id=c) for c in dict.fromkeys(g.get("category_id", 1) for g in gts)])
+        coco.createIndex()
+        return coco
+
     def compute_metrics(self):
         valid = self._instances()
+        results = self.results2json(valid, self.outfile_prefix)
+        if self.format_only:  # coco_metric.py:584-586
+            return {}
         gts = self._gt_list()
-        dts = []
-        # results2json (:630-669) + COCO.loadRes of the un-vendored xtcocotools / pycocotools, whose keypoint branch sets id,
-        # area and bbox of every result from the extent of its keypoints
-        for img_id, persons in valid.items():
-            for p in persons:
-                kp = np.asarray(p["keypoints"], np.float64)
-                x, y = kp[:, 0], kp[:, 1]
-                x0, x1, y0, y1 = float(x.min()), float(x.max()), float(y.min()), float(y.max())
-                d = dict(image_id=p["img_id"], category_id=p["category_id"], keypoints=kp.flatten().tolist(), score=float(p["score"]),
-                         id=len(dts) + 1, area=(x1 - x0) * (y1 - y0), bbox=[x0, y0, x1 - x0, y1 - y0])
-                dts.append(d)
+        # what the reference evaluates is the results file read back by COCO.loadRes: id, area and bbox from the keypoints
+        dts = self._gt_index(results).loadRes(results).dataset["annotations"] if results else []
         out = {}
         if self.prob_thr is None:  # the probability threshold of the classification analysis (:949-1003)
             by_key = {(g["image_id"], g["id"]): g for g in gts if not np.allclose(np.array(g["keypoints"]), 0)}

@@ -77,7 +77,8 @@ def _coco_gt(ann_file: str) -> list:
 def build_metric(cfg, ann_file: Optional[str] = None, device: str = "cuda"):
     """A ``CocoMetric`` config -> ``evaluation.CocoMetric``: ``ann_file`` loaded through the COCO index (its annotation list is
     the ground truth; when the config has none, the paired dataset's file, as the reference's CocoMetric takes it from the
-    MessageHub, coco_metric.py:196-216), every other key passed on unchanged."""
+    MessageHub, coco_metric.py:196-216), every other key passed on unchanged (``outfile_prefix`` / ``format_only`` among
+    them). A ``format_only`` metric needs no annotation file (coco_metric.py:156-167)."""
     from .evaluation import CocoMetric
 
     if not isinstance(cfg, dict):
@@ -86,15 +87,15 @@ def build_metric(cfg, ann_file: Optional[str] = None, device: str = "cuda"):
     kind = cfg.pop("type", "CocoMetric")
     if kind not in ("CocoMetric", "mmpose.CocoMetric"):
         raise NotImplementedError(f"metric type {kind!r}: only CocoMetric is implemented")
-    for k in ("outfile_prefix", "format_only", "collect_device", "pred_converter", "gt_converter"):
+    for k in ("collect_device", "pred_converter", "gt_converter"):
         if cfg.get(k):
             raise NotImplementedError(f"CocoMetric({k}=...) is not supported")
         cfg.pop(k, None)
     path = cfg.pop("ann_file", None) or ann_file
-    if path is None:
+    if path is None and not cfg.get("format_only"):
         raise ValueError("CocoMetric needs an ann_file (in its config or from its dataset)")
     cfg.setdefault("device", device)
-    return CocoMetric(_coco_gt(path), **cfg)
+    return CocoMetric(_coco_gt(path) if path is not None else None, **cfg)
 
 
 @EVALUATORS.register_module(name="MultiDatasetEvaluator", force=True)
