@@ -39,7 +39,11 @@ def main():
     from probpose_code_amd import apis, synthetic
     from probpose_code_amd.structures import merge_data_samples
 
-    ckpt = dict(state_dict=synthetic.synthetic_state_dict("small", seed=0, logit_scale=2.0)) if args.checkpoint == "synthetic" else args.checkpoint
+    ckpt = args.checkpoint
+    if ckpt == "synthetic":  # (the head kind - ProbMapHead with its towers, or the ViTPose baseline's HeatmapHead - from the config)
+        from probpose_code_amd.config import Config
+
+        ckpt = dict(state_dict=synthetic.synthetic_state_dict("small", seed=0, logit_scale=2.0, head=synthetic.head_kind_of(Config.fromfile(args.config))))
     opts = {"model.precision": args.precision} if args.precision else None
     if args.draw_heatmap:
         opts = dict(opts or {}, **{"model.test_cfg.output_heatmaps": True})
@@ -50,7 +54,8 @@ def main():
     results = merge_data_samples(apis.inference_topdown(model, args.img, boxes))
     pi = results.pred_instances
     out = [dict(bbox=pi.bboxes[i].tolist(), keypoints=pi.keypoints[i].tolist(), keypoint_scores=pi.keypoint_scores[i].tolist(),
-                keypoints_probs=pi.keypoints_probs[i].tolist(), keypoints_visible=pi.keypoints_visible[i].tolist())
+                keypoints_visible=pi.keypoints_visible[i].tolist(),
+                **(dict(keypoints_probs=pi.keypoints_probs[i].tolist()) if "keypoints_probs" in pi else {}))  # (HeatmapHead gives no probabilities)
            for i in range(len(pi.keypoints))]
     text = json.dumps(out, indent=1)
     if args.out_file:

@@ -569,6 +569,24 @@ int pp_probmap_decode_flags(const float* maps, const float* maps_flip, const int
                             float normalize, float* avg_out, float* conv_out, float* locs, double* keypoints, float* scores,
                             int flags, void* stream);
 
+/* UDP heatmap decode with DARK refinement (mmpose/codecs/udp_heatmap.py:146-196, heatmap_type "gaussian": the ViTPose baseline's
+ * codec), csrc/pp_udp_decode.hip; added under version 4, purely additive. maps / maps_flip / flip_indices as pp_probmap_decode_flags
+ * takes them - fp32 maps (B, K, H*W) of the final 1x1 conv, row-major or (PP_DECODE_PHASED; even H and W) in the phase-separated
+ * layout of pp_deconv_head, the flipped pass optional, PP_DECODE_SHIFT_HEATMAP honoured; no other flag. The average
+ * (a + flip_back(b)) * 0.5 is taken in fp32; `scores` (B, K) is its maximum and `locs` (B, K, 2) the first row-major index of that
+ * maximum as (x, y) - (-1, -1) where the maximum is <= 0 - both bit-equal to numpy on the same map. The map is then blurred with
+ * the separable Gaussian cv2.GaussianBlur(ks, sigma 0) uses (sigma = 0.3 ((ks - 1) / 2 - 1) + 0.8, taps normalised in double and
+ * rounded to fp32, fp32 sums, zero border), rescaled to its original maximum, clipped to [1e-3, 50] and logged; one Newton step
+ * from the seven-point fp32 derivative / Hessian, (H + eps32 I)^+ in fp64, the result rounded to fp32 and rescaled:
+ * `keypoints` (B, K, 2) f64 = loc / (W - 1, H - 1) * (in_w, in_h). A map with maximum <= 0 takes three of its seven points from the
+ * map of keypoint k - 1 (K - 1 for k = 0) of the same sample, as the reference's flat index does. blur_kernel_size odd, 1 .. 19;
+ * H, W >= 2, H * W <= 12288 and the two LDS images ((W + ks) H + (H + ks - 1) W floats) within 160 KiB, else PP_ERR_UNSUPPORTED.
+ * avg_out (optional) takes the averaged maps, row-major (B, K, H, W). A map with a non-finite value (or, for a map with maximum
+ * <= 0, such a neighbour) yields NaN locs / keypoints / scores. */
+int pp_udp_heatmap_decode(const float* maps, const float* maps_flip, const int32_t* flip_indices, int B, int K, int H, int W,
+                          double in_w, double in_h, int blur_kernel_size, float* avg_out, float* locs, double* keypoints,
+                          float* scores, int flags, void* stream);
+
 /* Split-K form of the towers' 3x3 convolution for stages with few output pixels: the contraction is cut into ksplit slices -
  * 1, 3 or 9: whole taps (any precision); any other count with Cin % (32 ksplit) == 0: channel ranges [s Cin / ksplit, ...) of all nine
  * taps (PP_PREC_F16X3 on the wide-tile kernel only, needs >= 192 tiles of 256 x 192; pp_conv3x3_splitk_slices returns such a

@@ -84,6 +84,8 @@ SIGNATURES = {
         c_int,
         [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_double, c_double, c_float, c_float, _P, _P, _P, _P, _P, c_int, _P],
     ),
+    "pp_udp_heatmap_decode": (
+        c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_double, c_double, c_int, _P, _P, _P, _P, c_int, _P]),
     "pp_deconv_head": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "pp_deconv_head_split": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "pp_gemm": (

@@ -207,3 +207,104 @@ class ProbMap(BaseKeypointCodec):
         hm = torch.from_numpy(np.ascontiguousarray(encoded, dtype=np.float32)).cuda()[None]
         kpts, scores = self.batch_decode(hm)
         return kpts[0], scores[0]
+
+
+@register(KEYPOINT_CODECS, reference_name="UDPHeatmap", mi355x_name="UDPHeatmapMI355X")
+class UDPHeatmap(BaseKeypointCodec):
+    """Unbiased-data-processing heatmap codec with DARK refinement (reference: ``mmpose/codecs/udp_heatmap.py:14-196``), the codec
+    of the ViTPose baseline; decode on the GPU (``pp_udp_heatmap_decode``: maximum of the map, Gaussian modulation, one Newton
+    step on the log map, rescale - for a whole batch in one launch, optionally together with the flip-test average).
+
+    Args are the reference's (udp_heatmap.py:68-88): ``input_size`` [w, h], ``heatmap_size`` [W, H], ``heatmap_type``
+    ("gaussian" only: "combined" belongs to heads with offset maps), ``sigma``, ``radius_factor``, ``blur_kernel_size``
+    (odd, at most 19; 11 for sigma 2, 17 for sigma 3)."""
+
+    label_mapping_table = dict(keypoint_weights="keypoint_weights")
+    field_mapping_table = dict(heatmaps="heatmaps")
+
+    def __init__(self, input_size: Tuple[int, int], heatmap_size: Tuple[int, int], heatmap_type: str = "gaussian",
+                 sigma: float = 2.0, radius_factor: float = 0.0546875, blur_kernel_size: int = 11) -> None:
+        super().__init__()
+        self.input_size = input_size
+        self.heatmap_size = heatmap_size
+        self.sigma = sigma
+        self.radius_factor = radius_factor
+        self.heatmap_type = heatmap_type
+        self.blur_kernel_size = blur_kernel_size
+        self.scale_factor = ((np.array(input_size) - 1) / (np.array(heatmap_size) - 1)).astype(np.float32)
+        if self.heatmap_type not in {"gaussian", "combined"}:
+            raise ValueError(
+                f"{self.__class__.__name__} got invalid `heatmap_type` value"
+                f"{self.heatmap_type}. Should be one of "
+                '{"gaussian", "combined"}'
+            )
+        if self.heatmap_type == "combined":
+            raise NotImplementedError("UDPHeatmap(heatmap_type='combined') (udp_heatmap.py:170-190: classification + offset maps) has no "
+                                      "MI355X kernel; the ViTPose configs use 'gaussian'")
+        if int(blur_kernel_size) % 2 != 1 or not 1 <= int(blur_kernel_size) <= _lib.PP_MAX_TAPS:
+            raise ValueError(f"blur_kernel_size must be odd and at most {_lib.PP_MAX_TAPS} (pp_udp_heatmap_decode), got {blur_kernel_size}")
+        self._tables: Dict[tuple, torch.Tensor] = {}
+
+    def encode(self, keypoints, keypoints_visible=None) -> dict:
+        raise NotImplementedError(
+            "UDPHeatmap.encode (udp_heatmap.py:90-144) generates training targets and is outside the "
+            "MI355X inference hot path (SURVEY.md 2: 'decode only; encode is training')."
+        )
+
+    def decode_device(self, heatmaps: torch.Tensor, heatmaps_flip: Optional[torch.Tensor] = None,
+                      flip_indices: Optional[Sequence[int]] = None, return_avg: bool = False,
+                      shift_heatmap: bool = False) -> Dict[str, torch.Tensor]:
+        """Batched decode on device tensors; nothing is copied to the host. Arguments and results as ``ProbMap.decode_device``:
+        ``keypoints`` (B, K, 2) f64 input-pixel space, ``scores`` (B, K) f32 (the maximum of the - averaged - map), ``locs``
+        (B, K, 2) f32 (that maximum's pixel; (-1, -1) where it is <= 0), optionally ``heatmaps`` (the averaged maps). A map with a
+        non-finite value gives NaN results."""
+        assert isinstance(heatmaps, torch.Tensor) and heatmaps.dim() == 4, "heatmaps should be a (B, K, H, W) tensor"
+        if not heatmaps.is_cuda:
+            raise RuntimeError("UDPHeatmap.decode_device needs tensors on the MI355X; there is no CPU fallback")
+        B, K, H, W = heatmaps.shape
+        Wc, Hc = self.heatmap_size
+        assert (H, W) == (Hc, Wc), f"heatmap shape {(H, W)} does not match codec heatmap_size {(Hc, Wc)}"
+        dev = heatmaps.device
+        hm = heatmaps.contiguous().float()
+        hmf = fi = None
+        if heatmaps_flip is not None:
+            assert heatmaps_flip.shape == heatmaps.shape
+            assert flip_indices is not None and len(flip_indices) == K
+            hmf = heatmaps_flip.contiguous().float()
+            key = (tuple(int(i) for i in flip_indices), str(dev))
+            if key not in self._tables:
+                self._tables[key] = torch.tensor(key[0], dtype=torch.int32, device=dev)
+            fi = self._tables[key]
+        out = dict(
+            locs=torch.empty((B, K, 2), dtype=torch.float32, device=dev),
+            keypoints=torch.empty((B, K, 2), dtype=torch.float64, device=dev),
+            scores=torch.empty((B, K), dtype=torch.float32, device=dev),
+        )
+        avg = torch.empty_like(hm) if return_avg else None
+        with torch.cuda.device(dev):
+            _lib.call(
+                "pp_udp_heatmap_decode", _lib.ptr(hm), _lib.ptr(hmf), _lib.ptr(fi), B, K, H, W, float(self.input_size[0]),
+                float(self.input_size[1]), int(self.blur_kernel_size), _lib.ptr(avg), _lib.ptr(out["locs"]),
+                _lib.ptr(out["keypoints"]), _lib.ptr(out["scores"]), 4 if (shift_heatmap and hmf is not None) else 0,
+                _lib.stream_ptr(dev),
+            )  # fmt: skip  (flags: PP_DECODE_SHIFT_HEATMAP = 4)
+        if return_avg:
+            out["heatmaps"] = avg
+        return out
+
+    def batch_decode(self, batch_heatmaps: torch.Tensor) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+        """(B, K, H, W) device tensor -> per-sample lists, each element shaped as ``decode`` returns."""
+        out = self.decode_device(batch_heatmaps)
+        kpts = out["keypoints"].cpu().numpy()
+        scores = out["scores"].cpu().numpy()
+        if not (np.isfinite(kpts).all() and np.isfinite(scores).all()):
+            raise FloatingPointError("UDPHeatmap.decode: non-finite keypoints / scores (a heatmap holds a non-finite value)")
+        return [kpts[i][None] for i in range(kpts.shape[0])], [scores[i][None] for i in range(scores.shape[0])]
+
+    def decode(self, encoded: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """udp_heatmap.py:146-196 for one sample: (K, H, W) numpy -> ((1, K, 2) f64, (1, K) f32)."""
+        assert isinstance(encoded, np.ndarray), "heatmaps should be numpy.ndarray"
+        assert encoded.ndim == 3, f"Invalid shape {encoded.shape}"
+        hm = torch.from_numpy(np.ascontiguousarray(encoded, dtype=np.float32)).cuda()[None]
+        kpts, scores = self.batch_decode(hm)
+        return kpts[0], scores[0]

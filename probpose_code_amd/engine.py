@@ -96,7 +96,8 @@ class ProbPoseEngine:
                  patch_padding: int = 2, mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375),
                  bgr_to_rgb: bool = True, temperature: float = 0.5, normalize: Optional[float] = 1.0,
                  input_size: Optional[Sequence[int]] = None, ln_eps: float = 1e-6, precision: str = "f16x3",
-                 device="cuda", plan: Optional[Dict[str, object]] = None):
+                 device="cuda", plan: Optional[Dict[str, object]] = None, head_kind: Optional[str] = None,
+                 blur_kernel_size: int = 11):
         if precision not in PREC:
             raise ValueError(f"precision must be one of {list(PREC)}, got {precision!r}")
         self.device = torch.device(device)
@@ -117,6 +118,15 @@ class ProbPoseEngine:
         self.dtype = _DTYPE[precision]
         self.fmt = _FMT[precision]
         self.w: PackedWeights = pack(state_dict, self.dtype, self.device, split=precision == "f16x3", num_heads=int(num_heads), fold_ln=bool(pl["ln_fold"]))
+        # "probmap": ProbMapHead (heatmap branch + four scalar towers, Sparsemax + OKS decode); "heatmap": HeatmapHead, the ViTPose baseline
+        # (the heatmap branch alone, UDP-DARK decode: pp_udp_heatmap_decode). Derived from the state dict's keys; an explicit value must agree.
+        self.head_kind = self.w.head_kind
+        if head_kind is not None and head_kind != self.head_kind:
+            raise ValueError(f"head_kind={head_kind!r}, but the state dict holds the weights of a {self.head_kind!r} head "
+                             f"({'no ' if self.head_kind == 'heatmap' else ''}scalar-tower keys)")
+        if blur_kernel_size % 2 != 1 or not 1 <= blur_kernel_size <= 2 * _lib.PP_MAX_RADIUS + 1:
+            raise ValueError(f"blur_kernel_size must be odd and at most {2 * _lib.PP_MAX_RADIUS + 1}, got {blur_kernel_size}")
+        self.blur_kernel_size = int(blur_kernel_size)
         self.heads = num_heads
         self.H, self.W = img_size
         self.P, self.pad = patch_size, patch_padding
@@ -136,9 +146,10 @@ class ProbPoseEngine:
         self.temperature = float(temperature)
         self.normalize = normalize
         self.ln_eps = float(ln_eps)
-        taps, radius = oks_kernel_taps(self.K, self.Hh, self.Wh)
-        self.taps = torch.from_numpy(taps).to(self.device)
-        self.radius = torch.from_numpy(radius).to(self.device)
+        if self.head_kind == "probmap":
+            taps, radius = oks_kernel_taps(self.K, self.Hh, self.Wh)
+            self.taps = torch.from_numpy(taps).to(self.device)
+            self.radius = torch.from_numpy(radius).to(self.device)
         self._ws: Dict[tuple, Dict[str, torch.Tensor]] = {}
         self._flip: Dict[tuple, torch.Tensor] = {}
         self._graphs: Dict[tuple, tuple] = {}  # insertion order = least recently used first (see capture / forward_graph)
@@ -246,10 +257,10 @@ class ProbPoseEngine:
         self.pools = ((4, 3), (2, 2), (2, 2))
         hs, ws_ = self.Hp, self.Wp
         self.tower_hw = []
-        for ph, pw_ in self.pools:
+        for ph, pw_ in self.pools if self.head_kind == "probmap" else ():
             self.tower_hw.append((hs, ws_))
             hs, ws_ = hs // ph, ws_ // pw_
-        if (hs, ws_) != (1, 1):
+        if self.head_kind == "probmap" and (hs, ws_) != (1, 1):
             raise ValueError(
                 f"scalar towers reduce the {self.Hp}x{self.Wp} feature map to {hs}x{ws_}; the reference "
                 "reshapes them to (B, 1, K) (probmap_head.py:780-783), which needs 1x1"
@@ -303,7 +314,9 @@ class ProbPoseEngine:
             xs=buf("h", (M, E)) if self._ln_fold_at(M) else None,
             lnst=buf("ln_stats", (M, E // 96, 2), f32) if self._ln_fold_at(M) else None,
             rowst=e(M, 2, dt=f32) if self.ln_fold_fused else None,  # (mean, rstd) per row between pp_proj_ffn_split_folded and pp_qkv_attention_split_folded
-            scalars=e(4, B, self.K, dt=f32), locs=e(B, self.K, 2, dt=f32),
+            # ("heatmap" head: no towers - the four scalar columns of the result record (pp_pack_records) stay zero, written once here)
+            scalars=e(4, B, self.K, dt=f32) if self.head_kind == "probmap" else torch.zeros((4, B, self.K), dtype=f32, device=dev),
+            locs=e(B, self.K, 2, dt=f32),
             keypoints=e(B, self.K, 2, dt=torch.float64), scores=e(B, self.K, dt=f32),
             heatmaps=e(B, self.K, self.Hh, self.Wh, dt=f32),
         )
@@ -715,6 +728,22 @@ class ProbPoseEngine:
             raise ValueError("flip_test needs flip_indices (dataset meta)")
         B = nb // passes
         ws = self._workspace(B, passes, slot)
+        if self.head_kind == "heatmap":
+            # HeatmapHead.predict (heatmap_head.py:215-268) + UDPHeatmap.decode: the heatmap branch alone - no towers, no second stream
+            with torch.cuda.device(self.device):
+                st = _lib.stream_ptr(self.device)
+                logits = self.heatmap_logits(feat_nhwc, nb, ws, st)
+                fi = self._flip_indices(flip_indices) if flip_test else None
+                lf = logits[B:] if flip_test else None
+                flags = (2 if self._logits_phased else 0) | (4 if (shift_heatmap and flip_test) else 0)  # PP_DECODE_PHASED | _SHIFT_HEATMAP
+                self._call("head_decode", "pp_udp_heatmap_decode", logits.data_ptr(), _lib.ptr(lf), _lib.ptr(fi), B, self.K, self.Hh, self.Wh,
+                           float(self.input_size[0]), float(self.input_size[1]), self.blur_kernel_size,
+                           ws["heatmaps"].data_ptr() if return_heatmaps else None, ws["locs"].data_ptr(), ws["keypoints"].data_ptr(),
+                           ws["scores"].data_ptr(), flags, st)
+            out = dict(keypoints=ws["keypoints"], scores=ws["scores"], locs=ws["locs"], scalars=ws["scalars"])  # (scalars: zeros, see _workspace)
+            if return_heatmaps:
+                out["heatmaps"] = ws["heatmaps"]
+            return out
         # Small batches: the heatmap branch (two deconvolutions, 1x1 conv, decode) and the four scalar towers read the same features and nothing of
         # each other - none of their launches fills the chip at these sizes, so the towers run on a second stream beside the heatmap branch
         # (fork / join by events: inside a capture they become two branches of the graph). B = 1: ~0.12 ms of the step.

@@ -356,6 +356,140 @@ class ProbMapHead(nn.Module):
         raise NotImplementedError("training (probmap_head.py:806-) is outside the MI355X inference hot path")
 
 
+@register(MODELS, reference_name="HeatmapHead", mi355x_name="HeatmapHeadMI355X")
+class HeatmapHead(nn.Module):
+    """heatmap_head.py:22-370, inference side: the head of the ViTPose baseline - ProbMapHead's heatmap branch without Sparsemax and
+    without the scalar towers (deconvolutions + BN + ReLU, a 1x1 conv), decoded by the ``UDPHeatmap`` codec. Constructor
+    arguments are the reference's; ``loss`` is accepted and ignored (training is out of scope). What the kernels do not cover is
+    refused: deconvolution kernels 3 / 2, intermediate conv layers, a final layer that is not the 1x1 conv (the ``-simple``
+    ViTPose variants, whose head is an upsample + 3x3 conv), no deconvolution at all."""
+
+    _version = 2
+
+    def __init__(self, in_channels: Union[int, Sequence[int]], out_channels: int,
+                 deconv_out_channels: Optional[Sequence[int]] = (256, 256, 256),
+                 deconv_kernel_sizes: Optional[Sequence[int]] = (4, 4, 4),
+                 conv_out_channels: Optional[Sequence[int]] = None, conv_kernel_sizes: Optional[Sequence[int]] = None,
+                 final_layer: dict = dict(kernel_size=1), loss=None, decoder=None, init_cfg=None):
+        super().__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.decoder = KEYPOINT_CODECS.build(decoder) if decoder is not None else None
+        if not deconv_out_channels:
+            raise NotImplementedError("HeatmapHead on MI355X needs at least one deconv layer (ViTPose's classic head has two; the "
+                                      "'-simple' variants upsample instead and are not implemented)")
+        if deconv_kernel_sizes is None or len(deconv_out_channels) != len(deconv_kernel_sizes):
+            raise ValueError(
+                '"deconv_out_channels" and "deconv_kernel_sizes" should be integer sequences with the same '
+                f"length. Got mismatched lengths {deconv_out_channels} and {deconv_kernel_sizes}"
+            )
+        layers, cin = [], in_channels
+        for cout, ks in zip(deconv_out_channels, deconv_kernel_sizes):
+            if ks not in (4, 3, 2):
+                raise ValueError(f"Unsupported kernel size {ks} fordeconvlutional layers in {self.__class__.__name__}")
+            if ks != 4:
+                raise NotImplementedError("the MI355X deconv kernel implements kernel 4 / stride 2 / pad 1 (the ViTPose config)")
+            layers += [nn.ConvTranspose2d(cin, cout, 4, stride=2, padding=1, output_padding=0, bias=False),
+                       nn.BatchNorm2d(cout), nn.ReLU(inplace=True)]
+            cin = cout
+        self.deconv_layers = nn.Sequential(*layers)
+        if conv_out_channels:
+            raise NotImplementedError("intermediate conv layers (conv_out_channels) have no MI355X kernel; the ViTPose head has none")
+        self.conv_layers = nn.Identity()
+        fl = dict(final_layer) if final_layer is not None else None
+        if fl is None or fl.get("kernel_size", 1) != 1 or fl.get("padding", 0) != 0 or fl.get("stride", 1) != 1:
+            raise NotImplementedError("final_layer must be the plain 1x1 conv of the ViTPose config (the '-simple' variants end in a "
+                                      "3x3 conv behind an upsample: not implemented)")
+        self.final_layer = nn.Conv2d(cin, out_channels, 1)
+        self._register_load_state_dict_pre_hook(self._load_state_dict_pre_hook)
+        self._owner = None
+        self.init_weights()
+
+    def init_weights(self):
+        """default_init_cfg (heatmap_head.py:127-134): Normal(std=0.001) convs, BN weight 1."""
+        for m in self.modules():
+            if isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):
+                nn.init.normal_(m.weight, std=0.001)
+                if m.bias is not None:
+                    nn.init.zeros_(m.bias)
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.ones_(m.weight)
+
+    def _load_state_dict_pre_hook(self, state_dict, prefix, local_meta, *args, **kwargs):
+        """heatmap_head.py:305-360: checkpoints of ``TopdownHeatmapSimpleHead`` (before MMPose 1.0) keep intermediate conv layers
+        and the final layer in one ``final_layer`` Sequential. Without intermediate conv layers - the only case built here - their
+        keys are ``final_layer.weight / .bias`` already and pass through; ``final_layer.n.*`` belongs to a head with intermediate
+        conv layers, for which the reference's hook asserts too (``isinstance(self.conv_layers, nn.Sequential)``)."""
+        version = local_meta.get("version", None)
+        if version and version >= self._version:
+            return
+        for _k in list(state_dict.keys()):
+            if not _k.startswith(prefix):
+                continue
+            k_parts = _k[len(prefix):].split(".")
+            if k_parts[0] == "final_layer" and len(k_parts) == 3:
+                assert False, ("old-style key '" + _k + "' (final_layer.n.*) belongs to a head with intermediate conv "
+                               "layers; this head has none")
+
+    @property
+    def _engine(self) -> ProbPoseEngine:
+        if self._owner is None:
+            raise RuntimeError("HeatmapHead (MI355X) must be built inside a TopdownPoseEstimator: "
+                               "the HIP engine is owned by the estimator")
+        return self._owner().engine
+
+    _to_nhwc = ProbMapHead._to_nhwc
+    decode = ProbMapHead.decode  # base_head.py:33-86 with the codec's batched branch
+
+    def forward(self, feats: Tuple[Tensor]) -> Tensor:
+        """heatmap_head.py:198-213 -> heatmaps (B, K, H, W)."""
+        out = self._engine.run_head(self._to_nhwc(feats), flip_test=False, return_heatmaps=True)
+        return out["heatmaps"].clone()
+
+    def predict(self, feats, batch_data_samples, test_cfg: dict = {}):
+        """heatmap_head.py:215-268. ``feats`` is ``[feats, feats_flip]`` under flip_test."""
+        flip = bool(test_cfg.get("flip_test", False))
+        if flip:
+            assert isinstance(feats, list) and len(feats) == 2
+            if test_cfg.get("flip_mode", "heatmap") != "heatmap":
+                raise NotImplementedError("MI355X head implements flip_mode='heatmap' (models/utils/tta.py:35-39; the ViTPose config): "
+                                          "'udp_combined' / 'offset' belong to other heads' outputs")
+            flip_indices = batch_data_samples[0].metainfo["flip_indices"]
+            x = torch.cat([self._to_nhwc(feats[0]), self._to_nhwc(feats[1])])
+        else:
+            flip_indices = None
+            x = self._to_nhwc(feats)
+        out = self._engine.run_head(x, flip, flip_indices, return_heatmaps=bool(test_cfg.get("output_heatmaps", False)),
+                                    shift_heatmap=flip and bool(test_cfg.get("shift_heatmap", False)))
+        return self.pack_predictions(out, test_cfg)
+
+    pack_predictions = ProbMapHead.pack_predictions
+
+    def pack_records(self, rec: np.ndarray, test_cfg: dict = {}, heatmaps: Optional[Tensor] = None):
+        """heatmap_head.py:262-268 + base_head.py:33-86 from the batch's host record ``rec`` (B, K, 7) float64 (the layout of
+        ``ProbMapHead.pack_records``; only x, y and the score are filled for this head): ``keypoints`` (1, K, 2) float64 and
+        ``keypoint_scores`` (1, K) float32 per crop, views of one batch array each."""
+        B, C = rec.shape[:2]
+        if not np.isfinite(rec).all():
+            bad = np.argwhere(~np.isfinite(rec).all(axis=(1, 2))).ravel().tolist()
+            raise FloatingPointError(
+                f"non-finite keypoints / scores for crop(s) {bad[:8]} of this batch: a value left the numeric domain of precision="
+                f"{self._engine.precision!r} (f16x3: operands are fp16 pairs, |x| <= 65504 - include/probpose_mi355x.h, 'numeric domain'; "
+                "ProbPoseEngine.domain_report(crops) shows the layer). Run the model with precision='f32' or rescale the checkpoint")
+        kpts = np.ascontiguousarray(rec[..., :2])
+        scores = np.ascontiguousarray(rec[..., 2].astype(np.float32)).reshape(B, 1, C)
+        preds = _BatchPreds()
+        preds.keypoints_batch = kpts
+        for pi in range(B):
+            preds.append(InstanceData(keypoints=kpts[pi:pi + 1], keypoint_scores=scores[pi]))
+        if test_cfg.get("output_heatmaps", False):
+            assert heatmaps is not None, "output_heatmaps needs the engine's heatmaps"
+            return preds, [PixelData(heatmaps=hm) for hm in heatmaps.detach().clone()]
+        return preds
+
+    def loss(self, *a, **k):
+        raise NotImplementedError("training (heatmap_head.py:270-303) is outside the MI355X inference hot path")
+
+
 # =================================================================================================
 @register(MODELS, reference_name="TopdownPoseEstimator", mi355x_name="TopdownPoseEstimatorMI355X")
 class TopdownPoseEstimator(nn.Module):
@@ -429,11 +563,13 @@ class TopdownPoseEstimator(nn.Module):
                                    "(`model.to('cuda')`, as init_model does, apis/inference.py:128)")
             dp, bb, hd = self.data_preprocessor, self.backbone, self.head
             codec = hd.decoder
+            heatmap = isinstance(hd, HeatmapHead)  # the ViTPose baseline: no towers, UDP-DARK decode (engine head_kind "heatmap")
             self._engine = ProbPoseEngine(
                 self.state_dict(), num_heads=bb.num_heads, img_size=bb.img_size, patch_size=bb.patch_size,
                 patch_padding=bb.patch_padding, mean=dp.mean_values, std=dp.std_values,
-                bgr_to_rgb=dp.channel_conversion, temperature=hd.temperature, normalize=hd.normalize,
-                input_size=tuple(codec.input_size), ln_eps=bb.ln_eps, precision=self.precision, device=dev)
+                bgr_to_rgb=dp.channel_conversion, temperature=getattr(hd, "temperature", 1.0), normalize=getattr(hd, "normalize", None),
+                input_size=tuple(codec.input_size), ln_eps=bb.ln_eps, precision=self.precision, device=dev,
+                head_kind="heatmap" if heatmap else "probmap", blur_kernel_size=int(getattr(codec, "blur_kernel_size", 11)) if heatmap else 11)
             assert (self._engine.Wh, self._engine.Hh) == tuple(codec.heatmap_size), (
                 f"decoder heatmap_size {tuple(codec.heatmap_size)} does not match the head's output "
                 f"{(self._engine.Wh, self._engine.Hh)}")

@@ -106,9 +106,13 @@ def _trained_like(sd: Dict[str, torch.Tensor], E: int, L: int, heads: int, g: to
 
 def synthetic_state_dict(arch: str = "small", img_size=(256, 192), num_keypoints: int = 17,
                          deconv_out_channels: Sequence[int] = (256, 256), seed: int = 0,
-                         logit_scale: float = 3.0, stats: str = "unit", **trained_kw) -> Dict[str, torch.Tensor]:
+                         logit_scale: float = 3.0, stats: str = "unit", head: str = "probmap", **trained_kw) -> Dict[str, torch.Tensor]:
     """``stats="unit"``: activations O(1) everywhere (the weights every round-1..5 parity figure was taken on);
-    ``stats="trained"``: the same network re-parametrised to a trained ViT's statistics (``_trained_like``)."""
+    ``stats="trained"``: the same network re-parametrised to a trained ViT's statistics (``_trained_like``).
+    ``head="heatmap"``: the state dict of a ``HeatmapHead`` model (the ViTPose baseline) - the same backbone and heatmap branch
+    (the same tensors as ``head="probmap"`` at equal seed, the final layer's weights centred per keypoint), no scalar-tower keys."""
+    if head not in ("probmap", "heatmap"):
+        raise ValueError(f"head must be 'probmap' or 'heatmap', got {head!r}")
     if stats not in ("unit", "trained"):
         raise ValueError(f"stats must be 'unit' or 'trained', got {stats!r}")
     a = ARCHS[arch] if isinstance(arch, str) else arch
@@ -154,7 +158,13 @@ def synthetic_state_dict(arch: str = "small", img_size=(256, 192), num_keypoints
         cin = cout
     sd["head.final_layer.weight"] = n(num_keypoints, cin, 1, 1, std=logit_scale / math.sqrt(cin))
     sd["head.final_layer.bias"] = n(num_keypoints, std=0.1)
-    for t in ("probability", "visibility", "oks", "error"):
+    if head == "heatmap":
+        # HeatmapHead's maps are decoded as they are (no Sparsemax in front). A 1x1 conv of random sign on ReLU'd (non-negative) maps gives every
+        # keypoint's map an offset of either sign, large against its peaks; with the flip-test average of two unrelated passes a map then often has
+        # no positive value at all. Weights centred per keypoint take that offset out: the maps swing around zero, their maxima are positive.
+        w = sd["head.final_layer.weight"]
+        sd["head.final_layer.weight"] = w - w.mean(dim=1, keepdim=True)
+    for t in ("probability", "visibility", "oks", "error") if head == "probmap" else ():
         for j in range(3):
             sd[f"head.{t}_layers.{4 * j}.weight"] = n(E, E, 3, 3, std=math.sqrt(2.0 / (9 * E)))
             sd[f"head.{t}_layers.{4 * j}.bias"] = n(E, std=0.1)
@@ -164,6 +174,13 @@ def synthetic_state_dict(arch: str = "small", img_size=(256, 192), num_keypoints
     if stats == "trained":
         _trained_like(sd, E, L, a["num_heads"], g, **trained_kw)
     return sd
+
+
+def head_kind_of(cfg) -> str:
+    """``head=`` of ``synthetic_state_dict`` for a config's ``model.head.type``: "heatmap" for ``HeatmapHead`` (the ViTPose baseline),
+    "probmap" otherwise."""
+    head_type = str(dict(dict(cfg["model"]).get("head") or {}).get("type", "ProbMapHead"))
+    return "heatmap" if head_type.split(".")[-1] in ("HeatmapHead", "HeatmapHeadMI355X") else "probmap"
 
 
 def synthetic_crops(batch: int, img_size=(256, 192), seed: int = 0) -> torch.Tensor:

@@ -146,6 +146,7 @@ class PackedWeights:
     t: Dict[str, torch.Tensor] = field(default_factory=dict)
     # name -> 2^-e of the split-fp16 Linear weight tensors stored as w * 2^e (weight_scale_exponent); absent = 1.0
     inv_scale: Dict[str, float] = field(default_factory=dict)
+    head_kind: str = "probmap"  # "probmap": heatmap branch + four scalar towers; "heatmap": the heatmap branch alone (HeatmapHead)
 
     def __getitem__(self, k):
         return self.t[k]
@@ -297,8 +298,9 @@ def pack(sd: Dict[str, torch.Tensor], dtype: torch.dtype, device, split: bool = 
         if split and wpad.shape[1] == 256:
             t["final.w_head"] = pack_head_split(wpad).to(device)
 
-    # ---- scalar towers
-    for c in range(3):
+    # ---- scalar towers (ProbMapHead only; a HeatmapHead state dict - the ViTPose baseline - has none)
+    head_kind = "probmap" if any(k.startswith(f"head.{TOWERS[0]}_layers.") for k in sd) else "heatmap"
+    for c in range(3 if head_kind == "probmap" else 0):
         ws, bs, wino = [], [], []
         for tw in TOWERS:
             base = f"head.{tw}_layers."
@@ -314,7 +316,8 @@ def pack(sd: Dict[str, torch.Tensor], dtype: torch.dtype, device, split: bool = 
             t["tower0.wino"] = op(torch.stack(wino), "tower0.wino")  # (4, 16, Cout, Cin): the first stage's Winograd form (pp_conv3x3_winograd_maxpool_relu)
         t[f"tower{c}.w"] = op(torch.stack(ws), f"tower{c}.w")
         t[f"tower{c}.b"] = f32(torch.stack(bs))
-    t["tower_out.w"] = f32(torch.stack([sd[f"head.{tw}_layers.12.weight"].float().reshape(K, -1) for tw in TOWERS]))
-    t["tower_out.b"] = f32(torch.stack([sd[f"head.{tw}_layers.12.bias"].float() for tw in TOWERS]))
+    if head_kind == "probmap":
+        t["tower_out.w"] = f32(torch.stack([sd[f"head.{tw}_layers.12.weight"].float().reshape(K, -1) for tw in TOWERS]))
+        t["tower_out.b"] = f32(torch.stack([sd[f"head.{tw}_layers.12.bias"].float() for tw in TOWERS]))
     return PackedWeights(dtype=dtype, embed_dims=E, num_layers=L, ffn_dims=Fd, num_keypoints=K,
-                         deconv_channels=deconv_channels, t=t, inv_scale=inv_scale)
+                         deconv_channels=deconv_channels, t=t, inv_scale=inv_scale, head_kind=head_kind)
