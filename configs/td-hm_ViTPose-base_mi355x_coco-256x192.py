@@ -1,0 +1,78 @@
+# ViTPose-base (classic head) on MI355X, inference and evaluation settings. Mirrors the model / codec / test keys and the val
+# dataset of the reference's configs/body_2d_keypoint/topdown_heatmap/coco/td-hm_ViTPose-base_8xb64-210e_coco-256x192.py;
+# training / optimizer entries are not part of the inference hot path and are left out. Backbone: ViT-B (768 wide, 12 layers,
+# 12 heads of 64); head: two deconvolutions + 1x1 conv, decoded by the UDP codec with DARK refinement (pp_udp_heatmap_decode).
+# Layer plan in f16x3 (ProbPoseEngine.layer_plan says it at run time): from 18 crops with flip test on, the folded-LayerNorm plan (pp_linear_ln_folded x4 + pp_attention per layer); below, the
+# small-batch plan (pp_skinny_linear).
+#   python tools/test.py configs/td-hm_ViTPose-base_mi355x_coco-256x192.py CHECKPOINT \
+#       --cfg-options test_dataloader.dataset.data_root=/data/coco/
+# NOT mirrored: the reference evaluates this model on the boxes of a person detector (`bbox_file=...detections_AP_H_56_person.json`).
+# Evaluation on detector boxes is not implemented here (CocoDataset refuses `bbox_file`); this config evaluates on the
+# GROUND-TRUTH boxes of the annotation file, like the ViTPose-small and ProbPose configs - the models are then compared on equal
+# boxes, but the AP is not the number the reference's config reports.
+custom_imports = dict(imports=["probpose_code_amd"], allow_failed_imports=False)
+default_scope = "mmpose"
+
+TEST_BATCH_SIZE = 64
+COCO_ROOT = "PATH/TO/COCO/DATASET/"
+
+codec = dict(type="UDPHeatmap", input_size=(192, 256), heatmap_size=(48, 64), sigma=2)
+
+model = dict(
+    type="TopdownPoseEstimator",
+    # MI355X-only key: operand precision of the MFMA kernels (see the ProbPose config)
+    precision="f16x3",
+    data_preprocessor=dict(
+        type="PoseDataPreprocessor", mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], bgr_to_rgb=True
+    ),
+    backbone=dict(
+        type="mmpretrain.VisionTransformer",
+        arch="base",
+        img_size=(256, 192),
+        patch_size=16,
+        qkv_bias=True,
+        drop_path_rate=0.3,
+        with_cls_token=False,
+        out_type="featmap",
+        patch_cfg=dict(padding=2),
+        init_cfg=None,
+    ),
+    head=dict(
+        type="HeatmapHead",
+        in_channels=768,
+        out_channels=17,
+        deconv_out_channels=(256, 256),
+        deconv_kernel_sizes=(4, 4),
+        loss=dict(type="KeypointMSELoss", use_target_weight=True),
+        decoder=codec,
+    ),
+    test_cfg=dict(flip_test=True, flip_mode="heatmap", shift_heatmap=False),
+)
+
+val_pipeline = [
+    dict(type="LoadImage"),
+    dict(type="GetBBoxCenterScale"),
+    dict(type="TopdownAffine", input_size=codec["input_size"], use_udp=True),
+    dict(type="PackPoseInputs"),
+]
+test_dataloader = dict(
+    batch_size=TEST_BATCH_SIZE,
+    num_workers=4,
+    persistent_workers=True,
+    drop_last=False,
+    sampler=dict(type="DefaultSampler", shuffle=False, round_up=False),
+    dataset=dict(
+        type="CocoDataset",
+        data_root=COCO_ROOT,
+        data_mode="topdown",
+        ann_file="annotations/person_keypoints_val2017.json",
+        data_prefix=dict(img="val2017/"),
+        test_mode=True,
+        pipeline=val_pipeline,
+    ),
+)
+val_dataloader = test_dataloader
+
+# (the metric reads the dataset's annotation file; `test_evaluator.ann_file=...` evaluates against another one)
+test_evaluator = dict(type="CocoMetric")
+val_evaluator = test_evaluator

@@ -40,10 +40,11 @@ def main():
     from probpose_code_amd.structures import merge_data_samples
 
     ckpt = args.checkpoint
-    if ckpt == "synthetic":  # (the head kind - ProbMapHead with its towers, or the ViTPose baseline's HeatmapHead - from the config)
+    if ckpt == "synthetic":  # (the backbone's arch and the head kind - ProbMapHead with its towers, or ViTPose's HeatmapHead - from the config)
         from probpose_code_amd.config import Config
 
-        ckpt = dict(state_dict=synthetic.synthetic_state_dict("small", seed=0, logit_scale=2.0, head=synthetic.head_kind_of(Config.fromfile(args.config))))
+        cfg = Config.fromfile(args.config)
+        ckpt = dict(state_dict=synthetic.synthetic_state_dict(synthetic.arch_of(cfg), seed=0, logit_scale=2.0, head=synthetic.head_kind_of(cfg)))
     opts = {"model.precision": args.precision} if args.precision else None
     if args.draw_heatmap:
         opts = dict(opts or {}, **{"model.test_cfg.output_heatmaps": True})

@@ -395,8 +395,10 @@ int pp_conv_gemm(int prec, int kind, const void* act_nhwc, const void* weight, c
 /* Multi-head self-attention of the backbone (mmpretrain MultiheadAttention [3P]:
  * softmax(q k^T * scale) v per head). qkv: (n_seq * seq_len, 3 * heads * head_dim) rows as the
  * qkv Linear emits them ([q | k | v], head-major inside each); out: (n_seq * seq_len, heads *
- * head_dim). Both bf16 or fp32 per `prec`. Supported (seq_len, head_dim): {192, 432} x {32, 64}
- * (fp32 432 x 64 exceeds one CU's LDS). */
+ * head_dim). Both bf16, fp32 or split fp16 per `prec`. Supported (seq_len, head_dim): {192, 432} x
+ * {32, 64} (fp32 432 x 64 exceeds one CU's LDS) and 192 x 80 (ViT-H; all three precisions: the
+ * q . k contraction runs over the head row zero-padded to 96 on chip, nothing is read or written
+ * beyond a head's 80 columns). Any other shape: PP_ERR_UNSUPPORTED. */
 int pp_attention(int prec, const void* qkv, void* out, int n_seq, int seq_len, int heads, int head_dim,
                  float scale, void* stream);
 
@@ -414,7 +416,7 @@ int pp_preproc_im2col(int prec, const void* img, int img_is_f32, void* patches, 
                       int bgr_to_rgb, void* stream);
 
 /* LayerNorm over the last dim of an fp32 (M, E) matrix (nn.LayerNorm(E, eps) of the ViT, eps 1e-6);
- * output bf16 or fp32. E in {384, 768, 1024}. */
+ * output bf16 or fp32. E in {384, 768, 1024, 1280}. */
 int pp_layernorm(const float* x, const float* gamma, const float* beta, void* y, int M, int E, float eps,
                  int out_bf16, void* stream);
 

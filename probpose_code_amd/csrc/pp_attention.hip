@@ -753,6 +753,7 @@ static int launch_attention_split_stream(const void* qkv, void* out, int n_seq, 
 }
 
 int attention_split_dma(const void* qkv, void* out, int n_seq, int heads, int head_dim, float scale, hipStream_t s);  // pp_attention_dma.hip
+int attention_hd80(int prec, const void* qkv, void* out, int n_seq, int heads, float scale, hipStream_t s);                  // pp_attention_hd80.hip
 
 }  // namespace pp
 
@@ -762,6 +763,9 @@ extern "C" int pp_attention(int prec, const void* qkv, void* out, int n_seq, int
     PP_REQUIRE(qkv && out, PP_ERR_INVALID_ARG, "pp_attention: qkv and out must be non-NULL");
     PP_REQUIRE(n_seq > 0 && heads > 0, PP_ERR_INVALID_ARG, "pp_attention: n_seq and heads must be positive");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // ViT-H 256x192: head dim 80 is 2.5 MFMA K-blocks, the q . k contraction zero-padded to 96 in LDS (all three precisions)
+    if (head_dim == 80 && seq_len == 192 && (prec == PP_PREC_BF16 || prec == PP_PREC_F32 || prec == PP_PREC_F16X3))
+        return attention_hd80(prec, qkv, out, n_seq, heads, scale, s);
 #define PP_ATT_CASE(T, HD, NT) \
     if (head_dim == HD && seq_len == NT * 16) return launch_attention<T, HD, NT>(qkv, out, n_seq, heads, scale, s);
     if (prec == PP_PREC_BF16) {
@@ -786,5 +790,5 @@ extern "C" int pp_attention(int prec, const void* qkv, void* out, int n_seq, int
 #undef PP_ATT_CASE
     return fail(PP_ERR_UNSUPPORTED,
                 "pp_attention: (seq_len, head_dim) not instantiated: supported 192/432 tokens x 32/64 "
-                "(fp32 at 432 x 64 exceeds one CU's LDS; PP_PREC_F16X3 covers it in two key stages)");
+                "(fp32 at 432 x 64 exceeds one CU's LDS; PP_PREC_F16X3 covers it in two key stages) and 192 tokens x 80");
 }

@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void preproc_im2col_kernel(const TIn* __restri
 
 // ---------------------------------------------------------------------------------------------
 // LayerNorm over the last dim of an fp32 [M, E] matrix, one wavefront per row, fp32 statistics
-// (two-pass: mean, then centred variance), output bf16 or fp32. E % 128 == 0, E <= 1024.
+// (two-pass: mean, then centred variance), output bf16 or fp32. E % 128 == 0, E <= 1280.
 template <typename TO, int EV>  // EV = E / 128 float2 pairs... per lane: EV * 2 floats
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, TO* __restrict__ y, int M,
@@ -165,7 +165,8 @@ static int launch_ln(const float* x, const float* g, const float* b, void* y, in
         case 384: hipLaunchKernelGGL((layernorm_kernel<TO, 3>), grid, block, 0, s, x, g, b, yo, M, eps); break;
         case 768: hipLaunchKernelGGL((layernorm_kernel<TO, 6>), grid, block, 0, s, x, g, b, yo, M, eps); break;
         case 1024: hipLaunchKernelGGL((layernorm_kernel<TO, 8>), grid, block, 0, s, x, g, b, yo, M, eps); break;
-        default: return fail(PP_ERR_UNSUPPORTED, "pp_layernorm: embed dim must be 384, 768 or 1024");
+        case 1280: hipLaunchKernelGGL((layernorm_kernel<TO, 10>), grid, block, 0, s, x, g, b, yo, M, eps); break;  // ViT-H
+        default: return fail(PP_ERR_UNSUPPORTED, "pp_layernorm: embed dim must be 384, 768, 1024 or 1280");
     }
     PP_LAUNCH_CHECK_AS("layernorm");
     return PP_OK;

@@ -236,6 +236,14 @@ class ProbPoseEngine:
                 if self.ln_fold:
                     self.layer_plan += ("; from the row count at which the twelve-wave Linear kernel engages: LayerNorm folded into the Linear "
                                         "layers (pp_linear_ln_folded x4 + pp_attention per layer, residual stream in the operand format)")
+                if self.hd == 80:
+                    self.layer_plan += "; attention at head dim 80: pp_attention_hd80.hip (the q . k contraction zero-padded to 96 on chip)"
+                # widths without any fused layer kernel (ViT-B / -L / -H): which batches leave this plan for the column-parallel one
+                if self._small_at(1):
+                    self.layer_plan += (f"; batches of fewer than {SMALL_PLAN_ROWS_BELOW} token rows: the small-batch plan (pp_skinny_linear x4 + "
+                                        "pp_attention per layer, LayerNorm in the Linear launches)")
+                elif self.small_plan and self.E > 1024:
+                    self.layer_plan += f"; no small-batch plan at E = {self.E} (pp_skinny_linear's LayerNorm tail ends at 1024 columns): this plan at every batch size"
             if pl["fuse_qkv_attn"] and not self.fuse_qkv_attn and self.E == 384 and self.hd == 32:
                 warnings.warn(
                     f"ProbPoseEngine: {self.Np}-token sequences ({img_size[0]}x{img_size[1]} input) miss the fused qkv + attention kernel, "

@@ -82,9 +82,10 @@ _VIT_ARCHS = {
     "small": dict(embed_dims=768, num_layers=8, num_heads=8, feedforward_channels=768 * 3),
     "base": dict(embed_dims=768, num_layers=12, num_heads=12, feedforward_channels=3072),
     "large": dict(embed_dims=1024, num_layers=24, num_heads=16, feedforward_channels=4096),
+    "huge": dict(embed_dims=1280, num_layers=32, num_heads=16, feedforward_channels=5120),  # head dim 80: csrc/pp_attention_hd80.hip
     "deit-small": dict(embed_dims=384, num_layers=12, num_heads=6, feedforward_channels=384 * 4),
 }
-_VIT_ARCHS.update({"s": _VIT_ARCHS["small"], "b": _VIT_ARCHS["base"], "l": _VIT_ARCHS["large"]})
+_VIT_ARCHS.update({"s": _VIT_ARCHS["small"], "b": _VIT_ARCHS["base"], "l": _VIT_ARCHS["large"], "h": _VIT_ARCHS["huge"]})
 
 
 class _Holder(nn.Module):

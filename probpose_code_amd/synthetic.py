@@ -26,6 +26,9 @@ ARCHS = {
     "small": dict(embed_dims=384, num_layers=12, num_heads=12, feedforward_channels=1536),
     # mmpretrain preset "base" (BASELINE config 4): 768 / 12 / 12 heads (head_dim 64) / 3072
     "base": dict(embed_dims=768, num_layers=12, num_heads=12, feedforward_channels=3072),
+    # mmpretrain presets "large" and "huge" (ViTPose-L / -H): 16 heads of 64 / of 80
+    "large": dict(embed_dims=1024, num_layers=24, num_heads=16, feedforward_channels=4096),
+    "huge": dict(embed_dims=1280, num_layers=32, num_heads=16, feedforward_channels=5120),
 }
 
 
@@ -181,6 +184,19 @@ def head_kind_of(cfg) -> str:
     "probmap" otherwise."""
     head_type = str(dict(dict(cfg["model"]).get("head") or {}).get("type", "ProbMapHead"))
     return "heatmap" if head_type.split(".")[-1] in ("HeatmapHead", "HeatmapHeadMI355X") else "probmap"
+
+
+def arch_of(cfg) -> Dict[str, int]:
+    """``arch=`` of ``synthetic_state_dict`` for a config's ``model.backbone.arch``: the explicit dict, or the preset a name stands for in
+    ``VisionTransformer`` ("base", "large", "huge": the ViTPose family)."""
+    arch = dict(dict(cfg["model"]).get("backbone") or {}).get("arch", "base")
+    if isinstance(arch, str):
+        from .pose_estimators import _VIT_ARCHS
+
+        if arch.lower() not in _VIT_ARCHS:
+            raise ValueError(f"model.backbone.arch={arch!r} is not in the default archs {sorted(_VIT_ARCHS)}")
+        arch = _VIT_ARCHS[arch.lower()]
+    return {k: int(dict(arch)[k]) for k in ("embed_dims", "num_layers", "num_heads", "feedforward_channels")}
 
 
 def synthetic_crops(batch: int, img_size=(256, 192), seed: int = 0) -> torch.Tensor:

@@ -57,8 +57,8 @@ def main(argv=None):
     if opts:
         cfg.merge_from_dict(opts)
     ckpt = args.checkpoint
-    if ckpt == "synthetic":  # (the head kind - ProbMapHead with its towers, or the ViTPose baseline's HeatmapHead - from the config)
-        ckpt = dict(state_dict=synthetic.synthetic_state_dict("small", seed=0, logit_scale=2.0, head=synthetic.head_kind_of(cfg)))
+    if ckpt == "synthetic":  # (the backbone's arch and the head kind - ProbMapHead with its towers, or ViTPose's HeatmapHead - from the config)
+        ckpt = dict(state_dict=synthetic.synthetic_state_dict(synthetic.arch_of(cfg), seed=0, logit_scale=2.0, head=synthetic.head_kind_of(cfg)))
     model = apis.init_model(cfg, ckpt, device=args.device)
     loader = cfg["test_dataloader"]
     dataset = build_dataset(loader["dataset"])
