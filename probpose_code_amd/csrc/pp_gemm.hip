@@ -312,6 +312,16 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(const GemmParams 
             // fp32 / split fp16: two 64-row halves staged as fp32 (64 x 512 B = one 32 KiB buffer each); a split row
             // leaves as 8 elements per lane = 16 bytes of hi halves + 16 bytes of lo halves.
             constexpr bool OUT_BF16 = OUT == FMT_BF16, OUT_SPLIT = OUT == FMT_SPLIT;
+            auto out_row = [&](int m) -> size_t {
+                if (GATHER == G_DECONV) {  // phase-interleaved output pixel (2y+py, 2x+px) of a (2H, 2W) map
+                    const int hw = p.H * p.Wd;
+                    const int b = m / hw, r = m - b * hw;
+                    const int y = r / p.Wd, x = r - y * p.Wd;
+                    const int py = p.py < 0 ? (z >> 1) : p.py, px = p.py < 0 ? (z & 1) : p.px;
+                    return ((size_t)b * (2 * p.H) + 2 * y + py) * (2 * p.Wd) + 2 * x + px;
+                }
+                return (size_t)m;
+            };
             constexpr int halves = OUT_BF16 ? 1 : 2;
             constexpr int lpr = OUT == FMT_F32 ? 32 : 16;  // lanes per output row
             constexpr int epl = OUT == FMT_F32 ? 4 : 8;    // elements per lane
@@ -327,8 +337,17 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(const GemmParams 
 #pragma unroll
                         for (int nf = 0; nf < 4; ++nf) {
                             const int nl = wy * 64 + nf * 16 + e_kg * 4;
-                            const f32x4 v = finish(acc[nf][mf], nf);
+                            f32x4 v = finish(acc[nf][mf], nf);
                             if constexpr (OUT_BF16) {
+                                if (p.residual) {  // bf16 output with an fp32 residual: added here, in fp32, so that the result is rounded ONCE
+                                    const int m = m0 + ml, nn = n0 + nl;
+                                    if (m < p.M) {
+                                        const size_t ro = p.res_mod > 0 ? (size_t)(m % p.res_mod) * p.ldres + nn : c_z + out_row(m) * p.ldres + nn;
+#pragma unroll
+                                        for (int j = 0; j < 4; ++j)
+                                            if (nn + j < p.N) v[j] += p.residual[ro + j];
+                                    }
+                                }
                                 const bf16x4 ov = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
                                 const int byte = nl * 2;
                                 *reinterpret_cast<bf16x4*>(cst + ml * 256 + ((((byte >> 4) ^ (ml & 15)) << 4) | (byte & 15))) = ov;
@@ -345,27 +364,13 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(const GemmParams 
                     const int ml = r0 + rl;
                     const int m = m0 + h * 64 + ml;
                     if (m >= p.M || n >= p.N) continue;
-                    size_t orow = m;
-                    if (GATHER == G_DECONV) {  // phase-interleaved output pixel (2y+py, 2x+px) of a (2H, 2W) map
-                        const int hw = p.H * p.Wd;
-                        const int b = m / hw, r = m - b * hw;
-                        const int y = r / p.Wd, x = r - y * p.Wd;
-                        const int py = p.py < 0 ? (z >> 1) : p.py, px = p.py < 0 ? (z & 1) : p.px;
-                        orow = ((size_t)b * (2 * p.H) + 2 * y + py) * (2 * p.Wd) + 2 * x + px;
-                    }
+                    const size_t orow = out_row(m);
                     const size_t eoff = c_z + orow * p.ldc + n;
                     const bool full = n + epl <= p.N;
                     const size_t roff = p.res_mod > 0 ? (size_t)(m % p.res_mod) * p.ldres + n : c_z + orow * p.ldres + n;
                     if constexpr (OUT_BF16) {
                         u32x4 raw = *reinterpret_cast<const u32x4*>(cst + ml * 256 + ((cl ^ (ml & 15)) << 4));
                         __bf16* o = reinterpret_cast<__bf16*>(Cb) + eoff;
-                        if (p.residual) {  // bf16 output with an fp32 residual: add in fp32, round once more
-                            bf16x8 cv = __builtin_bit_cast(bf16x8, raw);
-#pragma unroll
-                            for (int j = 0; j < 8; ++j)
-                                if (n + j < p.N) cv[j] = (__bf16)((float)cv[j] + p.residual[roff + j]);
-                            raw = __builtin_bit_cast(u32x4, cv);
-                        }
                         if (full) {
                             *reinterpret_cast<u32x4*>(o) = raw;
                         } else {

@@ -4,7 +4,7 @@ pp_conv_gemm (PP_CONV3X3 with groups 1 - 4, shared or separate inputs, bias / no
 PP_DECONV4X4S2 as the four single phases and as all four in one launch) in bf16 / fp32 / f16x3, pp_conv3x3_splitk (slices 1 / 3 / 9) +
 pp_sum_maxpool_relu_nhwc in bf16 / fp32, the bf16 pp_conv3x3_maxpool_relu and pp_deconv_head, pp_maxpool_relu_nhwc (every admitted format pair,
 windows that do not divide the map), pp_preproc_im2col (uint8 / fp32 input, pad 0 - 3, one or two passes, three output formats) and
-pp_layernorm (E 384 / 768 / 1024, the row classes of tests/fuzz_layer.py).
+pp_layernorm (E 384 / 768 / 1024 / 1280, the row classes of tests/fuzz_layer.py).
 
 Shapes: the engine's own maps (ViT-S 16 x 12 x 384, ViT-B 24 x 18 x 768, the tower stages 4 x 4, 6 x 6, 3 x 3, 2 x 2) and random ones down to 1 x 1.
 The dispatcher's predicates (panel_split_supported, conv_halo_supported, panel_gemm_supported, then the 128 x 128 kernel) are mirrored below;
@@ -617,7 +617,7 @@ def _main(seconds):
 
     # ------------------------------------------------------------------------------------------------- LayerNorm
     def case_layernorm(rng, g):
-        E = int(rng.choice([384, 768, 1024]))
+        E = int(rng.choice([384, 768, 1024, 1280]))
         fmt = int(rng.choice([0, 1, SPLIT]))
         M = int(rng.choice([1, 3, 4, 5, 192, 203, 12288, int(rng.integers(1, 30000))]))
         cls = str(rng.choice(["normal", "offset", "massive"]))

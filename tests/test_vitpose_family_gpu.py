@@ -12,6 +12,13 @@ weight seed 0, crop seed 100 unless noted; no map with a non-positive maximum in
   B = 2:  huge  unit 1 of 34 = 2.9 % (the f32 and bf16 cases)
   B = 1:  large unit 0 of 17, trained 0 of 17;  huge unit 0 of 17, trained 1 of 17 = 5.9 % at crop seed 100 - over the 5 % - and
           0 of 17 at crop seeds 101, 102, 103 and 105: the huge / trained case at B = 1 uses crop seed 101.
+  B = 64, crop seed 7 (test_b64_with_flip_against_the_oracle: the oracle runs on crops 0 - 7 and 56 - 63 only, 11 - 22 s of CPU per config):
+          config          left out, these 16 crops (of 272)   left out, all 64 crops (of 1088)
+          large unit       8 (2.9 %)                           18
+          large trained   10 (3.7 %)                           27
+          huge  unit       5 (1.8 %)                           23
+          huge  trained    4 (1.5 %)                           21
+          (crops 0 and 63 alone would not do: large / trained leaves out 3 of 34 there, over the 5 %)
 
 Which plan runs (``ProbPoseEngine.layer_plan``, checked with ``pp_launch_count``): B = 4 with flip test is 1 536 token rows - below the
 6 912 at which the small-batch plan ends - so base and large take pp_skinny_linear there and huge (E > 1024: no small-batch plan) the
@@ -54,13 +61,16 @@ def _model(arch, stats, precision="f16x3"):
 
 
 @functools.lru_cache(maxsize=16)
-def _oracle(arch, stats, B, seed):
-    """HeatmapHead.predict's maps on the CPU: logits of the final 1x1 conv, (a + flip_back(b)) * 0.5 in fp32."""
+def _oracle(arch, stats, B, seed, idx=None):
+    """HeatmapHead.predict's maps on the CPU: logits of the final 1x1 conv, (a + flip_back(b)) * 0.5 in fp32. ``idx``: a tuple of crop indices -
+    the oracle runs on ``synthetic_crops(B, seed)[idx]`` only (every crop's maps depend on that crop alone)."""
     from oracle import model_ref as M
     from probpose_code_amd import synthetic as S
 
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     sd, crops = _state_dict(arch, stats), S.synthetic_crops(B, seed=seed)
+    if idx is not None:
+        crops = crops[list(idx)]
     with torch.no_grad():
         x = M.preprocess(crops, S.IMG_MEAN, S.IMG_STD)
         _, a = M.head_heatmap(sd, M.vit_forward(sd, x, HEADS[arch]), normalize=None, return_logits=True)
@@ -222,11 +232,26 @@ def test_huge_b64_third_step_replays_a_graph_equal_to_eager(tmp_path):
             assert np.array_equal(x.pred_instances.keypoint_scores, y.pred_instances.keypoint_scores)
 
 
-def test_large_b64_takes_the_generic_plan():
-    model = _model("large", "unit")
+B64_CHECKED = tuple(range(8)) + tuple(range(56, 64))  # the first row tiles of the un-flipped half, the last of the flipped half
+
+
+@pytest.mark.parametrize("stats", ["unit", "trained"])
+@pytest.mark.parametrize("arch", ["large", "huge"])
+def test_b64_with_flip_against_the_oracle(arch, stats):
+    """The benchmarked batch: 64 crops with flip test are 24 576 token rows - the generic plan (large / unit: what
+    test_large_b64_takes_the_generic_plan asserted), qkv on the twelve-wave kernel (K = 1024 / 1280: 32 / 40 K-steps on its ring of three),
+    proj / fc1 / fc2 and the patch embedding on the 128 x 128 kernel at K up to 5120, the deconvolutions on wide tiles. Heatmaps and keypoints
+    of crops 0 - 7 and 56 - 63 against the oracle, every map finite."""
+    from probpose_code_amd import _lib
+
+    model = _model(arch, stats)
     out, counts = _forward(model.engine, 64, 7)
-    _check_plan(model.engine, "large", counts, small=False)
+    _check_plan(model.engine, arch, counts, small=False)
+    assert counts["linear_dma_tile"] == LAYERS[arch], counts  # (qkv of every layer; nothing else at these widths is a multiple of 192)
+    assert _lib.launch_count("pp_gemm.hip") >= 3 * LAYERS[arch] + 1 and _lib.launch_count("pp_panel_split.hip") >= 1
     assert np.isfinite(out["heatmaps"].cpu().numpy()).all()
+    sub = {k: out[k][list(B64_CHECKED)] for k in ("heatmaps", "keypoints", "scores", "locs")}
+    _check_against_oracle(sub, _oracle(arch, stats, 64, 7, B64_CHECKED), f"{arch} {stats} B 64, crops 0 - 7 and 56 - 63")
 
 
 def test_inference_topdown_and_the_tools_run_the_huge_config(tmp_path):
