@@ -4,8 +4,10 @@ image as one box, or ``--bboxes x0,y0,x1,y1;...`` - printed / saved as JSON; ``-
 
     python demo/image_demo.py IMG configs/td-pm_ProbPose-small_mi355x_coco-256x192.py CHECKPOINT --out-file out.json
     python demo/image_demo.py IMG CONFIG CHECKPOINT --draw-heatmap --out-img out.png
+    python demo/image_demo.py IMG configs/td-hm_ViTPose-small_mi355x_coco-256x192.py CHECKPOINT --cfg-options model.head.decoder.type=UDPExpMaxHeatmap
 
 CHECKPOINT may be "synthetic" (seeded random weights: plumbing check, BASELINE config 1)."""
+import ast
 import json
 import os
 import sys
@@ -14,6 +16,20 @@ from argparse import ArgumentParser
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def parse_cfg_options(items):
+    """``key=value`` pairs as tools/test.py reads them: Python literals where they parse as one, strings otherwise."""
+    opts = {}
+    for it in items or []:
+        if "=" not in it:
+            raise ValueError(f"--cfg-options takes key=value pairs, got {it!r}")
+        k, v = it.split("=", 1)
+        try:
+            opts[k] = ast.literal_eval(v)
+        except (ValueError, SyntaxError):
+            opts[k] = {"true": True, "false": False, "none": None}.get(v.lower(), v)
+    return opts
 
 
 def main():
@@ -26,6 +42,8 @@ def main():
     ap.add_argument("--bboxes", default=None, help="x0,y0,x1,y1;x0,y0,x1,y1;... (default: the whole image)")
     ap.add_argument("--precision", default=None, choices=[None, "f16x3", "bf16", "f32"],
                     help="overrides model.precision of the config (default there: f16x3, the mode within 1e-3 of the fp32 reference)")
+    ap.add_argument("--cfg-options", nargs="+", default=None, metavar="KEY=VALUE",
+                    help="override config keys as tools/test.py does, e.g. model.head.decoder.type=UDPExpMaxHeatmap (or ArgMaxProbMap)")
     ap.add_argument("--out-img", default=None, help="draw the predictions into this image file (PNG / JPEG by its extension)")
     ap.add_argument("--draw-heatmap", action="store_true", help="with --out-img: the probability areas of the keypoints under the poses")
     ap.add_argument("--kpt-thr", type=float, default=0.3, help="visibility threshold of the keypoints drawn")
@@ -45,7 +63,9 @@ def main():
 
         cfg = Config.fromfile(args.config)
         ckpt = dict(state_dict=synthetic.synthetic_state_dict(synthetic.arch_of(cfg), seed=0, logit_scale=2.0, head=synthetic.head_kind_of(cfg)))
-    opts = {"model.precision": args.precision} if args.precision else None
+    opts = parse_cfg_options(args.cfg_options) or None
+    if args.precision:
+        opts = dict(opts or {}, **{"model.precision": args.precision})
     if args.draw_heatmap:
         opts = dict(opts or {}, **{"model.test_cfg.output_heatmaps": True})
     model = apis.init_model(args.config, ckpt, device=args.device, cfg_options=opts)

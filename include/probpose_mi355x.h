@@ -589,6 +589,39 @@ int pp_udp_heatmap_decode(const float* maps, const float* maps_flip, const int32
                           double in_w, double in_h, int blur_kernel_size, float* avg_out, float* locs, double* keypoints,
                           float* scores, int flags, void* stream);
 
+/* The other two codecs of the reference's head x decode table (mmpose/codecs/udp_expmax_heatmap.py, argmax_probmap.py); added under
+ * version 4, purely additive: no existing entry point changes.
+ *
+ * pp_expmax_heatmap_decode = UDPExpMaxHeatmap.decode, heatmap_type "gaussian" (udp_expmax_heatmap.py:165-206:
+ * get_heatmap_expected_value, post_processing.py:308-381, then / (W - 1, H - 1) * input_size): the expected-OKS decode of
+ * pp_probmap_decode on the RAW fp32 maps of the final 1x1 conv - no temperature, no Sparsemax, no clamp: values below 0 and above 1
+ * pass through unchanged. A load mode of pp_probmap_decode's kernel (csrc/pp_decode.hip), the same arithmetic from the averaged map
+ * on: flip-back, channel permutation and fp32 average; separable OKS-kernel convolution in fp64, one rounding to fp32; first-occurrence
+ * argmax; one fp32 sub-pixel step; rescale in fp64; `scores` = the raw averaged map at the integer argmax. Row-major maps, or with
+ * PP_DECODE_PHASED the phase-separated layout of pp_deconv_head (even H, W % 8 == 0); PP_DECODE_SHIFT_HEATMAP honoured; any other
+ * flag is PP_ERR_INVALID_ARG. taps / radius as pp_probmap_decode takes them; K <= 17 (the reference's table of sigmas), else
+ * PP_ERR_UNSUPPORTED. Shape limits are pp_probmap_decode's. A map holding a non-finite value (in either pass) gives NaN locs /
+ * keypoints / scores (and NaN avg_out / conv_out maps) for that (crop, keypoint) only. Tallied as "pp_expmax_heatmap_decode". */
+int pp_expmax_heatmap_decode(const float* maps, const float* maps_flip, const int32_t* flip_indices, const double* taps,
+                             const int32_t* radius, int B, int K, int H, int W, double in_w, double in_h, float* avg_out,
+                             float* conv_out, float* locs, double* keypoints, float* scores, int flags, void* stream);
+
+/* pp_argmax_probmap_decode = ProbMapHead's map construction (probmap_head.py:637-646: x / T, Sparsemax over the H*W pixels,
+ * * normalize, clamp(0, 1) per pass; normalize < 0 = the head's normalize=None, as in pp_probmap_decode_flags), the flip-test
+ * average, then ArgMaxProbMap.decode, heatmap_type "gaussian" (argmax_probmap.py:150-196: get_heatmap_maximum +
+ * refine_keypoints_dark_udp + / (W - 1, H - 1) * input_size - the steps of UDPHeatmap.decode), csrc/pp_argmax_decode.hip. ONE
+ * launch, one 256-thread workgroup per (crop, keypoint); the averaged map stays in LDS unless avg_out is given. Its results are bit
+ * for bit those of pp_probmap_decode_flags(PP_DECODE_LOGITS | flags, avg_out = maps) followed by pp_udp_heatmap_decode(maps): both
+ * halves are the same device code (csrc/pp_decode_stages.h). logits row-major or PP_DECODE_PHASED (even H, W % 8 == 0);
+ * PP_DECODE_SHIFT_HEATMAP honoured; any other flag is PP_ERR_INVALID_ARG. W % 4 == 0, H * W <= 12288, blur_kernel_size odd,
+ * 1 .. 19, and the LDS above (512 B + max(H (W + 24) + 32, 2048, (H + ks - 1) W) + H ((W + ks - 1) | 1) floats) within 160 KiB, else
+ * PP_ERR_UNSUPPORTED. A non-finite logit gives NaN locs / keypoints / scores (and a NaN avg_out map) for that (crop, keypoint), and
+ * for one whose map has maximum <= 0 and takes points from that neighbour (see pp_udp_heatmap_decode). Tallied as
+ * "pp_argmax_probmap_decode". */
+int pp_argmax_probmap_decode(const float* logits, const float* logits_flip, const int32_t* flip_indices, int B, int K, int H, int W,
+                             double in_w, double in_h, float temperature, float normalize, int blur_kernel_size, float* avg_out,
+                             float* locs, double* keypoints, float* scores, int flags, void* stream);
+
 /* Split-K form of the towers' 3x3 convolution for stages with few output pixels: the contraction is cut into ksplit slices -
  * 1, 3 or 9: whole taps (any precision); any other count with Cin % (32 ksplit) == 0: channel ranges [s Cin / ksplit, ...) of all nine
  * taps (PP_PREC_F16X3 on the wide-tile kernel only, needs >= 192 tiles of 256 x 192; pp_conv3x3_splitk_slices returns such a

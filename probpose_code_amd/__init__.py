@@ -8,7 +8,7 @@ The compute lives in ``libprobpose_mi355x.so`` (hand-written HIP, C ABI declared
 operator interface for this path and nothing else.
 """
 from . import _lib  # noqa: F401  (fails loudly when the HIP library is missing)
-from .codecs import BaseKeypointCodec, ProbMap, UDPHeatmap, oks_kernel_taps  # noqa: F401
+from .codecs import ArgMaxProbMap, BaseKeypointCodec, ProbMap, UDPExpMaxHeatmap, UDPHeatmap, oks_kernel_taps  # noqa: F401
 from .config import Config  # noqa: F401
 from .engine import ProbPoseEngine, domain_report  # noqa: F401
 from .pipeline import StepPipeline  # noqa: F401

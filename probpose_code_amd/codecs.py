@@ -86,6 +86,7 @@ class ProbMap(BaseKeypointCodec):
 
     label_mapping_table = dict(keypoint_weights="keypoint_weights")
     field_mapping_table = dict(heatmaps="heatmaps")
+    decode_kind = "expmax"  # which decode the engine runs behind the head: expected-OKS maximisation ("expmax") or UDP argmax + DARK ("dark")
 
     def __init__(
         self,
@@ -152,7 +153,7 @@ class ProbMap(BaseKeypointCodec):
         if self.heatmap_type != "gaussian":
             raise NotImplementedError("only heatmap_type='gaussian' (the ProbPose setting) is decodable on MI355X")
         if not heatmaps.is_cuda:
-            raise RuntimeError("ProbMap.decode_device needs tensors on the MI355X; there is no CPU fallback")
+            raise RuntimeError(f"{type(self).__name__}.decode_device needs tensors on the MI355X; there is no CPU fallback")
         B, K, H, W = heatmaps.shape
         Wc, Hc = self.heatmap_size
         assert (H, W) == (Hc, Wc), f"heatmap shape {(H, W)} does not match codec heatmap_size {(Hc, Wc)}"
@@ -173,17 +174,21 @@ class ProbMap(BaseKeypointCodec):
         avg = torch.empty_like(hm) if return_avg else None
         conv = torch.empty_like(hm) if return_conv else None
         with torch.cuda.device(dev):
-            _lib.call(
-                "pp_probmap_decode_flags", _lib.ptr(hm), _lib.ptr(hmf), _lib.ptr(fi), _lib.ptr(taps), _lib.ptr(radius),
-                B, K, H, W, float(self.input_size[0]), float(self.input_size[1]), 1.0, 1.0,
-                _lib.ptr(avg), _lib.ptr(conv), _lib.ptr(out["locs"]), _lib.ptr(out["keypoints"]),
-                _lib.ptr(out["scores"]), 4 if shift_heatmap else 0, _lib.stream_ptr(dev),
-            )  # fmt: skip  (flags: PP_DECODE_SHIFT_HEATMAP = 4)
+            self._launch(hm, hmf, fi, taps, radius, avg, conv, out, shift_heatmap, dev)
         if return_avg:
             out["heatmaps"] = avg
         if return_conv:
             out["conv"] = conv
         return out
+
+    def _launch(self, hm, hmf, fi, taps, radius, avg, conv, out, shift_heatmap, dev) -> None:
+        B, K, H, W = hm.shape
+        _lib.call(
+            "pp_probmap_decode_flags", _lib.ptr(hm), _lib.ptr(hmf), _lib.ptr(fi), _lib.ptr(taps), _lib.ptr(radius),
+            B, K, H, W, float(self.input_size[0]), float(self.input_size[1]), 1.0, 1.0,
+            _lib.ptr(avg), _lib.ptr(conv), _lib.ptr(out["locs"]), _lib.ptr(out["keypoints"]),
+            _lib.ptr(out["scores"]), 4 if shift_heatmap else 0, _lib.stream_ptr(dev),
+        )  # fmt: skip  (flags: PP_DECODE_SHIFT_HEATMAP = 4)
 
     def _flip_tensor(self, flip_indices: Tuple[int, ...], device) -> torch.Tensor:
         key = ("flip", flip_indices, str(device))
@@ -221,6 +226,7 @@ class UDPHeatmap(BaseKeypointCodec):
 
     label_mapping_table = dict(keypoint_weights="keypoint_weights")
     field_mapping_table = dict(heatmaps="heatmaps")
+    decode_kind = "dark"
 
     def __init__(self, input_size: Tuple[int, int], heatmap_size: Tuple[int, int], heatmap_type: str = "gaussian",
                  sigma: float = 2.0, radius_factor: float = 0.0546875, blur_kernel_size: int = 11) -> None:
@@ -260,7 +266,7 @@ class UDPHeatmap(BaseKeypointCodec):
         non-finite value gives NaN results."""
         assert isinstance(heatmaps, torch.Tensor) and heatmaps.dim() == 4, "heatmaps should be a (B, K, H, W) tensor"
         if not heatmaps.is_cuda:
-            raise RuntimeError("UDPHeatmap.decode_device needs tensors on the MI355X; there is no CPU fallback")
+            raise RuntimeError(f"{type(self).__name__}.decode_device needs tensors on the MI355X; there is no CPU fallback")
         B, K, H, W = heatmaps.shape
         Wc, Hc = self.heatmap_size
         assert (H, W) == (Hc, Wc), f"heatmap shape {(H, W)} does not match codec heatmap_size {(Hc, Wc)}"
@@ -298,7 +304,7 @@ class UDPHeatmap(BaseKeypointCodec):
         kpts = out["keypoints"].cpu().numpy()
         scores = out["scores"].cpu().numpy()
         if not (np.isfinite(kpts).all() and np.isfinite(scores).all()):
-            raise FloatingPointError("UDPHeatmap.decode: non-finite keypoints / scores (a heatmap holds a non-finite value)")
+            raise FloatingPointError(f"{type(self).__name__}.decode: non-finite keypoints / scores (a heatmap holds a non-finite value)")
         return [kpts[i][None] for i in range(kpts.shape[0])], [scores[i][None] for i in range(scores.shape[0])]
 
     def decode(self, encoded: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
@@ -308,3 +314,81 @@ class UDPHeatmap(BaseKeypointCodec):
         hm = torch.from_numpy(np.ascontiguousarray(encoded, dtype=np.float32)).cuda()[None]
         kpts, scores = self.batch_decode(hm)
         return kpts[0], scores[0]
+
+
+@register(KEYPOINT_CODECS, reference_name="UDPExpMaxHeatmap", mi355x_name="UDPExpMaxHeatmapMI355X")
+class UDPExpMaxHeatmap(ProbMap):
+    """Gaussian heatmaps decoded by expected-OKS maximisation (reference: ``mmpose/codecs/udp_expmax_heatmap.py:16-254``): the
+    ViTPose heads with the ProbPose decoder. Decode on the GPU, ``pp_expmax_heatmap_decode``: ``ProbMap``'s arithmetic on the RAW maps
+    (values below 0 and above 1 pass through), for a whole batch in one launch, optionally together with the flip-test average.
+
+    Args are the reference's (udp_expmax_heatmap.py:79-101): ``input_size`` [w, h], ``heatmap_size`` [W, H], ``heatmap_type``
+    ("gaussian" only), ``sigma``, ``radius_factor``, ``blur_kernel_size``, ``increase_sigma_with_padding``, ``normalize`` and
+    ``parzen_size`` - the last two are stored; the reference's decode does not use them either (``normalize`` acts in ``encode``,
+    ``parzen_size`` is an argument ``get_heatmap_expected_value`` ignores)."""
+
+    decode_kind = "expmax"
+
+    def __init__(self, input_size: Tuple[int, int], heatmap_size: Tuple[int, int], heatmap_type: str = "gaussian",
+                 sigma: float = 2.0, radius_factor: float = 0.0546875, blur_kernel_size: int = 11,
+                 increase_sigma_with_padding=False, normalize=False, parzen_size=0.1) -> None:
+        super().__init__(input_size, heatmap_size, heatmap_type=heatmap_type, sigma=sigma, radius_factor=radius_factor,
+                         blur_kernel_size=blur_kernel_size, increase_sigma_with_padding=increase_sigma_with_padding)
+        self.normalize = normalize
+        self.parzen_size = parzen_size
+        if self.heatmap_type == "combined":
+            raise NotImplementedError("UDPExpMaxHeatmap(heatmap_type='combined') (udp_expmax_heatmap.py:228-249: classification + offset "
+                                      "maps, argmax decode) has no MI355X kernel; the expected-OKS decode is the 'gaussian' branch")
+
+    def encode(self, keypoints, keypoints_visible=None, id_similarity=0.0, keypoints_visibility=None) -> dict:
+        raise NotImplementedError(
+            "UDPExpMaxHeatmap.encode (udp_expmax_heatmap.py:110-200) generates training targets and is outside the "
+            "MI355X inference hot path (SURVEY.md 2: 'decode only; encode is training')."
+        )
+
+    def _launch(self, hm, hmf, fi, taps, radius, avg, conv, out, shift_heatmap, dev) -> None:
+        B, K, H, W = hm.shape
+        _lib.call(
+            "pp_expmax_heatmap_decode", _lib.ptr(hm), _lib.ptr(hmf), _lib.ptr(fi), _lib.ptr(taps), _lib.ptr(radius), B, K, H, W,
+            float(self.input_size[0]), float(self.input_size[1]), _lib.ptr(avg), _lib.ptr(conv), _lib.ptr(out["locs"]),
+            _lib.ptr(out["keypoints"]), _lib.ptr(out["scores"]), 4 if (shift_heatmap and hmf is not None) else 0, _lib.stream_ptr(dev),
+        )  # fmt: skip  (flags: PP_DECODE_SHIFT_HEATMAP = 4)
+
+    def batch_decode(self, batch_heatmaps: torch.Tensor) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+        """(B, K, H, W) device tensor -> per-sample lists, each element shaped as ``decode`` returns."""
+        out = self.decode_device(batch_heatmaps)
+        kpts = out["keypoints"].cpu().numpy()
+        scores = out["scores"].cpu().numpy()
+        if not (np.isfinite(kpts).all() and np.isfinite(scores).all()):
+            raise FloatingPointError("UDPExpMaxHeatmap.decode: non-finite keypoints / scores (a heatmap holds a non-finite value)")
+        return [kpts[i][None] for i in range(kpts.shape[0])], [scores[i][None] for i in range(scores.shape[0])]
+
+
+@register(KEYPOINT_CODECS, reference_name="ArgMaxProbMap", mi355x_name="ArgMaxProbMapMI355X")
+class ArgMaxProbMap(UDPHeatmap):
+    """Probability maps decoded by UDP argmax + DARK (reference: ``mmpose/codecs/argmax_probmap.py:18-260``): the ProbPose head with
+    the ViTPose decoder, the argmax column of the paper's decoding ablation. ``decode`` / ``decode_device`` take MAPS, as the
+    reference's decode does, and run ``pp_udp_heatmap_decode`` on them - the same steps as ``UDPHeatmap.decode``. Behind a
+    ``ProbMapHead`` the engine starts from the logits instead and runs Sparsemax, the flip-test average and this decode in one launch
+    (``pp_argmax_probmap_decode``).
+
+    Args are the reference's (argmax_probmap.py:74-92): ``input_size`` [w, h], ``heatmap_size`` [W, H], ``heatmap_type`` ("gaussian"
+    only), ``sigma`` (-1), ``radius_factor``, ``blur_kernel_size`` (odd, at most 19), ``increase_sigma_with_padding``."""
+
+    decode_kind = "dark"
+
+    def __init__(self, input_size: Tuple[int, int], heatmap_size: Tuple[int, int], heatmap_type: str = "gaussian",
+                 sigma: float = -1, radius_factor: float = 0.0546875, blur_kernel_size: int = 11,
+                 increase_sigma_with_padding=False) -> None:
+        if heatmap_type == "combined":
+            raise NotImplementedError("ArgMaxProbMap(heatmap_type='combined') (argmax_probmap.py: classification + offset maps) has no "
+                                      "MI355X kernel; ProbPose's maps are 'gaussian'")
+        super().__init__(input_size, heatmap_size, heatmap_type=heatmap_type, sigma=sigma, radius_factor=radius_factor,
+                         blur_kernel_size=blur_kernel_size)
+        self.increase_sigma_with_padding = increase_sigma_with_padding
+
+    def encode(self, keypoints, keypoints_visible=None, id_similarity=0.0, keypoints_visibility=None) -> dict:
+        raise NotImplementedError(
+            "ArgMaxProbMap.encode (argmax_probmap.py:101-170) generates training targets and is outside the "
+            "MI355X inference hot path (SURVEY.md 2: 'decode only; encode is training')."
+        )

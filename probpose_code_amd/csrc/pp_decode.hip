@@ -8,23 +8,18 @@
 //
 // Everything data-dependent but wave-uniform is a template parameter so the hot loops are branch-free register
 // code: the OKS-kernel radius (0..9, dispatched by a scalar switch) and the row length per thread.
+// The Sparsemax stage (and the lane / block reductions) live in pp_decode_stages.h: pp_argmax_decode.hip runs the same stage.
 #include "pp_common.h"
 
 // numpy evaluates the f32 sub-pixel expressions one rounding per operator; keep it so.
 #pragma clang fp contract(off)
 
+#include "pp_decode_stages.h"
+
 namespace pp {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int RM = PP_MAX_RADIUS;  // largest radius: the x-padding the row pass may read
-constexpr int PAD = 12;            // x-padding of the LDS map either side: >= RM and a multiple of 4, so that a pixel quad (y, 4 q .. 4 q + 3)
-                                   // is a 16-byte aligned slot (ds_write_b128 / ds_read_b128: one conflict-free access per quad)
 constexpr int ROWD_SLACK = 7;      // the fp64 row slots' pitch is W + 0..7, chosen per workgroup (conv_banded)
-#ifndef PP_DEC_THREADS
-#define PP_DEC_THREADS 256  // dev A/B: 128 (two waves per workgroup, 64 x 48 maps only) measured 53 us against 36: the chain gets longer, nothing is saved
-#endif
-constexpr int DEC_THREADS = PP_DEC_THREADS;
 #ifndef PP_DEC_GX
 #define PP_DEC_GX 7
 #endif
@@ -32,16 +27,6 @@ constexpr int GX = PP_DEC_GX;  // outputs per work item in the row pass (sliding
                        // stride of 7 dwords (all 32 banks of a ds_read_b32 lane group distinct) and write the fp64 slots at 14 dwords
                        // (conflict-free per 16-lane group); 6 was 2-way on both
 constexpr int GY = 4;  // outputs per work item in the column pass
-constexpr int RED_BYTES = 512;  // cross-wave reduction scratch at the head of the dynamic LDS region
-
-// i / d for 0 <= i < 2^20, 1 <= d <= 2^12 in three VALU instructions (the integer division is ~25, and the kernel did some forty
-// of them per thread): (i + 0.5) / d is at least 0.5 / d away from an integer, the float product is off by < q 2^-22.
-struct FastDiv {
-    float r;
-    __device__ __forceinline__ explicit FastDiv(int d) : r(1.0f / (float)d) {}
-    __device__ __forceinline__ int operator()(int i) const { return (int)(((float)i + 0.5f) * r); }
-};
-
 struct ArgBest {
     float v;
     int idx;
@@ -169,86 +154,16 @@ __device__ __forceinline__ ArgBest conv_banded(float* __restrict__ mapf, double*
     return best;
 }
 
-// ---- lane exchanges of the xor butterfly (32, 16, 8, 4, 2, 1 - the pairing order __shfl_xor loops have, so sums keep their
-// bits) without the LDS queue: the gfx950 row swaps for 32 / 16 (each lane ends up with its own and its partner's value: any
-// commutative op takes them in either order), DPP row rotate / shifts / quad permutes below that.
-__device__ __forceinline__ int dpp_xor8(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x128, 0xf, 0xf, false); }  // row_ror:8
-__device__ __forceinline__ int dpp_xor4(int v) {
-    const int t = __builtin_amdgcn_update_dpp(0, v, 0x104, 0xf, 0x5, false);  // row_shl:4 into lanes 0-3, 8-11 of a row
-    return __builtin_amdgcn_update_dpp(t, v, 0x114, 0xf, 0xa, false);         // row_shr:4 into lanes 4-7, 12-15
-}
-__device__ __forceinline__ int dpp_xor2(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x4e, 0xf, 0xf, false); }  // quad_perm [2,3,0,1]
-__device__ __forceinline__ int dpp_xor1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0xb1, 0xf, 0xf, false); }  // quad_perm [1,0,3,2]
-
-template <class T, class Op>
-__device__ __forceinline__ T wave_allreduce(T v, Op op) {
-    static_assert(sizeof(T) == 4, "one dword");
-    auto I = [](T x) { return __builtin_bit_cast(int, x); };
-    auto V = [](int x) { return __builtin_bit_cast(T, x); };
-    {
-        const auto s = __builtin_amdgcn_permlane32_swap((unsigned)I(v), (unsigned)I(v), false, false);
-        v = op(V((int)s[0]), V((int)s[1]));
-    }
-    {
-        const auto s = __builtin_amdgcn_permlane16_swap((unsigned)I(v), (unsigned)I(v), false, false);
-        v = op(V((int)s[0]), V((int)s[1]));
-    }
-    v = op(v, V(dpp_xor8(I(v))));
-    v = op(v, V(dpp_xor4(I(v))));
-    v = op(v, V(dpp_xor2(I(v))));
-    v = op(v, V(dpp_xor1(I(v))));
-    return v;
-}
-
-// ---- block-wide reductions for the in-register Sparsemax (4 waves)
-struct SmxStat {
-    float s0, s1;
-    int n;  // candidates of the two rows, n0 | n1 << 16 (a row has at most 12 288 pixels)
-};
-
-__device__ __forceinline__ void block_max2(float& a, float& b, float* scratch) {
-    a = wave_allreduce(a, [](float x, float y) { return fmaxf(x, y); });
-    b = wave_allreduce(b, [](float x, float y) { return fmaxf(x, y); });
-    if (lane_id() == 0) {
-        scratch[2 * wave_id()] = a;
-        scratch[2 * wave_id() + 1] = b;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < DEC_THREADS / WAVE; ++w) {
-        a = fmaxf(a, scratch[2 * w]);
-        b = fmaxf(b, scratch[2 * w + 1]);
-    }
-}
-
-// `quiet`: no lane of this wave has a candidate left (wave-uniform) - its partial sums are zeros without the exchanges
-__device__ __forceinline__ SmxStat block_sum_stat(SmxStat v, bool quiet, SmxStat* scratch) {
-    if (!quiet) {
-        v.s0 = wave_allreduce(v.s0, [](float x, float y) { return x + y; });
-        v.s1 = wave_allreduce(v.s1, [](float x, float y) { return x + y; });
-        v.n = wave_allreduce(v.n, [](int x, int y) { return x + y; });
-    }
-    if (lane_id() == 0) scratch[wave_id()] = v;
-    __syncthreads();
-    SmxStat r = scratch[0];
-#pragma unroll
-    for (int w = 1; w < DEC_THREADS / WAVE; ++w) {  // fixed order: every thread gets the same bits
-        r.s0 += scratch[w].s0;
-        r.s1 += scratch[w].s1;
-        r.n += scratch[w].n;
-    }
-    return r;
-}
-
-__device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
-
 // NV = 16-byte vectors of the H*W row per thread (3 for 64x48, 7 for 96x72). Needs W % 4 == 0.
-template <bool HAS_FLIP, bool FROM_LOGITS, int NV>
+// Load modes: FROM_LOGITS - head logits, Sparsemax first (sparsemax_average); otherwise maps, taken as they are. RAW (maps only) is the
+// form pp_expmax_heatmap_decode launches: the maps may also be phase-separated, and a map with a non-finite value decodes to NaN.
+template <bool HAS_FLIP, bool FROM_LOGITS, int NV, bool RAW = false>
 __global__ __launch_bounds__(DEC_THREADS) void probmap_decode_kernel(
     const float* __restrict__ hm, const float* __restrict__ hm_flip, const int32_t* __restrict__ flip_indices,
     const double* __restrict__ taps, const int32_t* __restrict__ radius, int K, int H, int W, double in_w,
     double in_h, float temperature, float normalize, float* __restrict__ avg_out, float* __restrict__ conv_out,
     float* __restrict__ locs, double* __restrict__ keypoints, float* __restrict__ scores, int phased, int cap, int shift) {
+    static_assert(!(RAW && FROM_LOGITS), "RAW is a maps mode");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int bk = blockIdx.x;
@@ -256,18 +171,7 @@ __global__ __launch_bounds__(DEC_THREADS) void probmap_decode_kernel(
     const int Wp = W + 2 * PAD;
     const int HW = H * W, HW4 = HW >> 2, W4 = W >> 2;
     const FastDiv div_w(W), div_w4(W4);
-    // A thread owns the pixel QUADS q = tid + 256 e (e < NV): pixels (y, x0 .. x0 + 3), y = q / (W / 4), x0 = 4 (q % (W / 4)) - the same
-    // quads whatever the memory layout of the input, so both layouts give the same bits; a quad is one 16-byte aligned LDS slot.
-    // (Measured and dropped, round 4: lane pairs (l, l + 32) sharing an octet, numbered row-parity-major, so that a half-wave reads 512
-    // contiguous bytes of one phase block and two v_permlane32_swap interleave the columns - 39.3 / 37.3 us against 37.8 / 35.8 for the
-    // two 8-byte loads per quad below: the octet order puts the lanes' 16-byte LDS stores 32 bytes apart, 2-way conflicts.)
-    auto quad = [&](int e, int& y, int& x0) -> bool {
-        const int i4 = tid + e * DEC_THREADS;
-        if (i4 >= HW4) return false;
-        y = div_w4(i4);
-        x0 = (i4 - y * W4) * 4;
-        return true;
-    };
+    const QuadMap quad(tid, H, W);  // the thread's pixel quads (pp_decode_stages.h)
 
     // all LDS in the one dynamic region (16-B aligned carve offsets)
     ArgBest* red = reinterpret_cast<ArgBest*>(smem);                                         // [4] cross-wave argmax
@@ -282,15 +186,43 @@ __global__ __launch_bounds__(DEC_THREADS) void probmap_decode_kernel(
     const f32x4* srcf = nullptr;
     if (HAS_FLIP) srcf = reinterpret_cast<const f32x4*>(hm_flip + ((size_t)b * K + flip_indices[k]) * HW);
 
+    // A non-finite input must not decode to a pixel with a plausible score: the keypoint comes out as NaN, which the host mirror
+    // turns into a FloatingPointError.
+    auto write_nan = [&]() {
+        const float qnan = __builtin_nanf("");
+        if (avg_out)
+            for (int i = tid; i < HW; i += DEC_THREADS) avg_out[(size_t)bk * HW + i] = qnan;
+        if (conv_out)
+            for (int i = tid; i < HW; i += DEC_THREADS) conv_out[(size_t)bk * HW + i] = qnan;
+        if (tid == 0) {
+            locs[2 * bk + 0] = locs[2 * bk + 1] = qnan;
+            keypoints[2 * bk + 0] = keypoints[2 * bk + 1] = (double)qnan;
+            scores[bk] = qnan;
+        }
+    };
+
     if constexpr (!FROM_LOGITS) {
         // ---- load + flip-back + average: partner of pixels (y, x..x+3) is the reversed vector at (y, W-4-x)
+        float chk = 0.f;  // (RAW only)
 #pragma unroll
         for (int e = 0; e < NV; ++e) {
             int y, x;
             if (quad(e, y, x)) {
-                f32x4 v = src[y * W4 + (x >> 2)];
+                f32x4 v;
+                if constexpr (RAW) v = load_quad(src, true, y, x, phased, HW4, W4);
+                else v = src[y * W4 + (x >> 2)];
+                if constexpr (RAW) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) chk = __builtin_fmaf(v[j], 0.f, chk);  // x * 0 is NaN for x = +-inf / NaN
+                }
                 if (HAS_FLIP && !shift) {
-                    const f32x4 f = srcf[y * W4 + (W4 - 1 - (x >> 2))];
+                    f32x4 f;
+                    if constexpr (RAW) f = load_quad(srcf, true, y, W - 4 - x, phased, HW4, W4);
+                    else f = srcf[y * W4 + (W4 - 1 - (x >> 2))];
+                    if constexpr (RAW) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) chk = __builtin_fmaf(f[j], 0.f, chk);
+                    }
                     v = (v + f32x4{f[3], f[2], f[1], f[0]}) * 0.5f;
                 } else if (HAS_FLIP) {
                     // shift_heatmap (tta.py:64-66): the flipped-back map moves one pixel to the right, column 0 keeps its value:
@@ -299,240 +231,40 @@ __global__ __launch_bounds__(DEC_THREADS) void probmap_decode_kernel(
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int xx = x + j;
-                        v[j] = (v[j] + fr_[xx >= 1 ? W - xx : W - 1]) * 0.5f;
+                        if constexpr (RAW) {
+                            const int xs = xx >= 1 ? W - xx : W - 1;
+                            const float fv = phased ? reinterpret_cast<const float*>(srcf)[(y & 1) * (HW >> 1) + (xs & 1) * (HW >> 2) + (y >> 1) * (W >> 1) + (xs >> 1)]
+                                                    : fr_[xs];
+                            chk = __builtin_fmaf(fv, 0.f, chk);
+                            v[j] = (v[j] + fv) * 0.5f;
+                        } else {
+                            v[j] = (v[j] + fr_[xx >= 1 ? W - xx : W - 1]) * 0.5f;
+                        }
                     }
                 }
                 *reinterpret_cast<f32x4*>(mapf + y * Wp + PAD + x) = v;  // 16-byte aligned slot
-                if (avg_out) reinterpret_cast<f32x4*>(avg_out + (size_t)bk * HW)[y * W4 + (x >> 2)] = v;
+                if constexpr (!RAW) {
+                    if (avg_out) reinterpret_cast<f32x4*>(avg_out + (size_t)bk * HW)[y * W4 + (x >> 2)] = v;
+                }
+            }
+        }
+        if constexpr (RAW) {
+            if (__syncthreads_or(chk != chk)) {  // (workgroup-uniform)
+                write_nan();
+                return;
+            }
+            if (avg_out) {
+#pragma unroll
+                for (int e = 0; e < NV; ++e) {
+                    int y, x;
+                    if (quad(e, y, x))
+                        reinterpret_cast<f32x4*>(avg_out + (size_t)bk * HW)[y * W4 + (x >> 2)] = *reinterpret_cast<const f32x4*>(mapf + y * Wp + PAD + x);
+                }
             }
         }
     } else {
-        // ---- Sparsemax of this keypoint's row and (flip test) of its mirror partner's row, both in registers.
-        // Sort-free threshold search (Michelot): candidates z > tau, tau <- tau + (sum_cand (z - tau) - 1) / |cand|,
-        // starting from tau = max - 1 (a lower bound of the solution), until no candidate is dropped. The
-        // correction form keeps the sums O(1), so fp32 accumulation loses nothing against the fp32 reference.
-        float* fscr = reinterpret_cast<float*>(smem);
-        SmxStat* sscr = reinterpret_cast<SmxStat*>(smem + 64);
-        f32x4 z0[NV], z1[NV];
-        float m0 = -__builtin_inff(), m1 = -__builtin_inff(), chk = 0.f;
-        // a division costs nine VALU instructions, the row has 24 per thread: multiply when the temperature is a normal power of two
-        const unsigned t_bits = __builtin_bit_cast(unsigned, temperature);
-        const bool t_pow2 = (t_bits & 0x007fffffu) == 0 && (t_bits >> 23) >= 2 && (t_bits >> 23) <= 252;
-        const float t_inv = __builtin_bit_cast(float, (254u << 23) - t_bits);
-        // The quad (y, x0 ..) of a row in memory. Row-major: one 16-byte vector. Phase-separated (the fused deconvolution head
-        // writes the four 2x2 output phases one after the other, each a (H/2, W/2) row-major block): two 8-byte pairs - columns
-        // x0 / 2, x0 / 2 + 1 of row y / 2 of the phases (y & 1, 0) and (y & 1, 1) - interleaved.
-        auto load_quad = [&](const f32x4* base, bool ok, int y, int x0) -> f32x4 {
-            const float ninf = -__builtin_inff();
-            f32x4 r{ninf, ninf, ninf, ninf};
-            if (!ok) return r;
-            if (!phased) return base[y * W4 + (x0 >> 2)];
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
-            const f32x2* pb = reinterpret_cast<const f32x2*>(base) + ((y & 1) * HW4 + (y >> 1) * W4 + (x0 >> 2));  // (in pairs: a phase block is HW4 / 2 pairs)
-            const f32x2 a = pb[0], c = pb[HW4 >> 1];
-            return f32x4{a[0], c[0], a[1], c[1]};
-        };
-#pragma unroll
-        for (int e = 0; e < NV; ++e) {
-            int y = 0, x0 = 0;
-            const bool ok = quad(e, y, x0);
-            z0[e] = load_quad(src, ok, y, x0);
-            z1[e] = z0[e];
-            if (HAS_FLIP) z1[e] = load_quad(srcf, ok, y, x0);
-            if (t_pow2) {  // x / 2^k == x * 2^-k bit for bit (-inf of a lane without a quad stays -inf)
-                z0[e] = z0[e] * t_inv;
-                if (HAS_FLIP) z1[e] = z1[e] * t_inv;
-            } else {
-                z0[e] = z0[e] / temperature;
-                if (HAS_FLIP) z1[e] = z1[e] / temperature;
-            }
-            if (!HAS_FLIP) { const float ninf = -__builtin_inff(); z1[e] = f32x4{ninf, ninf, ninf, ninf}; }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                m0 = fmaxf(m0, z0[e][j]);
-                m1 = fmaxf(m1, z1[e][j]);
-                if (ok) {  // x * 0 is NaN for x = +-inf / NaN: one fma per logit finds a non-finite input (fmaxf would skip a NaN)
-                    chk = __builtin_fmaf(z0[e][j], 0.f, chk);
-                    if (HAS_FLIP) chk = __builtin_fmaf(z1[e][j], 0.f, chk);
-                }
-            }
-        }
-        if (chk != chk) m0 = __builtin_inff();
-        block_max2(m0, m1, fscr);
-        // A non-finite logit (an operand beyond the split-fp16 range upstream - numeric domain, include/probpose_mi355x.h - or a NaN input) must not
-        // decode to pixel 0 with a plausible score: the keypoint comes out as NaN, which the host mirror turns into a FloatingPointError.
-        if (!(fabsf(m0) < __builtin_inff()) || (HAS_FLIP && !(fabsf(m1) < __builtin_inff()))) {  // (workgroup-uniform)
-            const float qnan = __builtin_nanf("");
-            if (avg_out)
-                for (int i = tid; i < HW; i += DEC_THREADS) avg_out[(size_t)bk * HW + i] = qnan;
-            if (conv_out)
-                for (int i = tid; i < HW; i += DEC_THREADS) conv_out[(size_t)bk * HW + i] = qnan;
-            if (tid == 0) {
-                locs[2 * bk + 0] = locs[2 * bk + 1] = qnan;
-                keypoints[2 * bk + 0] = keypoints[2 * bk + 1] = (double)qnan;
-                scores[bk] = qnan;
-            }
-            return;
-        }
-        // normalize < 0 stands for the head's `normalize=None` (probmap_head.py:249,642-646): no Sparsemax, the map is
-        // clamp(x / T, 0, 1) - the same code with threshold 0, no shift and scale 1
-        const bool smx = normalize >= 0.f;
-        if (!smx) {
-            m0 = m1 = 0.f;
-            normalize = 1.f;
-        }
-#pragma unroll
-        for (int e = 0; e < NV; ++e) {
-            z0[e] -= m0;
-            z1[e] -= m1;
-        }
-        float tau0 = smx ? -1.0f : 0.f, tau1 = tau0;
-        int prev = -1;
-        bool alive = true;  // the thresholds only rise: a thread without a candidate now has none in any later round
-        // COMPACT form of the threshold search (round 6). The search only ever looks at the candidates of its FIRST threshold (z > max - 1: the
-        // thresholds rise, nothing comes back) - a few dozen of a row's 3 072 logits on a peaked map - yet every round walked all 24 (48 with
-        // the flipped pass) values of every thread and paid a block-wide reduction: ~260 instructions x 4 - 6 rounds of the kernel's ~2 550 per
-        // wave. Now the first threshold's candidates are packed into an LDS list once (a block-wide prefix sum of the per-thread counts) and
-        // every wave runs the rounds on the list by itself: a lane per candidate, wave reductions, no barrier. Same rounds, same thresholds up
-        // to the order of the fp32 sums. Rows with more than SMX_CAP candidates (a flat map) keep the walk below.
-        constexpr int SMX_CAP = 1024;
-        bool compact_done = false;
-        if (smx) {
-            int c = 0;
-#pragma unroll
-            for (int e = 0; e < NV; ++e)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    c += z0[e][j] > -1.0f ? 1 : 0;
-                    if (HAS_FLIP) c += z1[e][j] > -1.0f ? (1 << 16) : 0;
-                }
-            int inc = c;  // inclusive prefix over the wave's lanes (both counts in one word: a row has 3 072 .. 12 288 values)
-#pragma unroll
-            for (int o = 1; o < WAVE; o <<= 1) {
-                const int t = __shfl_up(inc, o);
-                if (lane_id() >= o) inc += t;
-            }
-            int* wtot = reinterpret_cast<int*>(smem + 192);
-            if (lane_id() == WAVE - 1) wtot[wave_id()] = inc;
-            __syncthreads();
-            int base = 0, tot = 0;
-#pragma unroll
-            for (int w = 0; w < DEC_THREADS / WAVE; ++w) {
-                const int t = wtot[w];
-                base += w < wave_id() ? t : 0;
-                tot += t;
-            }
-            const int n0 = tot & 0xffff, n1 = tot >> 16;
-            if (n0 <= SMX_CAP && n1 <= SMX_CAP) {  // (workgroup-uniform)
-                float* L0 = mapf;            // the map region is not written before the thresholds are known
-                float* L1 = mapf + SMX_CAP;
-                const int off = base + inc - c;
-                int o0 = off & 0xffff, o1 = off >> 16;
-#pragma unroll
-                for (int e = 0; e < NV; ++e)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (z0[e][j] > -1.0f) L0[o0++] = z0[e][j];
-                        if (HAS_FLIP && z1[e][j] > -1.0f) L1[o1++] = z1[e][j];
-                    }
-                __syncthreads();
-                for (int iter = 0; iter < 64; ++iter) {
-                    float s0 = 0.f, s1 = 0.f;
-                    int n = 0;
-                    for (int i = lane_id(); i < n0; i += WAVE) {
-                        const float d0 = L0[i] - tau0;
-                        if (d0 > 0.f) {
-                            s0 += d0;
-                            n += 1;
-                        }
-                    }
-                    if (HAS_FLIP)
-                        for (int i = lane_id(); i < n1; i += WAVE) {
-                            const float d1 = L1[i] - tau1;
-                            if (d1 > 0.f) {
-                                s1 += d1;
-                                n += 1 << 16;
-                            }
-                        }
-                    s0 = wave_allreduce(s0, [](float x, float y) { return x + y; });
-                    if (HAS_FLIP) s1 = wave_allreduce(s1, [](float x, float y) { return x + y; });
-                    n = wave_allreduce(n, [](int x, int y) { return x + y; });
-                    if (n == prev) break;
-                    prev = n;
-                    tau0 = tau0 + (s0 - 1.0f) / (float)(n & 0xffff);
-                    if (HAS_FLIP) tau1 = tau1 + (s1 - 1.0f) / (float)(n >> 16);
-                }
-                compact_done = true;
-                __syncthreads();  // every wave is through with the lists before the map takes their place
-            }
-        }
-        for (int iter = 0; iter < ((smx && !compact_done) ? 64 : 0); ++iter) {
-            SmxStat st{0.f, 0.f, 0};
-            if (alive) {
-#pragma unroll
-                for (int e = 0; e < NV; ++e)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float d0 = z0[e][j] - tau0;
-                        if (d0 > 0.f) {
-                            st.s0 += d0;
-                            st.n += 1;
-                        }
-                        if (HAS_FLIP) {
-                            const float d1 = z1[e][j] - tau1;
-                            if (d1 > 0.f) {
-                                st.s1 += d1;
-                                st.n += 1 << 16;
-                            }
-                        }
-                    }
-                alive = st.n != 0;
-            }
-            st = block_sum_stat(st, __builtin_amdgcn_ballot_w64(alive) == 0, sscr + (iter & 1) * (DEC_THREADS / WAVE));
-            if (st.n == prev) break;
-            prev = st.n;
-            tau0 = tau0 + (st.s0 - 1.0f) / (float)(st.n & 0xffff);
-            if (HAS_FLIP) tau1 = tau1 + (st.s1 - 1.0f) / (float)(st.n >> 16);
-        }
-#pragma unroll
-        for (int e = 0; e < NV; ++e) {
-            int y, x0;
-            if (quad(e, y, x0)) {
-                f32x4 v;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = clamp01(fmaxf(z0[e][j] - tau0, 0.0f) * normalize);
-                *reinterpret_cast<f32x4*>(mapf + y * Wp + PAD + x0) = v;
-            }
-        }
-        if (HAS_FLIP) {
-            __syncthreads();
-#pragma unroll
-            for (int e = 0; e < NV; ++e) {
-                int y, xf;
-                if (quad(e, y, xf)) {
-                    // pixels xf .. xf + 3 of the flipped pass land at W-1-xf .. W-4-xf: the reversed quad at column W-4-xf; exactly
-                    // one thread owns each cell
-                    if (!shift) {
-                        f32x4* d = reinterpret_cast<f32x4*>(mapf + y * Wp + PAD + (W - 4 - xf));
-                        f32x4 v = *d;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[3 - j] = (v[3 - j] + clamp01(fmaxf(z1[e][j] - tau1, 0.0f) * normalize)) * 0.5f;
-                        *d = v;
-                    } else {
-                        // shift_heatmap (tta.py:64-66): flipped pixel q lands at column W - q (q >= 1; q = 0 falls off), and the last
-                        // one, q = W - 1, also at column 0 - still exactly one thread per cell
-                        float* row = mapf + y * Wp + PAD;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const int q = xf + j;
-                            const float pv = clamp01(fmaxf(z1[e][j] - tau1, 0.0f) * normalize);
-                            if (q >= 1) row[W - q] = (row[W - q] + pv) * 0.5f;
-                            if (q == W - 1) row[0] = (row[0] + pv) * 0.5f;
-                        }
-                    }
-                }
-            }
-        }
+        // ---- Sparsemax of this keypoint's row and (flip test) of its mirror partner's row, then their average into the map
+        if (!sparsemax_average<HAS_FLIP, NV>(src, srcf, smem, mapf, H, W, temperature, normalize, phased, shift, write_nan)) return;  // (workgroup-uniform)
         if (avg_out) {
             __syncthreads();
             for (int i4 = tid; i4 < HW4; i4 += DEC_THREADS) {
@@ -718,21 +450,25 @@ static long decode_rowd_doubles(int H, int W) {
 typedef void (*DecodeKernel)(const float*, const float*, const int32_t*, const double*, const int32_t*, int, int, int,
                              double, double, float, float, float*, float*, float*, double*, float*, int, int, int);
 
+// mode: 0 probability maps, 1 head logits (Sparsemax first), 2 raw maps of any layout with the non-finite check (pp_expmax_heatmap_decode)
 template <int NV>
-static DecodeKernel pick_kernel(bool from_logits, bool flip) {
+static DecodeKernel pick_kernel(int mode, bool flip) {
+    if (mode == 2) return flip ? probmap_decode_kernel<true, false, NV, true> : probmap_decode_kernel<false, false, NV, true>;
+    const bool from_logits = mode == 1;
     if (from_logits) return flip ? probmap_decode_kernel<true, true, NV> : probmap_decode_kernel<false, true, NV>;
     return flip ? probmap_decode_kernel<true, false, NV> : probmap_decode_kernel<false, false, NV>;
 }
 
 }  // namespace pp
 
-static int decode_launch(bool from_logits, const float* hm, const float* hm_flip, const int32_t* flip_indices,
+static int decode_launch(int mode, const float* hm, const float* hm_flip, const int32_t* flip_indices,
                          const double* taps, const int32_t* radius, int B, int K, int H, int W, double in_w,
                          double in_h, float temperature, float normalize, float* avg_out, float* conv_out, float* locs,
                          double* keypoints, float* scores, void* stream, int phased = 0, int shift = 0) {
     using namespace pp;
+    const bool from_logits = mode == 1;
     PP_REQUIRE(B >= 0 && K > 0 && H > 0 && W > 0, PP_ERR_INVALID_ARG, "pp_probmap_(head_)decode: bad B/K/H/W");
-    PP_REQUIRE(!phased || (from_logits && H % 2 == 0 && W % 8 == 0), PP_ERR_UNSUPPORTED,
+    PP_REQUIRE(!phased || (mode != 0 && H % 2 == 0 && W % 8 == 0), PP_ERR_UNSUPPORTED,
                "pp_probmap_head_decode_phased: needs an even height and a width that is a multiple of 8");
     if (B == 0) return PP_OK;  // empty batch: nothing to read or write (buffers may be NULL)
     PP_REQUIRE(hm && taps && radius && locs && keypoints && scores, PP_ERR_INVALID_ARG,
@@ -749,16 +485,17 @@ static int decode_launch(bool from_logits, const float* hm, const float* hm_flip
         PP_REQUIRE(temperature > 0.f, PP_ERR_INVALID_ARG, "pp_probmap_head_decode: temperature must be positive");
     const int nv = (H * W / 4 + DEC_THREADS - 1) / DEC_THREADS;
     DecodeKernel kern = nullptr;
-    if (nv <= 3) kern = pick_kernel<3>(from_logits, hm_flip != nullptr);        // 64 x 48
-    else if (nv <= 7) kern = pick_kernel<7>(from_logits, hm_flip != nullptr);   // 96 x 72
-    else if (nv <= 12) kern = pick_kernel<12>(from_logits, hm_flip != nullptr);
+    if (nv <= 3) kern = pick_kernel<3>(mode, hm_flip != nullptr);        // 64 x 48
+    else if (nv <= 7) kern = pick_kernel<7>(mode, hm_flip != nullptr);   // 96 x 72
+    else if (nv <= 12) kern = pick_kernel<12>(mode, hm_flip != nullptr);
     PP_REQUIRE(kern != nullptr, PP_ERR_UNSUPPORTED, "pp_probmap_decode: H*W exceeds 12288 pixels");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)lds));
     hipLaunchKernelGGL(kern, dim3(B * K), dim3(DEC_THREADS), lds, s, hm, hm_flip, flip_indices, taps, radius, K, H,
                        W, in_w, in_h, temperature, normalize, avg_out, conv_out, locs, keypoints, scores, phased, (int)cap, (hm_flip && shift) ? 1 : 0);
-    PP_LAUNCH_CHECK();
+    if (mode == 2) PP_LAUNCH_CHECK_AS("pp_expmax_heatmap_decode");
+    else PP_LAUNCH_CHECK();
     return PP_OK;
 }
 
@@ -766,7 +503,7 @@ extern "C" int pp_probmap_decode(const float* hm, const float* hm_flip, const in
                                  const double* taps, const int32_t* radius, int B, int K, int H, int W,
                                  double in_w, double in_h, float* avg_out, float* conv_out, float* locs,
                                  double* keypoints, float* scores, void* stream) {
-    return decode_launch(false, hm, hm_flip, flip_indices, taps, radius, B, K, H, W, in_w, in_h, 1.f, 1.f, avg_out,
+    return decode_launch(0, hm, hm_flip, flip_indices, taps, radius, B, K, H, W, in_w, in_h, 1.f, 1.f, avg_out,
                          conv_out, locs, keypoints, scores, stream);
 }
 
@@ -774,7 +511,7 @@ extern "C" int pp_probmap_head_decode(const float* logits, const float* logits_f
                                       const double* taps, const int32_t* radius, int B, int K, int H, int W,
                                       double in_w, double in_h, float temperature, float normalize, float* avg_out,
                                       float* conv_out, float* locs, double* keypoints, float* scores, void* stream) {
-    return decode_launch(true, logits, logits_flip, flip_indices, taps, radius, B, K, H, W, in_w, in_h, temperature,
+    return decode_launch(1, logits, logits_flip, flip_indices, taps, radius, B, K, H, W, in_w, in_h, temperature,
                          normalize, avg_out, conv_out, locs, keypoints, scores, stream);
 }
 
@@ -783,7 +520,7 @@ extern "C" int pp_probmap_head_decode_phased(const float* logits, const float* l
                                              double in_w, double in_h, float temperature, float normalize,
                                              float* avg_out, float* conv_out, float* locs, double* keypoints,
                                              float* scores, void* stream) {
-    return decode_launch(true, logits, logits_flip, flip_indices, taps, radius, B, K, H, W, in_w, in_h, temperature,
+    return decode_launch(1, logits, logits_flip, flip_indices, taps, radius, B, K, H, W, in_w, in_h, temperature,
                          normalize, avg_out, conv_out, locs, keypoints, scores, stream, 1);
 }
 
@@ -795,7 +532,19 @@ extern "C" int pp_probmap_decode_flags(const float* maps, const float* maps_flip
     PP_REQUIRE((flags & ~(PP_DECODE_LOGITS | PP_DECODE_PHASED | PP_DECODE_SHIFT_HEATMAP)) == 0, PP_ERR_INVALID_ARG, "pp_probmap_decode_flags: unknown flag");
     const bool logits = (flags & PP_DECODE_LOGITS) != 0;
     PP_REQUIRE(logits || !(flags & PP_DECODE_PHASED), PP_ERR_INVALID_ARG, "pp_probmap_decode_flags: PP_DECODE_PHASED needs PP_DECODE_LOGITS");
-    return decode_launch(logits, maps, maps_flip, flip_indices, taps, radius, B, K, H, W, in_w, in_h, logits ? temperature : 1.f,
+    return decode_launch(logits ? 1 : 0, maps, maps_flip, flip_indices, taps, radius, B, K, H, W, in_w, in_h, logits ? temperature : 1.f,
                          logits ? normalize : 1.f, avg_out, conv_out, locs, keypoints, scores, stream, (flags & PP_DECODE_PHASED) ? 1 : 0,
                          (flags & PP_DECODE_SHIFT_HEATMAP) ? 1 : 0);
+}
+
+// UDPExpMaxHeatmap.decode (udp_expmax_heatmap.py, heatmap_type "gaussian"): the expected-OKS decode on RAW maps - no temperature, no
+// Sparsemax, no clamp - row-major or phase-separated. The kernel's arithmetic behind a load mode of its own.
+extern "C" int pp_expmax_heatmap_decode(const float* maps, const float* maps_flip, const int32_t* flip_indices, const double* taps,
+                                        const int32_t* radius, int B, int K, int H, int W, double in_w, double in_h, float* avg_out,
+                                        float* conv_out, float* locs, double* keypoints, float* scores, int flags, void* stream) {
+    using namespace pp;
+    PP_REQUIRE((flags & ~(PP_DECODE_PHASED | PP_DECODE_SHIFT_HEATMAP)) == 0, PP_ERR_INVALID_ARG, "pp_expmax_heatmap_decode: unknown flag");
+    PP_REQUIRE(K <= 17, PP_ERR_UNSUPPORTED, "pp_expmax_heatmap_decode: the reference's OKS-kernel table has 17 sigmas (K <= 17)");
+    return decode_launch(2, maps, maps_flip, flip_indices, taps, radius, B, K, H, W, in_w, in_h, 1.f, 1.f, avg_out, conv_out, locs, keypoints,
+                         scores, stream, (flags & PP_DECODE_PHASED) ? 1 : 0, (flags & PP_DECODE_SHIFT_HEATMAP) ? 1 : 0);
 }

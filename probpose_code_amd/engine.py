@@ -97,7 +97,7 @@ class ProbPoseEngine:
                  bgr_to_rgb: bool = True, temperature: float = 0.5, normalize: Optional[float] = 1.0,
                  input_size: Optional[Sequence[int]] = None, ln_eps: float = 1e-6, precision: str = "f16x3",
                  device="cuda", plan: Optional[Dict[str, object]] = None, head_kind: Optional[str] = None,
-                 blur_kernel_size: int = 11):
+                 blur_kernel_size: int = 11, decode: Optional[str] = None):
         if precision not in PREC:
             raise ValueError(f"precision must be one of {list(PREC)}, got {precision!r}")
         self.device = torch.device(device)
@@ -127,6 +127,13 @@ class ProbPoseEngine:
         if blur_kernel_size % 2 != 1 or not 1 <= blur_kernel_size <= 2 * _lib.PP_MAX_RADIUS + 1:
             raise ValueError(f"blur_kernel_size must be odd and at most {2 * _lib.PP_MAX_RADIUS + 1}, got {blur_kernel_size}")
         self.blur_kernel_size = int(blur_kernel_size)
+        # The decoding rule behind the head (the codec's `decode_kind`): "expmax" - expected-OKS maximisation (ProbMap, UDPExpMaxHeatmap) - or
+        # "dark" - UDP argmax + DARK (UDPHeatmap, ArgMaxProbMap; `blur_kernel_size` is its Gaussian's). None: the head's own pairing
+        # (probmap -> expmax, heatmap -> dark). The two swapped pairings have launches of their own, see run_head.
+        own = "expmax" if self.head_kind == "probmap" else "dark"
+        if decode not in (None, "expmax", "dark"):
+            raise ValueError(f"decode must be 'expmax', 'dark' or None (the head's own: {own!r}), got {decode!r}")
+        self.decode = own if decode is None else decode
         self.heads = num_heads
         self.H, self.W = img_size
         self.P, self.pad = patch_size, patch_padding
@@ -146,7 +153,10 @@ class ProbPoseEngine:
         self.temperature = float(temperature)
         self.normalize = normalize
         self.ln_eps = float(ln_eps)
-        if self.head_kind == "probmap":
+        if self.decode == "expmax":
+            if self.head_kind == "heatmap" and self.K > 17:
+                raise ValueError(f"the expected-OKS decode is defined for at most 17 keypoints - the reference's OKS-kernel table "
+                                 f"(post_processing.py:16) has 17 sigmas - but the head has {self.K}")
             taps, radius = oks_kernel_taps(self.K, self.Hh, self.Wh)
             self.taps = torch.from_numpy(taps).to(self.device)
             self.radius = torch.from_numpy(radius).to(self.device)
@@ -744,10 +754,16 @@ class ProbPoseEngine:
                 fi = self._flip_indices(flip_indices) if flip_test else None
                 lf = logits[B:] if flip_test else None
                 flags = (2 if self._logits_phased else 0) | (4 if (shift_heatmap and flip_test) else 0)  # PP_DECODE_PHASED | _SHIFT_HEATMAP
-                self._call("head_decode", "pp_udp_heatmap_decode", logits.data_ptr(), _lib.ptr(lf), _lib.ptr(fi), B, self.K, self.Hh, self.Wh,
-                           float(self.input_size[0]), float(self.input_size[1]), self.blur_kernel_size,
-                           ws["heatmaps"].data_ptr() if return_heatmaps else None, ws["locs"].data_ptr(), ws["keypoints"].data_ptr(),
-                           ws["scores"].data_ptr(), flags, st)
+                if self.decode == "dark":
+                    self._call("head_decode", "pp_udp_heatmap_decode", logits.data_ptr(), _lib.ptr(lf), _lib.ptr(fi), B, self.K, self.Hh, self.Wh,
+                               float(self.input_size[0]), float(self.input_size[1]), self.blur_kernel_size,
+                               ws["heatmaps"].data_ptr() if return_heatmaps else None, ws["locs"].data_ptr(), ws["keypoints"].data_ptr(),
+                               ws["scores"].data_ptr(), flags, st)
+                else:  # UDPExpMaxHeatmap.decode: the expected-OKS decode on the raw maps
+                    self._call("head_decode", "pp_expmax_heatmap_decode", logits.data_ptr(), _lib.ptr(lf), _lib.ptr(fi), self.taps.data_ptr(),
+                               self.radius.data_ptr(), B, self.K, self.Hh, self.Wh, float(self.input_size[0]), float(self.input_size[1]),
+                               ws["heatmaps"].data_ptr() if return_heatmaps else None, None, ws["locs"].data_ptr(),
+                               ws["keypoints"].data_ptr(), ws["scores"].data_ptr(), flags, st)
             out = dict(keypoints=ws["keypoints"], scores=ws["scores"], locs=ws["locs"], scalars=ws["scalars"])  # (scalars: zeros, see _workspace)
             if return_heatmaps:
                 out["heatmaps"] = ws["heatmaps"]
@@ -770,11 +786,18 @@ class ProbPoseEngine:
             fi = self._flip_indices(flip_indices) if flip_test else None
             lf = logits[B:] if flip_test else None
             flags = 1 | (2 if self._logits_phased else 0) | (4 if (shift_heatmap and flip_test) else 0)  # PP_DECODE_LOGITS | _PHASED | _SHIFT_HEATMAP
-            self._call("head_decode", "pp_probmap_decode_flags", logits.data_ptr(), _lib.ptr(lf), _lib.ptr(fi), self.taps.data_ptr(),
-                      self.radius.data_ptr(), B, self.K, self.Hh, self.Wh, float(self.input_size[0]),
-                      float(self.input_size[1]), self.temperature, -1.0 if self.normalize is None else float(self.normalize),  # (< 0: no Sparsemax)
-                      ws["heatmaps"].data_ptr() if return_heatmaps else None, None, ws["locs"].data_ptr(),
-                      ws["keypoints"].data_ptr(), ws["scores"].data_ptr(), flags, st)
+            if self.decode == "expmax":
+                self._call("head_decode", "pp_probmap_decode_flags", logits.data_ptr(), _lib.ptr(lf), _lib.ptr(fi), self.taps.data_ptr(),
+                          self.radius.data_ptr(), B, self.K, self.Hh, self.Wh, float(self.input_size[0]),
+                          float(self.input_size[1]), self.temperature, -1.0 if self.normalize is None else float(self.normalize),  # (< 0: no Sparsemax)
+                          ws["heatmaps"].data_ptr() if return_heatmaps else None, None, ws["locs"].data_ptr(),
+                          ws["keypoints"].data_ptr(), ws["scores"].data_ptr(), flags, st)
+            else:  # ArgMaxProbMap.decode behind the head's Sparsemax: one launch from the logits (flags without PP_DECODE_LOGITS)
+                self._call("head_decode", "pp_argmax_probmap_decode", logits.data_ptr(), _lib.ptr(lf), _lib.ptr(fi), B, self.K, self.Hh, self.Wh,
+                           float(self.input_size[0]), float(self.input_size[1]), self.temperature,
+                           -1.0 if self.normalize is None else float(self.normalize), self.blur_kernel_size,
+                           ws["heatmaps"].data_ptr() if return_heatmaps else None, ws["locs"].data_ptr(), ws["keypoints"].data_ptr(),
+                           ws["scores"].data_ptr(), flags & ~1, st)
             if two:
                 self._fork_join(self._head_stream, cur)
             else:

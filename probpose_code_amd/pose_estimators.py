@@ -555,6 +555,22 @@ class TopdownPoseEstimator(nn.Module):
         self.reset_engine()
         return super()._apply(fn, *args, **kwargs)
 
+    def _engine_options(self) -> dict:
+        """The engine's constructor arguments as the module's parts give them (no device, no weights)."""
+        dp, bb, hd = self.data_preprocessor, self.backbone, self.head
+        codec = hd.decoder
+        heatmap = isinstance(hd, HeatmapHead)  # the ViTPose baseline: no towers (engine head_kind "heatmap")
+        # the codec chooses the decoding rule: "expmax" (ProbMap, UDPExpMaxHeatmap) or "dark" (UDPHeatmap, ArgMaxProbMap; the blur's
+        # kernel size is the codec's then); a codec without the attribute keeps the head's own pairing
+        decode = getattr(codec, "decode_kind", "dark" if heatmap else "expmax")
+        return dict(
+            num_heads=bb.num_heads, img_size=bb.img_size, patch_size=bb.patch_size,
+            patch_padding=bb.patch_padding, mean=dp.mean_values, std=dp.std_values,
+            bgr_to_rgb=dp.channel_conversion, temperature=getattr(hd, "temperature", 1.0), normalize=getattr(hd, "normalize", None),
+            input_size=tuple(codec.input_size), ln_eps=bb.ln_eps, precision=self.precision,
+            head_kind="heatmap" if heatmap else "probmap", decode=decode,
+            blur_kernel_size=int(getattr(codec, "blur_kernel_size", 11)) if decode == "dark" else 11)
+
     @property
     def engine(self) -> ProbPoseEngine:
         if self._engine is None:
@@ -562,15 +578,8 @@ class TopdownPoseEstimator(nn.Module):
             if dev.type != "cuda":
                 raise RuntimeError("the MI355X pose estimator has no CPU path: move the model to the GPU "
                                    "(`model.to('cuda')`, as init_model does, apis/inference.py:128)")
-            dp, bb, hd = self.data_preprocessor, self.backbone, self.head
-            codec = hd.decoder
-            heatmap = isinstance(hd, HeatmapHead)  # the ViTPose baseline: no towers, UDP-DARK decode (engine head_kind "heatmap")
-            self._engine = ProbPoseEngine(
-                self.state_dict(), num_heads=bb.num_heads, img_size=bb.img_size, patch_size=bb.patch_size,
-                patch_padding=bb.patch_padding, mean=dp.mean_values, std=dp.std_values,
-                bgr_to_rgb=dp.channel_conversion, temperature=getattr(hd, "temperature", 1.0), normalize=getattr(hd, "normalize", None),
-                input_size=tuple(codec.input_size), ln_eps=bb.ln_eps, precision=self.precision, device=dev,
-                head_kind="heatmap" if heatmap else "probmap", blur_kernel_size=int(getattr(codec, "blur_kernel_size", 11)) if heatmap else 11)
+            codec = self.head.decoder
+            self._engine = ProbPoseEngine(self.state_dict(), device=dev, **self._engine_options())
             assert (self._engine.Wh, self._engine.Hh) == tuple(codec.heatmap_size), (
                 f"decoder heatmap_size {tuple(codec.heatmap_size)} does not match the head's output "
                 f"{(self._engine.Wh, self._engine.Hh)}")
