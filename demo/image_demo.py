@@ -39,6 +39,8 @@ def main():
     ap.add_argument("checkpoint")
     ap.add_argument("--out-file", default=None)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--decode", default="host", choices=["host", "device"],
+                    help="device: a JPEG file is Huffman-decoded on the host and reconstructed on the GPU (the same pixels)")
     ap.add_argument("--bboxes", default=None, help="x0,y0,x1,y1;x0,y0,x1,y1;... (default: the whole image)")
     ap.add_argument("--precision", default=None, choices=[None, "f16x3", "bf16", "f32"],
                     help="overrides model.precision of the config (default there: f16x3, the mode within 1e-3 of the fp32 reference)")
@@ -69,6 +71,8 @@ def main():
     if args.draw_heatmap:
         opts = dict(opts or {}, **{"model.test_cfg.output_heatmaps": True})
     model = apis.init_model(args.config, ckpt, device=args.device, cfg_options=opts)
+    if args.decode == "device":
+        apis.use_device_decode(model)
     boxes = None
     if args.bboxes:
         boxes = np.array([[float(v) for v in b.split(",")] for b in args.bboxes.split(";")], np.float32)

@@ -757,6 +757,53 @@ int pp_draw_poses(const void* image_rgb, int img_h, int img_w, const float* keyp
 /* cv2.resize(src, (dst_w, dst_h), INTER_LINEAR) of an RGB uint8 image, restated in fp32 (half-pixel centres, edge clamp). */
 int pp_resize_bilinear_u8(const void* src_rgb, int src_h, int src_w, void* dst_rgb, int dst_h, int dst_w, void* stream);
 
+/* Split JPEG decoder (added under version 4: purely additive). The serial part - markers and Huffman codes - runs on host
+ * threads (csrc/pp_jpeg_host.h), the data-parallel rest - dequantisation, 8x8 inverse DCT, chroma upsampling, YCbCr -> BGR,
+ * HWC packing - in csrc/pp_jpeg.hip. The pixels are those of libjpeg-turbo's default decoder (islow IDCT, fancy upsampling)
+ * as mmcv.imread / cv2.imdecode / Pillow return them, bit for bit; the integer rules are stated in csrc/pp_jpeg.hip.
+ * Accepted: SOF0 / SOF1, 8 bits, Huffman coding, one interleaved scan, 1 component or 3 components with chroma sampled 1x1
+ * and luma 1x1, 2x1 or 2x2, any DQT / DHT tables, restart intervals. Everything else, and every irregular stream (bad code,
+ * wrong or missing RSTn, data ending early, coefficient index past 63, missing table, zero dimension), is
+ * PP_ERR_UNSUPPORTED with a reason: the caller decodes such a file on the host as before. No partial images. */
+typedef struct {
+    int32_t width, height, ncomp, precision;
+    int32_t hs, vs;                 /* luma sampling factors (chroma is 1x1)                              */
+    int32_t mcus_x, mcus_y;         /* MCU grid                                                          */
+    int32_t comp_bw[3], comp_bh[3]; /* 8x8 blocks per row / block rows of each component, whole MCUs    */
+    int32_t restart_interval;       /* MCUs between RSTn markers, 0: none                                */
+    int32_t supported;              /* 1: inside the accepted subset                                      */
+    int64_t coef_count;             /* int16 coefficients of all components = 64 x blocks                */
+    char reason[96];                /* why the file was refused ("" when supported)                      */
+} pp_jpeg_info;
+
+/* One image of a batched reconstruct (a device table of these drives both launches). coef: info.coef_count int16, per
+ * component [block_row][block_col][64] in natural order; qtables: ncomp x 64 uint16, natural order; planes:
+ * info.coef_count bytes of scratch (the component planes, 8-byte aligned); out: (height, width, 3) uint8 BGR. */
+typedef struct {
+    const int16_t* coef;
+    const uint16_t* qtables;
+    uint8_t* planes;
+    uint8_t* out;
+    int32_t width, height, ncomp, hs, vs, mcus_x, mcus_y, reserved;
+} pp_jpeg_desc;
+
+/* Host only, re-entrant, no HIP call. data_host: the file's bytes. PP_OK: *info describes a file pp_jpeg_entropy_decode
+ * accepts as far as its headers tell; PP_ERR_UNSUPPORTED: info->reason (and pp_last_error) say why. */
+int pp_jpeg_probe(const void* data_host, size_t size, pp_jpeg_info* info);
+/* Host only, re-entrant, no HIP call: the quantised coefficients of the file into coef_host (coef_capacity int16 values,
+ * PP_ERR_WORKSPACE when that is fewer than info->coef_count) and each component's quantisation table into qtables_host
+ * (3 x 64 uint16). On any status but PP_OK the buffers hold no image. */
+int pp_jpeg_entropy_decode(const void* data_host, size_t size, int16_t* coef_host, long long coef_capacity,
+                           uint16_t* qtables_host, pp_jpeg_info* info);
+/* Bytes of plane scratch for n images (infos_host: n pp_jpeg_info), each image's share rounded up to 256: image i's planes
+ * start at the sum of the shares before it. < 0: error. */
+long long pp_jpeg_scratch_bytes(const pp_jpeg_info* infos_host, int n);
+/* Pixels of n images of any mix of sizes and sampling in two launches ("jpeg_idct", "jpeg_color" of pp_launch_count):
+ * descriptors: n pp_jpeg_desc on the device; max_blocks / max_height / max_width: the largest block count
+ * (coef_count / 64), height and width in the table - they size the launch grids, every image is bounded by its own entry. */
+int pp_jpeg_reconstruct_bgr_batch(const pp_jpeg_desc* descriptors, int n, long long max_blocks, int max_height, int max_width,
+                                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,10 @@ SIGNATURES = {
     "pp_draw_poses": (
         c_int, [_P, c_int, c_int, _P, _P, _P, c_int, c_int, _P, _P, _P, c_int, c_double, c_float, c_float, c_float, _P, _P]),
     "pp_resize_bilinear_u8": (c_int, [_P, c_int, c_int, _P, c_int, c_int, _P]),
+    "pp_jpeg_probe": (c_int, [_P, ctypes.c_size_t, _P]),
+    "pp_jpeg_entropy_decode": (c_int, [_P, ctypes.c_size_t, _P, c_longlong, _P, _P]),
+    "pp_jpeg_scratch_bytes": (c_longlong, [_P, c_int]),
+    "pp_jpeg_reconstruct_bgr_batch": (c_int, [_P, c_int, c_longlong, c_int, c_int, _P]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -151,10 +151,28 @@ def _val_pipeline(model) -> T.Compose:
             steps[2]["input_size"] = tuple(int(v) for v in model.head.decoder.input_size)
         pipe = T.Compose([dict(t) for t in steps])
         for t in pipe.transforms:
-            if isinstance(t, T.TopdownAffine) and t.device is None:
+            if isinstance(t, (T.TopdownAffine, T.LoadImage)) and t.device is None:
                 t.device = str(next(model.parameters()).device)
         model._val_pipeline = pipe
     return pipe
+
+
+def use_device_decode(model, on: bool = True) -> None:
+    """Switch the ``LoadImage`` of the model's val pipeline to ``imdecode_backend="mi355x"`` (files decoded on the device,
+    ``jpeg.imread_device``) or back to the host decoder: what ``--decode device`` of the demo does."""
+    for t in _val_pipeline(model).transforms:
+        if isinstance(t, T.LoadImage):
+            t.imdecode_backend = "mi355x" if on else "cv2"
+
+
+def _load_frame(pipeline, path: str):
+    """A file for ``inference_topdown``: through the decoder the pipeline's ``LoadImage`` names."""
+    for t in pipeline.transforms:
+        if isinstance(t, T.LoadImage) and t.imdecode_backend == "mi355x":
+            from .jpeg import imread_device
+
+            return imread_device(path, t.device or "cuda")
+    return load_image_bgr(path)
 
 
 def _frame_batch(model, img, bboxes, bbox_format):
@@ -164,7 +182,7 @@ def _frame_batch(model, img, bboxes, bbox_format):
     img_path = img if isinstance(img, str) else None  # kept beside the decoded-once pixels (apis/inference.py:182-186: dict(img_path=img))
     if bboxes is None or len(bboxes) == 0:
         if isinstance(img, str):
-            img = load_image_bgr(img)  # (the reference opens the file for its size, then LoadImage reads it again per box)
+            img = _load_frame(pipeline, img)  # (the reference opens the file for its size, then LoadImage reads it again per box)
         h, w = img.shape[:2]
         bboxes = np.array([[0, 0, w, h]], dtype=np.float32)
     else:
@@ -173,7 +191,7 @@ def _frame_batch(model, img, bboxes, bbox_format):
         if bbox_format == "xywh":
             bboxes = T.bbox_xywh2xyxy(bboxes)
         if isinstance(img, str):
-            img = load_image_bgr(img)  # decoded once for all boxes
+            img = _load_frame(pipeline, img)  # decoded once for all boxes
     data_list = []
     for bbox in bboxes:
         data_info = dict(img=img)

@@ -3,7 +3,9 @@ and ``test_evaluator``): the person instances of a dataset in batches, the model
 
 ``test_dataset`` keeps every stage busy at once:
   * decode: the distinct images of the next batches are decoded on a thread pool (``apis.load_image_bgr``), at least two
-    batches ahead; an image is dropped once its last instance has been batched;
+    batches ahead; an image is dropped once its last instance has been batched. With ``decode="device"`` the threads run only
+    the Huffman half (``jpeg.entropy_decode``) and the images of a batch are reconstructed on the device in ONE
+    ``pp_jpeg_reconstruct_bgr_batch`` call on the producer stream, ahead of the warp that reads them in place;
   * crops: the val pipeline through ``Compose.batched`` - box arithmetic on the host, ONE ``pp_warp_affine_u8_batch`` launch
     for the batch, its images uploaded with one copy - on a producer stream, under the model step of the batch before;
   * model: ``test_step_stream`` (full batches replay the captured graph, a partial last batch runs kernel by kernel);
@@ -159,24 +161,32 @@ def build_evaluator(cfg, dataset=None, device: str = "cuda"):
 
 def _pipeline_of(model, dataset):
     from . import apis
-    from .transforms import TopdownAffine
+    from .transforms import LoadImage, TopdownAffine
 
     pipe = getattr(dataset, "pipeline", None)
     if pipe is None or not pipe.transforms:
         return apis._val_pipeline(model)
     dev = str(next(model.parameters()).device)
     for t in pipe.transforms:
-        if isinstance(t, TopdownAffine) and t.device is None:
+        if isinstance(t, (TopdownAffine, LoadImage)) and t.device is None:
             t.device = dev
     return pipe
 
 
 def test_dataset(model, dataset, evaluator=None, batch_size: int = 64, workers: int = 8, depth: int = 2,
-                 sink: Optional[Callable[[list], None]] = None) -> dict:
+                 sink: Optional[Callable[[list], None]] = None, decode: str = "host") -> dict:
     """Run ``model`` over every instance of ``dataset`` (``get_data_info(i)``, i in order) and return the evaluator's metrics
-    (``{}`` without one). ``sink``, when given, receives every batch's list of PoseDataSample, in order."""
+    (``{}`` without one). ``sink``, when given, receives every batch's list of PoseDataSample, in order. ``decode``: "host"
+    (``apis.load_image_bgr`` on the threads) or "device" (the split JPEG decoder of ``jpeg``: the same pixels; a file outside
+    its subset is decoded on the host as before)."""
+    from . import jpeg
     from .apis import load_image_bgr
-    from .transforms import pseudo_collate
+    from .transforms import BatchStaging, pseudo_collate
+
+    if decode not in ("host", "device"):
+        raise ValueError(f'decode must be "host" or "device", got {decode!r}')
+    decode_fn = jpeg.decode_or_host if decode == "device" else load_image_bgr
+    jpeg_staging = BatchStaging()
 
     n = len(dataset)
     infos = [dataset.get_data_info(i) for i in range(n)]
@@ -194,15 +204,29 @@ def test_dataset(model, dataset, evaluator=None, batch_size: int = 64, workers: 
         while submitted < min(k, len(plan)):
             for key in plan[submitted].images:
                 if key not in decoded:
-                    decoded[key] = pool.submit(load_image_bgr, key)
+                    decoded[key] = pool.submit(decode_fn, key)
             submitted += 1
 
     producer = torch.cuda.Stream(device=device)
+    on_device: Dict[str, torch.Tensor] = {}  # decode="device": image key -> its reconstructed pixels, until its last batch
+    fell_back = set()
+
+    def reconstruct(keys):
+        """The pixels of a batch's images; the coefficient sets among them that are not on the device yet in one call."""
+        results = {key: decoded[key].result() for key in keys if key not in on_device}
+        todo = [key for key, r in results.items() if isinstance(r, jpeg.JpegCoefficients)]
+        host = set(results) - set(todo) - fell_back  # files outside the decoder's subset: counted once
+        jpeg.fallbacks += len(host)
+        fell_back.update(host)
+        if todo:
+            with torch.cuda.stream(producer):
+                on_device.update(zip(todo, jpeg.reconstruct_batch([results[key] for key in todo], device, jpeg_staging)))
+        return [on_device[key] if key in on_device else results[key] for key in keys]
 
     def batches():
         for k, b in enumerate(plan):
             queue_until(k + 1 + ahead)
-            pixels = [decoded[key].result() for key in b.images]
+            pixels = reconstruct(b.images) if decode == "device" else [decoded[key].result() for key in b.images]
             data_list = []
             for i, j in zip(b.indices, b.crop_image):
                 d = dict(infos[i])
@@ -211,6 +235,7 @@ def test_dataset(model, dataset, evaluator=None, batch_size: int = 64, workers: 
             for key in b.images:
                 if last[key] == k:
                     del decoded[key]
+                    on_device.pop(key, None)
             with torch.cuda.stream(producer):
                 packed = pipeline.batched(data_list)
             consumer = torch.cuda.current_stream(device)

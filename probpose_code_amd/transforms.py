@@ -260,13 +260,16 @@ def fix_bbox_aspect_ratio_xyxy(bbox: np.ndarray, aspect_ratio: float = 3 / 4, pa
 class LoadImage(BaseTransform):
     """mmpose/datasets/transforms/loading.py:12-107: ``results['img']`` from ``img_path`` (BGR uint8; mmcv.imread [3P]) or the
     array / device tensor already there; ``img_shape``, ``ori_shape``; ``pad_to_aspect_ratio``: the image is padded with 255
-    so that the padded 3:4 box lies inside it, box (and keypoints, when present) shifted."""
+    so that the padded 3:4 box lies inside it, box (and keypoints, when present) shifted. ``imdecode_backend="mi355x"``: the
+    file is decoded on the device (``jpeg.imread_device``: the same pixels as a device tensor; files outside its subset go
+    through the host decoder); any other value: the host decoder."""
 
     def __init__(self, pad_to_aspect_ratio: bool = False, to_float32: bool = False, color_type: str = "color",
                  imdecode_backend: str = "cv2", backend_args: Optional[dict] = None, ignore_empty: bool = False, **kwargs):
         if color_type != "color":
             raise NotImplementedError("LoadImage: only color_type='color' (3-channel BGR) is implemented")
         self.pad_to_aspect_ratio, self.to_float32, self.ignore_empty = pad_to_aspect_ratio, to_float32, ignore_empty
+        self.imdecode_backend, self.device = imdecode_backend, kwargs.get("device")
 
     def transform(self, results: dict) -> Optional[dict]:
         try:
@@ -274,13 +277,18 @@ class LoadImage(BaseTransform):
                 from .apis import load_image_bgr
 
                 try:
-                    img = load_image_bgr(results["img_path"])
+                    if self.imdecode_backend == "mi355x":
+                        from .jpeg import imread_device
+
+                        img = imread_device(results["img_path"], self.device or "cuda")
+                    else:
+                        img = load_image_bgr(results["img_path"])
                 except OSError:
                     if self.ignore_empty:
                         return None
                     raise
                 if self.to_float32:
-                    img = img.astype(np.float32)
+                    img = img.astype(np.float32) if isinstance(img, np.ndarray) else img.float()
                 results["img"] = img
                 results["img_shape"] = img.shape[:2]
                 results["ori_shape"] = img.shape[:2]

@@ -7,7 +7,11 @@ written by PIL into a temp directory, 1-8 boxes per image, synthetic weights. On
     model_only      test_step_stream on pre-made crops, batches of --batch-size
     per_image_loop  apis.inference_topdown, one image (all its boxes) per call
 
-    python scripts/bench_dataset_eval.py --images 300 --step end_to_end    (default: all steps, one JSON line each)"""
+    python scripts/bench_dataset_eval.py --images 300 --step end_to_end    (default: all steps, one JSON line each)
+
+--decode device runs end_to_end* and decode_only through the split JPEG decoder (Huffman decoding on the threads, the rest
+on the GPU: decode_only then ends with the pixels on the device, the host figure with the pixels in host memory);
+--decode both prints the host line, the device line and the host line again (the spread of the host figure)."""
 import argparse
 import json
 import os
@@ -31,11 +35,12 @@ def main():
     ap.add_argument("--workers", type=int, default=8)
     ap.add_argument("--step", choices=STEPS, action="append")
     ap.add_argument("--data", default=None, help="reuse / keep the generated set in this directory")
+    ap.add_argument("--decode", default="host", choices=["host", "device", "both"], help="image decoder of the end_to_end* and decode_only steps")
     args = ap.parse_args()
 
     import torch
 
-    from probpose_code_amd import apis, runner, synthetic
+    from probpose_code_amd import apis, jpeg, runner, synthetic
     from probpose_code_amd.config import Config
     from probpose_code_amd.datasets import build_dataset
 
@@ -59,14 +64,29 @@ def main():
         torch.cuda.synchronize()
         return time.perf_counter() - t0
 
-    for step in args.step or STEPS:
+    def decode_all_on_device(pool):
+        futures = [pool.submit(jpeg.entropy_decode, p) for p in paths]
+        for lo in range(0, len(futures), 16):  # the images of a batch in one reconstruct call
+            jpeg.reconstruct_batch([f.result() for f in futures[lo:lo + 16]], "cuda:0", staging)
+
+    from probpose_code_amd.transforms import BatchStaging
+
+    staging = BatchStaging()
+    decoded_steps = ("end_to_end", "end_to_end_eval", "decode_only")
+    runs = [(step, mode) for step in args.step or STEPS
+            for mode in ((("host", "device", "host") if args.decode == "both" else (args.decode,)) if step in decoded_steps else ("host",))]
+    for step, mode in runs:
         if step in ("end_to_end", "end_to_end_eval"):
-            runner.test_dataset(model, dataset, None, args.batch_size, args.workers)  # warm-up: graph capture, pinned buffers
+            runner.test_dataset(model, dataset, None, args.batch_size, args.workers, decode=mode)  # warm-up: graph capture, pinned buffers
             ev = runner.build_evaluator(cfg.test_evaluator, dataset) if step == "end_to_end_eval" else None
-            dt = timed(lambda: runner.test_dataset(model, dataset, ev, args.batch_size, args.workers))
+            dt = timed(lambda: runner.test_dataset(model, dataset, ev, args.batch_size, args.workers, decode=mode))
         elif step == "decode_only":
             with ThreadPoolExecutor(max_workers=min(16, args.workers)) as pool:
-                dt = timed(lambda: list(pool.map(apis.load_image_bgr, paths)))
+                if mode == "device":
+                    decode_all_on_device(pool)  # warm-up: pinned buffer, allocator
+                    dt = timed(lambda: decode_all_on_device(pool))
+                else:
+                    dt = timed(lambda: list(pool.map(apis.load_image_bgr, paths)))
         elif step == "model_only":
             g = torch.Generator().manual_seed(0)
             crops = torch.randint(0, 256, (args.batch_size, 3, 256, 192), dtype=torch.uint8, generator=g).cuda()
@@ -96,7 +116,7 @@ def main():
             loop()
             dt = timed(loop)
         print(json.dumps(dict(step=step, instances=n, images=len(paths), seconds=round(dt, 4), instances_per_s=round(n / dt, 1),
-                              batch_size=args.batch_size, workers=args.workers)), flush=True)
+                              batch_size=args.batch_size, workers=args.workers, **(dict(decode=mode) if step in decoded_steps else {}))), flush=True)
 
 
 if __name__ == "__main__":

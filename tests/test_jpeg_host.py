@@ -1,0 +1,109 @@
+"""CPU: the host half of the split JPEG decoder (csrc/pp_jpeg_host.h behind pp_jpeg_probe / pp_jpeg_entropy_decode) against
+the numpy restatement on the whole grid; refusals with a reason for everything outside the subset; and seeded single-byte
+mutations that must end in OK or an error without a write past the caller's buffers (canary words behind them)."""
+import ctypes
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.join(HERE, "golden"))
+import jpeg_ref as J  # noqa: E402
+from make_golden_jpeg import truncations  # noqa: E402
+
+import pytest  # noqa: E402
+
+CANARY16 = 0x5AA5
+
+
+@pytest.fixture(scope="module")
+def jpeg(lib_built):
+    from probpose_code_amd import jpeg
+
+    return jpeg
+
+
+def test_entropy_decode_and_probe_equal_the_reference_on_the_grid(jpeg):
+    g = J.golden()
+    for name in g["names"]:
+        ref = J.golden_parsed(name)
+        info = jpeg.probe(g["jpg"][name])
+        assert info.supported == 1 and info.reason == b"", (name, info.reason)
+        c = jpeg.entropy_decode(g["jpg"][name])
+        for got in (info, c.info):
+            assert (got.width, got.height, got.ncomp, got.precision, got.hs, got.vs, got.mcus_x, got.mcus_y, got.restart_interval) == \
+                (ref["width"], ref["height"], ref["ncomp"], 8, ref["hs"], ref["vs"], ref["mcus_x"], ref["mcus_y"], ref["restart_interval"]), name
+            n = ref["ncomp"]
+            assert list(got.comp_bw)[:n] == ref["comp_bw"] and list(got.comp_bh)[:n] == ref["comp_bh"], name
+            assert got.coef_count == 64 * sum(w * h for w, h in zip(ref["comp_bw"], ref["comp_bh"])), name
+        assert c.coef.dtype == np.int16 and np.array_equal(c.coef, J.flat_coefficients(ref)), name
+        assert c.qtables.dtype == np.uint16 and np.array_equal(c.qtables, ref["qtables"]), name
+    assert any(J.golden_parsed(n)["restart_interval"] for n in g["names"])
+
+
+def _raw_decode(jpeg, data: bytes, capacity: int):
+    """pp_jpeg_entropy_decode into buffers with 64 canary words behind them: (status, info, coef, qtables, canaries intact)."""
+    coef = np.full(capacity + 64, CANARY16, np.uint16)
+    qt = np.full(3 * 64 + 64, CANARY16, np.uint16)
+    info = jpeg.JpegInfo()
+    st = jpeg._lib.lib.pp_jpeg_entropy_decode(data, len(data), coef.ctypes.data, capacity, qt.ctypes.data, ctypes.byref(info))
+    intact = bool((coef[capacity:] == CANARY16).all() and (qt[192:] == CANARY16).all())
+    return st, info, coef[:capacity].view(np.int16), qt[:192], intact
+
+
+def test_files_outside_the_subset_are_refused_with_a_reason(jpeg):
+    _lib = jpeg._lib
+    g = J.golden()
+    for name, data in g["refused"].items():
+        info = jpeg.probe(data)
+        assert info.supported == 0 and info.reason != b"", name
+        st, info2, _, _, intact = _raw_decode(jpeg, data, 1 << 16)
+        assert st == _lib.PP_ERR_UNSUPPORTED and info2.reason != b"" and intact, name
+        assert info2.reason.decode() in _lib.last_error()
+        try:
+            jpeg.entropy_decode(data)
+            raise AssertionError(f"{name} accepted")
+        except jpeg.JpegUnsupported as e:
+            assert e.reason
+    assert b"progressive" in jpeg.probe(g["refused"]["progressive"]).reason
+    assert b"components" in jpeg.probe(g["refused"]["cmyk"]).reason
+
+
+def test_truncated_files_and_short_buffers_fail_cleanly(jpeg):
+    _lib = jpeg._lib
+    g = J.golden()
+    for name in ("48x64_420_q95_smooth_r0", "37x29_444_q100_noise_r3", "31x50_422_noise_qtables", "33x17_grey_q75_bilevel_r3", "31x50_422_q95_noise_r1"):
+        assert name in g["jpg"], name
+        data = g["jpg"][name]
+        need = int(jpeg.probe(data).coef_count)
+        for kind, cut in truncations(data).items():
+            st, info, _, _, intact = _raw_decode(jpeg, cut, need)
+            assert st == _lib.PP_ERR_UNSUPPORTED and info.supported == 0 and info.reason != b"" and intact, (name, kind, st)
+        st, info, _, _, intact = _raw_decode(jpeg, data, need - 1)
+        assert st == _lib.PP_ERR_WORKSPACE and b"too small" in info.reason and intact, name
+        st, info, coef, _, intact = _raw_decode(jpeg, data, need)
+        assert st == _lib.PP_OK and intact and np.array_equal(coef, J.flat_coefficients(J.golden_parsed(name)))
+
+
+def test_single_byte_mutations_never_write_past_the_buffers(jpeg):
+    _lib = jpeg._lib
+    g = J.golden()
+    rng = np.random.default_rng(20240)
+    names = g["names"]
+    ok = refused = 0
+    for _ in range(400):
+        name = names[int(rng.integers(len(names)))]
+        data = bytearray(g["jpg"][name])
+        need = int(jpeg.probe(bytes(data)).coef_count)
+        data[int(rng.integers(len(data)))] = int(rng.integers(256))
+        info = jpeg.probe(bytes(data))
+        cap = need if not info.supported else min(int(info.coef_count), 1 << 20)  # (a mutated SOF may ask for more)
+        st, info, _, _, intact = _raw_decode(jpeg, bytes(data), cap)
+        assert intact, (name, "wrote past a buffer")
+        assert st in (_lib.PP_OK, _lib.PP_ERR_UNSUPPORTED, _lib.PP_ERR_WORKSPACE), (name, st)
+        assert (st == _lib.PP_OK) == (info.supported == 1) and (st == _lib.PP_OK or info.reason != b""), name
+        ok += st == _lib.PP_OK
+        refused += st != _lib.PP_OK
+    assert ok > 20 and refused > 20, (ok, refused)  # both outcomes exercised

@@ -42,6 +42,8 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=None, help="instances per step (default: test_dataloader.batch_size, else 64)")
     ap.add_argument("--workers", type=int, default=8, help="image decoding threads (at most 16)")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--decode", default="host", choices=["host", "device"],
+                    help="device: JPEG files are Huffman-decoded on the threads and reconstructed on the GPU (the same pixels)")
     ap.add_argument("--precision", default=None, choices=[None, "f16x3", "bf16", "f32"],
                     help="overrides model.precision of the config (default there: f16x3)")
     args = ap.parse_args(argv)
@@ -65,7 +67,7 @@ def main(argv=None):
     evaluator = runner.build_evaluator(cfg["test_evaluator"], dataset, device=args.device)
     batch_size = args.batch_size or int(loader.get("batch_size", 64))
     t0 = time.perf_counter()
-    metrics = runner.test_dataset(model, dataset, evaluator, batch_size=batch_size, workers=args.workers)
+    metrics = runner.test_dataset(model, dataset, evaluator, batch_size=batch_size, workers=args.workers, decode=args.decode)
     dt = time.perf_counter() - t0
     for k, v in metrics.items():
         print(f"{k}: {v:.4f}")
