@@ -10,7 +10,7 @@ a file -> quantised coefficients and quantisation tables -> pixels, by libjpeg's
   * YCbCr -> RGB with 16-bit fixed-point constants.
 
 It is the arbiter of the kernels' arithmetic: tests/test_jpeg_references.py pins it to Pillow's bundled libjpeg-turbo, bit
-for bit. It parses only what the grid needs (one interleaved Huffman scan) and raises ValueError on anything else."""
+for bit. It parses only what the tests need (one interleaved Huffman scan; fill bytes in front of any marker) and raises ValueError on anything else."""
 import numpy as np
 
 NATURAL = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14,
@@ -19,10 +19,11 @@ NATURAL = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 
 
 
 def _huff_table(counts, symbols):
+    """The canonical code of a DHT table: the bit string of every code -> its symbol."""
     table, code, k = {}, 0, 0
     for length in range(1, 17):
         for _ in range(counts[length - 1]):
-            table[(length, code)] = symbols[k]
+            table[format(code, f"0{length}b")] = symbols[k]
             code += 1
             k += 1
         code <<= 1
@@ -30,25 +31,30 @@ def _huff_table(counts, symbols):
 
 
 class _Bits:
+    """One entropy-coded segment as a string of '0' / '1' (slicing a string is what Python does fastest here)."""
+
     def __init__(self, segment: bytes):
-        self.bits = np.unpackbits(np.frombuffer(segment.replace(b"\xff\x00", b"\xff"), np.uint8)).tolist()
+        raw = segment.replace(b"\xff\x00", b"\xff")
+        self.bits = bin(int.from_bytes(raw, "big"))[2:].zfill(8 * len(raw)) if raw else ""
         self.p = 0
 
     def symbol(self, table):
-        code = 0
-        for length in range(1, 17):
-            code = (code << 1) | self.bits[self.p]  # IndexError: data ends early
-            self.p += 1
-            s = table.get((length, code))
+        bits, p = self.bits, self.p
+        for length in range(1, 17):  # (past the end the slice stays as short as one already tried: no false match)
+            s = table.get(bits[p:p + length])
             if s is not None:
+                self.p = p + length
                 return s
+        if p + 16 > len(bits):
+            raise IndexError("data ends early")
         raise ValueError("bad Huffman code")
 
     def extend(self, s):
-        v = 0
-        for _ in range(s):
-            v = (v << 1) | self.bits[self.p]
-            self.p += 1
+        chunk = self.bits[self.p:self.p + s]
+        if len(chunk) < s:
+            raise IndexError("data ends early")
+        self.p += s
+        v = int(chunk, 2)
         return v if v >= (1 << (s - 1)) else v - (1 << s) + 1
 
 
@@ -116,14 +122,17 @@ def parse(data: bytes) -> dict:
     segs, start, p = [], pos, pos
     while True:
         p = data.index(b"\xff", p)
-        nxt = data[p + 1]
-        if nxt == 0x00:
+        m = p + 1
+        while data[m] == 0xFF:  # fill bytes in front of a marker
+            m += 1
+        nxt = data[m]
+        if nxt == 0x00 and m == p + 1:
             p += 2
         elif 0xD0 <= nxt <= 0xD7:
             if nxt != 0xD0 + len(segs) % 8:
                 raise ValueError("wrong restart marker")
             segs.append(data[start:p])
-            start = p = p + 2
+            start = p = m + 1
         elif nxt == 0xD9:
             segs.append(data[start:p])
             break

@@ -2,7 +2,11 @@
 (tests/golden/jpeg_cases.npz: Pillow's pixels, which tests/jpeg_ref.py restates) with canary bytes around every output image
 and the plane scratch, the coefficient input compared after the launches, two calls compared and the launches counted;
 then the opt-in paths built on it: ``jpeg.imread_device``, ``runner.test_dataset(decode="device")`` and
-``inference_topdown`` under ``LoadImage(imdecode_backend="mi355x")``, each against the host decoder, bitwise."""
+``inference_topdown`` under ``LoadImage(imdecode_backend="mi355x")``, each against the host decoder, bitwise.
+Beyond the grid (tests/jpeg_sources.py), judged by tests/jpeg_ref.py alone - Pillow only encodes: widths that reach the second
+and third workgroup column of jpeg_color_kernel, 65 MCUs in a row and in a column, two workload-sized images, a batch whose
+launch bounds come from three different images; streams of other layouts (tests/jpeg_write.py) and the streams to refuse
+through ``jpeg.imread_device``; and tests/fuzz_jpeg.py for a few seconds."""
 import os
 import sys
 
@@ -15,13 +19,12 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import jpeg_ref as J  # noqa: E402
+import jpeg_sources as S  # noqa: E402
+from jpeg_harness import raw_reconstruct as _raw_reconstruct  # noqa: E402
 from make_golden_jpeg import truncations  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-CANARY = 0xA5
-GUARD = 4096
-GAP = 67  # canary bytes between two output images: odd, so the images start at every alignment
 CONFIG = os.path.join(ROOT, "configs", "td-pm_ProbPose-small_mi355x_cropcoco-coco-val-256x192.py")
 
 
@@ -41,65 +44,6 @@ def coefficients(jpeg):
         assert jpeg.probe(g["jpg"][name]).supported == 1, name  # no grid file may take the fallback
         out[name] = jpeg.entropy_decode(g["jpg"][name])
     return out
-
-
-def _align(v, a=256):
-    return (v + a - 1) // a * a
-
-
-def _raw_reconstruct(jpeg, coefs):
-    """pp_jpeg_reconstruct_bgr_batch on buffers of this test's own: the input block (descriptors, tables, coefficients), the
-    plane scratch and all output images inside canary bytes. Runs the call twice. Returns the images (numpy, BGR)."""
-    _lib = jpeg._lib
-    n = len(coefs)
-    off, o_qt, o_coef = _align(64 * n), [], []
-    for c in coefs:
-        o_qt.append(off)
-        off = _align(off + 384)
-        o_coef.append(off)
-        off = _align(off + 2 * c.coef.size)
-    host = np.zeros(off, np.uint8)
-    sizes = [int(np.prod(c.shape)) for c in coefs]
-    o_out, p = [], GUARD
-    for s in sizes:
-        o_out.append(p)
-        p += s + GAP
-    out = torch.full((p - GAP + GUARD,), CANARY, dtype=torch.uint8, device=DEV)
-    infos = (jpeg.JpegInfo * n)(*[c.info for c in coefs])
-    need = int(_lib.lib.pp_jpeg_scratch_bytes(infos, n))
-    assert need == sum(_align(int(c.info.coef_count)) for c in coefs)
-    scratch = torch.full((need + 2 * GUARD,), CANARY, dtype=torch.uint8, device=DEV)
-    dev = torch.empty(off, dtype=torch.uint8, device=DEV)
-    desc = host[:64 * n].view(jpeg._DESC)
-    planes = scratch.data_ptr() + GUARD
-    for i, c in enumerate(coefs):
-        host[o_qt[i]:o_qt[i] + 128 * len(c.qtables)].view(np.uint16)[:] = c.qtables.reshape(-1)
-        host[o_coef[i]:o_coef[i] + 2 * c.coef.size].view(np.int16)[:] = c.coef
-        desc[i] = (dev.data_ptr() + o_coef[i], dev.data_ptr() + o_qt[i], planes, out.data_ptr() + o_out[i], c.info.width, c.info.height,
-                   c.info.ncomp, c.info.hs, c.info.vs, c.info.mcus_x, c.info.mcus_y, 0)
-        planes += _align(int(c.info.coef_count))
-    dev.copy_(torch.from_numpy(host))
-    args = (dev.data_ptr(), n, max(int(c.info.coef_count) // 64 for c in coefs), max(c.info.height for c in coefs),
-            max(c.info.width for c in coefs), torch.cuda.current_stream().cuda_stream)
-    _lib.reset_launch_counts()
-    _lib.call("pp_jpeg_reconstruct_bgr_batch", *args)
-    torch.cuda.synchronize()
-    counts = (_lib.launch_count("jpeg_idct"), _lib.launch_count("jpeg_color"), _lib.launch_count("pp_jpeg.hip"))
-    assert counts == (1, 1, 2), f"launches per call {counts} for n = {n}"
-    first = out.cpu().numpy()
-    out[GUARD:len(out) - GUARD] = CANARY  # (the images and the gaps between them)
-    _lib.call("pp_jpeg_reconstruct_bgr_batch", *args)
-    torch.cuda.synchronize()
-    second = out.cpu().numpy()
-    assert np.array_equal(first, second), "a second launch gives other bytes"
-    assert np.array_equal(dev.cpu().numpy(), host), "the kernels changed their input"
-    sc = scratch.cpu().numpy()
-    assert (sc[:GUARD] == CANARY).all() and (sc[GUARD + need:] == CANARY).all(), "bytes outside the plane scratch written"
-    mask = np.ones(len(first), bool)
-    for o, s in zip(o_out, sizes):
-        mask[o:o + s] = False
-    assert (first[mask] == CANARY).all(), "bytes outside an output image written"
-    return [first[o:o + s].reshape(c.shape) for o, s, c in zip(o_out, sizes, coefs)]
 
 
 def _check(names, images):
@@ -195,6 +139,118 @@ def test_imread_device_falls_back_like_the_host_decoder(jpeg, tmp_path):
     assert isinstance(_host_outcome(str(tmp_path / "progressive.jpg")), torch.Tensor)  # the host decoder reads these two
     assert isinstance(_host_outcome(str(tmp_path / "cmyk.jpg")), torch.Tensor)
     assert jpeg._lib.launch_count("jpeg_idct") == 0 and jpeg._lib.launch_count("jpeg_color") == 0
+
+
+_REF = {}
+
+
+def _reference_bgr(data: bytes) -> np.ndarray:
+    """tests/jpeg_ref.py's pixels of a file as BGR, computed once and shared (do not modify)."""
+    if data not in _REF:
+        _REF[data] = np.ascontiguousarray(J.decode_rgb(data)[:, :, ::-1])
+    return _REF[data]
+
+
+def _host_half(jpeg, files):
+    out = []
+    for label, data in files:
+        info = jpeg.probe(data)
+        assert info.supported == 1, (label, info.reason)  # none of these may take the fallback
+        out.append(jpeg.entropy_decode(data))
+    return out
+
+
+def _check_reference(files, images):
+    assert len(files) == len(images)
+    for (label, data), img in zip(files, images):
+        ref = _reference_bgr(data)
+        assert img.shape == ref.shape, label
+        bad = (img != ref).any(axis=2)
+        assert not bad.any(), f"{label}: {int(bad.sum())} of {bad.size} pixels differ, the first at (y, x) = {tuple(int(v) for v in np.argwhere(bad)[0])}"
+
+
+@pytest.mark.parametrize("size", S.SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_sizes_beyond_the_grid_equal_the_reference(jpeg, size):
+    """5 x 257, 6 x 260, 3 x 515: pixels at x >= 256 and x >= 512 (blockIdx.x of jpeg_color_kernel 1 and 2), a tail of one
+    and of three pixels behind full threads, a full last thread, row offsets where the dword stores apply and where they do
+    not; 9 x 1037 and 1037 x 9: 65 MCUs in a row / in a column, tens of workgroups of jpeg_idct_kernel. Each sampling
+    alone, then the four in one batch."""
+    H, W = size
+    files = [(f"{H}x{W}_{s}", S.size_case(H, W, s)) for s in S.SAMPLINGS]
+    coefs = _host_half(jpeg, files)
+    for f, c in zip(files, coefs):
+        assert c.shape == (H, W, 3), f[0]
+        _check_reference([f], _raw_reconstruct(jpeg, [c]))
+    _check_reference(files, _raw_reconstruct(jpeg, coefs))
+
+
+def test_workload_sized_images_equal_the_reference(jpeg):
+    """480 x 640 4:2:0 q75 and 333 x 500 4:2:2 q90, every pixel (the dataset test compares keypoints inside the boxes)."""
+    files = [(n, S.source(n)) for n in ("480x640_420", "333x500_422")]
+    coefs = _host_half(jpeg, files)
+    assert [c.shape for c in coefs] == [(480, 640, 3), (333, 500, 3)]
+    for f, c in zip(files, coefs):
+        _check_reference([f], _raw_reconstruct(jpeg, [c]))
+
+
+def test_batch_whose_bounds_come_from_different_images(jpeg):
+    """480 x 640 with 1 x 1 and 5 x 257 - and 1037 x 9, 9 x 1037: max_blocks, max_height and max_width of the launch each come
+    from another image, so most workgroups of every image but one lie outside it."""
+    files = [("480x640_420", S.source("480x640_420")), ("1x1_420", S.encoded(1, 1, "420", 75, "noise", 0)), ("5x257_444", S.size_case(5, 257, "444"))]
+    _check_reference(files, _raw_reconstruct(jpeg, _host_half(jpeg, files)))
+    files = [("1037x9_422", S.size_case(1037, 9, "422")), ("1x1_420", files[1][1]), ("9x1037_grey", S.size_case(9, 1037, "grey")),
+             ("333x500_422", S.source("333x500_422"))]
+    _check_reference(files, _raw_reconstruct(jpeg, _host_half(jpeg, files)))
+
+
+def test_transcoded_layouts_decode_on_the_device(jpeg):
+    """Every must-decode layout of the small sources through ``imread_device``: no fallback, the reference's pixels; then the
+    twelve layouts of a source as one guarded batch."""
+    before = jpeg.fallbacks
+    for name in S.SMALL_SOURCES:
+        files = [(f"{name} {layout}", S.transcoded(name, layout)) for layout in S.LAYOUTS]
+        src = np.ascontiguousarray(J.reconstruct_rgb(S.source_parsed(name))[:, :, ::-1])
+        for label, data in files:
+            got = jpeg.imread_device(data, DEV)
+            assert got.is_cuda and got.dtype == torch.uint8, label
+            _check_reference([(label, data)], [got.cpu().numpy()])
+            assert np.array_equal(_reference_bgr(data), src), label  # (and those are the source's pixels)
+        assert jpeg.fallbacks == before, f"a layout of {name} took the host decoder"
+        _check_reference(files, _raw_reconstruct(jpeg, _host_half(jpeg, files)))
+
+
+def test_streams_outside_the_subset_take_the_host_decoder(jpeg, tmp_path):
+    """Three scans, 4:4:0, 4:1:1, Adobe transform 0, ids R G B without JFIF: one fallback each, the host decoder's pixels (or
+    its exception), no JPEG launch."""
+    jpeg._lib.reset_launch_counts()
+    for name in S.REFUSED:
+        data, word = S.refused(name)
+        path = str(tmp_path / (name + ".jpg"))
+        with open(path, "wb") as f:
+            f.write(data)
+        ref = _host_outcome(path)
+        for src in (path, data):
+            before = jpeg.fallbacks
+            try:
+                got = jpeg.imread_device(src, DEV)
+            except Exception as e:  # noqa: BLE001
+                got = e
+            assert jpeg.fallbacks == before + 1, name
+            if isinstance(ref, Exception):
+                assert type(got) is type(ref) and str(got) == str(ref), (name, got, ref)
+            else:
+                assert isinstance(got, torch.Tensor) and got.is_cuda and torch.equal(got.cpu(), ref), name
+        assert word.encode() in jpeg.probe(data).reason, name
+    assert jpeg._lib.launch_count("jpeg_idct") == 0 and jpeg._lib.launch_count("jpeg_color") == 0 and jpeg._lib.launch_count("pp_jpeg.hip") == 0
+
+
+def test_jpeg_differential_fuzz_against_the_reference():
+    """tests/fuzz_jpeg.py for a few seconds: random sizes up to 700 a side around the kernels' thresholds, sampling, quality,
+    content, stream layout, batches of 1..16 - no fallback, every image equal to tests/jpeg_ref.py byte for byte."""
+    import subprocess
+
+    r = subprocess.run([sys.executable, os.path.join(HERE, "fuzz_jpeg.py"), "8"], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "JPEG FUZZ OK" in r.stdout, (r.stdout[-800:], r.stderr[-800:])
 
 
 @pytest.fixture(scope="module")

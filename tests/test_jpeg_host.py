@@ -1,6 +1,8 @@
 """CPU: the host half of the split JPEG decoder (csrc/pp_jpeg_host.h behind pp_jpeg_probe / pp_jpeg_entropy_decode) against
 the numpy restatement on the whole grid; refusals with a reason for everything outside the subset; and seeded single-byte
-mutations that must end in OK or an error without a write past the caller's buffers (canary words behind them)."""
+mutations that must end in OK or an error without a write past the caller's buffers (canary words behind them). The same
+comparison on streams of other layouts - tables, slots, segments, markers, restart intervals no Pillow file has (transcoded by
+tests/jpeg_write.py, listed in tests/jpeg_sources.py) - and refusals that name their cause for the streams outside the subset."""
 import ctypes
 import os
 import sys
@@ -11,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import jpeg_ref as J  # noqa: E402
+import jpeg_sources as S  # noqa: E402
 from make_golden_jpeg import truncations  # noqa: E402
 
 import pytest  # noqa: E402
@@ -107,3 +110,42 @@ def test_single_byte_mutations_never_write_past_the_buffers(jpeg):
         ok += st == _lib.PP_OK
         refused += st != _lib.PP_OK
     assert ok > 20 and refused > 20, (ok, refused)  # both outcomes exercised
+
+
+def test_transcoded_layouts_decode_to_the_source_coefficients(jpeg):
+    """Every layout of every source: no refusal, the source's geometry, the layout's restart interval, the source's
+    coefficients and each component's own quantisation table whatever slot it sits in - with the canaries intact."""
+    _lib = jpeg._lib
+    for name, layout in S.layout_cases():
+        ref, data = S.source_parsed(name), S.transcoded(name, layout)
+        info = jpeg.probe(data)
+        assert info.supported == 1 and info.reason == b"", (name, layout, info.reason)
+        need = 64 * sum(w * h for w, h in zip(ref["comp_bw"], ref["comp_bh"]))
+        st, info2, coef, qt, intact = _raw_decode(jpeg, data, need)
+        assert st == _lib.PP_OK and info2.supported == 1 and info2.reason == b"" and intact, (name, layout, st, info2.reason)
+        for got in (info, info2):
+            assert (got.width, got.height, got.ncomp, got.precision, got.hs, got.vs, got.mcus_x, got.mcus_y) == \
+                (ref["width"], ref["height"], ref["ncomp"], 8, ref["hs"], ref["vs"], ref["mcus_x"], ref["mcus_y"]), (name, layout)
+            assert got.restart_interval == S.LAYOUTS[layout].get("restart", 0), (name, layout)
+            n = ref["ncomp"]
+            assert list(got.comp_bw)[:n] == ref["comp_bw"] and list(got.comp_bh)[:n] == ref["comp_bh"] and got.coef_count == need, (name, layout)
+        assert np.array_equal(coef, J.flat_coefficients(ref)), (name, layout)
+        assert np.array_equal(qt[:64 * n].reshape(n, 64), ref["qtables"]), (name, layout)
+        assert (qt[64 * n:] == CANARY16).all(), (name, layout)  # a grey file leaves the other two tables alone
+        c = jpeg.entropy_decode(data)  # the Python wrapper on the same bytes
+        assert np.array_equal(c.coef, coef) and np.array_equal(c.qtables, ref["qtables"]), (name, layout)
+    assert not np.array_equal(S.source_parsed("31x50_422")["qtables"][0], S.source_parsed("31x50_422")["qtables"][1])  # a wrong slot shows
+
+
+def test_streams_outside_the_subset_name_their_cause(jpeg):
+    _lib = jpeg._lib
+    for name in S.REFUSED:
+        data, word = S.refused(name)
+        info = jpeg.probe(data)
+        assert info.supported == 0 and word.encode() in info.reason, (name, info.reason)
+        st, info2, coef, qt, intact = _raw_decode(jpeg, data, 1 << 16)
+        assert st == _lib.PP_ERR_UNSUPPORTED and info2.supported == 0 and word.encode() in info2.reason and intact, (name, st, info2.reason)
+        assert (coef.view(np.uint16) == CANARY16).all() and (qt == CANARY16).all(), (name, "a refused file wrote to the buffers")
+        assert info2.reason.decode() in _lib.last_error()
+        with pytest.raises(jpeg.JpegUnsupported, match=word):
+            jpeg.entropy_decode(data)

@@ -1,6 +1,8 @@
 """CPU: the numpy restatement of the JPEG decoder (tests/jpeg_ref.py) - the arbiter of the GPU kernels' integer rules - equals
 Pillow's bundled libjpeg-turbo bit for bit: on the committed grid (tests/golden/jpeg_cases.npz, decoded by Pillow when the
-file was made) and against Pillow decoding the same bytes on the spot."""
+file was made) and against Pillow decoding the same bytes on the spot. Then the same for streams of other layouts
+(tests/jpeg_write.py transcodes Pillow's files: other tables, slots, segments, markers, restart intervals - tests/jpeg_sources.py
+lists them) and for the image sizes of the GPU tests beyond the grid: the writer and the reference are pinned to libjpeg-turbo."""
 import io
 import os
 import sys
@@ -11,7 +13,9 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import jpeg_ref as J  # noqa: E402
-
+import jpeg_sources as S  # noqa: E402
+import jpeg_write as JW  # noqa: E402
+from make_golden_jpeg import pillow_rgb  # noqa: E402
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -53,3 +57,88 @@ def test_reference_equals_pillow_on_the_spot():
         with Image.open(io.BytesIO(g["jpg"][name])) as im:
             rgb = np.asarray(im.convert("RGB"), dtype=np.uint8)
         assert np.array_equal(J.reconstruct_rgb(J.golden_parsed(name)), rgb), name
+
+
+def _need_libjpeg_turbo():
+    from PIL import features
+
+    if not features.check_feature("libjpeg_turbo"):
+        pytest.skip("this Pillow is not built on libjpeg-turbo: its pixels may differ by design")
+
+
+def test_transcoded_layouts_give_back_the_coefficients():
+    """The writer against the reference's parser: every layout of every source parses to the source's coefficients, tables
+    and geometry, with the restart interval the layout asked for - and so to the source's pixels."""
+    cases = S.layout_cases()
+    assert len(cases) == 12 * 6 + 2
+    for name, layout in cases:
+        src, got = S.source_parsed(name), S.transcoded_parsed(name, layout)
+        for k in ("width", "height", "ncomp", "hs", "vs", "mcus_x", "mcus_y", "comp_bw", "comp_bh"):
+            assert got[k] == src[k], (name, layout, k)
+        assert got["restart_interval"] == S.LAYOUTS[layout].get("restart", 0), (name, layout)
+        assert all(a.dtype == b.dtype and np.array_equal(a, b) for a, b in zip(got["coef"], src["coef"])), (name, layout)
+        assert np.array_equal(got["qtables"], src["qtables"]), (name, layout)
+        assert np.array_equal(J.reconstruct_rgb(got), J.reconstruct_rgb(src)), (name, layout)
+        assert (S.transcoded(name, layout) != S.source(name)), (name, layout)
+
+
+def test_transcoded_layouts_equal_pillow():
+    """Pillow(transcoded) == Pillow(source) == jpeg_ref.decode_rgb(transcoded), bit for bit."""
+    _need_libjpeg_turbo()
+    for name, layout in S.layout_cases():
+        src, got = pillow_rgb(S.source(name)), pillow_rgb(S.transcoded(name, layout))
+        assert got.shape == src.shape and np.array_equal(got, src), (name, layout)
+        assert np.array_equal(J.reconstruct_rgb(S.transcoded_parsed(name, layout)), got), (name, layout)
+
+
+def test_layouts_are_what_they_claim():
+    """The bytes of the layouts: fill bytes in front of RSTn and EOI, segment counts, 16-bit tables, long codes."""
+    name = "31x50_422"
+    parsed = S.source_parsed(name)
+    data = S.transcoded(name, "ids_odd_no_jfif_fill3_ri1")
+    assert data.count(b"\xff\xff\xff\xff\xd0") == 2 and data.count(b"\xff\xff\xff\xff\xd7") == 1  # 16 MCUs: RST0..7, RST0..6
+    assert data.endswith(b"\xff\xff\xff\xff\xd9") and b"JFIF" not in data
+    assert J.parse(data)["restart_interval"] == 1
+    assert S.transcoded(name, "slots_3_2_split").count(b"\xff\xc4\x00") == 4 and S.transcoded(name, "plain").count(b"\xff\xc4") == 1
+    assert S.transcoded(name, "slots_3_2_split").count(b"\xff\xdb\x00\x43") == 2 and S.transcoded(name, "pq1_sof1").count(b"\xff\xdb\x01\x04") == 1
+    assert b"\xff\xc1\x00\x11\x08" in S.transcoded(name, "pq1_sof1") and b"\xff\xdd\x00\x04\xff\xff" in S.transcoded(name, "ri65535")
+    assert b"\xff\xd0" not in S.transcoded(name, "ri65535")[-600:]
+    assert b"Adobe" in S.transcoded(name, "segments_adobe1") and b"Exif" in S.transcoded(name, "segments_adobe1")
+    for layout in ("fibonacci", "fibonacci_shared_ri5_fill2"):  # the common symbols sit behind a 9-bit lookup table
+        hist = JW.code_length_histogram(parsed, **S.LAYOUTS[layout])
+        assert hist[:10].sum() == 0 and hist[16] > hist.sum() // 2, (layout, hist)
+    hist = JW.code_length_histogram(parsed, **S.LAYOUTS["plain"])
+    assert hist[:10].sum() > 0.9 * hist.sum() and hist[0] == 0
+
+
+def test_reference_takes_fill_bytes_only_in_front_of_markers():
+    data = S.transcoded("33x17_420", "fibonacci_shared_ri5_fill2")
+    assert b"\xff\xff\xff\xd0" in data and data.endswith(b"\xff\xff\xff\xd9")
+    J.parse(data)
+    scan = data.index(b"\xff\xda")
+    for bad, why in ((b"\xff\xc0", "marker inside the scan"), (b"\xff\xff\x00", "marker inside the scan"), (b"\xff\xd1", "wrong restart marker")):
+        cut = data.index(b"\xff\xff\xff\xd0", scan)
+        with pytest.raises(ValueError, match=why):
+            J.parse(data[:cut] + bad + data[cut + 4:])
+
+
+def test_refused_streams_are_regular_files():
+    """What the split decoder must refuse is still a file libjpeg reads: three scans give the source's pixels."""
+    _need_libjpeg_turbo()
+    for name in S.REFUSED:
+        data, _ = S.refused(name)
+        rgb = pillow_rgb(data)
+        assert rgb.ndim == 3 and rgb.shape[2] == 3, name
+    assert np.array_equal(pillow_rgb(S.refused("three_scans")[0]), pillow_rgb(S.source(S.REFUSED_SOURCE)))
+    assert pillow_rgb(S.refused("sampling_1x2")[0]).shape == (31, 29, 3) and pillow_rgb(S.refused("sampling_4x1")[0]).shape == (39, 29, 3)
+
+
+def test_reference_equals_pillow_at_the_sizes_of_the_gpu_tests():
+    """5 x 257 .. 1037 x 9 at every sampling (and, above, the two workload-sized images): the arbiter of the GPU size tests."""
+    _need_libjpeg_turbo()
+    for H, W in S.SIZES:
+        for sampling in S.SAMPLINGS:
+            data = S.size_case(H, W, sampling)
+            rgb = J.decode_rgb(data)
+            assert rgb.shape == (H, W, 3) and np.array_equal(rgb, pillow_rgb(data)), (H, W, sampling)
+    assert {c for c in S.layout_cases() if c[0] in ("480x640_420", "333x500_422")} == {("480x640_420", "ri7_dht_split"), ("333x500_422", "slots_3_2_split")}
