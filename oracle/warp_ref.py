@@ -7,6 +7,8 @@ from this image, and the reference holds no golden image for the warp. The algor
 the inverse map in float64, source coordinates in fixed point with 5 fractional bits, 15-bit bilinear weights,
 round-half-up at the end. The box arithmetic around it (matrices) IS pinned: tests/golden/warp_boxes.npz.
 """
+from fractions import Fraction
+
 import numpy as np
 
 
@@ -29,17 +31,32 @@ def _round(v):  # saturate_cast<int>(double) = cvRound: nearest, ties to even
     return np.clip(np.rint(v), -2147483648, 2147483647).astype(np.int64)
 
 
-def warp_affine_u8(img, m, out_wh):
-    """img (H, W, C) uint8, m (2, 3) forward matrix, out_wh = (w, h). Returns (h, w, C) uint8."""
-    ih, iw, ic = img.shape
+def _row_term(a, ys, b, fused=False):
+    """a * y + b for every row y in float64. As cv2 (and this project's kernels) compute it, the product and the sum round
+    separately. ``fused=True`` rounds the exact a * y + b once, as a fused multiply-add would: tests use it to prove that a
+    row tells the two roundings apart (find_tie_row)."""
+    if not fused:
+        return a * ys + b
+    return np.array([float(Fraction(float(a)) * int(y) + Fraction(float(b))) for y in ys], np.float64)
+
+
+def fixed_point_coords(M, out_wh, fused=False):
+    """The source coordinates of every output pixel with 5 fractional bits, (X, Y) as (h, w) int64 arrays, from the INVERSE
+    map M (dst -> src): X = (round((M01 y + M02) 1024) + 16 + round(M00 x 1024)) >> 5."""
     w, h = out_wh
-    M = invert_affine(m)
     xs, ys = np.arange(w), np.arange(h)
     adelta, bdelta = _round(M[0, 0] * xs * 1024.0), _round(M[1, 0] * xs * 1024.0)
-    X0 = _round((M[0, 1] * ys + M[0, 2]) * 1024.0) + 16
-    Y0 = _round((M[1, 1] * ys + M[1, 2]) * 1024.0) + 16
-    X = (X0[:, None] + adelta[None, :]) >> 5
-    Y = (Y0[:, None] + bdelta[None, :]) >> 5
+    X0 = _round(_row_term(M[0, 1], ys, M[0, 2], fused) * 1024.0) + 16
+    Y0 = _round(_row_term(M[1, 1], ys, M[1, 2], fused) * 1024.0) + 16
+    return (X0[:, None] + adelta[None, :]) >> 5, (Y0[:, None] + bdelta[None, :]) >> 5
+
+
+def warp_affine_u8(img, m, out_wh, inverse=False, fused=False):
+    """img (H, W, C) uint8, m (2, 3) forward matrix, out_wh = (w, h). Returns (h, w, C) uint8. ``inverse=True``: m already
+    is the dst -> src map, float64, as the kernels are handed it (cv2's WARP_INVERSE_MAP)."""
+    ih, iw, ic = img.shape
+    M = np.asarray(m, np.float64).reshape(2, 3) if inverse else invert_affine(m)
+    X, Y = fixed_point_coords(M, out_wh, fused)
     sx, sy = np.clip(X >> 5, -32768, 32767), np.clip(Y >> 5, -32768, 32767)
     fx, fy = X & 31, Y & 31
     w00, w01, w10, w11 = (32 - fx) * (32 - fy) * 32, fx * (32 - fy) * 32, (32 - fx) * fy * 32, fx * fy * 32
@@ -87,15 +104,13 @@ def get_warp_matrix(center, scale, rot, output_size, inv=False):
     return get_affine_transform(dst, src) if inv else get_affine_transform(src, dst)
 
 
-def warp_affine_f32(img, m, out_wh):
+def warp_affine_f32(img, m, out_wh, inverse=False, fused=False):
     """cv2.warpAffine for float32 images (h, w, C), INTER_LINEAR, zero border: the coordinate arithmetic of the uint8 path,
-    float32 weights (1 - fy/32)(1 - fx/32), ... and a float32 sum of the four products."""
+    float32 weights (1 - fy/32)(1 - fx/32), ... and a float32 sum of the four products, left to right, each product and
+    each sum rounded on its own. ``inverse`` / ``fused`` as in warp_affine_u8."""
     ih, iw, ic = img.shape
-    w, h = out_wh
-    M = invert_affine(m)
-    xs, ys = np.arange(w), np.arange(h)
-    X = (_round((M[0, 1] * ys + M[0, 2]) * 1024.0)[:, None] + 16 + _round(M[0, 0] * xs * 1024.0)[None, :]) >> 5
-    Y = (_round((M[1, 1] * ys + M[1, 2]) * 1024.0)[:, None] + 16 + _round(M[1, 0] * xs * 1024.0)[None, :]) >> 5
+    M = np.asarray(m, np.float64).reshape(2, 3) if inverse else invert_affine(m)
+    X, Y = fixed_point_coords(M, out_wh, fused)
     sx, sy = np.clip(X >> 5, -32768, 32767), np.clip(Y >> 5, -32768, 32767)
     ax, ay = ((X & 31).astype(np.float32) / np.float32(32))[..., None], ((Y & 31).astype(np.float32) / np.float32(32))[..., None]
     one = np.float32(1)
@@ -106,8 +121,48 @@ def warp_affine_f32(img, m, out_wh):
         inside = (yy >= -1) & (yy <= ih) & (xx >= -1) & (xx <= iw)
         return np.where(inside[..., None], pad[np.clip(yy + 1, 0, ih + 1), np.clip(xx + 1, 0, iw + 1)], np.float32(0))
 
-    return (tap(sy, sx) * ((one - ay) * (one - ax)) + tap(sy, sx + 1) * ((one - ay) * ax) + tap(sy + 1, sx) * (ay * (one - ax))
-            + tap(sy + 1, sx + 1) * (ay * ax)).astype(np.float32)
+    with np.errstate(invalid="ignore"):  # inf * 0 = NaN is the wanted answer, not a warning
+        return (tap(sy, sx) * ((one - ay) * (one - ax)) + tap(sy, sx + 1) * ((one - ay) * ax) + tap(sy + 1, sx) * (ay * (one - ax))
+                + tap(sy + 1, sx + 1) * (ay * ax)).astype(np.float32)
+
+
+def find_tie_row(rng, out_h, src_h, col_scale=0.5, col_offset=0.25):
+    """An inverse map (2, 3) with M01 = M10 = 0 and a row y of the output at which the two roundings of M11 y + M12 part:
+      * fl(fl(M11 y) + M12) * 1024 = n + 0.5 exactly with n % 32 == 15, so the value is a tie, rounds to the even n + 1, and
+        n + 1 + 16 carries into the next 1/32 step of the source row;
+      * the exact M11 y + M12 (fractions.Fraction) lies below that value and rounds to another float64, so a fused
+        multiply-add lands on n: every pixel of row y then takes bilinear weights that are off by 1/32.
+    The source row stays inside [1, src_h - 2]. Returns (M, y). Found by search: a random M11 and y, M12 chosen so that
+    the doubly rounded sum hits the tie, kept when the exact value confirms the two conditions."""
+    while True:
+        y = int(rng.integers(max(1, out_h // 2), out_h))
+        m11 = float(rng.uniform(0.3, 0.7)) * src_h / out_h * 2.0
+        p = m11 * y  # fl(M11 y)
+        n = 1024 * int(rng.integers(1, max(2, src_h - 2))) + 32 * int(rng.integers(0, 32)) + 15  # source row in [1, src_h - 2)
+        t = (n + 0.5) / 1024.0
+        m12 = t - p
+        if p + m12 != t or t * 1024.0 != n + 0.5 or n % 32 != 15:
+            continue
+        exact = Fraction(m11) * y + Fraction(m12)
+        if not exact < Fraction(t) or float(exact) == t:
+            continue
+        if int(_round(np.float64(float(exact)) * 1024.0)) != n or int(_round(np.float64(t) * 1024.0)) != n + 1:
+            continue
+        return np.array([[col_scale, 0.0, col_offset], [0.0, m11, m12]], np.float64), y
+
+
+def tap_footprint(m, out_wh, tap_yx, inverse=False):
+    """(h, w) bool: the output pixels whose four-tap footprint holds the source element ``tap_yx`` = (row, column), taps of
+    weight zero included (NaN * 0 is NaN in cv2 as well)."""
+    M = np.asarray(m, np.float64).reshape(2, 3) if inverse else invert_affine(m)
+    X, Y = fixed_point_coords(M, out_wh)
+    sx, sy = np.clip(X >> 5, -32768, 32767), np.clip(Y >> 5, -32768, 32767)
+    return ((sy == tap_yx[0]) | (sy + 1 == tap_yx[0])) & ((sx == tap_yx[1]) | (sx + 1 == tap_yx[1]))
+
+
+def revert_matrix(input_center, input_scale, hm_wh):
+    """The forward matrix revert_heatmap hands to warpAffine for a map of ``hm_wh`` = (w, h)."""
+    return get_warp_matrix(np.asarray(input_center).reshape(2), np.asarray(input_scale).reshape(2), 0, hm_wh, inv=True)
 
 
 def revert_heatmap(heatmap, input_center, input_scale, img_shape):

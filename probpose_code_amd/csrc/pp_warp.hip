@@ -9,6 +9,9 @@
 //   * X = (round((M1 y + M2) 1024) + 16 + round(M0 x 1024)) >> 5  - coordinates with 5 fractional bits;
 //   * the four taps are weighted with 15-bit integer weights (32 - fx)(32 - fy) 32, ..., taps outside the image read
 //     the border value 0, result = (sum + 16384) >> 15.
+// This file is built with -ffp-contract=off (csrc/Makefile): cv2 rounds the product M1 y and the sum + M2 separately, and a
+// fused multiply-add lands on the other side of a rounding tie of (M1 y + M2) 1024 - a whole output row then takes weights
+// that are off by 1/32. The same holds for the float32 sum of the four products in the heatmap warp below.
 // One thread per output pixel (all three channels): HBM-bound on the 3 x 48 KiB each crop writes. pp_warp_affine_u8 cuts
 // the crops of one image, pp_warp_affine_u8_batch those of many images (a device table of image pointers) in one launch.
 #include "pp_common.h"
@@ -72,7 +75,11 @@ __global__ __launch_bounds__(256) void warp_affine_batch_kernel(const uint8_t* c
 // the (L2-resident) person maps, K running maxima in registers, one coalesced store per channel. HBM-bound on the
 // K x H x W floats written. cv2's float path: the same 5-fractional-bit source coordinates as above, the four weights
 // (1 - fy/32)(1 - fx/32), ... in float32 (exact), v = s00 w00 + s01 w01 + s10 w10 + s11 w11.
+// The merge is numpy's np.max: NaN in any person's value stays NaN (fmaxf would drop it), and the maxima start at -inf.
 constexpr int RV_MAXK = 32;
+
+// IEEE 754-2019 maximum (NaN if either operand is): one v_maximum3_f32 on gfx950, where fmaxf is one v_max_f32
+__device__ __forceinline__ float max_keep_nan(float acc, float v) { return __builtin_elementwise_maximum(acc, v); }
 
 __global__ __launch_bounds__(256) void revert_heatmaps_max_kernel(const float* __restrict__ hm, const double* __restrict__ inv,
                                                                   float* __restrict__ out, int n, int K, int hh, int hw,
@@ -81,7 +88,7 @@ __global__ __launch_bounds__(256) void revert_heatmaps_max_kernel(const float* _
     if (x >= W) return;
     float acc[RV_MAXK];
 #pragma unroll
-    for (int k = 0; k < RV_MAXK; ++k) acc[k] = -3.402823466e+38f;
+    for (int k = 0; k < RV_MAXK; ++k) acc[k] = -__builtin_huge_valf();
     for (int b = 0; b < n; ++b) {
         const double* M = inv + 6 * b;
         const int X0 = round_to_int((M[1] * y + M[2]) * 1024.0) + 16, Y0 = round_to_int((M[4] * y + M[5]) * 1024.0) + 16;
@@ -93,7 +100,7 @@ __global__ __launch_bounds__(256) void revert_heatmaps_max_kernel(const float* _
         const bool y0in = sy >= 0 && sy < hh, y1in = sy + 1 >= 0 && sy + 1 < hh;
         if (!((x0in || x1in) && (y0in || y1in))) {  // this person's map is 0 here (border value)
 #pragma unroll
-            for (int k = 0; k < RV_MAXK; ++k) acc[k] = fmaxf(acc[k], 0.f);
+            for (int k = 0; k < RV_MAXK; ++k) acc[k] = max_keep_nan(acc[k], 0.f);
             continue;
         }
         const float ax = (float)(X & 31) * (1.f / 32.f), ay = (float)(Y & 31) * (1.f / 32.f);
@@ -106,7 +113,7 @@ __global__ __launch_bounds__(256) void revert_heatmaps_max_kernel(const float* _
                 const float v00 = (x0in && y0in) ? sk[0] : 0.f, v01 = (x1in && y0in) ? sk[1] : 0.f;
                 const float v10 = (x0in && y1in) ? sk[hw] : 0.f, v11 = (x1in && y1in) ? sk[hw + 1] : 0.f;
                 const float v = v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11;
-                acc[k] = fmaxf(acc[k], v);
+                acc[k] = max_keep_nan(acc[k], v);
             }
         }
     }

@@ -100,6 +100,48 @@ def test_hip_warp_bit_exact_vs_oracle():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("kernel", ["pp_warp_affine_u8", "pp_warp_affine_u8_batch"])
+def test_hip_warp_row_on_a_rounding_tie(lib_built, kernel):
+    """The kernels take the inverse map as cv2 does: M4 * y and + M5 rounded separately. On a row y where that doubly rounded
+    value times 1024 is exactly n + 0.5 (n % 32 == 15) and the exact M4 y + M5 lies below it, a fused multiply-add rounds the
+    other way and every pixel of the row takes weights that are off by 1/32. First the row is shown to tell the two roundings
+    apart (oracle with fused rounding != oracle proper), then the crop kernel must equal the oracle proper byte for byte."""
+    import torch
+
+    from oracle import warp_ref
+    from probpose_code_amd import _lib
+
+    rng = np.random.default_rng(61)
+    img = rng.integers(0, 256, (97, 131, 3), dtype=np.uint8)
+    ties = [warp_ref.find_tie_row(rng, 256, 97, col_scale=0.6, col_offset=3.3) for _ in range(3)]
+    invs = np.stack([m for m, _ in ties])
+    want = []
+    for m, y in ties:
+        proper, fused = warp_ref.warp_affine_u8(img, m, (192, 256), inverse=True), warp_ref.warp_affine_u8(img, m, (192, 256), inverse=True, fused=True)
+        rows = (proper != fused).any(axis=(1, 2))
+        assert rows[y] and rows.sum() == 1 and (proper[y] != fused[y]).sum() > 100, y  # otherwise the row proves nothing
+        want.append(proper.transpose(2, 0, 1))
+    dev = torch.device("cuda")
+    stream = _lib.stream_ptr(dev)
+    t_img, t_inv = torch.from_numpy(img).to(dev), torch.from_numpy(invs).to(dev)
+    out = torch.full((3, 3, 256, 192), 7, dtype=torch.uint8, device=dev)
+    if kernel == "pp_warp_affine_u8":
+        _lib.call("pp_warp_affine_u8", t_img.data_ptr(), 97, 131, 3, t_inv.data_ptr(), out.data_ptr(), 3, 256, 192, stream)
+    else:
+        other = torch.from_numpy(rng.integers(0, 256, (40, 50, 3), dtype=np.uint8)).to(dev)  # image 0 of the batch: not the one the crops read
+        ptrs = torch.tensor([other.data_ptr(), t_img.data_ptr()], dtype=torch.int64, device=dev)
+        sides = torch.tensor([40, 50, 97, 131], dtype=torch.int32, device=dev)
+        crop_image = torch.tensor([1, 1, 1], dtype=torch.int32, device=dev)
+        _lib.call("pp_warp_affine_u8_batch", ptrs.data_ptr(), sides.data_ptr(), 3, crop_image.data_ptr(), t_inv.data_ptr(), 97, 131, out.data_ptr(),
+                  3, 256, 192, stream)
+    torch.cuda.synchronize()
+    got = out.cpu().numpy()
+    for i, (_, y) in enumerate(ties):
+        assert np.array_equal(got[i][:, y], want[i][:, y]), f"{kernel}: row {y} of crop {i}: {(got[i][:, y] != want[i][:, y]).sum()} bytes differ"
+        assert np.array_equal(got[i], want[i]), (kernel, i)
+
+
+@pytest.mark.gpu
 def test_inference_topdown_end_to_end():
     """image + boxes -> PoseDataSamples; equals pack_crops + test_step on the same crops; keypoints land inside the
     padded box in image coordinates; default box = whole image."""

@@ -1,8 +1,17 @@
 """Heatmaps back on the image: revert_heatmap + merge_data_samples + the posterior the visualiser
 draws. The warp itself is cv2's (absent here): the oracle restates the published algorithm (UNPINNED, see
-oracle/warp_ref.py); the matrix arithmetic has known answers."""
+oracle/warp_ref.py); the matrix arithmetic has known answers. The kernel is held to the oracle bit for bit (pp_warp.hip is
+built without multiply-add contraction): NaN and infinities through the merge, a row on a rounding tie of the coordinate
+arithmetic, refusals that write nothing, the posterior's 0 / 0 and NaN channels, and tests/fuzz_revert.py for a few seconds."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
 
 
 def test_warp_matrix_known_answers():
@@ -55,12 +64,12 @@ def test_hip_revert_matches_oracle(lib_built):
         got = revert_heatmap(hms[i], centers[i], scales[i], (240, 320))
         ref = warp_ref.revert_heatmap(hms[i], centers[i], scales[i], (240, 320))
         assert got.shape == ref.shape == (17, 240, 320)
-        assert np.abs(got - ref).max() <= 2e-7  # float32 sum of four products: fused vs separate multiply-add
+        assert np.array_equal(got, ref)  # the same four float32 products summed in the same order: no tolerance
     got = revert_heatmaps_max(hms, centers, scales, (240, 320)).cpu().numpy()
     ref = np.max([warp_ref.revert_heatmap(h, c, s, (240, 320)) for h, c, s in zip(hms, centers, scales)], axis=0)
-    assert np.abs(got - ref).max() <= 2e-7 and got.max() > 0.5
+    assert np.array_equal(got, ref) and got.max() > 0.5
     one = revert_heatmap(hms[0, 3], centers[0], scales[0], (240, 320))  # a single (h, w) map
-    assert one.shape == (240, 320) and np.abs(one - warp_ref.revert_heatmap(hms[0, 3:4], centers[0], scales[0], (240, 320))[0]).max() <= 2e-7
+    assert one.shape == (240, 320) and np.array_equal(one, warp_ref.revert_heatmap(hms[0, 3:4], centers[0], scales[0], (240, 320))[0])
 
 
 @pytest.mark.gpu
@@ -83,8 +92,8 @@ def test_merge_data_samples_heatmaps_and_posterior(lib_built):
     merged = merge_data_samples(samples)
     plain, padded, pad = warp_ref.merge_heatmaps(hms, centers, scales, ori)
     assert pad[0] > 0 and pad[1] > 0 and merged.image_pad.tolist() == pad.tolist()
-    assert merged.pred_fields.heatmaps.shape == padded.shape and np.abs(merged.pred_fields.heatmaps - padded).max() <= 2e-7
-    assert np.abs(merged.gt_fields.heatmaps - plain).max() <= 2e-7
+    assert merged.pred_fields.heatmaps.shape == padded.shape and np.array_equal(merged.pred_fields.heatmaps, padded)
+    assert np.array_equal(merged.gt_fields.heatmaps, plain)
     assert merged.pred_instances.keypoints.shape == (4, 17, 2) and merged.input_center.shape == (4, 2)
     post = posterior_heatmaps(merged.pred_fields.heatmaps, merged.pred_instances.keypoints_probs).cpu().numpy()
     ref = warp_ref.posterior(padded, probs)
@@ -99,3 +108,181 @@ def test_revert_needs_the_gpu():
         revert_heatmaps_max(np.zeros((1, 17, 64, 48), np.float32), [[10.0, 10.0]], [[96.0, 128.0]], (100, 100), device="cpu")
     with pytest.raises(RuntimeError):
         posterior_heatmaps(np.ones((17, 10, 10), np.float32), np.ones((1, 17)), device="cpu")
+
+
+# ------------------------------------------------------------------------------------ NaN and infinities through the merge
+def _merge_inputs(n):
+    """n persons whose windows lie inside a 240 x 320 image, maps with negative entries; person 0's tap (30, 20) is seen."""
+    rng = np.random.default_rng(40 + n)
+    hms = (rng.random((n, 17, 64, 48)).astype(np.float32) ** 4 - np.float32(0.2)).astype(np.float32)
+    centers = np.array([[150.0, 120.0], [90.0, 100.0], [200.0, 140.0]])[:n]
+    scales = np.array([[96.0, 128.0], [120.0, 160.0], [60.0, 80.0]])[:n]
+    return hms, centers, scales
+
+
+def _oracle_merge(hms, centers, scales, shape):
+    from oracle import warp_ref
+
+    with np.errstate(invalid="ignore"):
+        return np.max([warp_ref.revert_heatmap(h, c, s, shape) for h, c, s in zip(hms, centers, scales)], axis=0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 3])
+@pytest.mark.parametrize("special", [np.nan, np.inf, -np.inf], ids=["nan", "posinf", "neginf"])
+def test_merge_keeps_nan_and_infinities(lib_built, n, special):
+    """One poisoned tap of person 0: the merged map is numpy's np.max over the persons' maps - NaN wherever the tap is in a
+    pixel's four-tap footprint (an infinity times a weight of zero is NaN too), every other pixel as in the clean run."""
+    import fuzz_revert as FR
+    from oracle import warp_ref
+
+    hms, centers, scales = _merge_inputs(n)
+    k, tap = 5, (30, 20)
+    invs = np.stack([FR.inverse_map(c, s, (48, 64)) for c, s in zip(centers, scales)])
+    clean = FR.launch_revert(hms, invs, 240, 320)
+    assert np.array_equal(clean, _oracle_merge(hms, centers, scales, (240, 320)))
+    hms[0, k, tap[0], tap[1]] = special
+    got = FR.launch_revert(hms, invs, 240, 320)
+    want = _oracle_merge(hms, centers, scales, (240, 320))
+    touched = warp_ref.tap_footprint(warp_ref.revert_matrix(centers[0], scales[0], (48, 64)), (320, 240), tap)
+    assert 16 <= touched.sum() <= 64  # the window is 2 image pixels per map pixel: a footprint of about 4 x 4 pixels
+    own = warp_ref.revert_heatmap(hms[0], centers[0], scales[0], (240, 320))[k]  # person 0 alone
+    if np.isnan(special):
+        assert np.isnan(want[k][touched]).all()
+    else:  # +-inf where the tap has weight, NaN where its weight is zero - and the merge keeps that NaN
+        assert (np.isnan(own[touched]) | (own[touched] == special)).all() and np.isnan(own[touched]).any() and (own[touched] == special).any()
+        assert np.array_equal(np.isnan(want[k]), np.isnan(own))
+    assert np.array_equal(np.isnan(got[k]), np.isnan(want[k])), "NaN dropped (or invented) by the merge"
+    assert np.array_equal(got, want, equal_nan=True)
+    untouched = np.ones(got.shape, bool)
+    untouched[k][touched] = False
+    assert np.array_equal(FR.bits(got)[untouched], FR.bits(clean)[untouched])
+
+
+@pytest.mark.gpu
+def test_merge_of_minus_infinity_maps_and_merge_data_samples(lib_built):
+    """A map that is -inf everywhere: -inf on every pixel its window covers (the maxima start from -inf, not from -FLT_MAX), 0
+    outside the window; and merge_data_samples on poisoned samples agrees with the oracle's merge."""
+    import fuzz_revert as FR
+    from oracle import warp_ref
+    from probpose_code_amd.structures import PixelData, PoseDataSample, merge_data_samples
+
+    hm = np.full((1, 2, 64, 48), -np.inf, np.float32)
+    # 8 image pixels per map pixel, shifted by 1/64: every coordinate is 1/32 + k/8, so no tap has weight zero
+    cover = np.array([[0.125, 0.0, 1.0 / 64, 0.0, 0.125, 1.0 / 64]])
+    got = FR.launch_revert(hm, cover, 240, 320)
+    assert np.array_equal(got, warp_ref.warp_affine_f32(hm[0].transpose(1, 2, 0), cover.reshape(2, 3), (320, 240), inverse=True).transpose(2, 0, 1))
+    assert (got == -np.inf).all()
+    centers, scales = np.array([[150.0, 120.0]]), np.array([[96.0, 128.0]])
+    got = FR.launch_revert(hm, FR.inverse_map(centers[0], scales[0], (48, 64))[None], 240, 320)
+    want = _oracle_merge(hm, centers, scales, (240, 320))
+    assert np.array_equal(got, want, equal_nan=True)
+    assert (got[:, :50] == 0).all() and (got[:, 100:140, 130:170] == -np.inf).sum() >= 800 and not (got < -np.inf).any()
+    assert set(np.unique(got[~np.isnan(got)]).tolist()) == {0.0, -np.inf}
+    # merge_data_samples: three persons, one NaN tap, one all -inf map, a window over the corner (padding)
+    hms, centers, scales = _merge_inputs(3)
+    hms[0, 5, 30, 20], hms[2, 7] = np.nan, -np.inf
+    centers[1] = [5.0, 10.0]
+    samples = []
+    for i in range(3):
+        ds = PoseDataSample(metainfo=dict(ori_shape=(240, 320), input_center=centers[i], input_scale=scales[i], img_id=1))
+        ds.pred_fields = PixelData(heatmaps=hms[i])
+        ds.gt_fields = PixelData(heatmaps=hms[i])
+        samples.append(ds)
+    with np.errstate(invalid="ignore"):
+        plain, padded, pad = warp_ref.merge_heatmaps(hms, centers, scales, (240, 320))
+    merged = merge_data_samples(samples)
+    assert pad[0] > 0 and np.isnan(padded[5]).sum() >= 16 and np.isnan(plain[5]).sum() >= 16
+    assert np.array_equal(merged.pred_fields.heatmaps, padded, equal_nan=True)
+    assert np.array_equal(merged.gt_fields.heatmaps, plain, equal_nan=True)
+
+
+# ------------------------------------------------------------------------------------------------------ the rounding tie
+@pytest.mark.gpu
+def test_revert_row_on_a_rounding_tie(lib_built):
+    """A row y where fl(fl(M4 y) + M5) * 1024 is exactly n + 0.5 (n % 32 == 15) while the exact M4 y + M5 lies below: a fused
+    multiply-add rounds to n, the separate roundings of cv2 to n + 1, and the row's weights differ by 1/32. The kernel must
+    side with the oracle."""
+    import fuzz_revert as FR
+    from oracle import warp_ref
+
+    rng = np.random.default_rng(77)
+    M, y = warp_ref.find_tie_row(rng, 240, 64, col_scale=0.14, col_offset=0.3)
+    hm = rng.random((1, 17, 64, 48)).astype(np.float32)
+    want = warp_ref.warp_affine_f32(hm[0].transpose(1, 2, 0), M, (320, 240), inverse=True).transpose(2, 0, 1)
+    fused = warp_ref.warp_affine_f32(hm[0].transpose(1, 2, 0), M, (320, 240), inverse=True, fused=True).transpose(2, 0, 1)
+    differs = (want != fused).any(axis=(0, 2))
+    assert differs[y] and differs.sum() == 1 and (want[:, y] != fused[:, y]).sum() > 1000  # the row tells the two roundings apart
+    got = FR.launch_revert(hm, M.reshape(1, 6), 240, 320)
+    assert np.array_equal(got[:, y], want[:, y]), f"row {y}: {(got[:, y] != want[:, y]).sum()} floats differ from the unfused oracle"
+    assert np.array_equal(got, want)
+
+
+# --------------------------------------------------------------------------------------------------------------- refusals
+@pytest.mark.gpu
+def test_revert_refusals_write_nothing(lib_built):
+    """Every refused call returns its documented status and leaves the (rightly sized) output untouched."""
+    import torch
+
+    import fuzz_revert as FR
+    from probpose_code_amd import _lib
+
+    stream = _lib.stream_ptr(torch.device("cuda"))
+    cases = [  # (n, K, hm_h, hm_w, img_h, img_w, NULL argument, status)
+        (1, 33, 2, 2, 4, 4, None, _lib.PP_ERR_INVALID_ARG),
+        (0, 2, 2, 2, 4, 4, None, _lib.PP_ERR_INVALID_ARG),
+        (1, 1, 32768, 1, 4, 4, None, _lib.PP_ERR_UNSUPPORTED),
+        (1, 1, 2, 2, 65536, 1, None, _lib.PP_ERR_UNSUPPORTED),
+        (1, 2, 2, 2, 4, 4, "heatmaps", _lib.PP_ERR_INVALID_ARG),
+        (1, 2, 2, 2, 4, 4, "inverse_maps", _lib.PP_ERR_INVALID_ARG),
+        (1, 2, 2, 2, 4, 4, "out", _lib.PP_ERR_INVALID_ARG),
+    ]
+    for n, K, hh, hw, H, W, null, status in cases:
+        hm = torch.zeros(max(n, 1) * K * hh * hw, dtype=torch.float32, device="cuda")
+        inv = torch.tensor([[1.0, 0, 0, 0, 1.0, 0]] * max(n, 1), dtype=torch.float64, device="cuda")
+        out = FR.Guarded(K * H * W, 4, "cuda")
+        args = dict(heatmaps=hm.data_ptr(), inverse_maps=inv.data_ptr(), out=out.ptr)
+        if null:
+            args[null] = None
+        got = _lib.lib.pp_revert_heatmaps_max(args["heatmaps"], args["inverse_maps"], args["out"], n, K, hh, hw, H, W, stream)
+        torch.cuda.synchronize()
+        assert got == status, (n, K, hh, hw, H, W, null, got, _lib.last_error())
+        body = out.get(np.int32, "refused output", require_written=False)
+        assert (body == FR.UNWRITTEN32).all(), (n, K, hh, hw, H, W, null)
+
+
+# ---------------------------------------------------------------------------------------------------------- posterior edges
+@pytest.mark.gpu
+def test_posterior_zero_and_nan_channels(lib_built):
+    """An all-zero channel is 0 / 0 = NaN in every element, as numpy's is; one NaN in a channel makes its total - and the whole
+    channel - NaN; the channels next to them are bit-identical to the clean run."""
+    import torch
+
+    import fuzz_revert as FR
+
+    rng = np.random.default_rng(50)
+    K, H, W = 5, 37, 53
+    hm = (rng.random((K, H, W)) ** 6 + 2.0 ** -30).astype(np.float32)
+    pr = torch.from_numpy(rng.uniform(0.1, 1.0, (2, K)).astype(np.float32)).cuda().mean(dim=0)
+    clean, parts = FR.launch_posterior(hm, pr, return_scratch=True)
+    want, bound = FR.posterior_reference(hm, np.tile(pr.cpu().numpy(), (2, 1)))
+    FR.compare_posterior(clean, want, bound)
+    assert np.allclose(parts.sum(axis=1), hm.astype(np.float64).sum(axis=(1, 2)), rtol=1e-12)
+    bad = hm.copy()
+    bad[1] = 0.0
+    bad[3, 17, 29] = np.nan
+    got = FR.launch_posterior(bad, pr)
+    assert np.isnan(got[1]).all() and np.isnan(got[3]).all()
+    for k in (0, 2, 4):
+        assert np.array_equal(FR.bits(got[k]), FR.bits(clean[k]))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ref = bad / bad.sum(axis=(1, 2), keepdims=True) * pr.cpu().numpy()[:, None, None]
+    assert np.array_equal(np.isnan(got), np.isnan(ref))
+
+
+@pytest.mark.gpu
+def test_revert_differential_fuzz_against_the_oracle(lib_built):
+    """tests/fuzz_revert.py for a few seconds: revert + merge bit for bit against the oracle, the posterior within its derived
+    bound of fp64, canaries, written-everywhere and repeat launches."""
+    r = subprocess.run([sys.executable, os.path.join(HERE, "fuzz_revert.py"), "10"], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "REVERT FUZZ OK" in r.stdout, (r.stdout[-1500:], r.stderr[-1500:])
