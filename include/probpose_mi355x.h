@@ -327,7 +327,9 @@ int pp_skinny_conv1x1_planar(const void* act, const void* weight_padded, const f
 /* ConvTranspose2d(Cin -> Cout, k4, s2, p1, bias=False) + folded BatchNorm + ReLU of a SMALL batch (mmpose/models/heads/hybrid_heads/
  * probmap_head.py:435-472): act_nhwc (B, H, W, Cin), out_nhwc (B, 2H, 2W, Cout) PP_OUT_SPLIT; weight / bias as PP_DECONV4X4S2 of pp_conv_gemm
  * with py < 0 (four phase matrices (Cout, 4 Cin), BatchNorm folded). The four output phases are four column-parallel GEMMs of one launch on
- * pp_skinny_linear's tiles, the taps gathered by LDS-DMA (zeros outside the map); same sums in the same order as pp_conv_gemm. */
+ * pp_skinny_linear's tiles, the taps gathered by LDS-DMA (zeros outside the map); same sums in the same order as pp_conv_gemm.
+ * Cin % 32 == 0 and Cin >= 64 (a stage of two 32-channel blocks stays within one tap or steps into the next one once), Cout % 32 == 0, else
+ * PP_ERR_UNSUPPORTED: pp_conv_gemm serves every other width. */
 int pp_skinny_deconv(const void* act_nhwc, const void* weight, const float* bias, void* out_nhwc, int B, int H, int W, int Cin, int Cout,
                      void* stream);
 
@@ -386,7 +388,9 @@ int pp_proj_mlp_residual_layernorm(const void* attn, const void* wp, const float
  *                    matrices back to back, order (py, px) = (0,0), (0,1), (1,0), (1,1).
  * BatchNorm is folded into weight/bias by the caller; act_fn applies after bias. `groups`
  * launches several independent convolutions at once (the four towers): operand g is at
- * base + g * stride_*_g elements. ldc = row stride of out in elements. */
+ * base + g * stride_*_g elements. ldc = row stride of out in elements. Cin must be a multiple of the
+ * precision's K-tile - 64 channels (bf16), 32 (fp32, split fp16): a K-tile never straddles two taps - else
+ * PP_ERR_UNSUPPORTED. */
 int pp_conv_gemm(int prec, int kind, const void* act_nhwc, const void* weight, const float* bias, void* out,
                  int B, int H, int W, int Cin, int Cout, int py, int px, int groups,
                  long long stride_act_g, long long stride_w_g, long long stride_out_g,
@@ -540,7 +544,9 @@ int pp_proj_ffn_split_folded(const void* att, const void* wproj_packed, const fl
  * pp_conv_gemm with py < 0 (four phase matrices, folded BatchNorm); head_w (32, 256) bf16 = the 1x1 kernel, rows >= K
  * zero; head_b (K) fp32, K <= 28 (the kernel keeps both biases in the unused weight rows of its LDS image). The 256-channel
  * feature map is never stored. logits_phased (B, K, 4, H*W) fp32: output pixel
- * (2y + py, 2x + px) of map (b, k) sits at [b, k, 2 py + px, y W + x] - the layout pp_probmap_head_decode_phased reads. */
+ * (2y + py, 2x + px) of map (b, k) sits at [b, k, 2 py + px, y W + x] - the layout pp_probmap_head_decode_phased reads.
+ * Cout == 256, Cin % 64 == 0 (the kernel's stages are 64 channels of one tap) and H * W % 4 == 0, else PP_ERR_UNSUPPORTED: use
+ * pp_conv_gemm + pp_gemm. */
 int pp_deconv_head(const void* act_nhwc, const void* weight, const float* bias, const void* head_w, const float* head_b,
                    float* logits_phased, int B, int H, int W, int Cin, int Cout, int K, void* stream);
 

@@ -475,7 +475,8 @@ bool panel_gemm_supported(const GemmParams& p, int prec, int groups) {
     if (prec != PP_PREC_BF16 || (!p.out_bf16 && !partials) || p.residual || p.planar_P > 0) return false;
     if (p.ksplit > 1 && !partials) return false;
     if (p.act != ACT_NONE && p.act != ACT_RELU) return false;
-    if (p.Cin % 32 != 0 || p.K % 128 != 0 || p.ldc % 8 != 0) return false;
+    // Cin % 64 == 0: the DMA cursor moves 64 channels a stage and changes tap where it meets Cin (advance_cursor)
+    if (p.Cin % 64 != 0 || p.K % 128 != 0 || p.ldc % 8 != 0) return false;
     int BM, BN;
     if (p.gather == G_DECONV) { BM = 192; BN = 256; }
     else if (p.gather == G_CONV3) { BM = 256; BN = 192; }

@@ -648,8 +648,10 @@ extern "C" int pp_skinny_deconv(const void* act_nhwc, const void* weight, const 
     using namespace pp;
     PP_REQUIRE(act_nhwc && weight && out_nhwc, PP_ERR_INVALID_ARG, "pp_skinny_deconv: NULL argument");
     PP_REQUIRE(B > 0 && H > 0 && W > 0, PP_ERR_INVALID_ARG, "pp_skinny_deconv: bad shape");
-    PP_REQUIRE(Cin > 0 && Cin % 32 == 0 && (4 * Cin) % 64 == 0 && Cout > 0 && Cout % 32 == 0, PP_ERR_UNSUPPORTED,
-               "pp_skinny_deconv: needs Cin % 32 == 0 and Cout % 32 == 0");
+    // sk::KS <= Cin / 32: a stage's k-blocks lie inside one tap or step into the next one once (the cursor of skinny_linear_kernel's issue());
+    // at Cin = 32 a stage spans two taps and the cursor would read the neighbouring pixel's channels
+    PP_REQUIRE(Cin > 0 && Cin % 32 == 0 && sk::KS <= Cin / 32 && (4 * Cin) % (32 * sk::KS) == 0 && Cout > 0 && Cout % 32 == 0, PP_ERR_UNSUPPORTED,
+               "pp_skinny_deconv: needs Cin % 32 == 0, Cin >= 64 (a stage of two k-blocks within Cin / 32 blocks per tap) and Cout % 32 == 0");
     const long long M = (long long)B * H * W, K = 4ll * Cin;
     PP_REQUIRE(M * Cin * 4 < 0x7ffffff0ll && (long long)Cout * K * 4 < 0x7ffffff0ll && 4 * M * Cout * 4 < 0x7ffffff0ll, PP_ERR_UNSUPPORTED,
                "pp_skinny_deconv: operands must be smaller than 2 GiB");

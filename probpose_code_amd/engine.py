@@ -145,6 +145,14 @@ class ProbPoseEngine:
         self.hd = self.E // num_heads
         self.K = self.w.num_keypoints
         self.up = 2 ** len(self.w.deconv_channels)
+        if precision == "bf16":
+            # every bf16 convolution kernel walks K in tiles of 64 channels of one tap (pp_conv_gemm, pp_deconv_head): a deconvolution whose
+            # input width is no multiple of 64 has no bf16 kernel. Said here, by name, and not as PP_ERR_UNSUPPORTED at the first batch
+            for j, cin in enumerate([self.E] + list(self.w.deconv_channels)[:-1]):
+                if cin % 64 != 0:
+                    raise ValueError(f"precision 'bf16' needs every deconvolution's input width to be a multiple of 64 channels, but deconvolution "
+                                     f"{j} reads {cin} (deconv_out_channels = {tuple(self.w.deconv_channels)}); use precision 'f16x3' or 'f32', "
+                                     "which take multiples of 32")
         self.Hh, self.Wh = self.Hp * self.up, self.Wp * self.up  # heatmap size
         self.input_size = tuple(input_size) if input_size is not None else (self.W, self.H)
         self.mean = (np.asarray(mean, np.float32)).copy()
@@ -615,7 +623,7 @@ class ProbPoseEngine:
         for j, cout in enumerate(w.deconv_channels):
             dst = ws[f"d{j}"]
             wj = w[f"deconv{j}.w"]
-            if (j == nd - 1 and self.fuse_head and ob == 1 and cout == 256 and w.has("final.w_pad") and cin % 32 == 0
+            if (j == nd - 1 and self.fuse_head and ob == 1 and cout == 256 and w.has("final.w_pad") and cin % 64 == 0
                     and ww % 4 == 0 and self.K <= 28):
                 # last deconvolution + the 1x1 conv behind it in one kernel; the 256-channel map is never stored and the
                 # logits come out phase-separated (the decode kernel reads that layout directly)
@@ -632,7 +640,7 @@ class ProbPoseEngine:
                            self.K, st)
                 self._logits_phased = True
                 return ws["logits"]
-            if ob == 2 and self._small_at(nb * self.Np) and nb * hh * ww <= 1536 and cin % 32 == 0 and cout % 32 == 0:
+            if ob == 2 and self._small_at(nb * self.Np) and nb * hh * ww <= 1536 and cin % 32 == 0 and cin >= 64 and cout % 32 == 0:
                 # a FEW input pixels (<= 1 536: both deconvolutions of one crop, the first one up to four crops with flip test): the four phases as
                 # column-parallel GEMMs on pp_skinny_linear's tiles - 19.6 / 37.1 us against 61.2 / 44.8 for the 128 x 128 kernel's 24 / 96
                 # workgroups at B = 1; from 3 072 pixels on the 128 x 128 kernel wins (scripts/r06/skinny_deconv_sweep.py)

@@ -34,7 +34,7 @@ import torch.nn.functional as F
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 from fuzz_head import TOL as HEAD_TOL  # noqa: E402
-from fuzz_head import bad_pixels, conv3x3_64, conv_reach, deconv_phases, poison_, poison_ratio  # noqa: E402
+from fuzz_head import bad_pixels, conv3x3_64, conv_reach, deconv_phases, poison_, poison_ratio, run_guarded  # noqa: E402
 from fuzz_layer import (BF16, F16X3, F32, MASSIVE, MEM_CAP, SPLIT, Guard, Refused, cpu_rand, error_ratio, gelu64, layernorm64,  # noqa: E402
                         ln_factor, magnitude_factor, rows_of_class, run_entries, run_twice)
 from fuzz_layer import TOL as LAYER_TOL  # noqa: E402
@@ -143,8 +143,11 @@ def input_of_class(cls, B, H, W, C, g):
 
 # ----------------------------------------------------------------------------------------------------- the dispatcher, mirrored
 def conv_kernel(prec, kind, B, H, W, Cin, Cout, groups, fmt, act, opt):
-    """Which kernel pp_conv_gemm launches (pp_gemm.hip: panel_split_supported, conv_halo_supported, panel_gemm_supported, else gemm)."""
+    """Which kernel pp_conv_gemm launches (pp_gemm.hip: panel_split_supported, conv_halo_supported, panel_gemm_supported, else gemm); "refused":
+    Cin is no multiple of the precision's K-tile (64 channels in bf16, 32 in fp32 and f16x3), PP_ERR_UNSUPPORTED from every kernel."""
     M, K = B * H * W, (9 if kind == CONV3X3 else 4) * Cin
+    if Cin % (64 if prec == BF16 else 32) != 0:
+        return "refused"
 
     def tiles(bm, bn):
         return (Cout // bn) * ((M + bm - 1) // bm) * groups
@@ -165,7 +168,7 @@ def conv_kernel(prec, kind, B, H, W, Cin, Cout, groups, fmt, act, opt):
         if (opt["conv_halo"] and prec == BF16 and kind == CONV3X3 and fmt == 1 and act in (ACT_NONE, ACT_RELU) and H * W == 192
                 and (H + 2) * (W + 2) == 252 and Cin % 128 == 0 and Cout % 128 == 0 and tiles(384, 128) >= 192):
             return "pp_conv_halo.hip"
-        if prec == BF16 and fmt == 1 and act in (ACT_NONE, ACT_RELU) and Cin % 32 == 0 and K % 128 == 0:
+        if prec == BF16 and fmt == 1 and act in (ACT_NONE, ACT_RELU) and Cin % 64 == 0 and K % 128 == 0:
             bm, bn = (192, 256) if kind == DECONV else (256, 192)
             if Cout % bn == 0 and tiles(bm, bn) >= 192:
                 return "pp_panel_gemm.hip"
@@ -175,7 +178,7 @@ def conv_kernel(prec, kind, B, H, W, Cin, Cout, groups, fmt, act, opt):
 def splitk_kernel(prec, B, H, W, Cin, Cout, groups, ks, opt):
     """pp_conv3x3_splitk for whole-tap slices: the wide-tile bf16 kernel (fp32 partials) with enough tiles, else the 128 x 128 kernel."""
     M = B * H * W
-    if opt["panel"] and prec == BF16 and Cin % 32 == 0 and (9 * Cin // ks) % 128 == 0 and Cout % 192 == 0 and ks > 1:
+    if opt["panel"] and prec == BF16 and Cin % 64 == 0 and (9 * Cin // ks) % 128 == 0 and Cout % 192 == 0 and ks > 1:
         if (Cout // 192) * ((M + 255) // 256) * groups * ks >= 192:
             return "pp_panel_gemm.hip"
     return "pp_gemm.hip"
@@ -190,26 +193,190 @@ def b_around(tiles_per_img, rng, lo=1, hi=None):
     return min(B, hi) if hi else B
 
 
+# ----------------------------------------------------------------------------------------------------- GPU helpers and single cases
+def sp(x):
+    from probpose_code_amd.weights import to_split
+
+    return to_split(x.float()).cuda()
+
+
+def unsp(c):
+    from probpose_code_amd.weights import from_split
+
+    return from_split(c.float().cpu()).double()
+
+
+def launch(fn, *args):
+    from probpose_code_amd import _lib as L
+
+    try:
+        L.call(fn, *args)
+    except L.ProbPoseLibraryError as exc:
+        if "UNSUPPORTED" in str(exc) or "INVALID" in str(exc):
+            raise Refused(str(exc)) from None
+        raise
+    torch.cuda.synchronize()
+
+
+def ran():
+    from probpose_code_amd import _lib as L
+
+    return [k for k in KERNELS if L.launch_count(k) > 0]
+
+
+def apply_options(opt):
+    from probpose_code_amd import _lib as L
+
+    for k, v in opt.items():
+        if L.get_option(k) != v:
+            L.set_option(k, v)
+
+
+def dev(x, prec):
+    """CPU fp32 -> device operand of the precision; and the fp64 values the kernel multiplies (bf16-rounded for bf16)."""
+    if prec == F16X3:
+        return sp(x), x.double()
+    if prec == BF16:
+        return x.bfloat16().cuda(), x.bfloat16().double()
+    return x.cuda(), x.double()
+
+
+def out_of(snap_t, fmt):
+    return unsp(snap_t) if fmt == SPLIT else snap_t.cpu().double()
+
+
+def tol_ratio(got, ref, prec, fmt, fac):
+    if prec == F16X3:
+        return error_ratio(got, ref, fac[0] * fac[1], fac[0] * fac[1])
+    if prec == F32:
+        return error_ratio(got, ref, F32_TOL, F32_TOL)
+    return bf16_out_ratio(got, ref) if fmt == 1 else error_ratio(got, ref, BF16_F32OUT_TOL, BF16_F32OUT_TOL)
+
+
+def pick(n, rng, k):
+    return torch.unique(torch.tensor([0, n - 1] + rng.integers(0, n, k).tolist())) if n > k + 2 else torch.arange(n)
+
+
+def conv_gemm_case(prec, kind, B, H, W, Cin, Cout, groups, fmt, act, bias, shared, phase, cls, opt, oname, rng, g, record=None, kernels=None):
+    """One guarded launch pair of pp_conv_gemm -> (faults, error / tolerance, description). PP_CONV3X3 with `groups` problems on shared or
+    separate inputs; PP_DECONV4X4S2 with all four phases in one launch (phase < 0) or one launch each, `phase` first. ``opt``: the steering
+    options to run under (``oname``: the one that differs from the defaults, for the description). The kernels that ran are handed to
+    ``record`` and appended to ``kernels``."""
+    from probpose_code_amd import _lib as L
+
+    kname = "conv3x3" if kind == CONV3X3 else "deconv"
+    want = conv_kernel(prec, kind, B, H, W, Cin, Cout, groups if kind == CONV3X3 else (4 if phase < 0 else 1), fmt, act, opt)
+    apply_options(opt)
+    ng = 1 if shared else groups
+    x = torch.stack([input_of_class(cls, B, H, W, Cin, g) for _ in range(ng)])
+    if kind == CONV3X3:
+        w = cpu_rand(groups, Cout, Cin, 3, 3, g=g, scale=1 / math.sqrt(9 * Cin))
+        wk = w.permute(0, 1, 3, 4, 2).reshape(groups, Cout, 9 * Cin)
+    else:
+        w = cpu_rand(1, Cin, Cout, 4, 4, g=g, scale=1 / math.sqrt(4 * Cin))
+        wk = deconv_phases(w[0]).reshape(1, 4, Cout, 4 * Cin)
+    b = cpu_rand(groups, Cout, g=g, scale=0.3)
+    guard = Guard()
+    xd, xq = dev(x, prec)
+    wd, wq = dev(wk, prec)
+    xd, wd = guard.inp("act", xd), guard.inp("weight", wd)
+    bd = guard.inp("bias", b) if bias else None
+    odt = torch.bfloat16 if fmt == 1 else torch.float32
+    oh, ow = (H, W) if kind == CONV3X3 else (2 * H, 2 * W)
+    out = guard.out("out", (groups, B, oh, ow, Cout), dtype=odt)
+    sa = 0 if shared else B * H * W * Cin
+
+    def go():
+        if kind == CONV3X3:
+            launch("pp_conv_gemm", prec, CONV3X3, xd.data_ptr(), wd.data_ptr(), L.ptr(bd), out.data_ptr(), B, H, W, Cin, Cout, 0, 0, groups, sa,
+                   Cout * 9 * Cin, B * H * W * Cout, Cout if bias else 0, Cout, act, fmt, None)
+        elif phase < 0:
+            launch("pp_conv_gemm", prec, DECONV, xd.data_ptr(), wd.data_ptr(), L.ptr(bd), out.data_ptr(), B, H, W, Cin, Cout, -1, 0, 1, 0, 0, 0, 0,
+                   Cout, act, fmt, None)
+        else:  # the four phases, one launch each, `phase` first
+            for k in range(4):
+                py, px = divmod((phase + k) % 4, 2)
+                launch("pp_conv_gemm", prec, DECONV, xd.data_ptr(), wd[0, 2 * py + px].data_ptr(), L.ptr(bd), out.data_ptr(), B, H, W, Cin, Cout,
+                       py, px, 1, 0, 0, 0, 0, Cout, act, fmt, None)
+    L.reset_launch_counts()
+    faults, snap = run_guarded(guard, go)
+    got_k = ran()
+    if kernels is not None:
+        kernels += got_k
+    if record is not None:
+        record("pp_conv_gemm", prec, kname, got_k)
+    if got_k != [want]:
+        faults.append(f"kernel {got_k}, the mirrored dispatcher predicts {want}")
+    imgs = pick(B, rng, 1)
+    ratio = 0.0
+    fac = (HEAD_TOL["conv_pool"] if kind == CONV3X3 else HEAD_TOL["deconv_head"], magnitude_factor(xq[:, imgs].reshape(-1, Cin)))
+    for k in range(groups):
+        xi = xq[0 if shared or kind == DECONV else k][imgs].permute(0, 3, 1, 2)
+        if kind == CONV3X3:
+            ch = torch.from_numpy(rng.choice(Cout, min(Cout, 48), replace=False))
+            wt = wq[k].reshape(Cout, 3, 3, Cin).permute(0, 3, 1, 2)[ch]
+            ref = act64(conv3x3_64(xi, wt, b[k][ch].double() if bias else None), act)
+        else:
+            ch = torch.arange(Cout)
+            ph = wq[0].reshape(2, 2, Cout, 4 * Cin)
+            wt = torch.empty(Cin, Cout, 4, 4, dtype=torch.float64)  # the torch weight the (rounded) phase matrices stand for
+            for py in range(2):
+                for px in range(2):
+                    for ty in range(2):
+                        for tx in range(2):
+                            t = ty * 2 + tx
+                            wt[:, :, 3 - 2 * ty - py, 3 - 2 * tx - px] = ph[py, px, :, t * Cin:(t + 1) * Cin].t()
+            ref = act64(deconv64(xi, wt, b[0].double() if bias else None), act)
+        got = out_of(snap[0][k][imgs], fmt)[..., ch].permute(0, 3, 1, 2)
+        ratio = max(ratio, tol_ratio(got, ref, prec, fmt, fac))
+    info = (f"{PREC_NAME[prec]} {kname} B {B} {H}x{W} Cin {Cin} Cout {Cout} groups {groups} shared {shared} phase {phase} bias {bias} act {act} "
+            f"fmt {fmt} class {cls} option {oname}={opt.get(oname)} kernel {want}")
+    return faults, ratio, info
+
+
+def deconv_head_case(B, H, W, Cin, K, cls, rng, g, record=None):
+    """One guarded launch pair of pp_deconv_head (bf16: the last deconvolution to 256 channels + ReLU + the 1x1 convolution to K maps, logits in
+    the phase-separated layout) -> (faults, error / tolerance, description)."""
+    from probpose_code_amd import _lib as L
+
+    Cout = 256
+    x = input_of_class(cls, B, H, W, Cin, g)
+    w = cpu_rand(Cin, Cout, 4, 4, g=g, scale=1 / math.sqrt(4 * Cin))
+    b = cpu_rand(Cout, g=g, scale=0.2)
+    wf, bf = cpu_rand(K, Cout, g=g, scale=4 / math.sqrt(Cout)), cpu_rand(K, g=g)
+    wpad = torch.zeros(32, Cout)
+    wpad[:K] = wf
+    guard = Guard()
+    xd, phd = guard.inp("act", x.bfloat16().cuda()), guard.inp("weight", deconv_phases(w).bfloat16().cuda())
+    bd, hwd, bfd = guard.inp("bias", b), guard.inp("head_w", wpad.bfloat16().cuda()), guard.inp("head_b", bf)
+    lg = guard.out("logits", (B, K, 4, H * W))
+
+    def go():
+        launch("pp_deconv_head", xd.data_ptr(), phd.data_ptr(), bd.data_ptr(), hwd.data_ptr(), bfd.data_ptr(), lg.data_ptr(), B, H, W, Cin, Cout, K,
+               None)
+    L.reset_launch_counts()
+    faults, snap = run_guarded(guard, go)
+    got_k = ran()
+    if record is not None:
+        record("pp_deconv_head", BF16, "deconv", got_k)
+    if got_k != ["pp_panel_gemm.hip"]:
+        faults.append(f"kernels {got_k}")
+    imgs = pick(B, rng, 1)
+    xi = x[imgs].bfloat16().double().permute(0, 3, 1, 2)
+    wq, wfq = w.bfloat16().double(), wf.bfloat16().double()
+    mid = torch.relu(deconv64(xi, wq, b.double())).float().bfloat16().double()  # the kernel hands the 1x1 bf16 activations
+    ref = torch.einsum("bchw,kc->bkhw", mid, wfq) + bf.double().view(1, -1, 1, 1)
+    got = snap[0][imgs].cpu().double().reshape(len(imgs), K, 2, 2, H, W).permute(0, 1, 4, 2, 5, 3).reshape(len(imgs), K, 2 * H, 2 * W)
+    # a mid value at a rounding boundary may round the other way from fp32 than from fp64: one bf16 step of the largest product
+    flip = 2.0 ** -8 * float(mid.abs().max()) * float(wfq.abs().max())
+    return faults, error_ratio(got, ref, BF16_F32OUT_TOL, BF16_F32OUT_TOL + flip), f"B {B} {H}x{W} Cin {Cin} K {K} class {cls}"
+
+
 def _main(seconds):
     from probpose_code_amd import _lib as L
     from probpose_code_amd.weights import from_split, to_split
 
     table = {}  # (entry, prec, kind) -> {kernel: cases}
-
-    def sp(x):
-        return to_split(x.float()).cuda()
-
-    def unsp(c):
-        return from_split(c.float().cpu()).double()
-
-    def launch(fn, *args):
-        try:
-            L.call(fn, *args)
-        except L.ProbPoseLibraryError as exc:
-            if "UNSUPPORTED" in str(exc) or "INVALID" in str(exc):
-                raise Refused(str(exc)) from None
-            raise
-        torch.cuda.synchronize()
 
     def draw_options(rng):
         """The defaults with one steering option changed (set by apply_options; the standalone run restores them through run_entries, the suite's
@@ -222,11 +389,6 @@ def _main(seconds):
                          "psplit_conv_weight_major": 0, "psplit_deconv_weight_major": 1}[name]
         return opt, name
 
-    def apply_options(opt):
-        for k, v in opt.items():
-            if L.get_option(k) != v:
-                L.set_option(k, v)
-
     visits = {}
 
     def next_target(entry):
@@ -238,34 +400,10 @@ def _main(seconds):
             return cells[v]
         return cells[(v // 2) % len(cells)] if v % 2 == 0 else None
 
-    def ran():
-        return [k for k in KERNELS if L.launch_count(k) > 0]
-
     def record(entry, prec, kind, kernels):
         cell = table.setdefault((entry, PREC_NAME[prec], kind), {})
         for k in kernels:
             cell[k] = cell.get(k, 0) + 1
-
-    def dev(x, prec):
-        """CPU fp32 -> device operand of the precision; and the fp64 values the kernel multiplies (bf16-rounded for bf16)."""
-        if prec == F16X3:
-            return sp(x), x.double()
-        if prec == BF16:
-            return x.bfloat16().cuda(), x.bfloat16().double()
-        return x.cuda(), x.double()
-
-    def out_of(snap_t, fmt):
-        return unsp(snap_t) if fmt == SPLIT else snap_t.cpu().double()
-
-    def tol_ratio(got, ref, prec, fmt, fac):
-        if prec == F16X3:
-            return error_ratio(got, ref, fac[0] * fac[1], fac[0] * fac[1])
-        if prec == F32:
-            return error_ratio(got, ref, F32_TOL, F32_TOL)
-        return bf16_out_ratio(got, ref) if fmt == 1 else error_ratio(got, ref, BF16_F32OUT_TOL, BF16_F32OUT_TOL)
-
-    def pick(n, rng, k):
-        return torch.unique(torch.tensor([0, n - 1] + rng.integers(0, n, k).tolist())) if n > k + 2 else torch.arange(n)
 
     # ------------------------------------------------------------------------------------------------- pp_conv_gemm
     def case_conv_gemm(rng, g):
@@ -281,6 +419,8 @@ def _main(seconds):
             else:
                 H, W = int(rng.integers(1, 25)), int(rng.integers(1, 25))
                 Cin = int(rng.choice([64, 128, 192, 256, 384]))
+                if kind == DECONV:  # the widths between the K-tiles' multiples too (bf16: refused unless Cin % 64 == 0)
+                    Cin = int(rng.choice([64, 96, 128, 160, 192, 256, 384] + ([] if prec == BF16 else [32])))
             if kind == CONV3X3:
                 Cout = int(rng.choice([Cin, Cin, 192, 384, 128, 96, 64]))
                 groups = int(rng.integers(1, 5))
@@ -308,69 +448,7 @@ def _main(seconds):
             want = conv_kernel(prec, kind, B, H, W, Cin, Cout, groups if kind == CONV3X3 else (4 if phase < 0 else 1), fmt, act, opt)
             if target is None or target == (PREC_NAME[prec], kname, want):
                 break
-        apply_options(opt)
-        ng = 1 if shared else groups
-        x = torch.stack([input_of_class(cls, B, H, W, Cin, g) for _ in range(ng)])
-        if kind == CONV3X3:
-            w = cpu_rand(groups, Cout, Cin, 3, 3, g=g, scale=1 / math.sqrt(9 * Cin))
-            wk = w.permute(0, 1, 3, 4, 2).reshape(groups, Cout, 9 * Cin)
-        else:
-            w = cpu_rand(1, Cin, Cout, 4, 4, g=g, scale=1 / math.sqrt(4 * Cin))
-            wk = deconv_phases(w[0]).reshape(1, 4, Cout, 4 * Cin)
-        b = cpu_rand(groups, Cout, g=g, scale=0.3)
-        guard = Guard()
-        xd, xq = dev(x, prec)
-        wd, wq = dev(wk, prec)
-        xd, wd = guard.inp("act", xd), guard.inp("weight", wd)
-        bd = guard.inp("bias", b) if bias else None
-        odt = torch.bfloat16 if fmt == 1 else torch.float32
-        oh, ow = (H, W) if kind == CONV3X3 else (2 * H, 2 * W)
-        out = guard.out("out", (groups, B, oh, ow, Cout), dtype=odt)
-        sa = 0 if shared else B * H * W * Cin
-
-        def go():
-            if kind == CONV3X3:
-                launch("pp_conv_gemm", prec, CONV3X3, xd.data_ptr(), wd.data_ptr(), L.ptr(bd), out.data_ptr(), B, H, W, Cin, Cout, 0, 0, groups, sa,
-                       Cout * 9 * Cin, B * H * W * Cout, Cout if bias else 0, Cout, act, fmt, None)
-            elif phase < 0:
-                launch("pp_conv_gemm", prec, DECONV, xd.data_ptr(), wd.data_ptr(), L.ptr(bd), out.data_ptr(), B, H, W, Cin, Cout, -1, 0, 1, 0, 0, 0, 0,
-                       Cout, act, fmt, None)
-            else:  # the four phases, one launch each, `phase` first
-                for k in range(4):
-                    py, px = divmod((phase + k) % 4, 2)
-                    launch("pp_conv_gemm", prec, DECONV, xd.data_ptr(), wd[0, 2 * py + px].data_ptr(), L.ptr(bd), out.data_ptr(), B, H, W, Cin, Cout,
-                           py, px, 1, 0, 0, 0, 0, Cout, act, fmt, None)
-        L.reset_launch_counts()
-        faults, snap = run_twice(guard, go)
-        got_k = ran()
-        record("pp_conv_gemm", prec, kname, got_k)
-        if got_k != [want]:
-            faults.append(f"kernel {got_k}, the mirrored dispatcher predicts {want}")
-        imgs = pick(B, rng, 1)
-        ratio = 0.0
-        fac = (HEAD_TOL["conv_pool"] if kind == CONV3X3 else HEAD_TOL["deconv_head"], magnitude_factor(xq[:, imgs].reshape(-1, Cin)))
-        for k in range(groups):
-            xi = xq[0 if shared or kind == DECONV else k][imgs].permute(0, 3, 1, 2)
-            if kind == CONV3X3:
-                ch = torch.from_numpy(rng.choice(Cout, min(Cout, 48), replace=False))
-                wt = wq[k].reshape(Cout, 3, 3, Cin).permute(0, 3, 1, 2)[ch]
-                ref = act64(conv3x3_64(xi, wt, b[k][ch].double() if bias else None), act)
-            else:
-                ch = torch.arange(Cout)
-                ph = wq[0].reshape(2, 2, Cout, 4 * Cin)
-                wt = torch.empty(Cin, Cout, 4, 4, dtype=torch.float64)  # the torch weight the (rounded) phase matrices stand for
-                for py in range(2):
-                    for px in range(2):
-                        for ty in range(2):
-                            for tx in range(2):
-                                t = ty * 2 + tx
-                                wt[:, :, 3 - 2 * ty - py, 3 - 2 * tx - px] = ph[py, px, :, t * Cin:(t + 1) * Cin].t()
-                ref = act64(deconv64(xi, wt, b[0].double() if bias else None), act)
-            got = out_of(snap[0][k][imgs], fmt)[..., ch].permute(0, 3, 1, 2)
-            ratio = max(ratio, tol_ratio(got, ref, prec, fmt, fac))
-        info = (f"{PREC_NAME[prec]} {kname} B {B} {H}x{W} Cin {Cin} Cout {Cout} groups {groups} shared {shared} phase {phase} bias {bias} act {act} "
-                f"fmt {fmt} class {cls} option {oname}={opt.get(oname)} kernel {want}")
-        return faults, ratio, info
+        return conv_gemm_case(prec, kind, B, H, W, Cin, Cout, groups, fmt, act, bias, shared, phase, cls, opt, oname, rng, g, record)
 
     # ------------------------------------------------------------------------------------------------- split-K + sum-pool
     def case_splitk(rng, g):
@@ -489,35 +567,7 @@ def _main(seconds):
         B = int(rng.choice([1, 2, 5, 16, 64, int(rng.integers(1, 129))]))
         B = max(1, min(B, int(MEM_CAP // (H * W * (Cin * 2 + 28 * 16) * 2))))
         cls = str(rng.choice(["normal", "massive", "border"]))
-        x = input_of_class(cls, B, H, W, Cin, g)
-        w = cpu_rand(Cin, Cout, 4, 4, g=g, scale=1 / math.sqrt(4 * Cin))
-        b = cpu_rand(Cout, g=g, scale=0.2)
-        wf, bf = cpu_rand(K, Cout, g=g, scale=4 / math.sqrt(Cout)), cpu_rand(K, g=g)
-        wpad = torch.zeros(32, Cout)
-        wpad[:K] = wf
-        guard = Guard()
-        xd, phd = guard.inp("act", x.bfloat16().cuda()), guard.inp("weight", deconv_phases(w).bfloat16().cuda())
-        bd, hwd, bfd = guard.inp("bias", b), guard.inp("head_w", wpad.bfloat16().cuda()), guard.inp("head_b", bf)
-        lg = guard.out("logits", (B, K, 4, H * W))
-
-        def go():
-            launch("pp_deconv_head", xd.data_ptr(), phd.data_ptr(), bd.data_ptr(), hwd.data_ptr(), bfd.data_ptr(), lg.data_ptr(), B, H, W, Cin, Cout, K,
-                   None)
-        L.reset_launch_counts()
-        faults, snap = run_twice(guard, go)
-        got_k = ran()
-        record("pp_deconv_head", BF16, "deconv", got_k)
-        if got_k != ["pp_panel_gemm.hip"]:
-            faults.append(f"kernels {got_k}")
-        imgs = pick(B, rng, 1)
-        xi = x[imgs].bfloat16().double().permute(0, 3, 1, 2)
-        wq, wfq = w.bfloat16().double(), wf.bfloat16().double()
-        mid = torch.relu(deconv64(xi, wq, b.double())).float().bfloat16().double()  # the kernel hands the 1x1 bf16 activations
-        ref = torch.einsum("bchw,kc->bkhw", mid, wfq) + bf.double().view(1, -1, 1, 1)
-        got = snap[0][imgs].cpu().double().reshape(len(imgs), K, 2, 2, H, W).permute(0, 1, 4, 2, 5, 3).reshape(len(imgs), K, 2 * H, 2 * W)
-        # a mid value at a rounding boundary may round the other way from fp32 than from fp64: one bf16 step of the largest product
-        flip = 2.0 ** -8 * float(mid.abs().max()) * float(wfq.abs().max())
-        return faults, error_ratio(got, ref, BF16_F32OUT_TOL, BF16_F32OUT_TOL + flip), f"B {B} {H}x{W} Cin {Cin} K {K} class {cls}"
+        return deconv_head_case(B, H, W, Cin, K, cls, rng, g, record)
 
     # ------------------------------------------------------------------------------------------------- pooling alone
     def case_maxpool(rng, g):

@@ -127,38 +127,148 @@ def poison_ratio(got, ref, reach, rtol, atol):
     return error_ratio(got[both], ref[both], rtol, atol)
 
 
+# ----------------------------------------------------------------------------------------------------- GPU helpers and single cases
+def sp(x):
+    from probpose_code_amd.weights import to_split
+
+    return to_split(x.float()).cuda()
+
+
+def unsp(c):
+    from probpose_code_amd.weights import from_split
+
+    return from_split(c.float().cpu()).double()
+
+
+def launch(fn, *args):
+    from probpose_code_amd import _lib as L
+
+    try:
+        L.call(fn, *args)
+    except L.ProbPoseLibraryError as exc:
+        if "UNSUPPORTED" in str(exc) or "INVALID" in str(exc):
+            raise Refused(str(exc)) from None
+        raise
+    torch.cuda.synchronize()
+
+
+def run_twice(guard, go):
+    go()
+    faults = guard.faults()
+    first = guard.snapshot()
+    guard.rearm()
+    go()
+    if not bits_equal(first, guard.snapshot()):
+        faults.append("repeat launch differs")
+    faults += [f for f in guard.faults() if f not in faults]
+    return faults, first
+
+
+def pick(n, rng, k):
+    return torch.unique(torch.tensor([0, n - 1] + rng.integers(0, n, k).tolist())) if n > k + 2 else torch.arange(n)
+
+
+def run_guarded(guard, go):
+    """run_twice; a refusal (Refused) carries what the buffers show at that moment: exc.faults names every canary, output element or input that
+    changed although the library refused the launch."""
+    try:
+        return run_twice(guard, go)
+    except Refused as exc:
+        torch.cuda.synchronize()
+        f = [x for x in guard.faults() if not x.endswith("elements left unwritten")]
+        for name, full, n, init, _, _, pat in guard.outs:
+            if init is None and bool((full != pat).any()):
+                f.append(f"{name}: written by a refused launch")
+        exc.faults = f
+        raise
+
+
+def deconv_head_split_case(B, H, W, Cin, K, rng, g, must_accept=False):
+    """One guarded launch pair of pp_deconv_head_split (f16x3: the last deconvolution to 256 channels + ReLU + the 1x1 convolution to K maps,
+    logits in the phase-separated layout) -> (faults, error / tolerance, description). ``must_accept``: a refusal is a fault."""
+    from probpose_code_amd.weights import pack_head_split
+
+    Cout = 256
+    gd = torch.Generator(device="cuda").manual_seed(int(rng.integers(1 << 30)))
+    x = torch.randn(B, H, W, Cin, generator=gd, device="cuda")
+    w = cpu_rand(Cin, Cout, 4, 4, g=g, scale=1 / math.sqrt(4 * Cin))
+    b = cpu_rand(Cout, g=g, scale=0.2)
+    wf, bf = cpu_rand(K, Cout, g=g, scale=4 / math.sqrt(Cout)), cpu_rand(K, g=g)
+    wpad = torch.zeros(32, Cout)
+    wpad[:K] = wf
+    guard = Guard()
+    xd, phd, bd = guard.inp("act", sp(x)), guard.inp("weight", sp(deconv_phases(w))), guard.inp("bias", b)
+    hwd, bfd = guard.inp("head_w", pack_head_split(wpad)), guard.inp("head_b", bf)
+    lg = guard.out("logits", (B, K, 4, H * W))
+
+    def go():
+        launch("pp_deconv_head_split", xd.data_ptr(), phd.data_ptr(), bd.data_ptr(), hwd.data_ptr(), bfd.data_ptr(), lg.data_ptr(), B, H, W, Cin,
+               Cout, K, None)
+    try:
+        faults, snap = run_guarded(guard, go)
+    except Refused:
+        if must_accept:
+            return ["a shape with enough tiles was refused"], 0.0, f"B {B} {H}x{W} K {K}"
+        raise
+    imgs = pick(B, rng, 1)
+    ref = deconv_head64(x[imgs].permute(0, 3, 1, 2).cpu().double(), w.double(), b.double(), wf.double(), bf.double())
+    got = snap[0][imgs].cpu().reshape(len(imgs), K, 2, 2, H, W).permute(0, 1, 4, 2, 5, 3).reshape(len(imgs), K, 2 * H, 2 * W)
+    return faults, error_ratio(got, ref, TOL["deconv_head"], TOL["deconv_head"]), f"B {B} {H}x{W} K {K}"
+
+
+def splitk_case(B, H, W, Cin, C, G, ks, rng, g, lib_s=None, chans=None):
+    """One guarded launch pair of pp_conv3x3_splitk (f16x3, Cin -> C channels, G towers, ks slices) + pp_sum_maxpool_relu_nhwc (2 x 2 windows)
+    -> (faults, error / tolerance, description). ``lib_s``: the library's own slice count (refusing it is a fault); ``chans``: the
+    "ksplit_channels" option the caller has set, for the description."""
+    gd = torch.Generator(device="cuda").manual_seed(int(rng.integers(1 << 30)))
+    x = torch.randn(G, B, H, W, Cin, generator=gd, device="cuda")
+    shared = rng.random() < 0.5  # the four towers on one input (stride 0) or each on its own
+    poisoned = rng.random() < 0.25
+    if poisoned:
+        for k in range(G):
+            for i in {0, B - 1}:
+                poison_(x[k, i], g, int(rng.integers(1, 3)))
+    w = cpu_rand(G, C, Cin, 3, 3, g=g, scale=1 / math.sqrt(9 * Cin))
+    b = cpu_rand(G, C, g=g)
+    guard = Guard()
+    xd = guard.inp("act", sp(x[0] if shared else x))
+    wd = guard.inp("weight", sp(w.permute(0, 1, 3, 4, 2).reshape(G, C, 9 * Cin)))
+    bd = guard.inp("bias", b)
+    part = guard.out("partials", (ks, G, B, H, W, C))
+    pooled = guard.out("pooled", (G * B, H // 2, W // 2, C))
+
+    def go():
+        launch("pp_conv3x3_splitk", F16X3, xd.data_ptr(), wd.data_ptr(), part.data_ptr(), B, H, W, Cin, C, G, 0 if shared else B * H * W * Cin,
+               C * 9 * Cin, ks, None)
+        launch("pp_sum_maxpool_relu_nhwc", part.data_ptr(), ks, G * B * H * W * C, bd.data_ptr(), B, pooled.data_ptr(), SPLIT, G * B, H, W, C, 2, 2,
+               None)
+    try:
+        faults, snap = run_guarded(guard, go)
+    except Refused:
+        if ks == lib_s:
+            return ["the library's own slice count was refused"], 0.0, f"B {B} {H}x{W} C {C} slices {ks}"
+        raise
+    imgs, ch = pick(B, rng, 2), torch.from_numpy(rng.choice(C, min(C, 64), replace=False))
+    ratio = 0.0
+    for k in range(G):
+        xk = (x[0] if shared else x[k])[imgs].cpu()
+        xi = xk.permute(0, 3, 1, 2).double()
+        conv = conv3x3_64(xi, w[k][ch].double())
+        psum = snap[0][:, k][:, imgs][..., ch].cpu().double().sum(0).permute(0, 3, 1, 2)
+        pref = pool_relu64(conv + b[k][ch].double().view(1, -1, 1, 1), 2, 2)
+        pg = unsp(snap[1].view(G, B, H // 2, W // 2, C)[k][imgs])[..., ch].permute(0, 3, 1, 2)
+        if poisoned:
+            bad = bad_pixels(xk)
+            ratio = max(ratio, poison_ratio(psum, conv, conv_reach(bad), TOL["splitk"], TOL["splitk"]),
+                        poison_ratio(pg, pref, conv_reach(bad, 2, 2), TOL["splitk"], TOL["splitk"]))
+        else:
+            ratio = max(ratio, error_ratio(psum, conv, TOL["splitk"], TOL["splitk"]), error_ratio(pg, pref, TOL["splitk"], TOL["splitk"]))
+    return faults, ratio, f"B {B} {H}x{W} C {C}{'' if Cin == C else f' Cin {Cin}'} slices {ks} (library {lib_s}) ksplit_channels {chans} shared {shared} poison {poisoned}"
+
+
 def _main(seconds):
     from probpose_code_amd import _lib as L
     from probpose_code_amd.weights import from_split, pack_head_split, to_split, winograd_weights
-
-    def sp(x):
-        return to_split(x.float()).cuda()
-
-    def unsp(c):
-        return from_split(c.float().cpu()).double()
-
-    def launch(fn, *args):
-        try:
-            L.call(fn, *args)
-        except L.ProbPoseLibraryError as exc:
-            if "UNSUPPORTED" in str(exc) or "INVALID" in str(exc):
-                raise Refused(str(exc)) from None
-            raise
-        torch.cuda.synchronize()
-
-    def run_twice(guard, go):
-        go()
-        faults = guard.faults()
-        first = guard.snapshot()
-        guard.rearm()
-        go()
-        if not bits_equal(first, guard.snapshot()):
-            faults.append("repeat launch differs")
-        faults += [f for f in guard.faults() if f not in faults]
-        return faults, first
-
-    def pick(n, rng, k):
-        return torch.unique(torch.tensor([0, n - 1] + rng.integers(0, n, k).tolist())) if n > k + 2 else torch.arange(n)
 
     # ------------------------------------------------------------------------------------------------- deconvolution + 1x1 head
     def case_deconv_head(rng, g):
@@ -169,31 +279,7 @@ def _main(seconds):
         B = int(rng.choice([b_min - 1, b_min, b_min + 1, 64, 128, int(rng.integers(b_min, 301))]))
         B = max(1, min(B, int(MEM_CAP // (H * W * (Cin * 4 + 28 * 16) * 2))))
         K = int(rng.integers(1, 29))
-        gd = torch.Generator(device="cuda").manual_seed(int(rng.integers(1 << 30)))
-        x = torch.randn(B, H, W, Cin, generator=gd, device="cuda")
-        w = cpu_rand(Cin, Cout, 4, 4, g=g, scale=1 / math.sqrt(4 * Cin))
-        b = cpu_rand(Cout, g=g, scale=0.2)
-        wf, bf = cpu_rand(K, Cout, g=g, scale=4 / math.sqrt(Cout)), cpu_rand(K, g=g)
-        wpad = torch.zeros(32, Cout)
-        wpad[:K] = wf
-        guard = Guard()
-        xd, phd, bd = guard.inp("act", sp(x)), guard.inp("weight", sp(deconv_phases(w))), guard.inp("bias", b)
-        hwd, bfd = guard.inp("head_w", pack_head_split(wpad)), guard.inp("head_b", bf)
-        lg = guard.out("logits", (B, K, 4, H * W))
-
-        def go():
-            launch("pp_deconv_head_split", xd.data_ptr(), phd.data_ptr(), bd.data_ptr(), hwd.data_ptr(), bfd.data_ptr(), lg.data_ptr(), B, H, W, Cin,
-                   Cout, K, None)
-        try:
-            faults, snap = run_twice(guard, go)
-        except Refused:
-            if B >= b_min:
-                return ["a shape with enough tiles was refused"], 0.0, f"B {B} {H}x{W} K {K}"
-            raise
-        imgs = pick(B, rng, 1)
-        ref = deconv_head64(x[imgs].permute(0, 3, 1, 2).cpu().double(), w.double(), b.double(), wf.double(), bf.double())
-        got = snap[0][imgs].cpu().reshape(len(imgs), K, 2, 2, H, W).permute(0, 1, 4, 2, 5, 3).reshape(len(imgs), K, 2 * H, 2 * W)
-        return faults, error_ratio(got, ref, TOL["deconv_head"], TOL["deconv_head"]), f"B {B} {H}x{W} K {K}"
+        return deconv_head_split_case(B, H, W, Cin, K, rng, g, must_accept=B >= b_min)
 
     # ------------------------------------------------------------------------------------------------- first tower stage, Winograd form
     def case_winograd(rng, g):
@@ -247,50 +333,7 @@ def _main(seconds):
         lib_s = int(L.lib.pp_conv3x3_splitk_slices(F16X3, B, H, W, C, C, G))
         ks = int(rng.choice([lib_s, lib_s, 1, 3, 9]))
         B = max(1, min(B, int(MEM_CAP // (G * H * W * C * 4 * (ks + 2)))))
-        gd = torch.Generator(device="cuda").manual_seed(int(rng.integers(1 << 30)))
-        x = torch.randn(G, B, H, W, C, generator=gd, device="cuda")
-        shared = rng.random() < 0.5  # the four towers on one input (stride 0) or each on its own
-        poisoned = rng.random() < 0.25
-        if poisoned:
-            for k in range(G):
-                for i in {0, B - 1}:
-                    poison_(x[k, i], g, int(rng.integers(1, 3)))
-        w = cpu_rand(G, C, C, 3, 3, g=g, scale=1 / math.sqrt(9 * C))
-        b = cpu_rand(G, C, g=g)
-        guard = Guard()
-        xd = guard.inp("act", sp(x[0] if shared else x))
-        wd = guard.inp("weight", sp(w.permute(0, 1, 3, 4, 2).reshape(G, C, 9 * C)))
-        bd = guard.inp("bias", b)
-        part = guard.out("partials", (ks, G, B, H, W, C))
-        pooled = guard.out("pooled", (G * B, H // 2, W // 2, C))
-
-        def go():
-            launch("pp_conv3x3_splitk", F16X3, xd.data_ptr(), wd.data_ptr(), part.data_ptr(), B, H, W, C, C, G, 0 if shared else B * H * W * C,
-                   C * 9 * C, ks, None)
-            launch("pp_sum_maxpool_relu_nhwc", part.data_ptr(), ks, G * B * H * W * C, bd.data_ptr(), B, pooled.data_ptr(), SPLIT, G * B, H, W, C, 2, 2,
-                   None)
-        try:
-            faults, snap = run_twice(guard, go)
-        except Refused:
-            if ks == lib_s:
-                return ["the library's own slice count was refused"], 0.0, f"B {B} {H}x{W} C {C} slices {ks}"
-            raise
-        imgs, ch = pick(B, rng, 2), torch.from_numpy(rng.choice(C, 64, replace=False))
-        ratio = 0.0
-        for k in range(G):
-            xk = (x[0] if shared else x[k])[imgs].cpu()
-            xi = xk.permute(0, 3, 1, 2).double()
-            conv = conv3x3_64(xi, w[k][ch].double())
-            psum = snap[0][:, k][:, imgs][..., ch].cpu().double().sum(0).permute(0, 3, 1, 2)
-            pref = pool_relu64(conv + b[k][ch].double().view(1, -1, 1, 1), 2, 2)
-            pg = unsp(snap[1].view(G, B, H // 2, W // 2, C)[k][imgs])[..., ch].permute(0, 3, 1, 2)
-            if poisoned:
-                bad = bad_pixels(xk)
-                ratio = max(ratio, poison_ratio(psum, conv, conv_reach(bad), TOL["splitk"], TOL["splitk"]),
-                            poison_ratio(pg, pref, conv_reach(bad, 2, 2), TOL["splitk"], TOL["splitk"]))
-            else:
-                ratio = max(ratio, error_ratio(psum, conv, TOL["splitk"], TOL["splitk"]), error_ratio(pg, pref, TOL["splitk"], TOL["splitk"]))
-        return faults, ratio, f"B {B} {H}x{W} C {C} slices {ks} (library {lib_s}) ksplit_channels {chans} shared {shared} poison {poisoned}"
+        return splitk_case(B, H, W, C, C, G, ks, rng, g, lib_s=lib_s, chans=chans)
 
     # ------------------------------------------------------------------------------------------------- fused conv + pool, implicit GEMM
     def case_conv_pool(rng, g):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Fuzz of pp_skinny_linear / pp_skinny_deconv / pp_skinny_conv1x1_planar over random shapes against torch fp64: M from 1 to ~7 000 (ragged against every
-tile edge), N and K over the multiples the entry points admit, every epilogue (bias, GELU / ReLU, fp32 residual in place or broadcast table,
+tile edge), N and K over the multiples the entry points admit (deconvolutions: Cin from two 32-channel blocks up, odd block counts too), every epilogue (bias, GELU / ReLU, fp32 residual in place or broadcast table,
 LayerNorm tail, split or fp32 rows out), every tile shape forced in turn; the outputs sit between canaries (a write outside the tensor is caught),
 the LayerNorm counters must be back at zero.   python tests/fuzz_skinny.py [seconds]"""
 import math
@@ -100,7 +100,7 @@ while time.time() < t_end:
         L.set_option("skinny_xcd_order", 1)
     elif kind <= 8:  # ---- deconvolution
         B, H, W = int(rng.integers(1, 7)), int(rng.choice([2, 3, 8, 16, 32])), int(rng.choice([2, 5, 12, 24]))
-        Cin, Cout = int(rng.choice([64, 256, 384])), int(rng.choice([64, 256]))
+        Cin, Cout = int(rng.choice([64, 96, 160, 256, 384])), int(rng.choice([32, 64, 96, 256]))
         x = torch.randn(B, H, W, Cin, generator=g)
         wt = torch.randn(Cin, Cout, 4, 4, generator=g) * math.sqrt(2.0 / (4 * Cin))
         shift = torch.randn(Cout, generator=g) * 0.2

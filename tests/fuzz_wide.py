@@ -30,7 +30,9 @@ for unit-normal activation rows and weight rows of unit norm: fac = magnitude_fa
 No K-dependent term was needed: the K = 4096 / 5120 cases stay below a quarter of these bars in f16x3 and a tenth in f32. The bf16-output bar is
 one rounding of the result, which the 128 x 128 kernel missed with an fp32 residual (it rounded in front of the residual and again behind it: up
 to 1.54 of the bar) until csrc/pp_gemm.hip added the residual first; tests/test_wide_widths_gpu.py keeps those cases.
-``gemm_case``, ``skinny_case``, ``deconv_case`` and ``skinny_deconv_case`` are the single cases tests/test_wide_widths_gpu.py runs on its grid.
+``gemm_case``, ``skinny_case``, ``deconv_case`` and ``skinny_deconv_case`` are the single cases tests/test_wide_widths_gpu.py runs on its grid;
+tests/fuzz_edges.py runs them at the smallest shapes the argument checks admit, through their optional parameters (row pitches of pp_gemm_ws;
+map size and output width of the deconvolutions), whose defaults are the shapes above.
 python tests/fuzz_wide.py [seconds]"""
 import math
 import os
@@ -47,7 +49,7 @@ import fuzz_conv as FC  # noqa: E402
 from fuzz_conv import BF16_F32OUT_TOL, F32_TOL, bf16_out_ratio, deconv64  # noqa: E402
 from fuzz_head import TOL as HEAD_TOL  # noqa: E402
 from fuzz_head import deconv_phases  # noqa: E402
-from fuzz_layer import (BF16, F16X3, F32, MEM_CAP, TOL, Guard, Refused, cpu_rand, draw_e, error_ratio, gelu64, layernorm64,  # noqa: E402
+from fuzz_layer import (BF16, F16X3, F32, MEM_CAP, PATTERN, TOL, Guard, Refused, cpu_rand, draw_e, error_ratio, gelu64, layernorm64,  # noqa: E402
                         magnitude_factor, rows_of_class, run_entries, run_twice, sample_rows)
 
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
@@ -105,18 +107,20 @@ def wide_tiles(M, N):
     return (N // 192) * ((M + bm - 1) // bm)
 
 
-def gemm_kernel(prec, M, N, K, fmt, residual, planar=False):
-    """Which kernel pp_gemm_ws launches for dense row-major operands (lda = ldw = K, ldc = N), default options: linear_dma_supported, then
-    panel_split_supported, else the 128 x 128 kernel."""
+def gemm_kernel(prec, M, N, K, fmt, residual, planar=False, lda=None, ldw=None, ldc=None):
+    """Which kernel pp_gemm_ws launches for row-major operands (row pitches lda, ldw, ldc in elements; None: dense, lda = ldw = K, ldc = N),
+    default options: linear_dma_supported (dense operands only), then panel_split_supported (pitches that are multiples of 32 elements in f16x3,
+    of 8 in bf16), else the 128 x 128 kernel."""
+    lda, ldw, ldc = K if lda is None else lda, K if ldw is None else ldw, N if ldc is None else ldc
     if planar or N % 192 != 0:
         return "pp_gemm.hip"
     if prec == F16X3:
-        if fmt not in (0, 2) or K % 32 != 0 or N % 32 != 0 or (residual and fmt == 2):
+        if fmt not in (0, 2) or K % 32 != 0 or N % 32 != 0 or (residual and fmt == 2) or lda % 32 or ldw % 32 or ldc % 32:
             return "pp_gemm.hip"
-        if K >= 64 and (N // 192) * ((M + 191) // 192) >= 512:
+        if K >= 64 and (N // 192) * ((M + 191) // 192) >= 512 and (lda, ldw, ldc) == (K, K, N):
             return "linear_dma_tile"
     elif prec == BF16:
-        if K < (1536 if fmt else 768) or K % 128 != 0 or fmt not in (0, 1) or N % 8 != 0:
+        if K < (1536 if fmt else 768) or K % 128 != 0 or fmt not in (0, 1) or N % 8 != 0 or lda % 8 or ldw % 8 or ldc % 8:
             return "pp_gemm.hip"
     else:
         return "pp_gemm.hip"
@@ -174,15 +178,38 @@ def _launch(L, fn, *args):
     torch.cuda.synchronize()
 
 
+_run_twice = FC.run_guarded  # (run_twice; a refusal carries the state of the buffers: exc.faults)
+
+
+def _pitched(t, pad, fill=float("nan")):
+    """(rows, cols) -> (rows, cols + pad) with `fill` in the gap columns (NaN: a kernel that reads them poisons its sums)."""
+    return t if not pad else torch.cat([t, torch.full((t.shape[0], pad), fill, dtype=t.dtype, device=t.device)], dim=1)
+
+
+def _gap_faults(name, snap_t, N):
+    """A pitched output (rows, ldc): the gap columns N .. ldc are canaries and every element left of them was written."""
+    pat = PATTERN[snap_t.dtype]
+    bits = snap_t.contiguous().view({torch.float32: torch.int32, torch.bfloat16: torch.int16}[snap_t.dtype])
+    f = []
+    if bits.shape[1] > N and not bool((bits[:, N:] == pat).all()):
+        f.append(f"{name}: gap columns overwritten")
+    if bool((bits[:, :N] == pat).any()):
+        f.append(f"{name}: elements left unwritten")
+    return f
+
+
 def _unsplit(t):
     from probpose_code_amd.weights import from_split
 
     return from_split(t.float().cpu()).double()
 
 
-def gemm_case(prec, M, N, K, epi, seed, cls_a="normal", cls_w="normal", e=0, planar_P=0, rng=None, ran=None, must_accept=False):
+def gemm_case(prec, M, N, K, epi, seed, cls_a="normal", cls_w="normal", e=0, planar_P=0, rng=None, ran=None, must_accept=False, pad_a=0, pad_w=0,
+              pad_c=0):
     """One guarded launch pair of pp_gemm_ws -> (faults, error / tolerance, description); the kernels that ran are appended to ``ran``.
-    ``e``: the weights are stored times 2^e (f16x3 only); None: drawn by draw_e from the weights."""
+    ``e``: the weights are stored times 2^e (f16x3 only); None: drawn by draw_e from the weights. ``pad_a`` / ``pad_w`` / ``pad_c``: row pitches
+    lda = K + pad_a, ldw = K + pad_w, ldc = N + pad_c (row-major output only); the gap columns of the operands hold NaN, those of the output
+    (and of an in-place residual) are canaries that must stay untouched."""
     from probpose_code_amd import _lib as L
     from probpose_code_amd.weights import to_split
 
@@ -196,48 +223,52 @@ def gemm_case(prec, M, N, K, epi, seed, cls_a="normal", cls_w="normal", e=0, pla
     rows = sample_rows(M, 256, rng)
     e = (draw_e(rng, w) if prec == F16X3 else 0) if e is None else e
     guard = Guard()
+    assert not (planar_P and pad_c)
+    lda, ldw, ldc = K + pad_a, K + pad_w, N + pad_c
     if prec == F16X3:
-        ad, wd = to_split(x), to_split((w * 2.0 ** e).cuda())
+        ad, wd = to_split(_pitched(x, pad_a)), to_split(_pitched((w * 2.0 ** e).cuda(), pad_w))
         xq, wq = x[rows].cpu().double(), w.double()
     elif prec == BF16:
-        ad, wd = x.bfloat16(), w.bfloat16().cuda()
-        xq, wq = ad[rows].cpu().double(), w.bfloat16().double()
+        ad, wd = _pitched(x.bfloat16(), pad_a), _pitched(w.bfloat16().cuda(), pad_w)
+        xq, wq = ad[rows][:, :K].cpu().double(), w.bfloat16().double()
     else:
-        ad, wd = x, w.cuda()
+        ad, wd = _pitched(x, pad_a), _pitched(w.cuda(), pad_w)
         xq, wq = x[rows].cpu().double(), w.double()
     del x
     ad, wd = guard.inp("act", ad), guard.inp("weight", wd)
     bd = guard.inp("bias", bias) if bias is not None else None
     odt = torch.bfloat16 if fmt == 1 else torch.float32
-    oshape = (M // planar_P, N, planar_P) if planar_P else (M, N)
+    oshape = (M // planar_P, N, planar_P) if planar_P else (M, ldc)
     res = rr = None
     if res_kind != "none":
         r = torch.randn(res_mod if res_kind == "table" else M, N, generator=gd, device="cuda")
         rr = r.cpu().double()[rows % res_mod] if res_kind == "table" else r[rows].cpu().double()
         if res_kind == "in_place":
             assert fmt == 0 and not planar_P
-            res = out = guard.out("residual/out", oshape, init=r)
+            # (the gap columns of a pitched stream start as the canary's NaN payload: they are compared bit for bit below)
+            res = out = guard.out("residual/out", oshape, init=_pitched(r, pad_c).view(torch.int32).masked_fill_(
+                (torch.arange(ldc, device="cuda") >= N)[None], PATTERN[torch.float32]).view(torch.float32) if pad_c else r)
         else:
-            res = guard.inp("residual", r)
+            res = guard.inp("residual", _pitched(r, pad_c))  # (the residual's pitch is the output's)
     if res_kind != "in_place":
-        out = guard.out("out", oshape, dtype=odt)
+        out = guard.out("out", oshape, dtype=odt, must_write=not pad_c)
     ref = linear_ref64(xq, wq, bias, act, rr)
 
     def go():
-        _launch(L, "pp_gemm_ws", prec, ad.data_ptr(), wd.data_ptr(), L.ptr(bd), L.ptr(res), res_mod, out.data_ptr(), M, N, K, K, K, N, act, fmt,
+        _launch(L, "pp_gemm_ws", prec, ad.data_ptr(), wd.data_ptr(), L.ptr(bd), L.ptr(res), res_mod, out.data_ptr(), M, N, K, lda, ldw, ldc, act, fmt,
                 planar_P, 2.0 ** -e, None)
 
     info = (f"{PREC_NAME[prec]} M {M} N {N} K {K} bias {bias is not None} act {act} fmt {fmt} res {res_kind}/{res_mod} planar {planar_P} e {e} "
-            f"classes {cls_a} / {cls_w}")
+            f"classes {cls_a} / {cls_w}" + (f" lda {lda} ldw {ldw} ldc {ldc}" if pad_a or pad_w or pad_c else ""))
     L.reset_launch_counts()
     try:
-        faults, snap = run_twice(guard, go)
+        faults, snap = _run_twice(guard, go)
     except Refused as exc:
         if must_accept:
             return [f"a shape the engine sends was refused: {exc}"], 0.0, info
         raise
     got_k = [k for k in GEMM_KERNELS if L.launch_count(k) > 0]
-    want = gemm_kernel(prec, M, N, K, fmt, res is not None, bool(planar_P))
+    want = gemm_kernel(prec, M, N, K, fmt, res is not None, bool(planar_P), lda, ldw, ldc)
     if ran is not None:
         ran += got_k
     if got_k != [want]:
@@ -245,6 +276,9 @@ def gemm_case(prec, M, N, K, epi, seed, cls_a="normal", cls_w="normal", e=0, pla
     o = snap[0]
     if planar_P:
         o = o.permute(0, 2, 1).reshape(M, N)
+    elif pad_c:
+        faults += _gap_faults("out", o, N)
+        o = o[:, :N]
     got = _unsplit(o[rows]) if fmt == 2 else o[rows].cpu().double()
     fac = magnitude_factor(xq) * weight_factor(wq, K)
     if prec == F16X3:
@@ -324,19 +358,19 @@ def skinny_case(shape, M, codes, xcd, seed, e=0, rng=None):  # (e: as in gemm_ca
     return faults, ratio, f"{layer} M {M} N {N} K {K} xcd_order {xcd} e {e} (tile: out{' / ln_out' if ln else ''} {', '.join(parts)})"
 
 
-def _deconv_operands(prec, Cin, nb, cls, seed, rng):
-    """Activations (nb, 16, 12, Cin) on the GPU, phase matrices, shift; and the fp64 values of two or three images and of the torch weight the
-    kernel multiplies (bf16-rounded for bf16)."""
+def _deconv_operands(prec, Cin, nb, cls, seed, rng, H=MAP_H, W=MAP_W, cout=DECONV_COUT):
+    """Activations (nb, H, W, Cin) on the GPU (16 x 12 unless given), phase matrices, shift; and the fp64 values of two or three images and of
+    the torch weight the kernel multiplies (bf16-rounded for bf16)."""
     from probpose_code_amd.weights import to_split
 
     g = torch.Generator().manual_seed(int(seed))
     gd = torch.Generator(device="cuda").manual_seed(int(seed))
     if cls == "border":
-        x = FC.border_impulses(nb, MAP_H, MAP_W, Cin, g).cuda()
+        x = FC.border_impulses(nb, H, W, Cin, g).cuda()
     else:
-        x = rows_of_class(nb * MAP_H * MAP_W, Cin, cls, gd).reshape(nb, MAP_H, MAP_W, Cin)
-    w = cpu_rand(Cin, DECONV_COUT, 4, 4, g=g, scale=1 / math.sqrt(4 * Cin))
-    shift = cpu_rand(DECONV_COUT, g=g, scale=0.3)
+        x = rows_of_class(nb * H * W, Cin, cls, gd).reshape(nb, H, W, Cin)
+    w = cpu_rand(Cin, cout, 4, 4, g=g, scale=1 / math.sqrt(4 * Cin))
+    shift = cpu_rand(cout, g=g, scale=0.3)
     ph = deconv_phases(w)  # (2, 2, Cout, 4 Cin)
     imgs = torch.unique(torch.tensor([0, nb - 1, int(rng.integers(0, nb))]))
     if prec == F16X3:
@@ -349,19 +383,23 @@ def _deconv_operands(prec, Cin, nb, cls, seed, rng):
     return xd, wd, shift, imgs, xq, wq
 
 
-def deconv_case(prec, Cin, nb, phase, seed, act=ACT_RELU, fmt=None, bias=True, cls="normal", weight_major=0, rng=None, ran=None):
-    """pp_conv_gemm PP_DECONV4X4S2 at the first head deconvolution (nb, 16, 12, Cin) -> (nb, 32, 24, 256): all four phases in one launch
-    (phase < 0) or one launch each, `phase` first. ``weight_major``: option "psplit_deconv_weight_major" - honoured only while a phase's weight
-    set (4 Cin x 256 x 4 bytes) is at most 3 MiB, Cin = 768; above, the wide-tile kernel falls back to its row-major tile order."""
+def deconv_case(prec, Cin, nb, phase, seed, act=ACT_RELU, fmt=None, bias=True, cls="normal", weight_major=0, rng=None, ran=None, H=MAP_H, W=MAP_W,
+                cout=DECONV_COUT, only_phase=False):
+    """pp_conv_gemm PP_DECONV4X4S2 at the first head deconvolution (nb, 16, 12, Cin) -> (nb, 32, 24, 256) - or at the map ``H`` x ``W`` and the
+    ``cout`` output channels given: all four phases in one launch (phase < 0) or one launch each, `phase` first (``only_phase``: that one phase
+    alone; the pixels of the three others are canaries that must stay untouched). ``weight_major``: option "psplit_deconv_weight_major" -
+    honoured only while a phase's weight set (4 Cin x 256 x 4 bytes) is at most 3 MiB, Cin = 768; above, the wide-tile kernel falls back to
+    its row-major tile order."""
     from probpose_code_amd import _lib as L
 
     rng = rng if rng is not None else np.random.default_rng(seed)
     fmt = OPERAND_FMT[prec] if fmt is None else fmt
-    xd, wd, shift, imgs, xq, wq = _deconv_operands(prec, Cin, nb, cls, seed, rng)
+    MAP_H, MAP_W, DECONV_COUT = H, W, cout  # (the names the body below was written with)
+    xd, wd, shift, imgs, xq, wq = _deconv_operands(prec, Cin, nb, cls, seed, rng, H, W, cout)
     guard = Guard()
     xd, wd = guard.inp("act", xd), guard.inp("weight", wd)
     bd = guard.inp("bias", shift) if bias else None
-    out = guard.out("out", (nb, 2 * MAP_H, 2 * MAP_W, DECONV_COUT), dtype=torch.bfloat16 if fmt == 1 else torch.float32)
+    out = guard.out("out", (nb, 2 * MAP_H, 2 * MAP_W, DECONV_COUT), dtype=torch.bfloat16 if fmt == 1 else torch.float32, must_write=not only_phase)
     wflat = wd.reshape(4, DECONV_COUT, -1)
 
     def go():
@@ -369,7 +407,7 @@ def deconv_case(prec, Cin, nb, phase, seed, act=ACT_RELU, fmt=None, bias=True, c
             _launch(L, "pp_conv_gemm", prec, DECONV, xd.data_ptr(), wd.data_ptr(), L.ptr(bd), out.data_ptr(), nb, MAP_H, MAP_W, Cin, DECONV_COUT, -1, 0,
                     1, 0, 0, 0, 0, DECONV_COUT, act, fmt, None)
         else:
-            for k in range(4):
+            for k in range(1 if only_phase else 4):
                 py, px = divmod((phase + k) % 4, 2)
                 _launch(L, "pp_conv_gemm", prec, DECONV, xd.data_ptr(), wflat[2 * py + px].data_ptr(), L.ptr(bd), out.data_ptr(), nb, MAP_H, MAP_W, Cin,
                         DECONV_COUT, py, px, 1, 0, 0, 0, 0, DECONV_COUT, act, fmt, None)
@@ -377,7 +415,7 @@ def deconv_case(prec, Cin, nb, phase, seed, act=ACT_RELU, fmt=None, bias=True, c
     if weight_major:
         L.set_option("psplit_deconv_weight_major", 1)
     L.reset_launch_counts()
-    faults, snap = run_twice(guard, go)
+    faults, snap = _run_twice(guard, go)
     got_k = [k for k in FC.KERNELS if L.launch_count(k) > 0]
     want = FC.conv_kernel(prec, DECONV, nb, MAP_H, MAP_W, Cin, DECONV_COUT, 4 if phase < 0 else 1, fmt, act, FC.DEFAULT_OPTIONS)
     if ran is not None:
@@ -386,6 +424,17 @@ def deconv_case(prec, Cin, nb, phase, seed, act=ACT_RELU, fmt=None, bias=True, c
         faults.append(f"kernel {got_k}, the mirrored dispatcher predicts {want}")
     ref = FC.act64(deconv64(xq.permute(0, 3, 1, 2), wq, shift.double() if bias else None), act)
     got = (_unsplit(snap[0][imgs]) if fmt == 2 else snap[0][imgs].cpu().double()).permute(0, 3, 1, 2)
+    if only_phase:  # the one phase written whole, the three others still canaries (bit for bit, the whole batch)
+        py, px = divmod(phase, 2)
+        pat = PATTERN[snap[0].dtype]
+        bits = snap[0].view(torch.int16 if fmt == 1 else torch.int32)
+        mine = torch.zeros(2 * MAP_H, 2 * MAP_W, dtype=torch.bool, device="cuda")
+        mine[py::2, px::2] = True
+        if bool((bits[:, mine] == pat).any()):
+            faults.append("out: elements of the phase left unwritten")
+        if not bool((bits[:, ~mine] == pat).all()):
+            faults.append("out: pixels of another phase overwritten")
+        got, ref = got[:, :, py::2, px::2], ref[:, :, py::2, px::2]
     fac = magnitude_factor(xq.reshape(-1, Cin))
     if prec == F16X3:
         ratio = error_ratio(got, ref, HEAD_TOL["deconv_head"] * fac, HEAD_TOL["deconv_head"] * fac)
@@ -395,16 +444,18 @@ def deconv_case(prec, Cin, nb, phase, seed, act=ACT_RELU, fmt=None, bias=True, c
         ratio = bf16_out_ratio(got / fac, ref / fac)
     else:
         ratio = error_ratio(got, ref, BF16_F32OUT_TOL * fac, BF16_F32OUT_TOL * fac)
-    return faults, ratio, (f"{PREC_NAME[prec]} deconv nb {nb} Cin {Cin} phase {phase} bias {bias} act {act} fmt {fmt} class {cls} "
-                           f"weight_major {weight_major} kernel {want}")
+    return faults, ratio, (f"{PREC_NAME[prec]} deconv nb {nb} {MAP_H}x{MAP_W} Cin {Cin} Cout {DECONV_COUT} phase {phase}{' alone' if only_phase else ''} "
+                           f"bias {bias} act {act} fmt {fmt} class {cls} weight_major {weight_major} kernel {want}")
 
 
-def skinny_deconv_case(Cin, nb, code, seed, cls="normal", rng=None):
-    """pp_skinny_deconv (f16x3, shift + ReLU, split rows out) on nb x 192 <= 1 536 input pixels, tile code forced (0: the cost model's)."""
+def skinny_deconv_case(Cin, nb, code, seed, cls="normal", rng=None, H=MAP_H, W=MAP_W, cout=DECONV_COUT):
+    """pp_skinny_deconv (f16x3, shift + ReLU, split rows out) on nb x 192 <= 1 536 input pixels (or nb maps of ``H`` x ``W``, ``cout`` output
+    channels), tile code forced (0: the cost model's)."""
     from probpose_code_amd import _lib as L
 
     rng = rng if rng is not None else np.random.default_rng(seed)
-    xd, wd, shift, imgs, xq, wq = _deconv_operands(F16X3, Cin, nb, cls, seed, rng)
+    MAP_H, MAP_W, DECONV_COUT = H, W, cout
+    xd, wd, shift, imgs, xq, wq = _deconv_operands(F16X3, Cin, nb, cls, seed, rng, H, W, cout)
     guard = Guard()
     xd, wd, bd = guard.inp("act", xd), guard.inp("weight", wd), guard.inp("bias", shift)
     out = guard.out("out", (nb, 2 * MAP_H, 2 * MAP_W, DECONV_COUT))
@@ -414,13 +465,13 @@ def skinny_deconv_case(Cin, nb, code, seed, cls="normal", rng=None):
 
     L.set_option("skinny_tile", code)
     L.reset_launch_counts()
-    faults, snap = run_twice(guard, go)
+    faults, snap = _run_twice(guard, go)
     if L.launch_count("skinny_deconv") != 2:
         faults.append(f"pp_launch_count('skinny_deconv') = {L.launch_count('skinny_deconv')} after two launches")
     ref = torch.relu(deconv64(xq.permute(0, 3, 1, 2), wq, shift.double()))
     got = _unsplit(snap[0][imgs]).permute(0, 3, 1, 2)
     tol = HEAD_TOL["deconv_head"] * magnitude_factor(xq.reshape(-1, Cin))
-    return faults, error_ratio(got, ref, tol, tol), f"skinny deconv nb {nb} Cin {Cin} tile {code} class {cls}"
+    return faults, error_ratio(got, ref, tol, tol), f"skinny deconv nb {nb} {MAP_H}x{MAP_W} Cin {Cin} Cout {DECONV_COUT} tile {code} class {cls}"
 
 
 # ----------------------------------------------------------------------------------------------------- the fuzzer

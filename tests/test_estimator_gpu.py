@@ -94,6 +94,53 @@ def test_bf16_pred_instances_bounded(setup):
     assert worst <= 0.75 and flips <= 0.10 * B * 17
 
 
+def test_last_deconvolution_of_96_channels_is_never_fused_in_bf16():
+    """deconv_out_channels = (96, 256), B = 4 with flip test, fuse_head on: the last deconvolution reads 96 channels. pp_deconv_head (the
+    wide-tile bf16 kernel) moves its DMA cursor 64 channels a stage and changes tap where the cursor EQUALS Cin - never, at 96 - so it swept on
+    through the neighbouring pixels; the engine's gate (Cin % 32 == 0) sent the layer there. Now gate and library ask for Cin % 64 == 0.
+    No other bf16 kernel serves the width either: the 128 x 128 kernel's K-tile is 64 channels of ONE tap, and it has always refused a Cin
+    that is no multiple of it (PP_ERR_UNSUPPORTED) - so the unfused pair exists in the parity precisions only, and a bf16 engine says so
+    by name when it is built, instead of at its first batch. Checked here: the refusal, and the same head in f16x3 - whose launch trace shows
+    the unfused pair (pp_conv_gemm, then the 1x1 convolution) - against the oracle at the parity bound."""
+    import sys
+
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from launch_trace import trace_forward
+    from oracle import model_ref as M
+    from probpose_code_amd import ProbPoseEngine, _lib
+    from probpose_code_amd import synthetic as S
+
+    torch.set_num_threads(min(16, os.cpu_count()))
+    sd = S.synthetic_state_dict("small", seed=3, logit_scale=2.0, deconv_out_channels=(96, 256))
+    with pytest.raises(ValueError, match="multiple of 64 channels.*deconvolution 1 reads 96"):
+        ProbPoseEngine(sd, 12, precision="bf16", plan=dict(fuse_head=True))
+    # ... and the library itself, asked directly with the engine's arguments for that layer (bf16 operands of 8 maps of 32 x 24 x 96)
+    x = torch.zeros(8, 32, 24, 96, dtype=torch.bfloat16, device="cuda")
+    w = torch.zeros(4, 256, 4 * 96, dtype=torch.bfloat16, device="cuda")
+    hw, b, lg = torch.zeros(32, 256, dtype=torch.bfloat16, device="cuda"), torch.zeros(256, device="cuda"), torch.full((8, 17, 4, 768), 7.0, device="cuda")
+    for fn, args in (("pp_deconv_head", (x.data_ptr(), w.data_ptr(), b.data_ptr(), hw.data_ptr(), b.data_ptr(), lg.data_ptr(), 8, 32, 24, 96, 256, 17, None)),
+                     ("pp_conv_gemm", (0, 2, x.data_ptr(), w.data_ptr(), b.data_ptr(), lg.data_ptr(), 8, 32, 24, 96, 256, -1, -1, 1, 0, 0, 0, 0, 256, 2, 1, None))):
+        with pytest.raises(_lib.ProbPoseLibraryError, match="UNSUPPORTED"):
+            _lib.call(fn, *args)
+    torch.cuda.synchronize()
+    assert bool((lg == 7.0).all())
+    crops = S.synthetic_crops(4, seed=4)
+    ref = M.predict(sd, crops, 12, S.IMG_MEAN, S.IMG_STD, flip_test=True)
+    eng = ProbPoseEngine(sd, 12, precision="f16x3", plan=dict(fuse_head=True))
+    eng.forward(crops.cuda(), True, S.COCO_FLIP_INDICES)
+    calls, out = trace_forward(eng, crops.cuda(), dict(flip_test=True, return_heatmaps=False, shift_heatmap=False), S.COCO_FLIP_INDICES)
+    torch.cuda.synchronize()
+    head = [c.split("(")[0] for c in calls if c.startswith(("pp_deconv_head", "pp_skinny_conv1x1_planar("))
+            or (c.startswith(("pp_skinny_deconv(", "pp_conv_gemm(")) and "ws:d" in c)]
+    assert head == ["pp_skinny_deconv", "pp_conv_gemm", "pp_skinny_conv1x1_planar"], head
+    assert not eng._logits_phased
+    d = np.abs(out["keypoints"].cpu().numpy()[:, None] - ref["keypoints_input_space"]).max(-1)
+    print(f"deconv_out_channels (96, 256), f16x3, B = 4 + flip: keypoints L_inf {d[d < 2].max():.2e} px, {int((d >= 2).sum())} argmax flips")
+    assert (d < 2.0).all() and d.max() <= 1e-3
+    for i, name in enumerate(("keypoints_probs", "keypoints_visible", "keypoints_oks")):
+        assert np.abs(out["scalars"][i].cpu().numpy()[:, None] - ref[name]).max() <= 1e-3, name
+
+
 @pytest.mark.parametrize("precision", ["f16x3", "f32"])
 def test_full_path_bs64_within_1e3(precision):
     """The bench workload (bs 64, flip test) end to end in the parity modes against the oracle: keypoints <= 1e-3

@@ -171,6 +171,39 @@ def test_small_batches_take_the_column_parallel_plan_and_match_the_oracle(B, fli
 
 
 @gpu
+def test_narrow_second_deconvolution_takes_the_generic_kernel_and_matches_the_oracle():
+    """deconv_out_channels = (32, 256), one crop with flip test: the second deconvolution reads 32 channels on 1 536 input pixels. pp_skinny_deconv
+    requests two 32-channel blocks a stage and steps its (tap, block) cursor once per stage, so at one block per tap it read the neighbouring
+    pixel's channels; the engine's gate (Cin % 32 == 0) sent this layer there. Now the gate and the library ask for Cin >= 64, and the layer
+    runs on pp_conv_gemm's 128 x 128 kernel. The result against the oracle as for the shipped widths."""
+    import sys
+
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from launch_trace import trace_forward
+    from oracle import model_ref as M
+    from probpose_code_amd import ProbPoseEngine
+    from probpose_code_amd import synthetic as S
+
+    torch.set_num_threads(min(16, os.cpu_count()))
+    sd = S.synthetic_state_dict("small", seed=0, logit_scale=2.0, deconv_out_channels=(32, 256))
+    crops = S.synthetic_crops(1, seed=61)
+    ref = M.predict(sd, crops, 12, S.IMG_MEAN, S.IMG_STD, flip_test=True)
+    eng = ProbPoseEngine(sd, 12, precision="f16x3")
+    assert eng._small_at(2 * 192) and tuple(eng.w.deconv_channels) == (32, 256)
+    eng.forward(crops.cuda(), True, S.COCO_FLIP_INDICES)
+    calls, out = trace_forward(eng, crops.cuda(), dict(flip_test=True, return_heatmaps=False, shift_heatmap=False), S.COCO_FLIP_INDICES)
+    torch.cuda.synchronize()
+    deconvs = [c for c in calls if c.startswith("pp_deconv_head") or (c.startswith(("pp_skinny_deconv(", "pp_conv_gemm(")) and "ws:d" in c)]
+    assert len(deconvs) == 2 and deconvs[0].startswith("pp_skinny_deconv(") and ", 2, 16, 12, 384, 32, " in deconvs[0], deconvs  # 384 -> 32: unchanged
+    assert deconvs[1].startswith("pp_conv_gemm(") and ", 2, 32, 24, 32, 256, " in deconvs[1], deconvs                            # 32 -> 256
+    d = np.abs(out["keypoints"].cpu().numpy()[:, None] - ref["keypoints_input_space"]).max(-1)
+    print(f"deconv_out_channels (32, 256), B = 1 + flip: keypoints L_inf {d[d < 2].max():.2e} px, {int((d >= 2).sum())} argmax flips")
+    assert (d < 2.0).all() and d.max() <= 1e-3, f"{int((d >= 2).sum())} flips, {d[d < 2].max():.2e} px"
+    for i, name in enumerate(("keypoints_probs", "keypoints_visible", "keypoints_oks")):
+        assert np.abs(out["scalars"][i].cpu().numpy()[:, None] - ref[name]).max() <= 1e-3, name
+
+
+@gpu
 def test_small_plan_boundary_and_switch():
     """Row counts at the boundary: the last batch of the small plan and the first of the headline plan agree with the oracle and with each other's
     neighbours; `plan=dict(small_plan=False)` keeps the row-owner kernels for every batch size (and releases the plain weight copies)."""
