@@ -41,6 +41,8 @@ def main():
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--decode", default="host", choices=["host", "device"],
                     help="device: a JPEG file is Huffman-decoded on the host and reconstructed on the GPU (the same pixels)")
+    ap.add_argument("--encode", default="host", choices=["host", "device"],
+                    help="device: a .jpg / .jpeg --out-img is transformed on the GPU and Huffman-coded on the host (a file that decodes to the same pixels)")
     ap.add_argument("--bboxes", default=None, help="x0,y0,x1,y1;x0,y0,x1,y1;... (default: the whole image)")
     ap.add_argument("--precision", default=None, choices=[None, "f16x3", "bf16", "f32"],
                     help="overrides model.precision of the config (default there: f16x3, the mode within 1e-3 of the fp32 reference)")
@@ -91,7 +93,7 @@ def main():
         from probpose_code_amd.apis import load_image_bgr
         from probpose_code_amd.visualization import PoseLocalVisualizer
 
-        vis = PoseLocalVisualizer(radius=args.radius, line_width=args.thickness, alpha=args.alpha, device=args.device)
+        vis = PoseLocalVisualizer(radius=args.radius, line_width=args.thickness, alpha=args.alpha, device=args.device, image_encoder=args.encode)
         vis.set_dataset_meta(model.dataset_meta)
         vis.add_datasample("result", load_image_bgr(args.img)[:, :, ::-1], results, draw_heatmap=args.draw_heatmap, kpt_thr=args.kpt_thr,
                            out_file=args.out_img)

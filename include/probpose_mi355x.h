@@ -810,6 +810,47 @@ long long pp_jpeg_scratch_bytes(const pp_jpeg_info* infos_host, int n);
 int pp_jpeg_reconstruct_bgr_batch(const pp_jpeg_desc* descriptors, int n, long long max_blocks, int max_height, int max_width,
                                   void* stream);
 
+/* Split JPEG encoder (added under version 4: purely additive), the decoder's counterpart: colour conversion, edge
+ * expansion, chroma downsampling, 8x8 forward DCT and quantisation in csrc/pp_jpeg_enc.hip, Huffman coding and the marker
+ * segments on host threads (csrc/pp_jpeg_enc_host.h). The file holds the quantised coefficients, tables and sampling
+ * libjpeg-turbo's default compressor writes for the same pixels, quality and subsampling (islow FDCT, no smoothing, the
+ * annex K Huffman tables), so it decodes to the same pixels; the integer rules are stated in csrc/pp_jpeg_enc.hip.
+ * Written: baseline (SOF0) YCbCr JFIF files, 4:4:4 / 4:2:2 / 4:2:0, optional restart intervals. */
+
+/* One image of a batched forward transform (a device table of these drives both launches). src: height rows of width
+ * 3-byte pixels, row_stride bytes apart, B G R or (rgb != 0) R G B; qtables: 3 x 64 uint16, natural order, one table per
+ * component; planes: info.coef_count bytes of scratch, 8-byte aligned (pp_jpeg_scratch_bytes sizes a batch's);
+ * coef: info.coef_count int16 out, 16-byte aligned, in the layout of pp_jpeg_desc.coef. hs / vs / mcus_x / mcus_y: as
+ * pp_jpeg_encode_plan gives them. */
+typedef struct {
+    const uint8_t* src;
+    const uint16_t* qtables;
+    uint8_t* planes;
+    int16_t* coef;
+    int32_t width, height, row_stride, rgb, hs, vs, mcus_x, mcus_y;
+} pp_jpeg_enc_desc;
+
+/* Host only. qtables_host (3 x 64 uint16, natural order: luma, chroma, chroma) <- the tables of libjpeg's
+ * jpeg_set_quality(quality, force_baseline): annex K.1 scaled, clamped to 1..255. quality: 1..100. */
+int pp_jpeg_quality_tables(int quality, uint16_t* qtables_host);
+/* Host only. *info <- geometry of a width x height (1..65535) three-component file: MCU grid, comp_bw / comp_bh, coef_count.
+ * subsampling: 0 4:4:4, 1 4:2:2, 2 4:2:0. */
+int pp_jpeg_encode_plan(int width, int height, int subsampling, pp_jpeg_info* info);
+/* Quantised coefficients of n images of any mix of sizes and sampling in two launches ("jpeg_enc_color", "jpeg_enc_fdct" of
+ * pp_launch_count). descriptors: n pp_jpeg_enc_desc on the device; max_blocks / max_height / max_width: the largest block
+ * count (coef_count / 64), height and width in the table - they size the launch grids, every image is bounded by its own
+ * entry. The source pixels are only read. n == 0: PP_OK, nothing is launched. */
+int pp_jpeg_forward_batch(const pp_jpeg_enc_desc* descriptors, int n, long long max_blocks, int max_height, int max_width,
+                          void* stream);
+/* Host only. A capacity no file of this geometry exceeds, whatever its coefficients and restart interval. < 0: error. */
+long long pp_jpeg_encoded_bound(const pp_jpeg_info* info);
+/* Host only, re-entrant, no HIP call, no allocation: the file of coef_host (info->coef_count int16) and qtables_host
+ * (3 x 64 uint16, values 1..255) into out_host[0, capacity); *size_out <- its length. restart_interval: MCUs between RSTn
+ * markers, 0: none. PP_ERR_WORKSPACE: capacity too small; PP_ERR_INVALID_ARG: a coefficient no baseline code expresses (a DC
+ * difference outside -2047..2047, an AC value outside -1023..1023), an info that is no pp_jpeg_encode_plan result. */
+int pp_jpeg_entropy_encode(const int16_t* coef_host, const uint16_t* qtables_host, const pp_jpeg_info* info, int restart_interval,
+                           void* out_host, size_t capacity, size_t* size_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,11 @@ SIGNATURES = {
     "pp_jpeg_entropy_decode": (c_int, [_P, ctypes.c_size_t, _P, c_longlong, _P, _P]),
     "pp_jpeg_scratch_bytes": (c_longlong, [_P, c_int]),
     "pp_jpeg_reconstruct_bgr_batch": (c_int, [_P, c_int, c_longlong, c_int, c_int, _P]),
+    "pp_jpeg_quality_tables": (c_int, [c_int, _P]),
+    "pp_jpeg_encode_plan": (c_int, [c_int, c_int, c_int, _P]),
+    "pp_jpeg_forward_batch": (c_int, [_P, c_int, c_longlong, c_int, c_int, _P]),
+    "pp_jpeg_encoded_bound": (c_longlong, [_P]),
+    "pp_jpeg_entropy_encode": (c_int, [_P, _P, _P, c_int, _P, ctypes.c_size_t, _P]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

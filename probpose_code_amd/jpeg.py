@@ -9,6 +9,13 @@ any tables, restart intervals. Every other file - progressive, arithmetic-coded,
 scans, a damaged stream - is refused (``JpegUnsupported``); ``imread_device`` then decodes it with ``load_image_bgr``, so
 such a file gives the pixels or the exception it gave before. The path is opt-in: ``LoadImage(imdecode_backend="mi355x")``,
 ``runner.test_dataset(decode="device")``, ``--decode device`` of tools/test.py and demo/image_demo.py.
+
+The encoder is the same split the other way round: ``encode_batch`` converts, downsamples, transforms and quantises all
+images of a batch on the device (``pp_jpeg_forward_batch``: two launches), copies the coefficients to the host once and
+Huffman-codes them on host threads (``pp_jpeg_entropy_encode``, GIL-free). The file holds the coefficients, tables and
+sampling Pillow's ``Image.save(path, "JPEG", quality=q, subsampling=s)`` writes for the same pixels, so it decodes to the
+same pixels; its marker layout may differ. Opt-in as well: ``PoseLocalVisualizer(image_encoder="device")``, ``--encode device``
+of demo/image_demo.py.
 """
 import ctypes
 from typing import List, NamedTuple, Optional, Sequence, Union
@@ -20,6 +27,7 @@ from . import _lib
 
 fallbacks = 0  # files imread_device / the test loop handed to the host decoder since import (diagnostics)
 reconstruct_calls = 0  # pp_jpeg_reconstruct_bgr_batch calls since import
+forward_calls = 0  # pp_jpeg_forward_batch calls since import
 
 
 class JpegInfo(ctypes.Structure):
@@ -34,6 +42,11 @@ class JpegInfo(ctypes.Structure):
 _DESC = np.dtype([("coef", "<u8"), ("qtables", "<u8"), ("planes", "<u8"), ("out", "<u8"), ("width", "<i4"), ("height", "<i4"),
                   ("ncomp", "<i4"), ("hs", "<i4"), ("vs", "<i4"), ("mcus_x", "<i4"), ("mcus_y", "<i4"), ("reserved", "<i4")])
 assert _DESC.itemsize == 64
+# pp_jpeg_enc_desc: four pointers, eight int32
+_ENC_DESC = np.dtype([("src", "<u8"), ("qtables", "<u8"), ("planes", "<u8"), ("coef", "<u8"), ("width", "<i4"), ("height", "<i4"),
+                      ("row_stride", "<i4"), ("rgb", "<i4"), ("hs", "<i4"), ("vs", "<i4"), ("mcus_x", "<i4"), ("mcus_y", "<i4")])
+assert _ENC_DESC.itemsize == 64
+SUBSAMPLING = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}  # pp_jpeg_encode_plan's numbering (Pillow's as well)
 
 
 class JpegUnsupported(ValueError):
@@ -207,3 +220,162 @@ def decode_or_host(path: str):
         return entropy_decode(path)
     except JpegUnsupported:
         return _host_decode(path)
+
+
+# ------------------------------------------------------------------------------------------------------------ encoder
+def quality_tables(quality: int) -> np.ndarray:
+    """(3, 64) uint16 quantisation tables in natural order (luma, chroma, chroma) of libjpeg's quality 1..100."""
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
+        raise ValueError(f"quality must be an int in 1..100, got {quality!r}")
+    qt = np.zeros((3, 64), np.uint16)
+    _lib.call("pp_jpeg_quality_tables", int(quality), qt.ctypes.data)
+    return qt
+
+
+def encode_plan(width: int, height: int, subsampling: str = "4:2:0") -> JpegInfo:
+    """The block geometry (``JpegInfo``) of a width x height file with ``subsampling`` "4:4:4", "4:2:2" or "4:2:0"."""
+    if subsampling not in SUBSAMPLING:
+        raise ValueError(f"subsampling must be one of {sorted(SUBSAMPLING)}, got {subsampling!r}")
+    if not (1 <= int(width) <= 65535 and 1 <= int(height) <= 65535):
+        raise ValueError(f"a JPEG file holds 1..65535 pixels a side, got {width} x {height}")
+    info = JpegInfo()
+    _lib.call("pp_jpeg_encode_plan", int(width), int(height), SUBSAMPLING[subsampling], ctypes.byref(info))
+    return info
+
+
+def entropy_encode(coefficients: JpegCoefficients, restart_interval: int = 0) -> bytes:
+    """The host half of the encoder: the baseline JFIF file of ``coefficients`` (three components, tables (3, 64) with values
+    1..255). Thread-safe and GIL-free while it codes."""
+    info, coef = coefficients.info, np.ascontiguousarray(coefficients.coef, np.int16)
+    qt = np.ascontiguousarray(coefficients.qtables, np.uint16)
+    if qt.shape != (3, 64) or coef.size != info.coef_count:
+        raise ValueError("the encoder takes three (64,) tables and info.coef_count coefficients")
+    if not 0 <= int(restart_interval) <= 65535:
+        raise ValueError(f"restart_interval must be in 0..65535, got {restart_interval!r}")
+    bound = int(_lib.lib.pp_jpeg_encoded_bound(ctypes.byref(info)))
+    if bound < 0:
+        raise _lib.ProbPoseLibraryError("pp_jpeg_encoded_bound", _lib.lib.pp_status_string(bound).decode(), _lib.last_error())
+    out = np.empty(bound, np.uint8)
+    size = ctypes.c_size_t(0)
+    _lib.call("pp_jpeg_entropy_encode", coef.ctypes.data, qt.ctypes.data, ctypes.byref(info), int(restart_interval), out.ctypes.data,
+              out.size, ctypes.byref(size))
+    return out[:size.value].tobytes()
+
+
+def _encoder_images(images, device):
+    """``images`` as (H, W, 3) uint8 device tensors with dense pixel rows; ValueError for anything else."""
+    dev, checked = None, []
+    for im in images:
+        if isinstance(im, np.ndarray):
+            if im.dtype != np.uint8:
+                raise ValueError(f"the encoder takes (H, W, 3) uint8 images, got dtype {im.dtype}")
+            im = torch.from_numpy(np.ascontiguousarray(im))
+        if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
+            what = f"{tuple(im.shape)} {im.dtype}" if isinstance(im, torch.Tensor) else type(im).__name__
+            raise ValueError(f"the encoder takes (H, W, 3) uint8 images, got {what}")
+        if im.shape[0] == 0 or im.shape[1] == 0:
+            raise ValueError("empty image")
+        if im.shape[0] > 65535 or im.shape[1] > 65535:
+            raise ValueError(f"a JPEG file holds at most 65535 pixels a side, got {im.shape[1]} x {im.shape[0]}")
+        if im.is_cuda:
+            if dev is not None and im.device != dev:
+                raise ValueError(f"images of one batch must share a device: {im.device} and {dev}")
+            dev = im.device
+        checked.append(im)
+    dev = dev if dev is not None else torch.device(device or "cuda")
+    if dev.type != "cuda":
+        raise RuntimeError("probpose_code_amd.jpeg.encode_batch runs on the GPU only (no CPU fallback)")
+    out = []
+    for im in checked:
+        im = im.to(dev)  # a host array is uploaded first
+        if im.stride(2) != 1 or im.stride(1) != 3 or im.stride(0) < 3 * im.shape[1] or im.stride(0) >= 2 ** 31:
+            im = im.contiguous()  # (a view of whole rows, such as a vertical crop, is read in place)
+        out.append(im)
+    return out, dev
+
+
+def _stage_encode(images, qt, subsampling, channel_order, dev, staging):
+    """Pack the descriptor table and the tables of a batch into the pinned buffer and upload them with one copy. Returns (the
+    arguments of ``pp_jpeg_forward_batch``, (device block, pinned buffer, first and last byte of the coefficients in both, each
+    image's offset, the infos), the tensors the launches use)."""
+    n = len(images)
+    infos = [encode_plan(im.shape[1], im.shape[0], subsampling) for im in images]
+    # the block: descriptors (n x 64 bytes) | quantisation tables (3 x 64 u16) | per image: coefficients (int16)
+    o_qt = _align(64 * n)
+    off, o_coef = _align(o_qt + 384), []
+    for info in infos:
+        o_coef.append(off)
+        off = _align(off + 2 * int(info.coef_count))
+    total, head = off, o_coef[0]
+    scratch = torch.empty(sum(_align(int(i.coef_count)) for i in infos), dtype=torch.uint8, device=dev)
+    block = torch.empty(total, dtype=torch.uint8, device=dev)
+    blk = staging.acquire(total)
+    desc = blk[:64 * n].view(_ENC_DESC)
+    blk[o_qt:o_qt + 384].view(np.uint16)[:] = qt.reshape(-1)
+    base, planes = block.data_ptr(), scratch.data_ptr()
+    for i, (im, info) in enumerate(zip(images, infos)):
+        desc[i] = (im.data_ptr(), base + o_qt, planes, base + o_coef[i], info.width, info.height, im.stride(0), int(channel_order == "rgb"),
+                   info.hs, info.vs, info.mcus_x, info.mcus_y)
+        planes += _align(int(info.coef_count))
+    staging.upload(block, head)
+    args = (base, n, max(int(i.coef_count) // 64 for i in infos), max(int(i.height) for i in infos), max(int(i.width) for i in infos))
+    return args, (block, blk, head, total, o_coef, infos), (images, block, scratch)
+
+
+def forward_batch(images: Sequence, quality: int = 75, subsampling: str = "4:2:0", channel_order: str = "bgr", device=None,
+                  staging=None, copy: bool = True) -> List[JpegCoefficients]:
+    """The device half of the encoder for a batch of (H, W, 3) uint8 images of any mix of sizes: ONE
+    ``pp_jpeg_forward_batch`` call (two launches) on the current stream, then one copy of all coefficients into the pinned
+    buffer of ``staging`` (a ``transforms.BatchStaging``). Returns what ``entropy_decode`` gives for the finished files; with
+    ``copy=False`` the coefficient arrays are views of the pinned buffer, valid until ``staging`` is used again."""
+    global forward_calls
+    from .transforms import BatchStaging
+
+    if channel_order not in ("bgr", "rgb"):
+        raise ValueError(f"channel_order must be 'bgr' or 'rgb', got {channel_order!r}")
+    qt = quality_tables(quality)
+    if subsampling not in SUBSAMPLING:
+        raise ValueError(f"subsampling must be one of {sorted(SUBSAMPLING)}, got {subsampling!r}")
+    images, dev = _encoder_images(list(images), device)
+    n = len(images)
+    if n == 0:
+        return []
+    staging = staging if staging is not None else BatchStaging()
+    args, (block, blk, head, total, o_coef, infos), keep = _stage_encode(images, qt, subsampling, channel_order, dev, staging)
+    stream = torch.cuda.current_stream(dev)
+    _lib.call("pp_jpeg_forward_batch", *args, stream.cuda_stream)
+    forward_calls += 1
+    staging.buf[head:total].copy_(block[head:total], non_blocking=True)
+    stream.synchronize()  # the coefficients are in the pinned buffer; images, block and scratch (``keep``) are no longer read
+    del keep
+    views = [blk[o:o + 2 * int(info.coef_count)].view(np.int16) for o, info in zip(o_coef, infos)]
+    return [JpegCoefficients(info, v.copy() if copy else v, qt) for v, info in zip(views, infos)]
+
+
+def encode_batch(images: Sequence, quality: int = 75, subsampling: str = "4:2:0", channel_order: str = "bgr", restart_interval: int = 0,
+                 workers: int = 8, device=None, staging=None) -> List[bytes]:
+    """Baseline JPEG files of a batch of (H, W, 3) uint8 images (device tensors; a host array is uploaded first) of any mix
+    of sizes: ``forward_batch`` on the device, then Huffman coding on a pool of ``workers`` host threads (at most
+    ``runner.MAX_WORKERS``). ``quality`` 1..100, ``subsampling`` "4:4:4" / "4:2:2" / "4:2:0" and ``restart_interval`` (MCUs
+    between restart markers, 0: none) mean what they mean to Pillow's ``Image.save``; ``channel_order``: "bgr" or "rgb"
+    pixels. Each file decodes to the pixels Pillow's own file of that image decodes to."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from .runner import MAX_WORKERS
+
+    if isinstance(restart_interval, bool) or not isinstance(restart_interval, (int, np.integer)) or not 0 <= int(restart_interval) <= 65535:
+        raise ValueError(f"restart_interval must be an int in 0..65535, got {restart_interval!r}")
+    if isinstance(images, (torch.Tensor, np.ndarray)):
+        raise ValueError("encode_batch takes a sequence of (H, W, 3) images; imwrite_device takes one")
+    coefs = forward_batch(images, quality, subsampling, channel_order, device, staging, copy=False)  # (coded before staging is used again)
+    if len(coefs) <= 1 or int(workers) <= 1:
+        return [entropy_encode(c, restart_interval) for c in coefs]
+    with ThreadPoolExecutor(max_workers=max(1, min(MAX_WORKERS, int(workers), len(coefs)))) as pool:
+        return list(pool.map(lambda c: entropy_encode(c, restart_interval), coefs))
+
+
+def imwrite_device(path: str, image, **kw) -> None:
+    """One picture written as a baseline JPEG file by ``encode_batch`` (its keyword arguments)."""
+    data = encode_batch([image], **kw)[0]
+    with open(path, "wb") as f:
+        f.write(data)

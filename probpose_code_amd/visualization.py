@@ -171,7 +171,10 @@ class PoseLocalVisualizer:
     "mmpose" skeleton style, their boxes, and (``draw_heatmap``) the probability areas of the posterior maps on the padded
     canvas, stacked under the pose panel. Everything is drawn on the GPU; ``add_datasample`` copies the image back once."""
 
-    def __init__(self, name="visualizer", radius=3, line_width=1, alpha=0.8, device="cuda:0"):
+    def __init__(self, name="visualizer", radius=3, line_width=1, alpha=0.8, device="cuda:0", image_encoder="host"):
+        if image_encoder not in ("host", "device"):
+            raise ValueError(f"image_encoder must be 'host' or 'device', got {image_encoder!r}")
+        self.image_encoder = image_encoder  # "device": a .jpg / .jpeg out_file is written by jpeg.imwrite_device
         self.name = name
         self.radius = radius
         self.line_width = line_width
@@ -207,7 +210,9 @@ class PoseLocalVisualizer:
                        out_file=None, show_kpt_idx=False, skeleton_style="mmpose", show=False, wait_time=0, step=0):
         """Draw the predictions of one merged sample on ``image`` ((H, W, 3) uint8 RGB, host array or device tensor). Returns
         the (H, W, 3) pose panel, or with ``draw_heatmap`` (and heatmaps in ``pred_fields``) the (2H, W, 3) stack of the pose
-        panel over the probability areas resized to (H, W) (:796-865); ``out_file`` is written with Pillow."""
+        panel over the probability areas resized to (H, W) (:796-865); ``out_file`` is written with Pillow - or, for a visualizer
+        built with ``image_encoder="device"`` and a ``.jpg`` / ``.jpeg`` name, by the split JPEG encoder from the frame on the
+        device (Pillow's default quality 75 and 4:2:0: a file that decodes to the same pixels)."""
         if draw_gt:
             raise NotImplementedError("draw_gt: ground-truth drawing is outside ProbPose's demo")
         if show_kpt_idx:
@@ -249,9 +254,14 @@ class PoseLocalVisualizer:
             resize_rgb(panel, (H, W), out=out[H:])
         self._image = out.cpu().numpy()
         if out_file is not None:
-            from PIL import Image
+            if self.image_encoder == "device" and str(out_file).lower().endswith((".jpg", ".jpeg")):
+                from . import jpeg
 
-            Image.fromarray(self._image).save(out_file)
+                jpeg.imwrite_device(out_file, out, quality=75, subsampling="4:2:0", channel_order="rgb")
+            else:
+                from PIL import Image
+
+                Image.fromarray(self._image).save(out_file)
         return self._image
 
 
