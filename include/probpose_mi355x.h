@@ -850,6 +850,49 @@ long long pp_jpeg_encoded_bound(const pp_jpeg_info* info);
  * difference outside -2047..2047, an AC value outside -1023..1023), an info that is no pp_jpeg_encode_plan result. */
 int pp_jpeg_entropy_encode(const int16_t* coef_host, const uint16_t* qtables_host, const pp_jpeg_info* info, int restart_interval,
                            void* out_host, size_t capacity, size_t* size_out);
+/* Host only, re-entrant: the bytes SOI .. SOS of the file pp_jpeg_entropy_encode writes for these tables, geometry and
+ * restart interval (the same code writes both) into out_host[0, capacity); *size_out <- their length. A file is these
+ * headers, the stream of pp_jpeg_entropy_encode_batch, then FF D9. */
+int pp_jpeg_write_headers(const uint16_t* qtables_host, const pp_jpeg_info* info, int restart_interval, void* out_host,
+                          size_t capacity, size_t* size_out);
+
+/* Huffman coding on the device (csrc/pp_jpeg_entropy.hip; added under version 4: purely additive): the bytes
+ * pp_jpeg_entropy_encode writes between the SOS header and the EOI marker, bit for bit, from coefficients that stay where
+ * pp_jpeg_forward_batch left them. Restart interval 0 only. */
+
+/* What the coder leaves per image: the length of the stream in bytes (also when it did not fit: the capacity it needs) and
+ * PP_OK, PP_ERR_INVALID_ARG (a DC difference outside -2047..2047 or an AC value outside -1023..1023: the stream is
+ * undefined; or a descriptor without a plan's geometry) or PP_ERR_WORKSPACE (capacity below the need: nothing written). */
+typedef struct {
+    int64_t bytes;
+    int32_t status;
+    int32_t reserved;
+} pp_jpeg_ent_result;
+
+/* One image of a batched entropy coding (a device table of these drives every launch). coef: info.coef_count int16 in the
+ * layout of pp_jpeg_desc.coef, 16-byte aligned, only read; scratch: the image's share of pp_jpeg_entropy_scratch_bytes,
+ * 16-byte aligned, contents undefined before and after; out / capacity: where the stream goes and how many bytes fit;
+ * result: the image's slot; hs / vs / mcus_x / mcus_y: as pp_jpeg_encode_plan gives them. */
+typedef struct {
+    const int16_t* coef;
+    uint8_t* scratch;
+    uint8_t* out;
+    pp_jpeg_ent_result* result;
+    int64_t capacity;
+    int32_t hs, vs, mcus_x, mcus_y;
+    int64_t reserved;
+} pp_jpeg_ent_desc;
+
+/* Host only. Bytes of scratch for n images (infos_host: n pp_jpeg_encode_plan results), each image's share a multiple of
+ * 256: image i's share starts at the sum of the shares before it. < 0: error. */
+long long pp_jpeg_entropy_scratch_bytes(const pp_jpeg_info* infos_host, int n);
+/* The streams of n images of any mix of sizes and sampling in seven launches ("jpeg_ent_bits", "jpeg_ent_scan",
+ * "jpeg_ent_zero", "jpeg_ent_pack", "jpeg_ent_ffcount", "jpeg_ent_ffscan", "jpeg_ent_stuff" of pp_launch_count).
+ * descriptors: n pp_jpeg_ent_desc on the device; max_blocks: the largest block count (coef_count / 64) in the table - it
+ * sizes the grids, every image is bounded by its own entry. No allocation, no synchronisation, no read-back: the caller
+ * reads the result slots after the stream has run. An image's failure leaves the others untouched; nothing is written
+ * outside an image's scratch share, out[0, capacity) and result slot. n == 0: PP_OK, nothing is launched. */
+int pp_jpeg_entropy_encode_batch(const pp_jpeg_ent_desc* descriptors, int n, long long max_blocks, void* stream);
 
 #ifdef __cplusplus
 }

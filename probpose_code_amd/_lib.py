@@ -172,6 +172,9 @@ SIGNATURES = {
     "pp_jpeg_forward_batch": (c_int, [_P, c_int, c_longlong, c_int, c_int, _P]),
     "pp_jpeg_encoded_bound": (c_longlong, [_P]),
     "pp_jpeg_entropy_encode": (c_int, [_P, _P, _P, c_int, _P, ctypes.c_size_t, _P]),
+    "pp_jpeg_write_headers": (c_int, [_P, _P, c_int, _P, ctypes.c_size_t, _P]),
+    "pp_jpeg_entropy_scratch_bytes": (c_longlong, [_P, c_int]),
+    "pp_jpeg_entropy_encode_batch": (c_int, [_P, c_int, c_longlong, _P]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1,5 +1,6 @@
 // The data-parallel half of the split JPEG encoder: from (H, W, 3) uint8 pixels on the device to the quantised coefficients
-// the host's Huffman coder (csrc/pp_jpeg_enc_host.h) writes into a file. Two launches per batch of images of any mix of
+// the Huffman coder writes into a file - the host's (csrc/pp_jpeg_enc_host.h), or the device's (csrc/pp_jpeg_entropy.hip), which
+// reads them where this file leaves them and writes the same bytes. Two launches per batch of images of any mix of
 // sizes and sampling, driven by a device table of pp_jpeg_enc_desc:
 //   jpeg_enc_color  BGR / RGB -> YCbCr, edge expansion, chroma downsampling into the component planes (uint8, whole MCUs);
 //   jpeg_enc_fdct   level shift, 8x8 forward DCT, quantisation into int16 coefficients in natural order - the layout of
@@ -260,6 +261,13 @@ extern "C" int pp_jpeg_entropy_encode(const int16_t* coef_host, const uint16_t* 
                                       int restart_interval, void* out_host, size_t capacity, size_t* size_out) {
     const int st = pp::jpeg::entropy_encode(coef_host, qtables_host, info, restart_interval, reinterpret_cast<uint8_t*>(out_host), capacity, size_out);
     if (st != PP_OK) pp::set_error("pp_jpeg_entropy_encode: %s", pp::jpeg::g_reason);
+    return st;
+}
+
+extern "C" int pp_jpeg_write_headers(const uint16_t* qtables_host, const pp_jpeg_info* info, int restart_interval, void* out_host,
+                                     size_t capacity, size_t* size_out) {
+    const int st = pp::jpeg::write_headers(qtables_host, info, restart_interval, reinterpret_cast<uint8_t*>(out_host), capacity, size_out);
+    if (st != PP_OK) pp::set_error("pp_jpeg_write_headers: %s", pp::jpeg::g_reason);
     return st;
 }
 

@@ -7,6 +7,8 @@
 // DRI when a restart interval is asked for, SOS (one interleaved scan), entropy-coded data with byte stuffing, EOI.
 // Quantisation tables follow libjpeg: annex K.1 scaled by jpeg_quality_scaling, clamped to 1..255 (force_baseline).
 // Every write is checked against the caller's capacity; every coefficient against what a baseline code can express.
+// entropy_encode is also the contract of the device coder (csrc/pp_jpeg_entropy.hip), which writes the bytes between the SOS
+// header and EOI bit for bit and derives its code tables from the arrays below; write_headers gives the bytes in front.
 #pragma once
 #include "pp_jpeg_host.h"
 
@@ -22,11 +24,11 @@ static const uint8_t kStdChromaQ[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 
                                         99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
 
 // ITU T.81 annex K.3 - K.6: code counts per length 1..16, then the symbols in code order
-static const uint8_t kDcLumaBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
-static const uint8_t kDcChromaBits[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
-static const uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
-static const uint8_t kAcLumaBits[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d};
-static const uint8_t kAcLumaVals[162] = {
+static constexpr uint8_t kDcLumaBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
+static constexpr uint8_t kDcChromaBits[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
+static constexpr uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+static constexpr uint8_t kAcLumaBits[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d};
+static constexpr uint8_t kAcLumaVals[162] = {
     0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1,
     0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26,
     0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56,
@@ -35,8 +37,8 @@ static const uint8_t kAcLumaVals[162] = {
     0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6,
     0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
     0xfa};
-static const uint8_t kAcChromaBits[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77};
-static const uint8_t kAcChromaVals[162] = {
+static constexpr uint8_t kAcChromaBits[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77};
+static constexpr uint8_t kAcChromaVals[162] = {
     0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
     0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19,
     0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55,
@@ -207,19 +209,8 @@ inline void write_dht(BitWriter& w, int tc_th, const uint8_t* bits, const uint8_
     w.raw(vals, (size_t)nvals);
 }
 
-// pp_jpeg_entropy_encode: coef (info->coef_count int16, the layout of pp_jpeg_entropy_decode) + qtables (3 x 64 uint16,
-// natural order, values 1..255) -> a baseline JFIF file in out[0, capacity); *size_out <- its length.
-inline int entropy_encode(const int16_t* coef, const uint16_t* qtables, const pp_jpeg_info* info, int restart_interval, uint8_t* out,
-                          size_t capacity, size_t* size_out) {
-    if (!coef || !qtables || !info || !out || !size_out) return enc_fail(PP_ERR_INVALID_ARG, "NULL argument");
-    *size_out = 0;
-    if (!plan_consistent(*info)) return enc_fail(PP_ERR_INVALID_ARG, "info is not a pp_jpeg_encode_plan result");
-    if (restart_interval < 0 || restart_interval > 65535) return enc_fail(PP_ERR_INVALID_ARG, "restart interval outside 0..65535");
-    for (int i = 0; i < 192; ++i)
-        if (qtables[i] < 1 || qtables[i] > 255) return enc_fail(PP_ERR_INVALID_ARG, "quantisation value outside 1..255 (baseline)");
-    static const EncTables tables;
-    BitWriter w{out, out + capacity};
-    // ---- headers
+// The marker segments SOI .. SOS of a file into w (the caller checks w.full). Cr gets a table of its own where it differs from Cb's.
+inline void put_headers(BitWriter& w, const uint16_t* qtables, const pp_jpeg_info* info, int restart_interval) {
     w.marker(0xD8);
     static const uint8_t app0[16] = {0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
     w.marker(0xE0);
@@ -256,6 +247,41 @@ inline int entropy_encode(const int16_t* coef, const uint16_t* qtables, const pp
     static const uint8_t sos[12] = {0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
     w.marker(0xDA);
     w.raw(sos, 12);
+}
+
+// The argument checks pp_jpeg_entropy_encode and pp_jpeg_write_headers share.
+inline int check_file_args(const uint16_t* qtables, const pp_jpeg_info* info, int restart_interval) {
+    if (!plan_consistent(*info)) return enc_fail(PP_ERR_INVALID_ARG, "info is not a pp_jpeg_encode_plan result");
+    if (restart_interval < 0 || restart_interval > 65535) return enc_fail(PP_ERR_INVALID_ARG, "restart interval outside 0..65535");
+    for (int i = 0; i < 192; ++i)
+        if (qtables[i] < 1 || qtables[i] > 255) return enc_fail(PP_ERR_INVALID_ARG, "quantisation value outside 1..255 (baseline)");
+    return PP_OK;
+}
+
+// pp_jpeg_write_headers: the bytes SOI .. SOS of the file entropy_encode writes for these tables, geometry and restart
+// interval, into out[0, capacity); *size_out <- their length. The device coder's stream and FF D9 complete the file.
+inline int write_headers(const uint16_t* qtables, const pp_jpeg_info* info, int restart_interval, uint8_t* out, size_t capacity,
+                         size_t* size_out) {
+    if (!qtables || !info || !out || !size_out) return enc_fail(PP_ERR_INVALID_ARG, "NULL argument");
+    *size_out = 0;
+    if (const int st = check_file_args(qtables, info, restart_interval)) return st;
+    BitWriter w{out, out + capacity};
+    put_headers(w, qtables, info, restart_interval);
+    if (w.full) return enc_fail(PP_ERR_WORKSPACE, "output buffer too small");
+    *size_out = (size_t)(w.p - out);
+    return PP_OK;
+}
+
+// pp_jpeg_entropy_encode: coef (info->coef_count int16, the layout of pp_jpeg_entropy_decode) + qtables (3 x 64 uint16,
+// natural order, values 1..255) -> a baseline JFIF file in out[0, capacity); *size_out <- its length.
+inline int entropy_encode(const int16_t* coef, const uint16_t* qtables, const pp_jpeg_info* info, int restart_interval, uint8_t* out,
+                          size_t capacity, size_t* size_out) {
+    if (!coef || !qtables || !info || !out || !size_out) return enc_fail(PP_ERR_INVALID_ARG, "NULL argument");
+    *size_out = 0;
+    if (const int st = check_file_args(qtables, info, restart_interval)) return st;
+    static const EncTables tables;
+    BitWriter w{out, out + capacity};
+    put_headers(w, qtables, info, restart_interval);
     if (w.full) return enc_fail(PP_ERR_WORKSPACE, "output buffer too small");
     // ---- the scan
     const int16_t* plane[3];

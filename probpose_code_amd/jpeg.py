@@ -16,6 +16,11 @@ Huffman-codes them on host threads (``pp_jpeg_entropy_encode``, GIL-free). The f
 sampling Pillow's ``Image.save(path, "JPEG", quality=q, subsampling=s)`` writes for the same pixels, so it decodes to the
 same pixels; its marker layout may differ. Opt-in as well: ``PoseLocalVisualizer(image_encoder="device")``, ``--encode device``
 of demo/image_demo.py.
+
+``encode_batch(..., entropy="device")`` codes on the device as well (``pp_jpeg_entropy_encode_batch``, csrc/pp_jpeg_entropy.hip:
+seven launches behind the forward call's two, on the same stream): the coefficients never leave the device, the host
+receives the finished streams and puts ``pp_jpeg_write_headers``' bytes in front and ``FF D9`` behind. The files are byte
+for byte those of the host coder. Restart interval 0 only; the default stays ``entropy="host"``.
 """
 import ctypes
 from typing import List, NamedTuple, Optional, Sequence, Union
@@ -28,6 +33,7 @@ from . import _lib
 fallbacks = 0  # files imread_device / the test loop handed to the host decoder since import (diagnostics)
 reconstruct_calls = 0  # pp_jpeg_reconstruct_bgr_batch calls since import
 forward_calls = 0  # pp_jpeg_forward_batch calls since import
+entropy_device_calls = 0  # pp_jpeg_entropy_encode_batch calls since import
 
 
 class JpegInfo(ctypes.Structure):
@@ -46,6 +52,13 @@ assert _DESC.itemsize == 64
 _ENC_DESC = np.dtype([("src", "<u8"), ("qtables", "<u8"), ("planes", "<u8"), ("coef", "<u8"), ("width", "<i4"), ("height", "<i4"),
                       ("row_stride", "<i4"), ("rgb", "<i4"), ("hs", "<i4"), ("vs", "<i4"), ("mcus_x", "<i4"), ("mcus_y", "<i4")])
 assert _ENC_DESC.itemsize == 64
+# pp_jpeg_ent_desc: four pointers, the capacity, four int32, eight reserved bytes; pp_jpeg_ent_result
+_ENT_DESC = np.dtype([("coef", "<u8"), ("scratch", "<u8"), ("out", "<u8"), ("result", "<u8"), ("capacity", "<i8"), ("hs", "<i4"),
+                      ("vs", "<i4"), ("mcus_x", "<i4"), ("mcus_y", "<i4"), ("reserved", "<i8")])
+assert _ENT_DESC.itemsize == 64
+_ENT_RESULT = np.dtype([("bytes", "<i8"), ("status", "<i4"), ("reserved", "<i4")])
+assert _ENT_RESULT.itemsize == 16
+ENTROPY = ("host", "device")
 SUBSAMPLING = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}  # pp_jpeg_encode_plan's numbering (Pillow's as well)
 
 
@@ -294,15 +307,19 @@ def _encoder_images(images, device):
     return out, dev
 
 
-def _stage_encode(images, qt, subsampling, channel_order, dev, staging):
+def _stage_encode(images, qt, subsampling, channel_order, dev, staging, entropy=False):
     """Pack the descriptor table and the tables of a batch into the pinned buffer and upload them with one copy. Returns (the
     arguments of ``pp_jpeg_forward_batch``, (device block, pinned buffer, first and last byte of the coefficients in both, each
-    image's offset, the infos), the tensors the launches use)."""
+    image's offset, the infos), the tensors the launches use). ``entropy``: the table and result slots of
+    ``pp_jpeg_entropy_encode_batch`` travel in the same copy; the returned tuple then ends with an ``_EntropyJob``."""
     n = len(images)
     infos = [encode_plan(im.shape[1], im.shape[0], subsampling) for im in images]
-    # the block: descriptors (n x 64 bytes) | quantisation tables (3 x 64 u16) | per image: coefficients (int16)
+    # the block: descriptors (n x 64 bytes) | quantisation tables (3 x 64 u16) | with entropy: its descriptors (n x 64 bytes),
+    # result slots (n x 16 bytes) | per image: coefficients (int16)
     o_qt = _align(64 * n)
-    off, o_coef = _align(o_qt + 384), []
+    o_ent = _align(o_qt + 384)
+    o_res = _align(o_ent + 64 * n) if entropy else o_ent
+    off, o_coef = (_align(o_res + 16 * n) if entropy else o_ent), []
     for info in infos:
         o_coef.append(off)
         off = _align(off + 2 * int(info.coef_count))
@@ -317,9 +334,130 @@ def _stage_encode(images, qt, subsampling, channel_order, dev, staging):
         desc[i] = (im.data_ptr(), base + o_qt, planes, base + o_coef[i], info.width, info.height, im.stride(0), int(channel_order == "rgb"),
                    info.hs, info.vs, info.mcus_x, info.mcus_y)
         planes += _align(int(info.coef_count))
+    job = None
+    if entropy:
+        blk[o_res:o_res + 16 * n] = 0
+        job = _entropy_job(blk[o_ent:o_ent + 64 * n].view(_ENT_DESC), infos, [base + o for o in o_coef], block[o_res:o_res + 16 * n], dev)
     staging.upload(block, head)
     args = (base, n, max(int(i.coef_count) // 64 for i in infos), max(int(i.height) for i in infos), max(int(i.width) for i in infos))
+    if entropy:
+        return args, (block, blk, head, total, o_coef, infos), (images, block, scratch), (base + o_ent, job)
     return args, (block, blk, head, total, o_coef, infos), (images, block, scratch)
+
+
+def write_headers(qtables: np.ndarray, info: JpegInfo, restart_interval: int = 0) -> bytes:
+    """The bytes SOI .. SOS of the file ``entropy_encode`` writes for these tables and this geometry (one code path)."""
+    qt = np.ascontiguousarray(qtables, np.uint16)
+    if qt.shape != (3, 64):
+        raise ValueError("the encoder takes three (64,) tables")
+    out = np.empty(1024, np.uint8)
+    size = ctypes.c_size_t(0)
+    _lib.call("pp_jpeg_write_headers", qt.ctypes.data, ctypes.byref(info), int(restart_interval), out.ctypes.data, out.size, ctypes.byref(size))
+    return out[:size.value].tobytes()
+
+
+class _EntropyJob(NamedTuple):
+    """The device buffers of one ``pp_jpeg_entropy_encode_batch`` call: ``results`` (n x 16 bytes, a view of the uploaded
+    block), the streams (``out``: image i's at ``o_out[i]``, ``capacity[i]`` bytes), the scratch, and the infos."""
+
+    results: torch.Tensor
+    out: torch.Tensor
+    o_out: list
+    capacity: list
+    scratch: torch.Tensor
+    infos: list
+
+
+def _entropy_job(desc: np.ndarray, infos, coef_ptrs, results: torch.Tensor, dev) -> "_EntropyJob":
+    """Allocate the scratch and the stream buffers of a batch and fill ``desc`` (a host view of n ``_ENT_DESC`` rows that
+    the caller uploads). A stream gets ``pp_jpeg_encoded_bound`` bytes: no stream of its geometry is longer."""
+    shares, capacity = [], []
+    for info in infos:
+        one = int(_lib.lib.pp_jpeg_entropy_scratch_bytes(ctypes.byref(info), 1))
+        bound = int(_lib.lib.pp_jpeg_encoded_bound(ctypes.byref(info)))
+        if one < 0 or bound < 0:
+            raise _lib.ProbPoseLibraryError("pp_jpeg_entropy_scratch_bytes", _lib.lib.pp_status_string(min(one, bound)).decode(), _lib.last_error())
+        shares.append(one)
+        capacity.append(_align(bound))
+    scratch = torch.empty(sum(shares), dtype=torch.uint8, device=dev)
+    out = torch.empty(sum(capacity), dtype=torch.uint8, device=dev)
+    o_out, s_at, o_at = [], scratch.data_ptr(), 0
+    for i, info in enumerate(infos):
+        desc[i] = (coef_ptrs[i], s_at, out.data_ptr() + o_at, results.data_ptr() + 16 * i, capacity[i], info.hs, info.vs, info.mcus_x,
+                   info.mcus_y, 0)
+        o_out.append(o_at)
+        s_at += shares[i]
+        o_at += capacity[i]
+    return _EntropyJob(results, out, o_out, capacity, scratch, list(infos))
+
+
+def _entropy_launch(desc_ptr: int, job: "_EntropyJob", stream) -> None:
+    global entropy_device_calls
+    _lib.call("pp_jpeg_entropy_encode_batch", desc_ptr, len(job.infos), max(int(i.coef_count) // 64 for i in job.infos), stream.cuda_stream)
+    entropy_device_calls += 1
+
+
+def _entropy_collect(job: "_EntropyJob", qtables, stream, staging) -> List[bytes]:
+    """The files of a coded batch: the result slots first (one copy, one synchronisation), then the used bytes of every
+    stream into the pinned buffer (one copy per image, one synchronisation), each between its headers and ``FF D9``."""
+    res = job.results.cpu().numpy().view(_ENT_RESULT)  # (waits for the stream: the launches have run)
+    for i, r in enumerate(res):
+        if int(r["status"]) != _lib.PP_OK:
+            why = ("a coefficient no baseline code expresses (DC difference outside -2047..2047 or AC outside -1023..1023)"
+                   if int(r["status"]) == _lib.PP_ERR_INVALID_ARG else f"the stream needs {int(r['bytes'])} bytes, {job.capacity[i]} were given")
+            raise _lib.ProbPoseLibraryError("pp_jpeg_entropy_encode_batch", _lib.lib.pp_status_string(int(r["status"])).decode(), f"image {i}: {why}")
+    sizes = [int(r["bytes"]) for r in res]
+    at, offs = 0, []
+    for sz in sizes:
+        offs.append(at)
+        at += _align(sz)
+    blk = staging.acquire(max(at, 1))
+    for o, sz, oo in zip(offs, sizes, job.o_out):
+        staging.buf[o:o + sz].copy_(job.out[oo:oo + sz], non_blocking=True)
+    stream.synchronize()
+    return [write_headers(qt, info) + blk[o:o + sz].tobytes() + b"\xff\xd9" for qt, info, o, sz in zip(qtables, job.infos, offs, sizes)]
+
+
+def entropy_encode_device(coefficients: Sequence[JpegCoefficients], device=None, staging=None) -> List[bytes]:
+    """The files ``entropy_encode`` gives for a list of ``JpegCoefficients`` (three components, geometry of ``encode_plan``),
+    coded on the device: the coefficient arrays are uploaded with the table in one copy, then ONE
+    ``pp_jpeg_entropy_encode_batch`` call (seven launches) on the current stream. Invalid coefficients raise what
+    ``entropy_encode`` raises for them (``ProbPoseLibraryError``, PP_ERR_INVALID_ARG)."""
+    from .transforms import BatchStaging
+
+    coefficients = list(coefficients)
+    n = len(coefficients)
+    if n == 0:
+        return []
+    dev = torch.device(device or "cuda")
+    if dev.type != "cuda":
+        raise RuntimeError("probpose_code_amd.jpeg.entropy_encode_device runs on the GPU only (no CPU fallback)")
+    staging = staging if staging is not None else BatchStaging()
+    infos, qts = [], []
+    for c in coefficients:
+        coef, qt = np.asarray(c.coef), np.ascontiguousarray(c.qtables, np.uint16)
+        if qt.shape != (3, 64) or coef.size != c.info.coef_count or coef.dtype != np.int16:
+            raise ValueError("the encoder takes three (64,) tables and info.coef_count int16 coefficients")
+        write_headers(qt, c.info)  # (refuses an info that is no encode_plan result, and tables outside 1..255, before any GPU work)
+        infos.append(c.info)
+        qts.append(qt)
+    # the block: descriptors (n x 64 bytes) | result slots (n x 16 bytes) | per image: coefficients (int16)
+    o_res = _align(64 * n)
+    off, o_coef = _align(o_res + 16 * n), []
+    for info in infos:
+        o_coef.append(off)
+        off = _align(off + 2 * int(info.coef_count))
+    block = torch.empty(off, dtype=torch.uint8, device=dev)
+    blk = staging.acquire(off)
+    blk[o_res:o_res + 16 * n] = 0
+    for o, c in zip(o_coef, coefficients):
+        blk[o:o + 2 * c.coef.size].view(np.int16)[:] = np.asarray(c.coef).reshape(-1)
+    base = block.data_ptr()
+    job = _entropy_job(blk[:64 * n].view(_ENT_DESC), infos, [base + o for o in o_coef], block[o_res:o_res + 16 * n], dev)
+    staging.upload(block, off)
+    stream = torch.cuda.current_stream(dev)
+    _entropy_launch(base, job, stream)
+    return _entropy_collect(job, qts, stream, staging)
 
 
 def forward_batch(images: Sequence, quality: int = 75, subsampling: str = "4:2:0", channel_order: str = "bgr", device=None,
@@ -353,12 +491,18 @@ def forward_batch(images: Sequence, quality: int = 75, subsampling: str = "4:2:0
 
 
 def encode_batch(images: Sequence, quality: int = 75, subsampling: str = "4:2:0", channel_order: str = "bgr", restart_interval: int = 0,
-                 workers: int = 8, device=None, staging=None) -> List[bytes]:
+                 workers: int = 8, device=None, staging=None, entropy: str = "host") -> List[bytes]:
     """Baseline JPEG files of a batch of (H, W, 3) uint8 images (device tensors; a host array is uploaded first) of any mix
     of sizes: ``forward_batch`` on the device, then Huffman coding on a pool of ``workers`` host threads (at most
     ``runner.MAX_WORKERS``). ``quality`` 1..100, ``subsampling`` "4:4:4" / "4:2:2" / "4:2:0" and ``restart_interval`` (MCUs
     between restart markers, 0: none) mean what they mean to Pillow's ``Image.save``; ``channel_order``: "bgr" or "rgb"
-    pixels. Each file decodes to the pixels Pillow's own file of that image decodes to."""
+    pixels. Each file decodes to the pixels Pillow's own file of that image decodes to.
+
+    ``entropy="device"`` codes on the device instead (restart interval 0 only): the forward launches, then
+    ``pp_jpeg_entropy_encode_batch`` on the same stream; the coefficients stay on the device and ``workers`` is not used. A
+    batch of n images then costs one upload (tables and descriptors), 1 + n downloads (the result slots, then the used
+    bytes of each stream) and two synchronisations, one after each kind of download. The files are byte for byte those
+    of ``entropy="host"``; invalid coefficients raise the same ``ProbPoseLibraryError``."""
     from concurrent.futures import ThreadPoolExecutor
 
     from .runner import MAX_WORKERS
@@ -367,6 +511,12 @@ def encode_batch(images: Sequence, quality: int = 75, subsampling: str = "4:2:0"
         raise ValueError(f"restart_interval must be an int in 0..65535, got {restart_interval!r}")
     if isinstance(images, (torch.Tensor, np.ndarray)):
         raise ValueError("encode_batch takes a sequence of (H, W, 3) images; imwrite_device takes one")
+    if entropy not in ENTROPY:
+        raise ValueError(f"entropy must be one of {ENTROPY}, got {entropy!r}")
+    if entropy == "device":
+        if int(restart_interval) != 0:
+            raise ValueError("entropy='device' codes without restart intervals: restart_interval must be 0")
+        return _encode_batch_device(images, quality, subsampling, channel_order, device, staging)
     coefs = forward_batch(images, quality, subsampling, channel_order, device, staging, copy=False)  # (coded before staging is used again)
     if len(coefs) <= 1 or int(workers) <= 1:
         return [entropy_encode(c, restart_interval) for c in coefs]
@@ -374,8 +524,32 @@ def encode_batch(images: Sequence, quality: int = 75, subsampling: str = "4:2:0"
         return list(pool.map(lambda c: entropy_encode(c, restart_interval), coefs))
 
 
+def _encode_batch_device(images, quality, subsampling, channel_order, device, staging) -> List[bytes]:
+    """``encode_batch`` with both halves on the device: nine launches on the current stream, no coefficient copy."""
+    global forward_calls
+    from .transforms import BatchStaging
+
+    if channel_order not in ("bgr", "rgb"):
+        raise ValueError(f"channel_order must be 'bgr' or 'rgb', got {channel_order!r}")
+    qt = quality_tables(quality)
+    if subsampling not in SUBSAMPLING:
+        raise ValueError(f"subsampling must be one of {sorted(SUBSAMPLING)}, got {subsampling!r}")
+    images, dev = _encoder_images(list(images), device)
+    if len(images) == 0:
+        return []
+    staging = staging if staging is not None else BatchStaging()
+    args, _, keep, (ent_ptr, job) = _stage_encode(images, qt, subsampling, channel_order, dev, staging, entropy=True)
+    stream = torch.cuda.current_stream(dev)
+    _lib.call("pp_jpeg_forward_batch", *args, stream.cuda_stream)
+    forward_calls += 1
+    _entropy_launch(ent_ptr, job, stream)
+    files = _entropy_collect(job, [qt] * len(images), stream, staging)
+    del keep
+    return files
+
+
 def imwrite_device(path: str, image, **kw) -> None:
-    """One picture written as a baseline JPEG file by ``encode_batch`` (its keyword arguments)."""
+    """One picture written as a baseline JPEG file by ``encode_batch`` (its keyword arguments, ``entropy`` among them)."""
     data = encode_batch([image], **kw)[0]
     with open(path, "wb") as f:
         f.write(data)

@@ -206,21 +206,10 @@ class PoseLocalVisualizer:
             raise ValueError(f"unknown draw_type {draw_type!r}")
         return render_probability_areas(posterior, image_rgb, image_pad, boxes)
 
-    def add_datasample(self, name, image, data_sample, draw_gt=False, draw_bbox=True, draw_heatmap=False, kpt_thr=0.3,
-                       out_file=None, show_kpt_idx=False, skeleton_style="mmpose", show=False, wait_time=0, step=0):
-        """Draw the predictions of one merged sample on ``image`` ((H, W, 3) uint8 RGB, host array or device tensor). Returns
-        the (H, W, 3) pose panel, or with ``draw_heatmap`` (and heatmaps in ``pred_fields``) the (2H, W, 3) stack of the pose
-        panel over the probability areas resized to (H, W) (:796-865); ``out_file`` is written with Pillow - or, for a visualizer
-        built with ``image_encoder="device"`` and a ``.jpg`` / ``.jpeg`` name, by the split JPEG encoder from the frame on the
-        device (Pillow's default quality 75 and 4:2:0: a file that decodes to the same pixels)."""
-        if draw_gt:
-            raise NotImplementedError("draw_gt: ground-truth drawing is outside ProbPose's demo")
-        if show_kpt_idx:
-            raise NotImplementedError("show_kpt_idx: keypoint index text is not drawn")
-        if skeleton_style != "mmpose":
-            raise NotImplementedError(f"skeleton_style={skeleton_style!r}: only the 'mmpose' style is drawn")
-        if show:
-            raise NotImplementedError("show: no window system; use out_file or get_image()")
+    def draw_datasample(self, image, data_sample, draw_bbox=True, draw_heatmap=False, kpt_thr=0.3):
+        """The drawing half of ``add_datasample``: the predictions of one merged sample drawn on ``image`` ((H, W, 3) uint8
+        RGB, host array or device tensor), returned as the (H, W, 3) - with ``draw_heatmap`` and heatmaps in ``pred_fields``
+        (2H, W, 3) - uint8 RGB DEVICE tensor. No host copy, no file: a video loop hands it to ``jpeg.encode_batch``."""
         from .structures import _image_padding, posterior_heatmaps
 
         img = _as_device_image(image, self.device)
@@ -252,6 +241,25 @@ class PoseLocalVisualizer:
                 boxes = src.bboxes if "bboxes" in src else None
             panel = render_probability_areas(posterior, img, pad, boxes)
             resize_rgb(panel, (H, W), out=out[H:])
+        return out
+
+    def add_datasample(self, name, image, data_sample, draw_gt=False, draw_bbox=True, draw_heatmap=False, kpt_thr=0.3,
+                       out_file=None, show_kpt_idx=False, skeleton_style="mmpose", show=False, wait_time=0, step=0):
+        """Draw the predictions of one merged sample on ``image`` ((H, W, 3) uint8 RGB, host array or device tensor). Returns
+        the (H, W, 3) pose panel, or with ``draw_heatmap`` (and heatmaps in ``pred_fields``) the (2H, W, 3) stack of the pose
+        panel over the probability areas resized to (H, W) (:796-865); ``out_file`` is written with Pillow - or, for a visualizer
+        built with ``image_encoder="device"`` and a ``.jpg`` / ``.jpeg`` name, by the split JPEG encoder from the frame on the
+        device (Pillow's default quality 75 and 4:2:0: a file that decodes to the same pixels). ``draw_datasample`` plus the
+        copy to the host and the file."""
+        if draw_gt:
+            raise NotImplementedError("draw_gt: ground-truth drawing is outside ProbPose's demo")
+        if show_kpt_idx:
+            raise NotImplementedError("show_kpt_idx: keypoint index text is not drawn")
+        if skeleton_style != "mmpose":
+            raise NotImplementedError(f"skeleton_style={skeleton_style!r}: only the 'mmpose' style is drawn")
+        if show:
+            raise NotImplementedError("show: no window system; use out_file or get_image()")
+        out = self.draw_datasample(image, data_sample, draw_bbox=draw_bbox, draw_heatmap=draw_heatmap, kpt_thr=kpt_thr)
         self._image = out.cpu().numpy()
         if out_file is not None:
             if self.image_encoder == "device" and str(out_file).lower().endswith((".jpg", ".jpeg")):

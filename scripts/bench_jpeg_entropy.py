@@ -1,0 +1,127 @@
+"""Times of the device Huffman coder (csrc/pp_jpeg_entropy.hip) beside the host coder it can replace, on the seeded
+photo-like frames of scripts/bench_jpeg_encode.py (640x480 and 1920x1080, quality 75, 4:2:0), in ONE run with the two paths
+alternated and medians of --rounds:
+
+    entropy_call   pp_jpeg_entropy_encode_batch alone (its seven launches) in device-event time, n = 1 and n = 16, with the
+                   shader clock read right behind the timed launches;
+    encode_batch   jpeg.encode_batch to the file bytes in host memory, entropy="device" beside entropy="host" (the yardstick:
+                   the path as it was, measured in the same run), n = 1 and n = 16, at 1 and 8 workers;
+    video_demo     demo/video_demo.py on --frames full-HD frames (synthetic checkpoint, --decode device), frames per second of
+                   its loop with --entropy host and --entropy device (--demo-rounds alternations).
+
+One JSON line per figure.
+
+    python scripts/bench_jpeg_entropy.py [--rounds 7] [--frames 64] [--demo-rounds 3]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "demo"))
+from scripts.bench_jpeg_decode import photo_like  # noqa: E402
+from scripts.bench_jpeg_encode import shader_clock  # noqa: E402
+
+CFG = os.path.join(ROOT, "configs", "td-pm_ProbPose-small_mi355x_coco-256x192.py")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--frames", type=int, default=64)
+    ap.add_argument("--demo-rounds", type=int, default=3)
+    args = ap.parse_args()
+
+    import torch
+
+    from probpose_code_amd import _lib, jpeg
+    from probpose_code_amd.transforms import BatchStaging
+    from probpose_code_amd.video import MjpegAviWriter
+
+    dev = torch.device("cuda:0")
+    staging = BatchStaging()
+    hd_frames = None
+    for W, H in ((640, 480), (1920, 1080)):
+        rng = np.random.default_rng(W)
+        host_frames = [photo_like(rng, H, W) for _ in range(4)]
+        frames = [torch.from_numpy(host_frames[k % 4]).to(dev) for k in range(16)]
+        size = f"{W}x{H}"
+        if W == 1920:
+            hd_frames = frames
+        a = jpeg.encode_batch(frames[:4], channel_order="rgb", staging=staging, entropy="host")
+        b = jpeg.encode_batch(frames[:4], channel_order="rgb", staging=staging, entropy="device")
+        assert a == b, "the two coders disagree"
+        print(json.dumps(dict(figure="file", size=size, file_bytes=[len(f) for f in a])), flush=True)
+
+        for n in (1, 16):
+            qt = jpeg.quality_tables(75)
+            call_args, _, keep, (ent_ptr, job) = jpeg._stage_encode(frames[:n], qt, "4:2:0", "rgb", dev, staging, entropy=True)
+            stream = torch.cuda.current_stream(dev)
+            _lib.call("pp_jpeg_forward_batch", *call_args, stream.cuda_stream)
+            ent_args = (ent_ptr, n, max(int(i.coef_count) // 64 for i in job.infos), stream.cuda_stream)
+            for _ in range(3):
+                _lib.call("pp_jpeg_entropy_encode_batch", *ent_args)
+            torch.cuda.synchronize()
+            us = []
+            for _ in range(args.rounds):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                _lib.call("pp_jpeg_entropy_encode_batch", *ent_args)
+                e1.record()
+                e1.synchronize()
+                us.append(e0.elapsed_time(e1) * 1e3)
+            sclk = shader_clock()  # right behind the timed launches
+            res = job.results.cpu().numpy().view(jpeg._ENT_RESULT)
+            assert (res["status"] == 0).all()
+            print(json.dumps(dict(figure="entropy_call", size=size, n=n, device_event_us=round(statistics.median(us), 1), min_us=round(min(us), 1),
+                                  max_us=round(max(us), 1), rounds=args.rounds, stream_bytes=int(res["bytes"].sum()),
+                                  coefficient_bytes=int(sum(2 * int(i.coef_count) for i in job.infos)), sclk_mhz=sclk)), flush=True)
+            del keep, job
+
+        for n in (1, 16):
+            for workers in (1, 8):
+                paths = {e: (lambda e=e: jpeg.encode_batch(frames[:n], channel_order="rgb", workers=workers, staging=staging, entropy=e))
+                         for e in ("host", "device")}
+                times = {k: [] for k in paths}
+                for fn in paths.values():
+                    fn()  # warm-up
+                for _ in range(args.rounds):
+                    for name, fn in paths.items():
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        fn()
+                        torch.cuda.synchronize()
+                        times[name].append(time.perf_counter() - t0)
+                for name, ts in times.items():
+                    print(json.dumps(dict(figure="encode_batch", size=size, entropy=name, n=n, workers=workers, ms=round(statistics.median(ts) * 1e3, 3),
+                                          min_ms=round(min(ts) * 1e3, 3), max_ms=round(max(ts) * 1e3, 3), rounds=args.rounds)), flush=True)
+
+    if args.frames > 0:
+        import video_demo
+
+        with tempfile.TemporaryDirectory() as td:
+            src = os.path.join(td, "in.avi")
+            with MjpegAviWriter(src, 25) as w:
+                for k in range(0, args.frames, 16):
+                    for f in jpeg.encode_batch([hd_frames[(k + j) % 16] for j in range(min(16, args.frames - k))], channel_order="rgb", staging=staging):
+                        w.write(f)
+            fps = {"host": [], "device": []}
+            for _ in range(args.demo_rounds):
+                for e in fps:
+                    done = video_demo.main([src, CFG, "synthetic", "--out-video", os.path.join(td, f"out_{e}.avi"), "--decode", "device", "--entropy", e])
+                    fps[e].append(done["frames"] / done["seconds"])
+            same = open(os.path.join(td, "out_host.avi"), "rb").read() == open(os.path.join(td, "out_device.avi"), "rb").read()
+            for e, v in fps.items():
+                print(json.dumps(dict(figure="video_demo", size="1920x1080", frames=args.frames, entropy=e, frames_per_s=round(statistics.median(v), 1),
+                                      min=round(min(v), 1), max=round(max(v), 1), rounds=args.demo_rounds, outputs_equal=same, sclk_mhz=shader_clock())),
+                      flush=True)
+
+
+if __name__ == "__main__":
+    main()
