@@ -53,6 +53,8 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--decode", default="host", choices=["host", "device"],
                     help="device: a frame is Huffman-decoded on the host and reconstructed on the GPU (the same pixels)")
+    ap.add_argument("--decode-entropy", default="host", choices=["host", "device"],
+                    help="device (needs --decode device): a frame's Huffman codes are decoded on the GPU as well (the same pixels)")
     ap.add_argument("--entropy", default="host", choices=["host", "device"],
                     help="device: the drawn frames are Huffman-coded on the GPU as well (the same files)")
     ap.add_argument("--quality", type=int, default=75, help="JPEG quality of the written frames, 1..100")
@@ -78,6 +80,8 @@ def main(argv=None):
 
     if not 1 <= args.workers <= MAX_WORKERS:
         ap.error(f"--workers must be in 1..{MAX_WORKERS}")
+    if args.decode_entropy == "device" and args.decode != "device":
+        ap.error("--decode-entropy device needs --decode device")
     if args.depth < 1 or args.encode_batch < 1 or not 1 <= args.quality <= 100:
         ap.error("--depth and --encode-batch are at least 1, --quality is in 1..100")
     frames, fps = frame_source(args.input)
@@ -105,7 +109,7 @@ def main(argv=None):
 
     def decoded():
         for data in frames:
-            img = jpeg.imread_device(data, args.device) if args.decode == "device" else jpeg._host_decode(data)  # (H, W, 3) BGR
+            img = jpeg.imread_device(data, args.device, entropy=args.decode_entropy) if args.decode == "device" else jpeg._host_decode(data)  # (H, W, 3) BGR
             shown.append(img)
             yield img, boxes
 

@@ -894,6 +894,79 @@ long long pp_jpeg_entropy_scratch_bytes(const pp_jpeg_info* infos_host, int n);
  * outside an image's scratch share, out[0, capacity) and result slot. n == 0: PP_OK, nothing is launched. */
 int pp_jpeg_entropy_encode_batch(const pp_jpeg_ent_desc* descriptors, int n, long long max_blocks, void* stream);
 
+/* Huffman decoding on the device (csrc/pp_jpeg_huffdec.hip; added under version 4: purely additive): the coefficients
+ * pp_jpeg_entropy_decode gives, bit for bit, from the file's own entropy-coded bytes, by self-synchronising passes. The
+ * stream is cut into subsequences of 128 raw bytes, each decoded by one thread from a guessed state (bit position, block
+ * inside the MCU, zigzag index); a decoder started wrongly falls into step with the true one after a short distance, so
+ * passes that hand every subsequence its predecessor's exit state converge, and a final check proves it: an image is
+ * accepted only if every subsequence's entry equals its predecessor's exit. Files without a restart interval only; an
+ * image the passes did not synchronise is PP_ERR_UNSUPPORTED, never wrong data. */
+
+/* One Huffman table in the form the device reads (the host decoder's own lookup): look[next 9 bits] = length << 8 | symbol
+ * for codes of at most 9 bits (0: longer); maxcode[len] the largest code of a length (-1: none; [17] = INT32_MAX);
+ * vals[code + valoffset[len]] the symbol of a longer code. */
+typedef struct {
+    uint16_t look[512];
+    int32_t maxcode[18];
+    int32_t valoffset[18];
+    uint8_t vals[256];
+} pp_jpeg_huff_table;
+
+/* What pp_jpeg_scan_prepare reads from a file's headers: geometry, each component's quantisation table (natural order, as
+ * pp_jpeg_entropy_decode returns them), each component's tables (tables[2 c] DC, tables[2 c + 1] AC) and where the
+ * entropy-coded segment lies in the file: from behind the SOS header to the first marker, which must be EOI. */
+typedef struct {
+    pp_jpeg_info info;
+    uint16_t qtables[3 * 64];
+    pp_jpeg_huff_table tables[6];
+    int64_t stream_offset, stream_bytes;
+} pp_jpeg_scan;
+
+/* What the decoder leaves per image. status: PP_OK, PP_ERR_UNSUPPORTED (reason 1: not synchronised within sync_passes;
+ * 2: data ends before the last block; 3: a bit pattern that is no code, a category or a zigzag index no baseline stream
+ * holds; 4: a DC coefficient outside int16; 5: data after the last block) or PP_ERR_INVALID_ARG (reason 6: the
+ * descriptor describes no file of the subset). On any status but PP_OK the coefficients are undefined. passes: the
+ * synchronisation launches that were needed (1 + the last one in which a subsequence was decoded again); blocks: the
+ * blocks counted along the chain. */
+typedef struct {
+    int32_t status, passes, blocks, reason;
+} pp_jpeg_hd_result;
+
+/* One image of a batched Huffman decode (a device table of these drives every launch). stream / stream_bytes: the
+ * entropy-coded segment, byte stuffing included, only read (fewer than 2^28 bytes); tables: its 2 x ncomp
+ * pp_jpeg_huff_table, 4-byte aligned; coef: mcus_x * mcus_y * blocks-per-MCU * 64 int16 out in the layout of
+ * pp_jpeg_desc.coef, 16-byte aligned; scratch: the image's share of pp_jpeg_huffman_scratch_bytes, 16-byte aligned,
+ * contents undefined before and after; result: the image's slot. */
+typedef struct {
+    const uint8_t* stream;
+    const pp_jpeg_huff_table* tables;
+    int16_t* coef;
+    uint8_t* scratch;
+    pp_jpeg_hd_result* result;
+    int64_t stream_bytes;
+    int32_t hs, vs, mcus_x, mcus_y, ncomp, reserved;
+} pp_jpeg_hd_desc;
+
+/* Host only, re-entrant, no HIP call, no per-bit work: the headers of a file through the parser of pp_jpeg_probe, and the
+ * bounds of its entropy-coded segment by a search for FF bytes. PP_ERR_UNSUPPORTED with scan->info.reason: everything
+ * pp_jpeg_probe refuses, a file with a restart interval (it keeps the host Huffman decoder), a segment that no EOI marker
+ * ends, a segment of 2^28 bytes or more. */
+int pp_jpeg_scan_prepare(const void* data_host, size_t size, pp_jpeg_scan* scan);
+/* Host only. Bytes of scratch for n images with segments of stream_bytes_host[i] bytes (infos_host: their pp_jpeg_info),
+ * each image's share a multiple of 256: image i's share starts at the sum of the shares before it. < 0: error. */
+long long pp_jpeg_huffman_scratch_bytes(const pp_jpeg_info* infos_host, const long long* stream_bytes_host, int n);
+/* The coefficients of n images of any mix of sizes and sampling in sync_passes + 4 launches (sync_passes x "jpeg_hd_sync",
+ * "jpeg_hd_scan", "jpeg_hd_zero", "jpeg_hd_write", "jpeg_hd_dc" of pp_launch_count). descriptors: n pp_jpeg_hd_desc on
+ * the device; max_stream_bytes / max_blocks: the longest segment and the largest block count in the table - they size the
+ * grids, every image is bounded by its own entry. sync_passes: 1 .. 64; a launch carries states 32 subsequences on inside
+ * a workgroup's 256 and one across its border, so p launches cover a synchronisation distance of 128 (32 (p - 1) + 2)
+ * bytes (p = 3: 8448). No allocation, no synchronisation, no read-back: the caller reads the result slots after the
+ * stream has run. An image's failure leaves the others untouched; nothing is written outside an image's scratch share,
+ * its coefficients and its result slot; the same input gives the same bytes launch after launch. n == 0: PP_OK, nothing
+ * is launched. */
+int pp_jpeg_huffman_decode_batch(const pp_jpeg_hd_desc* descriptors, int n, long long max_stream_bytes, long long max_blocks,
+                                 int sync_passes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,21 +157,24 @@ def _val_pipeline(model) -> T.Compose:
     return pipe
 
 
-def use_device_decode(model, on: bool = True) -> None:
+def use_device_decode(model, on: bool = True, entropy: str = "host") -> None:
     """Switch the ``LoadImage`` of the model's val pipeline to ``imdecode_backend="mi355x"`` (files decoded on the device,
-    ``jpeg.imread_device``) or back to the host decoder: what ``--decode device`` of the demo does."""
+    ``jpeg.imread_device``) or back to the host decoder: what ``--decode device`` of the demo does. ``entropy="device"``:
+    ``"mi355x-huffman"``, the Huffman codes decoded on the device as well (``--decode-entropy device``)."""
+    if entropy not in ("host", "device"):
+        raise ValueError(f'entropy must be "host" or "device", got {entropy!r}')
     for t in _val_pipeline(model).transforms:
         if isinstance(t, T.LoadImage):
-            t.imdecode_backend = "mi355x" if on else "cv2"
+            t.imdecode_backend = ("mi355x-huffman" if entropy == "device" else "mi355x") if on else "cv2"
 
 
 def _load_frame(pipeline, path: str):
     """A file for ``inference_topdown``: through the decoder the pipeline's ``LoadImage`` names."""
     for t in pipeline.transforms:
-        if isinstance(t, T.LoadImage) and t.imdecode_backend == "mi355x":
+        if isinstance(t, T.LoadImage) and t.imdecode_backend in ("mi355x", "mi355x-huffman"):
             from .jpeg import imread_device
 
-            return imread_device(path, t.device or "cuda")
+            return imread_device(path, t.device or "cuda", entropy="device" if t.imdecode_backend == "mi355x-huffman" else "host")
     return load_image_bgr(path)
 
 

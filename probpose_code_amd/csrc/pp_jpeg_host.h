@@ -8,6 +8,11 @@
 // tables; restart intervals. Everything else - and every irregularity of the stream - is PP_ERR_UNSUPPORTED with a reason:
 // the caller then decodes the file with the host decoder it used before. Nothing is guessed, no partial image is returned.
 // Every read of the input is checked against `size`, every write against the caller's capacities.
+//
+// scan_prepare (pp_jpeg_scan_prepare) is the host's share when the Huffman codes are decoded on the device as well
+// (csrc/pp_jpeg_huffdec.hip): the same header parser, the components' tables in the form the device reads, and the bounds of
+// the entropy-coded segment by a search for FF bytes - no bit of it is decoded here. It refuses what the parser refuses,
+// files with a restart interval (they keep entropy_decode) and a segment that no EOI marker ends.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -48,6 +53,7 @@ struct HuffTable {
 // Canonical table from the 16 counts and the symbols (ITU T.81 annex C). False: counts that no prefix code has.
 inline bool build_huff(HuffTable& h, const uint8_t* counts, const uint8_t* symbols, int n_symbols) {
     std::memset(h.look, 0, sizeof(h.look));
+    std::memset(h.vals, 0, sizeof(h.vals));  // (scan_prepare copies the whole table)
     std::memcpy(h.vals, symbols, (size_t)n_symbols);
     int32_t code = 0, k = 0;
     for (int len = 1; len <= 16; ++len) {
@@ -384,6 +390,49 @@ inline int entropy_decode(const uint8_t* data, size_t size, int16_t* coef, long 
     if (p >= size || data[p] != 0xFF) return refuse(info, "no EOI after the scan");
     while (p < size && data[p] == 0xFF) ++p;
     if (p >= size || data[p] != 0xD9) return refuse(info, "no EOI after the scan (several scans?)");
+    return PP_OK;
+}
+
+// pp_jpeg_scan_prepare: what the device Huffman decoder (csrc/pp_jpeg_huffdec.hip) needs of a file, read from its headers.
+// No bit of the entropy-coded segment is decoded here: its end is the first FF that no 00 follows, and the marker there
+// must be EOI (what entropy_decode demands behind the last MCU).
+inline int scan_prepare(const uint8_t* data, size_t size, pp_jpeg_scan* scan) {
+    if (!data || !scan) {
+        std::snprintf(g_reason, sizeof(g_reason), "NULL argument");
+        return PP_ERR_INVALID_ARG;
+    }
+    std::memset(scan, 0, sizeof(*scan));
+    pp_jpeg_info* info = &scan->info;
+    Header h;
+    const int st = parse_header(data, size, h, info);
+    if (st != PP_OK) return st;
+    fill_info(h, info);
+    if (h.restart_interval != 0) return refuse(info, "restart interval: the device Huffman decoder takes files without one");
+    for (int c = 0; c < h.ncomp; ++c) {
+        std::memcpy(scan->qtables + 64 * c, h.q[h.comp[c].tq], 64 * sizeof(uint16_t));
+        const HuffTable* src[2] = {&h.dc[h.comp[c].td], &h.ac[h.comp[c].ta]};
+        for (int t = 0; t < 2; ++t) {
+            pp_jpeg_huff_table& dst = scan->tables[2 * c + t];
+            std::memcpy(dst.look, src[t]->look, sizeof(dst.look));
+            std::memcpy(dst.vals, src[t]->vals, sizeof(dst.vals));
+            for (int len = 1; len <= 17; ++len) dst.maxcode[len] = src[t]->maxcode[len];
+            for (int len = 1; len <= 16; ++len) dst.valoffset[len] = src[t]->valoffset[len];
+        }
+    }
+    size_t end = h.scan_pos;
+    for (;;) {
+        const void* ff = end < size ? std::memchr(data + end, 0xFF, size - end) : nullptr;
+        if (!ff) return refuse(info, "no EOI after the scan");
+        end = (size_t)(reinterpret_cast<const uint8_t*>(ff) - data);
+        if (end + 1 < size && data[end + 1] == 0x00) end += 2;  // a stuffed data byte
+        else break;
+    }
+    size_t p = end;
+    while (p < size && data[p] == 0xFF) ++p;
+    if (p >= size || data[p] != 0xD9) return refuse(info, "no EOI after the scan (several scans?)");
+    if (end - h.scan_pos >= ((size_t)1 << 28)) return refuse(info, "entropy-coded segment of 2^28 bytes or more");
+    scan->stream_offset = (int64_t)h.scan_pos;
+    scan->stream_bytes = (int64_t)(end - h.scan_pos);
     return PP_OK;
 }
 

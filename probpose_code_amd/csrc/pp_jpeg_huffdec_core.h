@@ -1,0 +1,300 @@
+// The decode core of the device Huffman decoder (csrc/pp_jpeg_huffdec.hip), shared with its sequential host restatement
+// (scripts/jpeg_huffdec_host_check.cpp): the bit reader over a byte-stuffed stream, the decoder state, one subsequence's
+// decode and the addressing of a block. Plain C++ that compiles for host and device; nothing here touches the GPU.
+//
+// The entropy-coded segment is cut into subsequences of HD_S raw bytes. A decoder state is (raw bit position, block index
+// inside the MCU, zigzag index: 0 = the DC symbol is due). A position counts raw bits, stuffed bytes included, and is
+// canonical: it never points into a stuffed 00 (a 00 whose predecessor is FF) but at the byte behind it, so two decoders at
+// the same place hold the same state whichever side of a subsequence boundary the FF lies on. Past the stream's length the
+// reader supplies zeros. Every symbol consumes at least one bit; a bit pattern that is no code consumes exactly one and
+// leaves the rest of the state alone. Whatever no valid stream holds - such a pattern, a DC category above 11, an AC
+// category above 10, a zigzag index past 63 - is decoded by a fixed rule and reported in `bad`: a speculative decoder meets
+// these legitimately, on the true chain they refuse the image.
+#pragma once
+#include <cstdint>
+
+#include "../../include/probpose_mi355x.h"
+
+#if defined(__HIPCC__)
+#define PP_HD_FN __host__ __device__ __forceinline__
+#else
+#define PP_HD_FN inline
+#endif
+namespace pp {
+namespace hd {
+
+constexpr int HD_S = 128;          // raw bytes per subsequence: one per thread
+constexpr int HD_WG = 256;         // subsequences per workgroup
+constexpr int HD_INNER = 32;       // iterations a workgroup makes over its own subsequences per synchronisation launch
+constexpr int HD_MAX_PASSES = 64;  // largest sync_passes
+constexpr int HD_DEFAULT_PASSES = 3;  // covers ((3 - 1) * HD_INNER + 2) * HD_S = 8448 bytes of synchronisation distance
+constexpr long long HD_MAX_STREAM = 1ll << 28;  // bytes: bit positions stay below 2^31
+constexpr int HD_LOOK_BITS = 9;
+constexpr int HD_TABLE_WORDS = (int)(sizeof(pp_jpeg_huff_table) / 4);
+
+// reasons of a result slot (pp_jpeg_hd_result.reason)
+enum { HD_OK = 0, HD_NOT_SYNCHRONISED = 1, HD_ENDS_EARLY = 2, HD_BAD_CODE = 3, HD_DC_RANGE = 4, HD_TRAILING = 5, HD_BAD_DESC = 6 };
+// bits of `bad`
+enum { BAD_CODE = 1u, BAD_CATEGORY = 2u, BAD_INDEX = 4u, BAD_DC_RANGE = 8u };
+
+// zigzag position -> natural (row-major) position
+PP_HD_FN int natural_of(int k) {
+    constexpr uint8_t t[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                               41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                               30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+    return t[k & 63];
+}
+
+struct State {
+    uint32_t pos;  // raw bit position
+    uint32_t bk;   // block inside the MCU << 8 | zigzag index
+};
+PP_HD_FN bool same(State a, State b) { return a.pos == b.pos && a.bk == b.bk; }
+
+struct Stream {
+    const uint8_t* d;
+    long long len;
+};
+PP_HD_FN uint32_t byte_at(const Stream& s, long long i) { return i < s.len ? (uint32_t)s.d[i] : 0u; }
+PP_HD_FN bool stuffed(const Stream& s, long long i) { return i > 0 && i < s.len && s.d[i] == 0 && s.d[i - 1] == 0xFF; }
+PP_HD_FN uint32_t canonical(const Stream& s, uint32_t pos) {
+    const long long b = (long long)(pos >> 3);
+    return stuffed(s, b) ? (uint32_t)((b + 1) << 3) : pos;
+}
+
+// What a descriptor's numbers say: blocks per MCU, luma blocks per MCU, blocks of the scan; valid = 0 for a descriptor that
+// describes no file of the subset.
+struct Geometry {
+    int valid, bpm, lum;
+    long long nblk, mcus;
+};
+PP_HD_FN Geometry geometry(const pp_jpeg_hd_desc& d) {
+    Geometry g{0, 1, 1, 0, 0};
+    const bool sampling = d.ncomp == 1 ? (d.hs == 1 && d.vs == 1)
+                                       : (d.ncomp == 3 && ((d.hs == 1 && d.vs == 1) || (d.hs == 2 && d.vs == 1) || (d.hs == 2 && d.vs == 2)));
+    if (!sampling || d.mcus_x < 1 || d.mcus_y < 1 || d.mcus_x > 8192 || d.mcus_y > 8192 || !d.stream || !d.tables || !d.coef || !d.scratch ||
+        !d.result || d.stream_bytes < 0 || d.stream_bytes >= HD_MAX_STREAM || ((uintptr_t)d.coef & 15) || ((uintptr_t)d.scratch & 15) ||
+        ((uintptr_t)d.tables & 3) || ((uintptr_t)d.result & 3))
+        return g;
+    g.valid = 1;
+    g.lum = d.hs * d.vs;
+    g.bpm = d.ncomp == 1 ? 1 : g.lum + 2;
+    g.mcus = (long long)d.mcus_x * d.mcus_y;
+    g.nblk = g.mcus * g.bpm;
+    return g;
+}
+
+// An image's share of scratch: byte offsets of its regions.
+struct Layout {
+    long long nsub, nwg, o_entry, o_exit, o_cnt, o_first, o_bexit, o_open, total;
+};
+PP_HD_FN long long align16(long long v) { return (v + 15) / 16 * 16; }
+PP_HD_FN Layout layout(long long stream_bytes) {
+    Layout L;
+    L.nsub = stream_bytes > 0 ? (stream_bytes + HD_S - 1) / HD_S : 1;
+    L.nwg = (L.nsub + HD_WG - 1) / HD_WG;
+    L.o_entry = 64;
+    L.o_exit = L.o_entry + 8 * L.nsub;
+    L.o_cnt = L.o_exit + 8 * L.nsub;
+    L.o_first = align16(L.o_cnt + 4 * L.nsub);
+    L.o_bexit = align16(L.o_first + 4 * L.nsub);
+    L.o_open = align16(L.o_bexit + 2 * 8 * L.nwg);
+    L.total = (L.o_open + 4 * L.nwg + 255) / 256 * 256;
+    return L;
+}
+
+struct Header {  // first 64 bytes of the share
+    uint32_t passes, flags, synced, total, endpos, done;
+};
+
+// Index in d.coef (in blocks) of block g of the scan; component <- 0 luma, 1 Cb, 2 Cr.
+PP_HD_FN long long block_index(const pp_jpeg_hd_desc& d, const Geometry& G, long long g, int& comp) {
+    const long long mcu = g / G.bpm;
+    const int j = (int)(g - mcu * G.bpm);
+    if (j < G.lum) {
+        comp = 0;
+        const long long my = mcu / d.mcus_x, mx = mcu - my * d.mcus_x;
+        return (my * d.vs + j / d.hs) * ((long long)d.mcus_x * d.hs) + mx * d.hs + j % d.hs;
+    }
+    comp = 1 + j - G.lum;
+    return G.mcus * G.lum + (long long)(j - G.lum) * G.mcus + mcu;  // a chroma plane is one block per MCU, in MCU order
+}
+
+// Index in d.coef (in blocks) of block k of component c in scan order (what the DC prefix sums walk).
+PP_HD_FN long long component_block(const pp_jpeg_hd_desc& d, const Geometry& G, int c, long long k) {
+    if (c > 0) return G.mcus * G.lum + (long long)(c - 1) * G.mcus + k;
+    const long long mcu = k / G.lum;
+    const int j = (int)(k - mcu * G.lum);
+    const long long my = mcu / d.mcus_x, mx = mcu - my * d.mcus_x;
+    return (my * d.vs + j / d.hs) * ((long long)d.mcus_x * d.hs) + mx * d.hs + j % d.hs;
+}
+
+// MSB-first reader from a raw bit position on. `limit`: the data bits loaded before the first data byte at or behind raw
+// byte `end_byte`, known as soon as that byte is loaded - the subsequence is done when consumed() reaches it.
+struct Reader {
+    Stream s;
+    long long next, end_byte;
+    uint64_t acc = 0;
+    uint32_t prev;  // the raw byte in front of `next` (what makes a 00 a stuffed one)
+    int n = 0, loaded = 0, limit = 0x7fffffff;
+    PP_HD_FN Reader(const Stream& s_, uint32_t pos, long long end_byte_)
+        : s(s_), next((long long)(pos >> 3)), end_byte(end_byte_), prev(pos >> 3 ? byte_at(s_, (long long)(pos >> 3) - 1) : 0u) {
+        fill();
+        n -= (int)(pos & 7);
+    }
+    PP_HD_FN void fill() {  // at least 57 bits afterwards; skips exactly the bytes stuffed() names
+        while (n <= 56) {
+            uint32_t b = byte_at(s, next);
+            if (b == 0u && prev == 0xFFu && next < s.len) b = byte_at(s, ++next);
+            if (next >= end_byte && limit == 0x7fffffff) limit = loaded;
+            acc = (acc << 8) | b;
+            prev = b;
+            ++next;
+            n += 8;
+            loaded += 8;
+        }
+    }
+    PP_HD_FN uint32_t peek(int k) const { return (uint32_t)(acc >> (n - k)) & ((1u << k) - 1u); }  // k <= 16
+    PP_HD_FN int consumed() const { return loaded - n; }
+    PP_HD_FN uint32_t position() const {  // of the next unread bit: walk back over the bytes still held
+        long long j = next;
+        for (int b = (n + 7) >> 3; b > 0; --b) {
+            --j;
+            if (stuffed(s, j)) --j;
+        }
+        return (uint32_t)(j * 8 + ((8 - (n & 7)) & 7));
+    }
+};
+
+// One symbol of table t, -1: no such code (nothing consumed).
+PP_HD_FN int symbol(Reader& r, const pp_jpeg_huff_table& t) {
+    const uint32_t e = t.look[r.peek(HD_LOOK_BITS)];
+    const int len9 = (int)(e >> 8);
+    if (len9 >= 1 && len9 <= HD_LOOK_BITS) {
+        r.n -= len9;
+        return (int)(e & 255u);
+    }
+    for (int len = HD_LOOK_BITS + 1; len <= 16; ++len) {
+        const int32_t code = (int32_t)r.peek(len);
+        if (code <= t.maxcode[len]) {
+            const int32_t idx = code + t.valoffset[len];
+            if (idx < 0 || idx > 255) return -1;
+            r.n -= len;
+            return t.vals[idx];
+        }
+    }
+    return -1;
+}
+
+PP_HD_FN int receive_extend(Reader& r, int s) {  // 1 <= s <= 15
+    const int v = (int)r.peek(s);
+    r.n -= s;
+    return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
+}
+
+struct CountSink {
+    uint32_t blocks = 0;
+    PP_HD_FN void coef(int, int) {}
+    PP_HD_FN void block_done() { ++blocks; }
+    PP_HD_FN bool stop() const { return false; }
+};
+
+// Stores every coefficient at kNatural[k] of its block; stops behind the image's last block. Every store is checked.
+struct WriteSink {
+    const pp_jpeg_hd_desc& d;
+    const Geometry& G;
+    long long g, base = -1;
+    bool finished = false;
+    PP_HD_FN WriteSink(const pp_jpeg_hd_desc& d_, const Geometry& G_, long long first) : d(d_), G(G_), g(first) {}
+    PP_HD_FN void coef(int k, int v) {
+        if (g >= G.nblk) return;
+        if (base < 0) {
+            int comp;
+            base = block_index(d, G, g, comp) * 64;
+        }
+        if (base >= 0 && base + 64 <= G.nblk * 64) d.coef[base + natural_of(k)] = (int16_t)v;
+    }
+    PP_HD_FN void block_done() {
+        ++g;
+        base = -1;
+        if (g >= G.nblk) finished = true;
+    }
+    PP_HD_FN bool stop() const { return g >= G.nblk; }
+};
+
+// tabs: the image's 2 * ncomp tables (DC, AC of component 0, 1, 2). Decodes from `in` to the first symbol boundary at or
+// behind raw byte `end_byte` (or until the sink stops). At most 8 HD_S + 64 symbols: bounded whatever the data.
+template <class Sink>
+PP_HD_FN State run(const Stream& st, const pp_jpeg_huff_table* tabs, State in, long long end_byte, const Geometry& G, Sink& sink, uint32_t& bad) {
+    Reader r(st, in.pos, end_byte);
+    int blk = (int)(in.bk >> 8), k = (int)(in.bk & 255u);
+    if (blk >= G.bpm) blk = 0;
+    if (k > 63) k = 0;
+    for (int it = 0; it < 8 * HD_S + 64; ++it) {
+        r.fill();
+        if (r.consumed() >= r.limit || sink.stop()) break;
+        const int comp = blk < G.lum ? 0 : 1 + blk - G.lum;
+        const int sym = symbol(r, tabs[2 * comp + (k > 0 ? 1 : 0)]);
+        if (sym < 0) {
+            r.n -= 1;
+            bad |= BAD_CODE;
+            continue;
+        }
+        bool end = false;
+        if (k == 0) {
+            int s = sym;
+            if (s > 11) {
+                bad |= BAD_CATEGORY;
+                s = 0;
+            }
+            sink.coef(0, s ? receive_extend(r, s) : 0);
+            k = 1;
+        } else {
+            const int rr = sym >> 4, s = sym & 15;
+            if (s == 0) {
+                if (rr == 15) {
+                    k += 16;
+                    if (k > 63) {
+                        bad |= BAD_INDEX;
+                        end = true;
+                    }
+                } else {
+                    end = true;
+                }
+            } else {
+                k += rr;
+                if (k > 63) {
+                    bad |= BAD_INDEX;
+                    end = true;
+                } else {
+                    if (s > 10) bad |= BAD_CATEGORY;
+                    sink.coef(k, receive_extend(r, s));
+                    if (++k == 64) end = true;
+                }
+            }
+        }
+        if (end) {
+            sink.block_done();
+            blk = blk + 1 == G.bpm ? 0 : blk + 1;
+            k = 0;
+        }
+    }
+    return State{r.position(), ((uint32_t)blk << 8) | (uint32_t)k};
+}
+
+// The result slot of an image from what the launches left in its header: the host decoder's verdict. The bits in front of
+// the EOI marker are those behind the last block, less a stuffed 00 that ends the segment (the last data byte was FF).
+PP_HD_FN pp_jpeg_hd_result verdict(const Stream& st, const Geometry& G, const Header& h, bool range_bad) {
+    pp_jpeg_hd_result r{PP_OK, (int32_t)h.passes + 1, (int32_t)h.total, HD_OK};
+    const long long bits = st.len * 8, data_bits = bits - (stuffed(st, st.len - 1) ? 8 : 0);
+    if (!h.synced) r.reason = HD_NOT_SYNCHRONISED;
+    else if ((long long)h.total < G.nblk || !h.done || (long long)h.endpos > bits) r.reason = HD_ENDS_EARLY;
+    else if (h.flags) r.reason = HD_BAD_CODE;
+    else if (range_bad) r.reason = HD_DC_RANGE;
+    else if (data_bits - (long long)h.endpos >= 8) r.reason = HD_TRAILING;
+    if (r.reason != HD_OK) r.status = PP_ERR_UNSUPPORTED;
+    return r;
+}
+
+}  // namespace hd
+}  // namespace pp

@@ -21,6 +21,14 @@ of demo/image_demo.py.
 seven launches behind the forward call's two, on the same stream): the coefficients never leave the device, the host
 receives the finished streams and puts ``pp_jpeg_write_headers``' bytes in front and ``FF D9`` behind. The files are byte
 for byte those of the host coder. Restart interval 0 only; the default stays ``entropy="host"``.
+
+``decode_batch(..., entropy="device")`` decodes the Huffman codes on the device as well (``pp_jpeg_huffman_decode_batch``,
+csrc/pp_jpeg_huffdec.hip: ``sync_passes`` + 4 launches in front of the reconstruct call's two, on the same stream): the host
+only reads the headers (``scan_prepare``), a file goes up as its own bytes and the coefficients never cross the bus. The
+stream is decoded in subsequences of 128 bytes by self-synchronising passes; an image the passes did not synchronise, or
+whose stream is damaged, is refused by its result slot - never decoded wrongly - and goes through ``entropy_decode``.
+Files with a restart interval keep the host Huffman decoder. The pixels are those of ``entropy="host"``, which stays
+the default.
 """
 import ctypes
 from typing import List, NamedTuple, Optional, Sequence, Union
@@ -34,6 +42,8 @@ fallbacks = 0  # files imread_device / the test loop handed to the host decoder 
 reconstruct_calls = 0  # pp_jpeg_reconstruct_bgr_batch calls since import
 forward_calls = 0  # pp_jpeg_forward_batch calls since import
 entropy_device_calls = 0  # pp_jpeg_entropy_encode_batch calls since import
+huffman_device_calls = 0  # pp_jpeg_huffman_decode_batch calls since import
+unsynchronised = 0  # images the device Huffman decoder refused by their result slot since import (each also counts in fallbacks)
 
 
 class JpegInfo(ctypes.Structure):
@@ -59,6 +69,36 @@ assert _ENT_DESC.itemsize == 64
 _ENT_RESULT = np.dtype([("bytes", "<i8"), ("status", "<i4"), ("reserved", "<i4")])
 assert _ENT_RESULT.itemsize == 16
 ENTROPY = ("host", "device")
+
+
+class HuffTable(ctypes.Structure):
+    """pp_jpeg_huff_table of include/probpose_mi355x.h."""
+    _fields_ = [("look", ctypes.c_uint16 * 512), ("maxcode", ctypes.c_int32 * 18), ("valoffset", ctypes.c_int32 * 18),
+                ("vals", ctypes.c_uint8 * 256)]
+
+
+class _Scan(ctypes.Structure):
+    """pp_jpeg_scan of include/probpose_mi355x.h."""
+    _fields_ = [("info", JpegInfo), ("qtables", ctypes.c_uint16 * 192), ("tables", HuffTable * 6), ("stream_offset", ctypes.c_int64),
+                ("stream_bytes", ctypes.c_int64)]
+
+
+TABLE_BYTES = ctypes.sizeof(HuffTable)
+assert TABLE_BYTES == 1424
+# pp_jpeg_hd_desc: five pointers, the stream's length, six int32; pp_jpeg_hd_result
+_HD_DESC = np.dtype([("stream", "<u8"), ("tables", "<u8"), ("coef", "<u8"), ("scratch", "<u8"), ("result", "<u8"), ("stream_bytes", "<i8"),
+                     ("hs", "<i4"), ("vs", "<i4"), ("mcus_x", "<i4"), ("mcus_y", "<i4"), ("ncomp", "<i4"), ("reserved", "<i4")])
+assert _HD_DESC.itemsize == 72
+_HD_RESULT = np.dtype([("status", "<i4"), ("passes", "<i4"), ("blocks", "<i4"), ("reason", "<i4")])
+assert _HD_RESULT.itemsize == 16
+SUBSEQUENCE_BYTES = 128  # HD_S of csrc/pp_jpeg_huffdec_core.h
+INNER_ITERATIONS = 32  # HD_INNER
+MAX_SYNC_PASSES = 64
+# p launches carry a decoder state over 32 (p - 1) + 2 subsequences: 3 launches cover 8448 bytes, above the 8 KiB the default is to cover
+DEFAULT_SYNC_PASSES = 3
+assert SUBSEQUENCE_BYTES * (INNER_ITERATIONS * (DEFAULT_SYNC_PASSES - 1) + 2) >= 8192
+HD_REASONS = {0: "", 1: "not synchronised", 2: "data ends before the last MCU", 3: "bad Huffman code, category or coefficient index",
+              4: "DC coefficient out of range", 5: "data after the last MCU", 6: "descriptor outside the subset"}
 SUBSAMPLING = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}  # pp_jpeg_encode_plan's numbering (Pillow's as well)
 
 
@@ -119,8 +159,190 @@ def entropy_decode(data) -> JpegCoefficients:
     return JpegCoefficients(info, coef, qt[:int(info.ncomp)])
 
 
+class JpegScan(NamedTuple):
+    """What ``scan_prepare`` reads from a file's headers: ``info`` (geometry), ``qtables`` (ncomp, 64) uint16 in natural order,
+    ``tables`` (the 2 x ncomp ``pp_jpeg_huff_table`` of the components as uint8: DC, AC of each), ``stream`` (the entropy-coded
+    segment, byte stuffing included, a uint8 view of ``data``) and ``data`` (the file's bytes)."""
+
+    info: JpegInfo
+    qtables: np.ndarray
+    tables: np.ndarray
+    stream: np.ndarray
+    data: bytes
+
+    @property
+    def shape(self):
+        return (int(self.info.height), int(self.info.width), 3)
+
+
+def scan_prepare(data) -> JpegScan:
+    """The host's share of ``entropy="device"``: the headers of a file (bytes or a path) and the bounds of its entropy-coded
+    segment; no bit of it is decoded. Thread-safe and GIL-free. Raises ``JpegUnsupported`` for what ``entropy_decode`` refuses
+    by the headers, for a file with a restart interval and for a segment no EOI marker ends."""
+    raw = _bytes_of(data)
+    scan = _Scan()
+    st = _lib.lib.pp_jpeg_scan_prepare(raw, len(raw), ctypes.byref(scan))
+    if st == _lib.PP_ERR_UNSUPPORTED:
+        raise JpegUnsupported(scan.info.reason.decode("utf-8", "replace"))
+    _lib.check("pp_jpeg_scan_prepare", st)
+    ncomp = int(scan.info.ncomp)
+    info = JpegInfo.from_buffer_copy(scan.info)
+    qt = np.frombuffer(scan, np.uint16, 64 * ncomp, _Scan.qtables.offset).reshape(ncomp, 64).copy()
+    tables = np.frombuffer(scan, np.uint8, 2 * ncomp * TABLE_BYTES, _Scan.tables.offset).copy()
+    stream = np.frombuffer(raw, np.uint8, int(scan.stream_bytes), int(scan.stream_offset))
+    return JpegScan(info, qt, tables, stream, raw)
+
+
 def _align(v: int, a: int = 256) -> int:
     return (v + a - 1) // a * a
+
+
+class _HuffmanJob(NamedTuple):
+    """The device buffers of one ``pp_jpeg_huffman_decode_batch`` call: ``coef`` (image i's int16 coefficients, views of one
+    tensor), ``results`` (n x 16 bytes, a view of the uploaded block), ``desc_ptr`` / ``args`` (the call's arguments),
+    ``recon`` (the arguments of ``pp_jpeg_reconstruct_bgr_batch`` on the same coefficients and its output tensors, or None)
+    and ``keep`` (every tensor the launches use)."""
+
+    coef: list
+    results: torch.Tensor
+    args: tuple
+    recon: Optional[tuple]
+    keep: tuple
+
+
+def _sync_passes(sync_passes) -> int:
+    p = DEFAULT_SYNC_PASSES if sync_passes is None else sync_passes
+    if isinstance(p, bool) or not isinstance(p, (int, np.integer)) or not 1 <= int(p) <= MAX_SYNC_PASSES:
+        raise ValueError(f"sync_passes must be an int in 1..{MAX_SYNC_PASSES}, got {sync_passes!r}")
+    return int(p)
+
+
+def _stage_huffman(scans: Sequence[JpegScan], device, staging, sync_passes: int, reconstruct: bool) -> _HuffmanJob:
+    """Pack the descriptor tables, the Huffman and quantisation tables and the streams of a batch into the pinned buffer and
+    upload them with one copy. ``reconstruct``: the descriptors of ``pp_jpeg_reconstruct_bgr_batch`` travel in the same copy
+    and point at the coefficients where the decoder leaves them."""
+    n = len(scans)
+    infos = (JpegInfo * n)(*[s.info for s in scans])
+    lens = (ctypes.c_longlong * n)(*[int(s.stream.size) for s in scans])
+    shares = []
+    for i in range(n):
+        one = int(_lib.lib.pp_jpeg_huffman_scratch_bytes(ctypes.byref(infos[i]), ctypes.byref(lens, 8 * i), 1))
+        if one < 0:
+            raise _lib.ProbPoseLibraryError("pp_jpeg_huffman_scratch_bytes", _lib.lib.pp_status_string(one).decode(), _lib.last_error())
+        shares.append(one)
+    # the block: decoder descriptors (n x 72 bytes) | result slots (n x 16) | reconstruct descriptors (n x 64) | per image:
+    # Huffman tables, quantisation tables (3 x 64 u16), stream bytes
+    o_res = _align(72 * n)
+    o_rec = _align(o_res + 16 * n)
+    off, o_tab, o_qt, o_str = _align(o_rec + 64 * n), [], [], []
+    for s in scans:
+        o_tab.append(off)
+        off = _align(off + s.tables.size)
+        o_qt.append(off)
+        off = _align(off + 384)
+        o_str.append(off)
+        off = _align(off + max(int(s.stream.size), 1))
+    total = off
+    counts = [int(s.info.coef_count) for s in scans]
+    o_coef, at = [], 0
+    for c in counts:
+        o_coef.append(at)
+        at += _align(2 * c) // 2
+    coef_all = torch.empty(max(at, 1), dtype=torch.int16, device=device)
+    scratch = torch.empty(sum(shares), dtype=torch.uint8, device=device)
+    block = torch.empty(total, dtype=torch.uint8, device=device)
+    planes = torch.empty(sum(_align(c) for c in counts), dtype=torch.uint8, device=device) if reconstruct else None
+    out = [torch.empty(s.shape, dtype=torch.uint8, device=device) for s in scans] if reconstruct else None
+    blk = staging.acquire(total)
+    desc = blk[:72 * n].view(_HD_DESC)
+    rec = blk[o_rec:o_rec + 64 * n].view(_DESC)
+    blk[o_res:o_res + 16 * n] = 0
+    base, s_at, p_at = block.data_ptr(), scratch.data_ptr(), (planes.data_ptr() if reconstruct else 0)
+    for i, s in enumerate(scans):
+        info = s.info
+        if s.tables.size != 2 * int(info.ncomp) * TABLE_BYTES or s.tables.dtype != np.uint8 or s.stream.dtype != np.uint8:
+            raise ValueError("a JpegScan holds 2 x ncomp tables and its stream as uint8")
+        blk[o_tab[i]:o_tab[i] + s.tables.size] = s.tables
+        blk[o_qt[i]:o_qt[i] + 128 * len(s.qtables)].view(np.uint16)[:] = s.qtables.reshape(-1)
+        blk[o_str[i]:o_str[i] + s.stream.size] = s.stream
+        coef_ptr = coef_all.data_ptr() + 2 * o_coef[i]
+        desc[i] = (base + o_str[i], base + o_tab[i], coef_ptr, s_at, base + o_res + 16 * i, s.stream.size, info.hs, info.vs, info.mcus_x,
+                   info.mcus_y, info.ncomp, 0)
+        s_at += shares[i]
+        if reconstruct:
+            rec[i] = (coef_ptr, base + o_qt[i], p_at, out[i].data_ptr(), info.width, info.height, info.ncomp, info.hs, info.vs, info.mcus_x,
+                      info.mcus_y, 0)
+            p_at += _align(counts[i])
+    staging.upload(block, total)
+    max_blocks = max(c // 64 for c in counts)
+    args = (base, n, max(int(s.stream.size) for s in scans), max_blocks, sync_passes)
+    recon = ((base + o_rec, n, max_blocks, max(int(s.info.height) for s in scans), max(int(s.info.width) for s in scans)), out) if reconstruct else None
+    return _HuffmanJob([coef_all[o:o + c] for o, c in zip(o_coef, counts)], block[o_res:o_res + 16 * n], args, recon, (block, scratch, coef_all, planes))
+
+
+def _huffman_launch(job: _HuffmanJob, stream) -> None:
+    global huffman_device_calls
+    _lib.call("pp_jpeg_huffman_decode_batch", *job.args, stream.cuda_stream)
+    huffman_device_calls += 1
+
+
+def huffman_decode_device(scans: Sequence[JpegScan], device="cuda", staging=None, sync_passes: Optional[int] = None):
+    """The Huffman half on the device for a batch of ``JpegScan`` of any mix of sizes and sampling: one upload of the
+    descriptors, tables and stream bytes through the pinned buffer of ``staging``, then ONE ``pp_jpeg_huffman_decode_batch``
+    call (``sync_passes`` + 4 launches, default ``DEFAULT_SYNC_PASSES``) on the current stream, then one read-back of the
+    result slots. Returns (the int16 device tensors of ``info.coef_count`` coefficients in ``entropy_decode``'s layout, the
+    slots as a structured array: status, passes, blocks, reason). Where ``status`` is not ``PP_OK`` (``HD_REASONS[reason]``
+    says why: above all "not synchronised") the coefficients are undefined."""
+    from .transforms import BatchStaging
+
+    scans = list(scans)
+    passes = _sync_passes(sync_passes)
+    if len(scans) == 0:
+        return [], np.zeros(0, _HD_RESULT)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("probpose_code_amd.jpeg.huffman_decode_device runs on the GPU only (no CPU fallback)")
+    job = _stage_huffman(scans, device, staging if staging is not None else BatchStaging(), passes, False)
+    _huffman_launch(job, torch.cuda.current_stream(device))
+    return job.coef, job.results.cpu().numpy().view(_HD_RESULT).copy()
+
+
+def decode_scans(scans: Sequence[JpegScan], device="cuda", staging=None, sync_passes: Optional[int] = None) -> List[torch.Tensor]:
+    """The (H, W, 3) uint8 BGR device tensors of a batch of ``JpegScan``: one upload, ``pp_jpeg_huffman_decode_batch`` and
+    ``pp_jpeg_reconstruct_bgr_batch`` on the coefficients where they lie, one read-back of the result slots. An image whose
+    slot is not ``PP_OK`` is decoded again through ``entropy_decode`` (outside its subset: by the host decoder) and counted
+    in ``fallbacks`` and ``unsynchronised``."""
+    global fallbacks, unsynchronised, reconstruct_calls
+    from .transforms import BatchStaging
+
+    scans = list(scans)
+    passes = _sync_passes(sync_passes)
+    if len(scans) == 0:
+        return []
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("probpose_code_amd.jpeg.decode_scans runs on the GPU only (no CPU fallback)")
+    staging = staging if staging is not None else BatchStaging()
+    job = _stage_huffman(scans, device, staging, passes, True)
+    stream = torch.cuda.current_stream(device)
+    _huffman_launch(job, stream)
+    _lib.call("pp_jpeg_reconstruct_bgr_batch", *job.recon[0], stream.cuda_stream)
+    reconstruct_calls += 1
+    out = list(job.recon[1])
+    res = job.results.cpu().numpy().view(_HD_RESULT)  # (waits for the stream: the launches have run)
+    again = [i for i, r in enumerate(res) if int(r["status"]) != _lib.PP_OK]
+    fallbacks += len(again)
+    unsynchronised += len(again)
+    coefs = []
+    for i in again:
+        try:
+            coefs.append((i, entropy_decode(scans[i].data)))
+        except JpegUnsupported:
+            out[i] = torch.from_numpy(_host_decode(scans[i].data)).to(device)
+    if coefs:
+        for (i, _), t in zip(coefs, reconstruct_batch([c for _, c in coefs], device, staging)):
+            out[i] = t
+    return out
 
 
 def _stage(coefficients: Sequence[JpegCoefficients], device, staging, out, scratch):
@@ -190,11 +412,16 @@ def reconstruct_batch(coefficients: Sequence[JpegCoefficients], device="cuda", s
     return out
 
 
-def imread_device(path_or_bytes: Union[str, bytes], device="cuda", staging=None) -> torch.Tensor:
+def imread_device(path_or_bytes: Union[str, bytes], device="cuda", staging=None, entropy: str = "host") -> torch.Tensor:
     """A file (path or bytes) as the (H, W, 3) uint8 BGR device tensor ``torch.from_numpy(load_image_bgr(path)).to(device)``
     gives, decoded on the device where the file is inside the subset. Any other file goes through ``load_image_bgr`` and an
-    upload: the same pixels, the same exceptions."""
+    upload: the same pixels, the same exceptions. ``entropy``: "host" (Huffman decoding on the host) or "device"
+    (``decode_batch``'s device path for this one file)."""
     global fallbacks
+    if entropy not in ENTROPY:
+        raise ValueError(f"entropy must be one of {ENTROPY}, got {entropy!r}")
+    if entropy == "device":
+        return decode_batch([path_or_bytes], device, entropy="device", staging=staging)[0]
     try:
         c = entropy_decode(path_or_bytes)
     except (JpegUnsupported, OSError):  # (an unreadable path: the host decoder raises what it always raised)
@@ -225,6 +452,50 @@ def _host_decode(path_or_bytes) -> np.ndarray:
     with Image.open(io.BytesIO(raw)) as im:
         rgb = np.asarray(im.convert("RGB"), dtype=np.uint8)
     return np.ascontiguousarray(rgb[:, :, ::-1])
+
+
+def decode_batch(files: Sequence, device="cuda", entropy: str = "host", staging=None, sync_passes: Optional[int] = None) -> List[torch.Tensor]:
+    """The (H, W, 3) uint8 BGR device tensors ``imread_device`` gives for a batch of files (paths or bytes) of any mix of sizes
+    and sampling. ``entropy="host"``: ``entropy_decode`` per file, one ``reconstruct_batch``. ``entropy="device"``: the host only
+    prepares the files (``scan_prepare``), their bytes go up in one copy, ``pp_jpeg_huffman_decode_batch`` and
+    ``pp_jpeg_reconstruct_bgr_batch`` run on the current stream, and the result slots come back in one copy. A file the
+    preparation refuses goes the ``entropy="host"`` way; an image whose slot is not ``PP_OK`` (not synchronised within
+    ``sync_passes``, a damaged stream) goes through ``entropy_decode`` - or, outside its subset, through the host decoder - and
+    is counted in ``fallbacks`` and in ``unsynchronised``. Pixels and exceptions are those of ``imread_device``."""
+    global fallbacks
+    from .transforms import BatchStaging
+
+    if entropy not in ENTROPY:
+        raise ValueError(f"entropy must be one of {ENTROPY}, got {entropy!r}")
+    if isinstance(files, (str, bytes, bytearray, memoryview, np.ndarray)):
+        raise ValueError("decode_batch takes a sequence of files; imread_device takes one")
+    files = list(files)
+    device = torch.device(device)
+    staging = staging if staging is not None else BatchStaging()
+    out = [None] * len(files)
+    scans, coefs = [], []
+    for i, f in enumerate(files):
+        try:
+            if entropy == "device":
+                raw = _bytes_of(f)
+                try:
+                    scans.append((i, scan_prepare(raw)))
+                    continue
+                except JpegUnsupported:
+                    pass
+                coefs.append((i, entropy_decode(raw)))
+            else:
+                coefs.append((i, entropy_decode(f)))
+        except (JpegUnsupported, OSError):  # (an unreadable path: the host decoder raises what it always raised)
+            fallbacks += 1
+            out[i] = torch.from_numpy(_host_decode(f)).to(device)
+    if scans:
+        for (i, _), t in zip(scans, decode_scans([s for _, s in scans], device, staging, sync_passes)):
+            out[i] = t
+    if coefs:
+        for (i, _), t in zip(coefs, reconstruct_batch([c for _, c in coefs], device, staging)):
+            out[i] = t
+    return out
 
 
 def decode_or_host(path: str):

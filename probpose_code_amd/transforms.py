@@ -262,7 +262,8 @@ class LoadImage(BaseTransform):
     array / device tensor already there; ``img_shape``, ``ori_shape``; ``pad_to_aspect_ratio``: the image is padded with 255
     so that the padded 3:4 box lies inside it, box (and keypoints, when present) shifted. ``imdecode_backend="mi355x"``: the
     file is decoded on the device (``jpeg.imread_device``: the same pixels as a device tensor; files outside its subset go
-    through the host decoder); any other value: the host decoder."""
+    through the host decoder); ``"mi355x-huffman"``: the same with the Huffman codes decoded on the device as well
+    (``imread_device(..., entropy="device")``); any other value: the host decoder."""
 
     def __init__(self, pad_to_aspect_ratio: bool = False, to_float32: bool = False, color_type: str = "color",
                  imdecode_backend: str = "cv2", backend_args: Optional[dict] = None, ignore_empty: bool = False, **kwargs):
@@ -277,10 +278,11 @@ class LoadImage(BaseTransform):
                 from .apis import load_image_bgr
 
                 try:
-                    if self.imdecode_backend == "mi355x":
+                    if self.imdecode_backend in ("mi355x", "mi355x-huffman"):
                         from .jpeg import imread_device
 
-                        img = imread_device(results["img_path"], self.device or "cuda")
+                        img = imread_device(results["img_path"], self.device or "cuda",
+                                            entropy="device" if self.imdecode_backend == "mi355x-huffman" else "host")
                     else:
                         img = load_image_bgr(results["img_path"])
                 except OSError:
