@@ -61,4 +61,26 @@ constexpr int WAVE = 64;
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (WAVE - 1); }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 
+// Exclusive prefix of v over the 256 threads of a workgroup; total <- the sum. lds: four words.
+__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* lds, uint32_t& total) {
+    uint32_t incl = v;
+#pragma unroll
+    for (int o = 1; o < WAVE; o <<= 1) {
+        const uint32_t up = __shfl_up(incl, o);
+        if (lane_id() >= o) incl += up;
+    }
+    if (lane_id() == WAVE - 1) lds[wave_id()] = incl;
+    __syncthreads();
+    uint32_t before = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const uint32_t s = lds[w];
+        if (w < wave_id()) before += s;
+        total += s;
+    }
+    __syncthreads();  // (lds is free for the next call)
+    return before + incl - v;
+}
+
 }  // namespace pp

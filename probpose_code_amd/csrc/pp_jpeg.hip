@@ -32,6 +32,9 @@
 
 namespace pp {
 
+// what probpose_code_amd/jpeg.py mirrors (_DESC)
+static_assert(sizeof(pp_jpeg_desc) == 64 && offsetof(pp_jpeg_desc, width) == 32, "four pointers, eight int32");
+
 __device__ __forceinline__ int descale(int v, int n) { return (v + (1 << (n - 1))) >> n; }
 
 // One 8-point pass of jidctint's islow IDCT; `shift`: 11 after the column pass, 18 after the row pass.

@@ -31,6 +31,9 @@
 
 namespace pp {
 
+// what probpose_code_amd/jpeg.py mirrors (_ENC_DESC)
+static_assert(sizeof(pp_jpeg_enc_desc) == 64 && offsetof(pp_jpeg_enc_desc, width) == 32, "four pointers, eight int32");
+
 // Converts one row segment of NP = 4 * HS pixels starting at column x0 of source row `row`; columns past W - 1 repeat it.
 template <int HS>
 __device__ __forceinline__ void load_row(const uint8_t* __restrict__ row, int x0, int W, int rgb, int (&R)[4 * HS], int (&G)[4 * HS],

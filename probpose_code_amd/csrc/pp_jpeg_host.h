@@ -21,6 +21,15 @@
 
 #include "../../include/probpose_mi355x.h"
 
+// This header itself stays plain host C++. It also carries PP_HOST_DEVICE, because it is the one header both device cores
+// (pp_jpeg_entropy_core.h, pp_jpeg_huffdec_core.h) include for jpeg::kNatural: the function qualifier of what they share
+// with their sequential host checks - host and device under hipcc, plain inline under a host compiler.
+#if defined(__HIPCC__)
+#define PP_HOST_DEVICE __host__ __device__ __forceinline__
+#else
+#define PP_HOST_DEVICE inline
+#endif
+
 namespace pp {
 namespace jpeg {
 

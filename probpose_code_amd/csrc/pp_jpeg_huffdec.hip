@@ -49,28 +49,6 @@ using namespace hd;
 constexpr int HD_STRIDE_WGS = 256;  // workgroups per image of the grid-stride launch
 constexpr int HD_DC_ITEMS = 8;      // blocks per thread and round of the DC prefix sums
 
-// Exclusive prefix of v over the 256 threads of a workgroup; total <- the sum. lds: four words.
-__device__ __forceinline__ uint32_t hd_block_scan(uint32_t v, uint32_t* lds, uint32_t& total) {
-    uint32_t incl = v;
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const uint32_t up = __shfl_up(incl, o);
-        if (lane_id() >= o) incl += up;
-    }
-    if (lane_id() == WAVE - 1) lds[wave_id()] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        const uint32_t s = lds[w];
-        if (w < wave_id()) before += s;
-        total += s;
-    }
-    __syncthreads();  // (lds is free for the next call)
-    return before + incl - v;
-}
-
 // The image's 2 x ncomp tables from the descriptor into LDS (each workgroup keeps its own copy for its random lookups).
 __device__ __forceinline__ const pp_jpeg_huff_table* tables_to_lds(const pp_jpeg_hd_desc& d, uint32_t* lds) {
     const uint32_t* src = reinterpret_cast<const uint32_t*>(d.tables);
@@ -194,7 +172,7 @@ __global__ __launch_bounds__(256) void jpeg_hd_scan_kernel(const pp_jpeg_hd_desc
             if (!same(want, entry_g[i])) ok = 0;
         }
         uint32_t total;
-        const uint32_t before = hd_block_scan(v, red, total);
+        const uint32_t before = block_scan(v, red, total);
         if (i < L.nsub) first_g[i] = carry + before;
         carry += total;
     }
@@ -272,7 +250,7 @@ __global__ __launch_bounds__(256) void jpeg_hd_dc_kernel(const pp_jpeg_hd_desc* 
                     v[j] = sum;  // inclusive inside the thread
                 }
                 uint32_t total;
-                const uint32_t before = hd_block_scan((uint32_t)sum, red, total);  // (a round's sums stay far inside int32)
+                const uint32_t before = block_scan((uint32_t)sum, red, total);  // (a round's sums stay far inside int32)
                 const long long mine = carry + (int32_t)before;
 #pragma unroll
                 for (int j = 0; j < HD_DC_ITEMS; ++j)

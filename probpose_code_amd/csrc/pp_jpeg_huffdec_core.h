@@ -13,13 +13,8 @@
 #pragma once
 #include <cstdint>
 
-#include "../../include/probpose_mi355x.h"
+#include "pp_jpeg_host.h"
 
-#if defined(__HIPCC__)
-#define PP_HD_FN __host__ __device__ __forceinline__
-#else
-#define PP_HD_FN inline
-#endif
 namespace pp {
 namespace hd {
 
@@ -32,32 +27,28 @@ constexpr long long HD_MAX_STREAM = 1ll << 28;  // bytes: bit positions stay bel
 constexpr int HD_LOOK_BITS = 9;
 constexpr int HD_TABLE_WORDS = (int)(sizeof(pp_jpeg_huff_table) / 4);
 
+// what probpose_code_amd/jpeg.py mirrors (TABLE_BYTES, _HD_DESC, _HD_RESULT)
+static_assert(sizeof(pp_jpeg_huff_table) == 1424 && sizeof(pp_jpeg_hd_desc) == 72 && sizeof(pp_jpeg_hd_result) == 16, "jpeg.py mirrors these");
+static_assert(offsetof(pp_jpeg_hd_desc, stream_bytes) == 40, "five pointers, then the stream's length");
+
 // reasons of a result slot (pp_jpeg_hd_result.reason)
 enum { HD_OK = 0, HD_NOT_SYNCHRONISED = 1, HD_ENDS_EARLY = 2, HD_BAD_CODE = 3, HD_DC_RANGE = 4, HD_TRAILING = 5, HD_BAD_DESC = 6 };
 // bits of `bad`
 enum { BAD_CODE = 1u, BAD_CATEGORY = 2u, BAD_INDEX = 4u, BAD_DC_RANGE = 8u };
 
-// zigzag position -> natural (row-major) position
-PP_HD_FN int natural_of(int k) {
-    constexpr uint8_t t[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                               41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                               30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-    return t[k & 63];
-}
-
 struct State {
     uint32_t pos;  // raw bit position
     uint32_t bk;   // block inside the MCU << 8 | zigzag index
 };
-PP_HD_FN bool same(State a, State b) { return a.pos == b.pos && a.bk == b.bk; }
+PP_HOST_DEVICE bool same(State a, State b) { return a.pos == b.pos && a.bk == b.bk; }
 
 struct Stream {
     const uint8_t* d;
     long long len;
 };
-PP_HD_FN uint32_t byte_at(const Stream& s, long long i) { return i < s.len ? (uint32_t)s.d[i] : 0u; }
-PP_HD_FN bool stuffed(const Stream& s, long long i) { return i > 0 && i < s.len && s.d[i] == 0 && s.d[i - 1] == 0xFF; }
-PP_HD_FN uint32_t canonical(const Stream& s, uint32_t pos) {
+PP_HOST_DEVICE uint32_t byte_at(const Stream& s, long long i) { return i < s.len ? (uint32_t)s.d[i] : 0u; }
+PP_HOST_DEVICE bool stuffed(const Stream& s, long long i) { return i > 0 && i < s.len && s.d[i] == 0 && s.d[i - 1] == 0xFF; }
+PP_HOST_DEVICE uint32_t canonical(const Stream& s, uint32_t pos) {
     const long long b = (long long)(pos >> 3);
     return stuffed(s, b) ? (uint32_t)((b + 1) << 3) : pos;
 }
@@ -68,7 +59,7 @@ struct Geometry {
     int valid, bpm, lum;
     long long nblk, mcus;
 };
-PP_HD_FN Geometry geometry(const pp_jpeg_hd_desc& d) {
+PP_HOST_DEVICE Geometry geometry(const pp_jpeg_hd_desc& d) {
     Geometry g{0, 1, 1, 0, 0};
     const bool sampling = d.ncomp == 1 ? (d.hs == 1 && d.vs == 1)
                                        : (d.ncomp == 3 && ((d.hs == 1 && d.vs == 1) || (d.hs == 2 && d.vs == 1) || (d.hs == 2 && d.vs == 2)));
@@ -88,8 +79,8 @@ PP_HD_FN Geometry geometry(const pp_jpeg_hd_desc& d) {
 struct Layout {
     long long nsub, nwg, o_entry, o_exit, o_cnt, o_first, o_bexit, o_open, total;
 };
-PP_HD_FN long long align16(long long v) { return (v + 15) / 16 * 16; }
-PP_HD_FN Layout layout(long long stream_bytes) {
+PP_HOST_DEVICE long long align16(long long v) { return (v + 15) / 16 * 16; }
+PP_HOST_DEVICE Layout layout(long long stream_bytes) {
     Layout L;
     L.nsub = stream_bytes > 0 ? (stream_bytes + HD_S - 1) / HD_S : 1;
     L.nwg = (L.nsub + HD_WG - 1) / HD_WG;
@@ -108,7 +99,7 @@ struct Header {  // first 64 bytes of the share
 };
 
 // Index in d.coef (in blocks) of block g of the scan; component <- 0 luma, 1 Cb, 2 Cr.
-PP_HD_FN long long block_index(const pp_jpeg_hd_desc& d, const Geometry& G, long long g, int& comp) {
+PP_HOST_DEVICE long long block_index(const pp_jpeg_hd_desc& d, const Geometry& G, long long g, int& comp) {
     const long long mcu = g / G.bpm;
     const int j = (int)(g - mcu * G.bpm);
     if (j < G.lum) {
@@ -121,7 +112,7 @@ PP_HD_FN long long block_index(const pp_jpeg_hd_desc& d, const Geometry& G, long
 }
 
 // Index in d.coef (in blocks) of block k of component c in scan order (what the DC prefix sums walk).
-PP_HD_FN long long component_block(const pp_jpeg_hd_desc& d, const Geometry& G, int c, long long k) {
+PP_HOST_DEVICE long long component_block(const pp_jpeg_hd_desc& d, const Geometry& G, int c, long long k) {
     if (c > 0) return G.mcus * G.lum + (long long)(c - 1) * G.mcus + k;
     const long long mcu = k / G.lum;
     const int j = (int)(k - mcu * G.lum);
@@ -137,12 +128,12 @@ struct Reader {
     uint64_t acc = 0;
     uint32_t prev;  // the raw byte in front of `next` (what makes a 00 a stuffed one)
     int n = 0, loaded = 0, limit = 0x7fffffff;
-    PP_HD_FN Reader(const Stream& s_, uint32_t pos, long long end_byte_)
+    PP_HOST_DEVICE Reader(const Stream& s_, uint32_t pos, long long end_byte_)
         : s(s_), next((long long)(pos >> 3)), end_byte(end_byte_), prev(pos >> 3 ? byte_at(s_, (long long)(pos >> 3) - 1) : 0u) {
         fill();
         n -= (int)(pos & 7);
     }
-    PP_HD_FN void fill() {  // at least 57 bits afterwards; skips exactly the bytes stuffed() names
+    PP_HOST_DEVICE void fill() {  // at least 57 bits afterwards; skips exactly the bytes stuffed() names
         while (n <= 56) {
             uint32_t b = byte_at(s, next);
             if (b == 0u && prev == 0xFFu && next < s.len) b = byte_at(s, ++next);
@@ -154,9 +145,9 @@ struct Reader {
             loaded += 8;
         }
     }
-    PP_HD_FN uint32_t peek(int k) const { return (uint32_t)(acc >> (n - k)) & ((1u << k) - 1u); }  // k <= 16
-    PP_HD_FN int consumed() const { return loaded - n; }
-    PP_HD_FN uint32_t position() const {  // of the next unread bit: walk back over the bytes still held
+    PP_HOST_DEVICE uint32_t peek(int k) const { return (uint32_t)(acc >> (n - k)) & ((1u << k) - 1u); }  // k <= 16
+    PP_HOST_DEVICE int consumed() const { return loaded - n; }
+    PP_HOST_DEVICE uint32_t position() const {  // of the next unread bit: walk back over the bytes still held
         long long j = next;
         for (int b = (n + 7) >> 3; b > 0; --b) {
             --j;
@@ -167,7 +158,7 @@ struct Reader {
 };
 
 // One symbol of table t, -1: no such code (nothing consumed).
-PP_HD_FN int symbol(Reader& r, const pp_jpeg_huff_table& t) {
+PP_HOST_DEVICE int symbol(Reader& r, const pp_jpeg_huff_table& t) {
     const uint32_t e = t.look[r.peek(HD_LOOK_BITS)];
     const int len9 = (int)(e >> 8);
     if (len9 >= 1 && len9 <= HD_LOOK_BITS) {
@@ -186,7 +177,7 @@ PP_HD_FN int symbol(Reader& r, const pp_jpeg_huff_table& t) {
     return -1;
 }
 
-PP_HD_FN int receive_extend(Reader& r, int s) {  // 1 <= s <= 15
+PP_HOST_DEVICE int receive_extend(Reader& r, int s) {  // 1 <= s <= 15
     const int v = (int)r.peek(s);
     r.n -= s;
     return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
@@ -194,9 +185,9 @@ PP_HD_FN int receive_extend(Reader& r, int s) {  // 1 <= s <= 15
 
 struct CountSink {
     uint32_t blocks = 0;
-    PP_HD_FN void coef(int, int) {}
-    PP_HD_FN void block_done() { ++blocks; }
-    PP_HD_FN bool stop() const { return false; }
+    PP_HOST_DEVICE void coef(int, int) {}
+    PP_HOST_DEVICE void block_done() { ++blocks; }
+    PP_HOST_DEVICE bool stop() const { return false; }
 };
 
 // Stores every coefficient at kNatural[k] of its block; stops behind the image's last block. Every store is checked.
@@ -205,27 +196,27 @@ struct WriteSink {
     const Geometry& G;
     long long g, base = -1;
     bool finished = false;
-    PP_HD_FN WriteSink(const pp_jpeg_hd_desc& d_, const Geometry& G_, long long first) : d(d_), G(G_), g(first) {}
-    PP_HD_FN void coef(int k, int v) {
+    PP_HOST_DEVICE WriteSink(const pp_jpeg_hd_desc& d_, const Geometry& G_, long long first) : d(d_), G(G_), g(first) {}
+    PP_HOST_DEVICE void coef(int k, int v) {
         if (g >= G.nblk) return;
         if (base < 0) {
             int comp;
             base = block_index(d, G, g, comp) * 64;
         }
-        if (base >= 0 && base + 64 <= G.nblk * 64) d.coef[base + natural_of(k)] = (int16_t)v;
+        if (base >= 0 && base + 64 <= G.nblk * 64) d.coef[base + jpeg::kNatural[k & 63]] = (int16_t)v;
     }
-    PP_HD_FN void block_done() {
+    PP_HOST_DEVICE void block_done() {
         ++g;
         base = -1;
         if (g >= G.nblk) finished = true;
     }
-    PP_HD_FN bool stop() const { return g >= G.nblk; }
+    PP_HOST_DEVICE bool stop() const { return g >= G.nblk; }
 };
 
 // tabs: the image's 2 * ncomp tables (DC, AC of component 0, 1, 2). Decodes from `in` to the first symbol boundary at or
 // behind raw byte `end_byte` (or until the sink stops). At most 8 HD_S + 64 symbols: bounded whatever the data.
 template <class Sink>
-PP_HD_FN State run(const Stream& st, const pp_jpeg_huff_table* tabs, State in, long long end_byte, const Geometry& G, Sink& sink, uint32_t& bad) {
+PP_HOST_DEVICE State run(const Stream& st, const pp_jpeg_huff_table* tabs, State in, long long end_byte, const Geometry& G, Sink& sink, uint32_t& bad) {
     Reader r(st, in.pos, end_byte);
     int blk = (int)(in.bk >> 8), k = (int)(in.bk & 255u);
     if (blk >= G.bpm) blk = 0;
@@ -284,7 +275,7 @@ PP_HD_FN State run(const Stream& st, const pp_jpeg_huff_table* tabs, State in, l
 
 // The result slot of an image from what the launches left in its header: the host decoder's verdict. The bits in front of
 // the EOI marker are those behind the last block, less a stuffed 00 that ends the segment (the last data byte was FF).
-PP_HD_FN pp_jpeg_hd_result verdict(const Stream& st, const Geometry& G, const Header& h, bool range_bad) {
+PP_HOST_DEVICE pp_jpeg_hd_result verdict(const Stream& st, const Geometry& G, const Header& h, bool range_bad) {
     pp_jpeg_hd_result r{PP_OK, (int32_t)h.passes + 1, (int32_t)h.total, HD_OK};
     const long long bits = st.len * 8, data_bits = bits - (stuffed(st, st.len - 1) ? 8 : 0);
     if (!h.synced) r.reason = HD_NOT_SYNCHRONISED;

@@ -37,6 +37,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .staging import BatchStaging, StagedBlock, _align
 
 fallbacks = 0  # files imread_device / the test loop handed to the host decoder since import (diagnostics)
 reconstruct_calls = 0  # pp_jpeg_reconstruct_bgr_batch calls since import
@@ -123,6 +124,25 @@ class JpegCoefficients(NamedTuple):
         return (int(self.info.height), int(self.info.width), 3)
 
 
+def _cuda_device(device, function: str) -> torch.device:
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"probpose_code_amd.jpeg.{function} runs on the GPU only (no CPU fallback)")
+    return device
+
+
+def _check_entropy(entropy) -> None:
+    if entropy not in ENTROPY:
+        raise ValueError(f"entropy must be one of {ENTROPY}, got {entropy!r}")
+
+
+def _size(query: str, value) -> int:
+    """What a size query of the library returned; a negative value is its status."""
+    if value < 0:
+        raise _lib.ProbPoseLibraryError(query, _lib.lib.pp_status_string(value).decode(), _lib.last_error())
+    return int(value)
+
+
 def _bytes_of(data) -> bytes:
     if isinstance(data, (bytes, bytearray, memoryview)):
         return bytes(data)
@@ -193,20 +213,28 @@ def scan_prepare(data) -> JpegScan:
     return JpegScan(info, qt, tables, stream, raw)
 
 
-def _align(v: int, a: int = 256) -> int:
-    return (v + a - 1) // a * a
+class _ReconJob(NamedTuple):
+    """One ``pp_jpeg_reconstruct_bgr_batch`` call: ``args`` (its arguments), ``out`` (the (H, W, 3) output tensors), ``block``
+    (the uploaded ``StagedBlock``) and ``keep`` (the other tensors the launches use)."""
+
+    args: tuple
+    out: list
+    block: StagedBlock
+    keep: tuple
 
 
 class _HuffmanJob(NamedTuple):
-    """The device buffers of one ``pp_jpeg_huffman_decode_batch`` call: ``coef`` (image i's int16 coefficients, views of one
-    tensor), ``results`` (n x 16 bytes, a view of the uploaded block), ``desc_ptr`` / ``args`` (the call's arguments),
-    ``recon`` (the arguments of ``pp_jpeg_reconstruct_bgr_batch`` on the same coefficients and its output tensors, or None)
-    and ``keep`` (every tensor the launches use)."""
+    """One ``pp_jpeg_huffman_decode_batch`` call: ``coef`` (image i's int16 coefficients, views of one tensor), ``results``
+    (n x 16 bytes, a view of the uploaded block), ``args`` (the call's arguments), ``recon_args`` / ``out`` (the arguments of
+    ``pp_jpeg_reconstruct_bgr_batch`` on the same coefficients and its output tensors, or None), ``block`` (the uploaded
+    ``StagedBlock``) and ``keep`` (the other tensors the launches use)."""
 
     coef: list
     results: torch.Tensor
     args: tuple
-    recon: Optional[tuple]
+    recon_args: Optional[tuple]
+    out: Optional[list]
+    block: StagedBlock
     keep: tuple
 
 
@@ -224,25 +252,12 @@ def _stage_huffman(scans: Sequence[JpegScan], device, staging, sync_passes: int,
     n = len(scans)
     infos = (JpegInfo * n)(*[s.info for s in scans])
     lens = (ctypes.c_longlong * n)(*[int(s.stream.size) for s in scans])
-    shares = []
-    for i in range(n):
-        one = int(_lib.lib.pp_jpeg_huffman_scratch_bytes(ctypes.byref(infos[i]), ctypes.byref(lens, 8 * i), 1))
-        if one < 0:
-            raise _lib.ProbPoseLibraryError("pp_jpeg_huffman_scratch_bytes", _lib.lib.pp_status_string(one).decode(), _lib.last_error())
-        shares.append(one)
+    shares = [_size("pp_jpeg_huffman_scratch_bytes", _lib.lib.pp_jpeg_huffman_scratch_bytes(ctypes.byref(infos[i]), ctypes.byref(lens, 8 * i), 1))
+              for i in range(n)]
     # the block: decoder descriptors (n x 72 bytes) | result slots (n x 16) | reconstruct descriptors (n x 64) | per image:
     # Huffman tables, quantisation tables (3 x 64 u16), stream bytes
-    o_res = _align(72 * n)
-    o_rec = _align(o_res + 16 * n)
-    off, o_tab, o_qt, o_str = _align(o_rec + 64 * n), [], [], []
-    for s in scans:
-        o_tab.append(off)
-        off = _align(off + s.tables.size)
-        o_qt.append(off)
-        off = _align(off + 384)
-        o_str.append(off)
-        off = _align(off + max(int(s.stream.size), 1))
-    total = off
+    blk = StagedBlock([("desc", 72 * n), ("results", 16 * n), ("recon", 64 * n)],
+                      [("tables", [s.tables.size for s in scans]), ("qtables", [384] * n), ("stream", [max(int(s.stream.size), 1) for s in scans])])
     counts = [int(s.info.coef_count) for s in scans]
     o_coef, at = [], 0
     for c in counts:
@@ -250,34 +265,34 @@ def _stage_huffman(scans: Sequence[JpegScan], device, staging, sync_passes: int,
         at += _align(2 * c) // 2
     coef_all = torch.empty(max(at, 1), dtype=torch.int16, device=device)
     scratch = torch.empty(sum(shares), dtype=torch.uint8, device=device)
-    block = torch.empty(total, dtype=torch.uint8, device=device)
+    blk.acquire(staging, device)
     planes = torch.empty(sum(_align(c) for c in counts), dtype=torch.uint8, device=device) if reconstruct else None
     out = [torch.empty(s.shape, dtype=torch.uint8, device=device) for s in scans] if reconstruct else None
-    blk = staging.acquire(total)
-    desc = blk[:72 * n].view(_HD_DESC)
-    rec = blk[o_rec:o_rec + 64 * n].view(_DESC)
-    blk[o_res:o_res + 16 * n] = 0
-    base, s_at, p_at = block.data_ptr(), scratch.data_ptr(), (planes.data_ptr() if reconstruct else 0)
+    desc, rec = blk.host("desc", _HD_DESC), blk.host("recon", _DESC)
+    blk.host("results")[:] = 0
+    tables, qtables, streams = blk.hosts("tables"), blk.hosts("qtables", np.uint16), blk.hosts("stream")
+    p_tables, p_qtables, p_streams, p_results = blk.ptrs("tables"), blk.ptrs("qtables"), blk.ptrs("stream"), blk.ptr("results")
+    s_at, p_at = scratch.data_ptr(), (planes.data_ptr() if reconstruct else 0)
     for i, s in enumerate(scans):
         info = s.info
         if s.tables.size != 2 * int(info.ncomp) * TABLE_BYTES or s.tables.dtype != np.uint8 or s.stream.dtype != np.uint8:
             raise ValueError("a JpegScan holds 2 x ncomp tables and its stream as uint8")
-        blk[o_tab[i]:o_tab[i] + s.tables.size] = s.tables
-        blk[o_qt[i]:o_qt[i] + 128 * len(s.qtables)].view(np.uint16)[:] = s.qtables.reshape(-1)
-        blk[o_str[i]:o_str[i] + s.stream.size] = s.stream
+        tables[i][:] = s.tables
+        qtables[i][:64 * len(s.qtables)] = s.qtables.reshape(-1)
+        streams[i][:s.stream.size] = s.stream
         coef_ptr = coef_all.data_ptr() + 2 * o_coef[i]
-        desc[i] = (base + o_str[i], base + o_tab[i], coef_ptr, s_at, base + o_res + 16 * i, s.stream.size, info.hs, info.vs, info.mcus_x,
-                   info.mcus_y, info.ncomp, 0)
+        desc[i] = (p_streams[i], p_tables[i], coef_ptr, s_at, p_results + 16 * i, s.stream.size, info.hs, info.vs, info.mcus_x, info.mcus_y,
+                   info.ncomp, 0)
         s_at += shares[i]
         if reconstruct:
-            rec[i] = (coef_ptr, base + o_qt[i], p_at, out[i].data_ptr(), info.width, info.height, info.ncomp, info.hs, info.vs, info.mcus_x,
+            rec[i] = (coef_ptr, p_qtables[i], p_at, out[i].data_ptr(), info.width, info.height, info.ncomp, info.hs, info.vs, info.mcus_x,
                       info.mcus_y, 0)
             p_at += _align(counts[i])
-    staging.upload(block, total)
+    blk.upload()
     max_blocks = max(c // 64 for c in counts)
-    args = (base, n, max(int(s.stream.size) for s in scans), max_blocks, sync_passes)
-    recon = ((base + o_rec, n, max_blocks, max(int(s.info.height) for s in scans), max(int(s.info.width) for s in scans)), out) if reconstruct else None
-    return _HuffmanJob([coef_all[o:o + c] for o, c in zip(o_coef, counts)], block[o_res:o_res + 16 * n], args, recon, (block, scratch, coef_all, planes))
+    args = (blk.base, n, max(int(s.stream.size) for s in scans), max_blocks, sync_passes)
+    recon_args = (blk.ptr("recon"), n, max_blocks, max(int(s.info.height) for s in scans), max(int(s.info.width) for s in scans)) if reconstruct else None
+    return _HuffmanJob([coef_all[o:o + c] for o, c in zip(o_coef, counts)], blk.device("results"), args, recon_args, out, blk, (scratch, coef_all, planes))
 
 
 def _huffman_launch(job: _HuffmanJob, stream) -> None:
@@ -293,15 +308,11 @@ def huffman_decode_device(scans: Sequence[JpegScan], device="cuda", staging=None
     result slots. Returns (the int16 device tensors of ``info.coef_count`` coefficients in ``entropy_decode``'s layout, the
     slots as a structured array: status, passes, blocks, reason). Where ``status`` is not ``PP_OK`` (``HD_REASONS[reason]``
     says why: above all "not synchronised") the coefficients are undefined."""
-    from .transforms import BatchStaging
-
     scans = list(scans)
     passes = _sync_passes(sync_passes)
     if len(scans) == 0:
         return [], np.zeros(0, _HD_RESULT)
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("probpose_code_amd.jpeg.huffman_decode_device runs on the GPU only (no CPU fallback)")
+    device = _cuda_device(device, "huffman_decode_device")
     job = _stage_huffman(scans, device, staging if staging is not None else BatchStaging(), passes, False)
     _huffman_launch(job, torch.cuda.current_stream(device))
     return job.coef, job.results.cpu().numpy().view(_HD_RESULT).copy()
@@ -312,47 +323,32 @@ def decode_scans(scans: Sequence[JpegScan], device="cuda", staging=None, sync_pa
     ``pp_jpeg_reconstruct_bgr_batch`` on the coefficients where they lie, one read-back of the result slots. An image whose
     slot is not ``PP_OK`` is decoded again through ``entropy_decode`` (outside its subset: by the host decoder) and counted
     in ``fallbacks`` and ``unsynchronised``."""
-    global fallbacks, unsynchronised, reconstruct_calls
-    from .transforms import BatchStaging
-
+    global reconstruct_calls
     scans = list(scans)
     passes = _sync_passes(sync_passes)
     if len(scans) == 0:
         return []
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("probpose_code_amd.jpeg.decode_scans runs on the GPU only (no CPU fallback)")
+    device = _cuda_device(device, "decode_scans")
     staging = staging if staging is not None else BatchStaging()
     job = _stage_huffman(scans, device, staging, passes, True)
     stream = torch.cuda.current_stream(device)
     _huffman_launch(job, stream)
-    _lib.call("pp_jpeg_reconstruct_bgr_batch", *job.recon[0], stream.cuda_stream)
+    _lib.call("pp_jpeg_reconstruct_bgr_batch", *job.recon_args, stream.cuda_stream)
     reconstruct_calls += 1
-    out = list(job.recon[1])
+    out = list(job.out)
     res = job.results.cpu().numpy().view(_HD_RESULT)  # (waits for the stream: the launches have run)
     again = [i for i, r in enumerate(res) if int(r["status"]) != _lib.PP_OK]
-    fallbacks += len(again)
-    unsynchronised += len(again)
-    coefs = []
-    for i in again:
-        try:
-            coefs.append((i, entropy_decode(scans[i].data)))
-        except JpegUnsupported:
-            out[i] = torch.from_numpy(_host_decode(scans[i].data)).to(device)
-    if coefs:
-        for (i, _), t in zip(coefs, reconstruct_batch([c for _, c in coefs], device, staging)):
-            out[i] = t
-    return out
+    for i, decoded in zip(again, _step_down([scans[i].data for i in again], "huffman", device)):
+        out[i] = decoded
+    return _reconstruct_pending(out, device, staging)
 
 
-def _stage(coefficients: Sequence[JpegCoefficients], device, staging, out, scratch):
-    """Pack the descriptor table, the tables and the coefficients of a batch into the pinned buffer, upload them with one copy
-    and return (the arguments of ``pp_jpeg_reconstruct_bgr_batch``, the output tensors, the tensors the launches read)."""
+def _stage(coefficients: Sequence[JpegCoefficients], device, staging, out, scratch) -> _ReconJob:
+    """Pack the descriptor table, the tables and the coefficients of a batch into the pinned buffer and upload them with one
+    copy."""
     n = len(coefficients)
     infos = (JpegInfo * n)(*[c.info for c in coefficients])
-    need = int(_lib.lib.pp_jpeg_scratch_bytes(infos, n))
-    if need < 0:
-        raise _lib.ProbPoseLibraryError("pp_jpeg_scratch_bytes", _lib.lib.pp_status_string(need).decode(), _lib.last_error())
+    need = _size("pp_jpeg_scratch_bytes", _lib.lib.pp_jpeg_scratch_bytes(infos, n))
     if scratch is None:
         scratch = torch.empty(need, dtype=torch.uint8, device=device)
     elif scratch.numel() < need or scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.data_ptr() % 8:
@@ -366,30 +362,22 @@ def _stage(coefficients: Sequence[JpegCoefficients], device, staging, out, scrat
             if tuple(t.shape) != c.shape or t.dtype != torch.uint8 or not t.is_contiguous() or t.device != scratch.device:
                 raise ValueError(f"out tensors must be contiguous uint8 {c.shape} on {scratch.device}")
     # the block: descriptors (n x 64 bytes) | per image: quantisation tables (3 x 64 u16), coefficients (int16)
-    off, o_qt, o_coef = _align(64 * n), [], []
-    for c in coefficients:
-        o_qt.append(off)
-        off = _align(off + 384)
-        o_coef.append(off)
-        off = _align(off + 2 * c.coef.size)
-    total = off
-    dev = torch.empty(total, dtype=torch.uint8, device=device)
-    blk = staging.acquire(total)
-    desc = blk[:64 * n].view(_DESC)
-    base, planes = dev.data_ptr(), scratch.data_ptr()
+    blk = StagedBlock([("desc", 64 * n)], [("qtables", [384] * n), ("coef", [2 * c.coef.size for c in coefficients])]).acquire(staging, device)
+    desc, planes = blk.host("desc", _DESC), scratch.data_ptr()
+    qtables, coef, p_qtables, p_coef = blk.hosts("qtables", np.uint16), blk.hosts("coef", np.int16), blk.ptrs("qtables"), blk.ptrs("coef")
     for i, c in enumerate(coefficients):
         info = c.info
         if c.coef.size != info.coef_count or c.coef.dtype != np.int16:
             raise ValueError("coefficient array does not match its info")
-        blk[o_qt[i]:o_qt[i] + 128 * len(c.qtables)].view(np.uint16)[:] = c.qtables.reshape(-1)
-        blk[o_coef[i]:o_coef[i] + 2 * c.coef.size].view(np.int16)[:] = c.coef
-        desc[i] = (base + o_coef[i], base + o_qt[i], planes, out[i].data_ptr(), info.width, info.height, info.ncomp, info.hs, info.vs,
-                   info.mcus_x, info.mcus_y, 0)
+        qtables[i][:64 * len(c.qtables)] = c.qtables.reshape(-1)
+        coef[i][:] = c.coef
+        desc[i] = (p_coef[i], p_qtables[i], planes, out[i].data_ptr(), info.width, info.height, info.ncomp, info.hs, info.vs, info.mcus_x,
+                   info.mcus_y, 0)
         planes += _align(int(info.coef_count))
-    staging.upload(dev, total)
-    args = (base, n, max(int(c.info.coef_count) // 64 for c in coefficients), max(int(c.info.height) for c in coefficients),
+    blk.upload()
+    args = (blk.base, n, max(int(c.info.coef_count) // 64 for c in coefficients), max(int(c.info.height) for c in coefficients),
             max(int(c.info.width) for c in coefficients))
-    return args, list(out), (dev, scratch)
+    return _ReconJob(args, list(out), blk, (scratch,))
 
 
 def reconstruct_batch(coefficients: Sequence[JpegCoefficients], device="cuda", staging=None, out: Optional[Sequence[torch.Tensor]] = None,
@@ -399,16 +387,42 @@ def reconstruct_batch(coefficients: Sequence[JpegCoefficients], device="cuda", s
     ``pp_jpeg_reconstruct_bgr_batch`` call (two launches) on the current stream. Returns the (H, W, 3) uint8 BGR device
     tensors. ``out`` / ``scratch``: caller-provided output tensors (contiguous, of those shapes) and plane scratch."""
     global reconstruct_calls
-    from .transforms import BatchStaging
-
     if len(coefficients) == 0:
         return []
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("probpose_code_amd.jpeg.reconstruct_batch runs on the GPU only (no CPU fallback)")
-    args, out, _ = _stage(coefficients, device, staging if staging is not None else BatchStaging(), out, scratch)
-    _lib.call("pp_jpeg_reconstruct_bgr_batch", *args, torch.cuda.current_stream(device).cuda_stream)
+    device = _cuda_device(device, "reconstruct_batch")
+    job = _stage(coefficients, device, staging if staging is not None else BatchStaging(), out, scratch)
+    _lib.call("pp_jpeg_reconstruct_bgr_batch", *job.args, torch.cuda.current_stream(device).cuda_stream)
     reconstruct_calls += 1
+    return job.out
+
+
+def _step_down(sources: list, failed: str, device) -> list:
+    """One step down the ladder device Huffman decoder -> ``entropy_decode`` -> host decoder for files (paths or bytes), counted
+    first. ``failed="huffman"``: refused by the result slot (``fallbacks``, ``unsynchronised``), on to ``entropy_decode`` and, outside
+    its subset, to the host decoder. ``failed="entropy"``: refused by ``entropy_decode`` or unreadable (``fallbacks``), on to the host
+    decoder, which raises what it always raised. Per file its ``JpegCoefficients``, still to be reconstructed, or its pixels."""
+    global fallbacks, unsynchronised
+    fallbacks += len(sources)
+    if failed == "huffman":
+        unsynchronised += len(sources)
+    out = []
+    for source in sources:
+        decoded = None
+        if failed == "huffman":
+            try:
+                decoded = entropy_decode(source)
+            except JpegUnsupported:
+                pass
+        out.append(decoded if decoded is not None else torch.from_numpy(_host_decode(source)).to(device))
+    return out
+
+
+def _reconstruct_pending(out: list, device, staging) -> list:
+    """``out`` with every ``JpegCoefficients`` in it replaced by its pixels: one ``reconstruct_batch`` for all of them."""
+    todo = [i for i, c in enumerate(out) if isinstance(c, JpegCoefficients)]
+    if todo:
+        for i, t in zip(todo, reconstruct_batch([out[i] for i in todo], device, staging)):
+            out[i] = t
     return out
 
 
@@ -417,16 +431,13 @@ def imread_device(path_or_bytes: Union[str, bytes], device="cuda", staging=None,
     gives, decoded on the device where the file is inside the subset. Any other file goes through ``load_image_bgr`` and an
     upload: the same pixels, the same exceptions. ``entropy``: "host" (Huffman decoding on the host) or "device"
     (``decode_batch``'s device path for this one file)."""
-    global fallbacks
-    if entropy not in ENTROPY:
-        raise ValueError(f"entropy must be one of {ENTROPY}, got {entropy!r}")
+    _check_entropy(entropy)
     if entropy == "device":
         return decode_batch([path_or_bytes], device, entropy="device", staging=staging)[0]
     try:
         c = entropy_decode(path_or_bytes)
     except (JpegUnsupported, OSError):  # (an unreadable path: the host decoder raises what it always raised)
-        fallbacks += 1
-        return torch.from_numpy(_host_decode(path_or_bytes)).to(device)
+        return _step_down([path_or_bytes], "entropy", device)[0]
     return reconstruct_batch([c], device, staging)[0]
 
 
@@ -462,40 +473,30 @@ def decode_batch(files: Sequence, device="cuda", entropy: str = "host", staging=
     preparation refuses goes the ``entropy="host"`` way; an image whose slot is not ``PP_OK`` (not synchronised within
     ``sync_passes``, a damaged stream) goes through ``entropy_decode`` - or, outside its subset, through the host decoder - and
     is counted in ``fallbacks`` and in ``unsynchronised``. Pixels and exceptions are those of ``imread_device``."""
-    global fallbacks
-    from .transforms import BatchStaging
-
-    if entropy not in ENTROPY:
-        raise ValueError(f"entropy must be one of {ENTROPY}, got {entropy!r}")
+    _check_entropy(entropy)
     if isinstance(files, (str, bytes, bytearray, memoryview, np.ndarray)):
         raise ValueError("decode_batch takes a sequence of files; imread_device takes one")
     files = list(files)
     device = torch.device(device)
     staging = staging if staging is not None else BatchStaging()
-    out = [None] * len(files)
-    scans, coefs = [], []
+    out = [None] * len(files)  # per file: its pixels, or its JpegCoefficients until _reconstruct_pending
+    scans = []
     for i, f in enumerate(files):
         try:
             if entropy == "device":
-                raw = _bytes_of(f)
+                f = _bytes_of(f)
                 try:
-                    scans.append((i, scan_prepare(raw)))
+                    scans.append((i, scan_prepare(f)))
                     continue
                 except JpegUnsupported:
                     pass
-                coefs.append((i, entropy_decode(raw)))
-            else:
-                coefs.append((i, entropy_decode(f)))
+            out[i] = entropy_decode(f)
         except (JpegUnsupported, OSError):  # (an unreadable path: the host decoder raises what it always raised)
-            fallbacks += 1
-            out[i] = torch.from_numpy(_host_decode(f)).to(device)
+            out[i] = _step_down([files[i]], "entropy", device)[0]
     if scans:
         for (i, _), t in zip(scans, decode_scans([s for _, s in scans], device, staging, sync_passes)):
             out[i] = t
-    if coefs:
-        for (i, _), t in zip(coefs, reconstruct_batch([c for _, c in coefs], device, staging)):
-            out[i] = t
-    return out
+    return _reconstruct_pending(out, device, staging)
 
 
 def decode_or_host(path: str):
@@ -536,10 +537,7 @@ def entropy_encode(coefficients: JpegCoefficients, restart_interval: int = 0) ->
         raise ValueError("the encoder takes three (64,) tables and info.coef_count coefficients")
     if not 0 <= int(restart_interval) <= 65535:
         raise ValueError(f"restart_interval must be in 0..65535, got {restart_interval!r}")
-    bound = int(_lib.lib.pp_jpeg_encoded_bound(ctypes.byref(info)))
-    if bound < 0:
-        raise _lib.ProbPoseLibraryError("pp_jpeg_encoded_bound", _lib.lib.pp_status_string(bound).decode(), _lib.last_error())
-    out = np.empty(bound, np.uint8)
+    out = np.empty(_size("pp_jpeg_encoded_bound", _lib.lib.pp_jpeg_encoded_bound(ctypes.byref(info))), np.uint8)
     size = ctypes.c_size_t(0)
     _lib.call("pp_jpeg_entropy_encode", coef.ctypes.data, qt.ctypes.data, ctypes.byref(info), int(restart_interval), out.ctypes.data,
               out.size, ctypes.byref(size))
@@ -566,9 +564,7 @@ def _encoder_images(images, device):
                 raise ValueError(f"images of one batch must share a device: {im.device} and {dev}")
             dev = im.device
         checked.append(im)
-    dev = dev if dev is not None else torch.device(device or "cuda")
-    if dev.type != "cuda":
-        raise RuntimeError("probpose_code_amd.jpeg.encode_batch runs on the GPU only (no CPU fallback)")
+    dev = _cuda_device(dev if dev is not None else (device or "cuda"), "encode_batch")
     out = []
     for im in checked:
         im = im.to(dev)  # a host array is uploaded first
@@ -578,42 +574,55 @@ def _encoder_images(images, device):
     return out, dev
 
 
-def _stage_encode(images, qt, subsampling, channel_order, dev, staging, entropy=False):
-    """Pack the descriptor table and the tables of a batch into the pinned buffer and upload them with one copy. Returns (the
-    arguments of ``pp_jpeg_forward_batch``, (device block, pinned buffer, first and last byte of the coefficients in both, each
-    image's offset, the infos), the tensors the launches use). ``entropy``: the table and result slots of
-    ``pp_jpeg_entropy_encode_batch`` travel in the same copy; the returned tuple then ends with an ``_EntropyJob``."""
+class _EntropyJob(NamedTuple):
+    """One ``pp_jpeg_entropy_encode_batch`` call and its device buffers: ``desc_ptr`` (the uploaded descriptor table),
+    ``results`` (n x 16 bytes, a view of the uploaded block), the streams (``out``: image i's at ``o_out[i]``, ``capacity[i]``
+    bytes), the scratch, the infos and ``block`` (the uploaded ``StagedBlock``)."""
+
+    desc_ptr: int
+    results: torch.Tensor
+    out: torch.Tensor
+    o_out: list
+    capacity: list
+    scratch: torch.Tensor
+    infos: list
+    block: StagedBlock
+
+
+class _ForwardJob(NamedTuple):
+    """One ``pp_jpeg_forward_batch`` call: ``args`` (its arguments), ``block`` (the uploaded ``StagedBlock``; the coefficients
+    are its per-image region "coef", behind everything the upload sent), ``infos``, ``qt`` (the tables), ``keep`` (the other
+    tensors the launches use) and ``entropy`` (the ``pp_jpeg_entropy_encode_batch`` call on the same coefficients, or None)."""
+
+    args: tuple
+    block: StagedBlock
+    infos: list
+    qt: np.ndarray
+    keep: tuple
+    entropy: Optional[_EntropyJob]
+
+
+def _stage_encode(images, qt, subsampling, channel_order, dev, staging, entropy=False) -> _ForwardJob:
+    """Pack the descriptor table and the tables of a batch into the pinned buffer and upload them with one copy. ``entropy``:
+    the table and result slots of ``pp_jpeg_entropy_encode_batch`` travel in the same copy."""
     n = len(images)
     infos = [encode_plan(im.shape[1], im.shape[0], subsampling) for im in images]
     # the block: descriptors (n x 64 bytes) | quantisation tables (3 x 64 u16) | with entropy: its descriptors (n x 64 bytes),
     # result slots (n x 16 bytes) | per image: coefficients (int16)
-    o_qt = _align(64 * n)
-    o_ent = _align(o_qt + 384)
-    o_res = _align(o_ent + 64 * n) if entropy else o_ent
-    off, o_coef = (_align(o_res + 16 * n) if entropy else o_ent), []
-    for info in infos:
-        o_coef.append(off)
-        off = _align(off + 2 * int(info.coef_count))
-    total, head = off, o_coef[0]
+    blk = StagedBlock([("desc", 64 * n), ("qtables", 384)] + ([("entropy", 64 * n), ("results", 16 * n)] if entropy else []),
+                      [("coef", [2 * int(i.coef_count) for i in infos])])
     scratch = torch.empty(sum(_align(int(i.coef_count)) for i in infos), dtype=torch.uint8, device=dev)
-    block = torch.empty(total, dtype=torch.uint8, device=dev)
-    blk = staging.acquire(total)
-    desc = blk[:64 * n].view(_ENC_DESC)
-    blk[o_qt:o_qt + 384].view(np.uint16)[:] = qt.reshape(-1)
-    base, planes = block.data_ptr(), scratch.data_ptr()
+    blk.acquire(staging, dev)
+    desc, planes, p_qtables, p_coef = blk.host("desc", _ENC_DESC), scratch.data_ptr(), blk.ptr("qtables"), blk.ptrs("coef")
+    blk.host("qtables", np.uint16)[:] = qt.reshape(-1)
     for i, (im, info) in enumerate(zip(images, infos)):
-        desc[i] = (im.data_ptr(), base + o_qt, planes, base + o_coef[i], info.width, info.height, im.stride(0), int(channel_order == "rgb"),
+        desc[i] = (im.data_ptr(), p_qtables, planes, p_coef[i], info.width, info.height, im.stride(0), int(channel_order == "rgb"),
                    info.hs, info.vs, info.mcus_x, info.mcus_y)
         planes += _align(int(info.coef_count))
-    job = None
-    if entropy:
-        blk[o_res:o_res + 16 * n] = 0
-        job = _entropy_job(blk[o_ent:o_ent + 64 * n].view(_ENT_DESC), infos, [base + o for o in o_coef], block[o_res:o_res + 16 * n], dev)
-    staging.upload(block, head)
-    args = (base, n, max(int(i.coef_count) // 64 for i in infos), max(int(i.height) for i in infos), max(int(i.width) for i in infos))
-    if entropy:
-        return args, (block, blk, head, total, o_coef, infos), (images, block, scratch), (base + o_ent, job)
-    return args, (block, blk, head, total, o_coef, infos), (images, block, scratch)
+    job = _entropy_job(blk, "entropy", infos, p_coef, dev) if entropy else None
+    blk.upload(before="coef")  # (the coefficient regions are only written on the device)
+    args = (blk.base, n, max(int(i.coef_count) // 64 for i in infos), max(int(i.height) for i in infos), max(int(i.width) for i in infos))
+    return _ForwardJob(args, blk, infos, qt, (images, scratch), job)
 
 
 def write_headers(qtables: np.ndarray, info: JpegInfo, restart_interval: int = 0) -> bytes:
@@ -627,44 +636,34 @@ def write_headers(qtables: np.ndarray, info: JpegInfo, restart_interval: int = 0
     return out[:size.value].tobytes()
 
 
-class _EntropyJob(NamedTuple):
-    """The device buffers of one ``pp_jpeg_entropy_encode_batch`` call: ``results`` (n x 16 bytes, a view of the uploaded
-    block), the streams (``out``: image i's at ``o_out[i]``, ``capacity[i]`` bytes), the scratch, and the infos."""
-
-    results: torch.Tensor
-    out: torch.Tensor
-    o_out: list
-    capacity: list
-    scratch: torch.Tensor
-    infos: list
-
-
-def _entropy_job(desc: np.ndarray, infos, coef_ptrs, results: torch.Tensor, dev) -> "_EntropyJob":
-    """Allocate the scratch and the stream buffers of a batch and fill ``desc`` (a host view of n ``_ENT_DESC`` rows that
-    the caller uploads). A stream gets ``pp_jpeg_encoded_bound`` bytes: no stream of its geometry is longer."""
+def _entropy_job(blk: StagedBlock, desc: str, infos, p_coef, dev) -> _EntropyJob:
+    """Allocate the scratch and the stream buffers of a batch, fill the n ``_ENT_DESC`` rows of region ``desc`` of ``blk`` and
+    clear its "results" region; ``p_coef``: the device addresses of the coefficients. The caller uploads the block. A stream
+    gets ``pp_jpeg_encoded_bound`` bytes: no stream of its geometry is longer."""
     shares, capacity = [], []
     for info in infos:
         one = int(_lib.lib.pp_jpeg_entropy_scratch_bytes(ctypes.byref(info), 1))
         bound = int(_lib.lib.pp_jpeg_encoded_bound(ctypes.byref(info)))
-        if one < 0 or bound < 0:
-            raise _lib.ProbPoseLibraryError("pp_jpeg_entropy_scratch_bytes", _lib.lib.pp_status_string(min(one, bound)).decode(), _lib.last_error())
+        _size("pp_jpeg_entropy_scratch_bytes", min(one, bound))
         shares.append(one)
         capacity.append(_align(bound))
     scratch = torch.empty(sum(shares), dtype=torch.uint8, device=dev)
     out = torch.empty(sum(capacity), dtype=torch.uint8, device=dev)
+    rows, p_results = blk.host(desc, _ENT_DESC), blk.ptr("results")
+    blk.host("results")[:] = 0
     o_out, s_at, o_at = [], scratch.data_ptr(), 0
     for i, info in enumerate(infos):
-        desc[i] = (coef_ptrs[i], s_at, out.data_ptr() + o_at, results.data_ptr() + 16 * i, capacity[i], info.hs, info.vs, info.mcus_x,
+        rows[i] = (p_coef[i], s_at, out.data_ptr() + o_at, p_results + 16 * i, capacity[i], info.hs, info.vs, info.mcus_x,
                    info.mcus_y, 0)
         o_out.append(o_at)
         s_at += shares[i]
         o_at += capacity[i]
-    return _EntropyJob(results, out, o_out, capacity, scratch, list(infos))
+    return _EntropyJob(blk.ptr(desc), blk.device("results"), out, o_out, capacity, scratch, list(infos), blk)
 
 
-def _entropy_launch(desc_ptr: int, job: "_EntropyJob", stream) -> None:
+def _entropy_launch(job: _EntropyJob, stream) -> None:
     global entropy_device_calls
-    _lib.call("pp_jpeg_entropy_encode_batch", desc_ptr, len(job.infos), max(int(i.coef_count) // 64 for i in job.infos), stream.cuda_stream)
+    _lib.call("pp_jpeg_entropy_encode_batch", job.desc_ptr, len(job.infos), max(int(i.coef_count) // 64 for i in job.infos), stream.cuda_stream)
     entropy_device_calls += 1
 
 
@@ -689,46 +688,58 @@ def _entropy_collect(job: "_EntropyJob", qtables, stream, staging) -> List[bytes
     return [write_headers(qt, info) + blk[o:o + sz].tobytes() + b"\xff\xd9" for qt, info, o, sz in zip(qtables, job.infos, offs, sizes)]
 
 
+def _stage_entropy(coefficients, dev, staging) -> _EntropyJob:
+    """Pack the descriptor table, the result slots and the coefficients of a batch into the pinned buffer and upload them
+    with one copy."""
+    n = len(coefficients)
+    # the block: descriptors (n x 64 bytes) | result slots (n x 16 bytes) | per image: coefficients (int16)
+    blk = StagedBlock([("desc", 64 * n), ("results", 16 * n)], [("coef", [2 * int(c.info.coef_count) for c in coefficients])]).acquire(staging, dev)
+    for view, c in zip(blk.hosts("coef", np.int16), coefficients):
+        view[:] = np.asarray(c.coef).reshape(-1)
+    job = _entropy_job(blk, "desc", [c.info for c in coefficients], blk.ptrs("coef"), dev)
+    blk.upload()
+    return job
+
+
 def entropy_encode_device(coefficients: Sequence[JpegCoefficients], device=None, staging=None) -> List[bytes]:
     """The files ``entropy_encode`` gives for a list of ``JpegCoefficients`` (three components, geometry of ``encode_plan``),
     coded on the device: the coefficient arrays are uploaded with the table in one copy, then ONE
     ``pp_jpeg_entropy_encode_batch`` call (seven launches) on the current stream. Invalid coefficients raise what
     ``entropy_encode`` raises for them (``ProbPoseLibraryError``, PP_ERR_INVALID_ARG)."""
-    from .transforms import BatchStaging
-
     coefficients = list(coefficients)
-    n = len(coefficients)
-    if n == 0:
+    if len(coefficients) == 0:
         return []
-    dev = torch.device(device or "cuda")
-    if dev.type != "cuda":
-        raise RuntimeError("probpose_code_amd.jpeg.entropy_encode_device runs on the GPU only (no CPU fallback)")
+    dev = _cuda_device(device or "cuda", "entropy_encode_device")
     staging = staging if staging is not None else BatchStaging()
-    infos, qts = [], []
+    qts = []
     for c in coefficients:
         coef, qt = np.asarray(c.coef), np.ascontiguousarray(c.qtables, np.uint16)
         if qt.shape != (3, 64) or coef.size != c.info.coef_count or coef.dtype != np.int16:
             raise ValueError("the encoder takes three (64,) tables and info.coef_count int16 coefficients")
         write_headers(qt, c.info)  # (refuses an info that is no encode_plan result, and tables outside 1..255, before any GPU work)
-        infos.append(c.info)
         qts.append(qt)
-    # the block: descriptors (n x 64 bytes) | result slots (n x 16 bytes) | per image: coefficients (int16)
-    o_res = _align(64 * n)
-    off, o_coef = _align(o_res + 16 * n), []
-    for info in infos:
-        o_coef.append(off)
-        off = _align(off + 2 * int(info.coef_count))
-    block = torch.empty(off, dtype=torch.uint8, device=dev)
-    blk = staging.acquire(off)
-    blk[o_res:o_res + 16 * n] = 0
-    for o, c in zip(o_coef, coefficients):
-        blk[o:o + 2 * c.coef.size].view(np.int16)[:] = np.asarray(c.coef).reshape(-1)
-    base = block.data_ptr()
-    job = _entropy_job(blk[:64 * n].view(_ENT_DESC), infos, [base + o for o in o_coef], block[o_res:o_res + 16 * n], dev)
-    staging.upload(block, off)
+    job = _stage_entropy(coefficients, dev, staging)
     stream = torch.cuda.current_stream(dev)
-    _entropy_launch(base, job, stream)
+    _entropy_launch(job, stream)
     return _entropy_collect(job, qts, stream, staging)
+
+
+def _forward(images, quality, subsampling, channel_order, device, staging, entropy: bool) -> Optional[_ForwardJob]:
+    """What ``forward_batch`` and ``_encode_batch_device`` begin with: the options and images checked, the batch staged and
+    ``pp_jpeg_forward_batch`` enqueued on the current stream. None for no images."""
+    global forward_calls
+    if channel_order not in ("bgr", "rgb"):
+        raise ValueError(f"channel_order must be 'bgr' or 'rgb', got {channel_order!r}")
+    qt = quality_tables(quality)
+    if subsampling not in SUBSAMPLING:
+        raise ValueError(f"subsampling must be one of {sorted(SUBSAMPLING)}, got {subsampling!r}")
+    images, dev = _encoder_images(list(images), device)
+    if len(images) == 0:
+        return None
+    job = _stage_encode(images, qt, subsampling, channel_order, dev, staging if staging is not None else BatchStaging(), entropy)
+    _lib.call("pp_jpeg_forward_batch", *job.args, torch.cuda.current_stream(dev).cuda_stream)
+    forward_calls += 1
+    return job
 
 
 def forward_batch(images: Sequence, quality: int = 75, subsampling: str = "4:2:0", channel_order: str = "bgr", device=None,
@@ -737,28 +748,14 @@ def forward_batch(images: Sequence, quality: int = 75, subsampling: str = "4:2:0
     ``pp_jpeg_forward_batch`` call (two launches) on the current stream, then one copy of all coefficients into the pinned
     buffer of ``staging`` (a ``transforms.BatchStaging``). Returns what ``entropy_decode`` gives for the finished files; with
     ``copy=False`` the coefficient arrays are views of the pinned buffer, valid until ``staging`` is used again."""
-    global forward_calls
-    from .transforms import BatchStaging
-
-    if channel_order not in ("bgr", "rgb"):
-        raise ValueError(f"channel_order must be 'bgr' or 'rgb', got {channel_order!r}")
-    qt = quality_tables(quality)
-    if subsampling not in SUBSAMPLING:
-        raise ValueError(f"subsampling must be one of {sorted(SUBSAMPLING)}, got {subsampling!r}")
-    images, dev = _encoder_images(list(images), device)
-    n = len(images)
-    if n == 0:
+    job = _forward(images, quality, subsampling, channel_order, device, staging, False)
+    if job is None:
         return []
-    staging = staging if staging is not None else BatchStaging()
-    args, (block, blk, head, total, o_coef, infos), keep = _stage_encode(images, qt, subsampling, channel_order, dev, staging)
-    stream = torch.cuda.current_stream(dev)
-    _lib.call("pp_jpeg_forward_batch", *args, stream.cuda_stream)
-    forward_calls += 1
-    staging.buf[head:total].copy_(block[head:total], non_blocking=True)
-    stream.synchronize()  # the coefficients are in the pinned buffer; images, block and scratch (``keep``) are no longer read
-    del keep
-    views = [blk[o:o + 2 * int(info.coef_count)].view(np.int16) for o, info in zip(o_coef, infos)]
-    return [JpegCoefficients(info, v.copy() if copy else v, qt) for v, info in zip(views, infos)]
+    blk = job.block
+    head = blk.head_bytes("coef")
+    blk.staging.buf[head:blk.total].copy_(blk.dev[head:blk.total], non_blocking=True)
+    torch.cuda.current_stream(blk.dev.device).synchronize()  # the coefficients are in the pinned buffer; ``job`` is no longer read
+    return [JpegCoefficients(info, v.copy() if copy else v, job.qt) for v, info in zip(blk.hosts("coef", np.int16), job.infos)]
 
 
 def encode_batch(images: Sequence, quality: int = 75, subsampling: str = "4:2:0", channel_order: str = "bgr", restart_interval: int = 0,
@@ -782,8 +779,7 @@ def encode_batch(images: Sequence, quality: int = 75, subsampling: str = "4:2:0"
         raise ValueError(f"restart_interval must be an int in 0..65535, got {restart_interval!r}")
     if isinstance(images, (torch.Tensor, np.ndarray)):
         raise ValueError("encode_batch takes a sequence of (H, W, 3) images; imwrite_device takes one")
-    if entropy not in ENTROPY:
-        raise ValueError(f"entropy must be one of {ENTROPY}, got {entropy!r}")
+    _check_entropy(entropy)
     if entropy == "device":
         if int(restart_interval) != 0:
             raise ValueError("entropy='device' codes without restart intervals: restart_interval must be 0")
@@ -797,26 +793,12 @@ def encode_batch(images: Sequence, quality: int = 75, subsampling: str = "4:2:0"
 
 def _encode_batch_device(images, quality, subsampling, channel_order, device, staging) -> List[bytes]:
     """``encode_batch`` with both halves on the device: nine launches on the current stream, no coefficient copy."""
-    global forward_calls
-    from .transforms import BatchStaging
-
-    if channel_order not in ("bgr", "rgb"):
-        raise ValueError(f"channel_order must be 'bgr' or 'rgb', got {channel_order!r}")
-    qt = quality_tables(quality)
-    if subsampling not in SUBSAMPLING:
-        raise ValueError(f"subsampling must be one of {sorted(SUBSAMPLING)}, got {subsampling!r}")
-    images, dev = _encoder_images(list(images), device)
-    if len(images) == 0:
+    job = _forward(images, quality, subsampling, channel_order, device, staging, True)
+    if job is None:
         return []
-    staging = staging if staging is not None else BatchStaging()
-    args, _, keep, (ent_ptr, job) = _stage_encode(images, qt, subsampling, channel_order, dev, staging, entropy=True)
-    stream = torch.cuda.current_stream(dev)
-    _lib.call("pp_jpeg_forward_batch", *args, stream.cuda_stream)
-    forward_calls += 1
-    _entropy_launch(ent_ptr, job, stream)
-    files = _entropy_collect(job, [qt] * len(images), stream, staging)
-    del keep
-    return files
+    stream = torch.cuda.current_stream(job.block.dev.device)
+    _entropy_launch(job.entropy, stream)
+    return _entropy_collect(job.entropy, [job.qt] * len(job.infos), stream, job.block.staging)  # (``job`` lives until the streams are down)
 
 
 def imwrite_device(path: str, image, **kw) -> None:

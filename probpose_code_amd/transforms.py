@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from .registry import OVERRIDE_REFERENCE_NAMES, TRANSFORMS
+from .staging import BatchStaging, _align  # noqa: F401  (BatchStaging is imported from here as well)
 
 
 def bbox_xywh2xyxy(bbox: np.ndarray) -> np.ndarray:
@@ -125,34 +126,6 @@ def warp_affine_crops(img: torch.Tensor, mats: np.ndarray, input_size: Tuple[int
     _lib.call("pp_warp_affine_u8", img.data_ptr(), img.shape[0], img.shape[1], img.shape[2], inv.data_ptr(), out.data_ptr(), n, h, w,
               torch.cuda.current_stream(img.device).cuda_stream)
     return out
-
-
-class BatchStaging:
-    """The reused pinned host buffer behind ``warp_affine_crops_batch``: the tables and the host images of one batch are
-    packed into it and go to the device in ONE host-to-device copy. An event recorded after the copy guards it: the next
-    batch waits for that copy before it writes into the buffer (a copy in flight still reads it)."""
-
-    def __init__(self):
-        self.buf: Optional[torch.Tensor] = None
-        self.ev: Optional[torch.cuda.Event] = None
-
-    def acquire(self, nbytes: int) -> np.ndarray:
-        if self.ev is not None:
-            self.ev.synchronize()
-        if self.buf is None or self.buf.numel() < nbytes:
-            self.buf = torch.empty(1 << max(20, (nbytes - 1).bit_length()), dtype=torch.uint8, pin_memory=True)
-        return self.buf.numpy()
-
-    def upload(self, dev: torch.Tensor, nbytes: int) -> None:
-        stream = torch.cuda.current_stream(dev.device)
-        dev[:nbytes].copy_(self.buf[:nbytes], non_blocking=True)
-        if self.ev is None:
-            self.ev = torch.cuda.Event()
-        self.ev.record(stream)
-
-
-def _align(v: int, a: int = 256) -> int:
-    return (v + a - 1) // a * a
 
 
 def warp_affine_crops_batch(images: Sequence, crop_image: Sequence[int], mats: np.ndarray, input_size: Tuple[int, int],

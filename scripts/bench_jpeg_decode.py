@@ -100,7 +100,8 @@ def main():
 
         coefs = [jpeg.entropy_decode(p) for p in paths[:16]]
         for n in (1, 16):
-            call_args, out, keep = jpeg._stage(coefs[:n], dev, staging, None, None)
+            job = jpeg._stage(coefs[:n], dev, staging, None, None)
+            call_args = job.args
             stream = torch.cuda.current_stream(dev).cuda_stream
             for _ in range(3):
                 _lib.call("pp_jpeg_reconstruct_bgr_batch", *call_args, stream)
@@ -117,7 +118,7 @@ def main():
             med = statistics.median(us)
             print(json.dumps(dict(figure="reconstruct_call", size=size, n=n, device_event_us=round(med, 1), min_us=round(min(us), 1), bytes_moved=int(moved),
                                   gb_per_s=round(moved / med / 1e3, 1), share_of_hbm_peak=round(moved / (med * 1e-6) / HBM_PEAK, 4))), flush=True)
-            del out, keep
+            del job
 
 
 if __name__ == "__main__":

@@ -101,7 +101,8 @@ def main():
 
         for n in (1, 16):
             qt = jpeg.quality_tables(75)
-            call_args, (block, blk, head, total, o_coef, infos), keep = jpeg._stage_encode(frames[:n], qt, "4:2:0", "rgb", dev, staging)
+            job = jpeg._stage_encode(frames[:n], qt, "4:2:0", "rgb", dev, staging)
+            call_args, infos = job.args, job.infos
             stream = torch.cuda.current_stream(dev).cuda_stream
             for _ in range(3):
                 _lib.call("pp_jpeg_forward_batch", *call_args, stream)
@@ -119,7 +120,7 @@ def main():
             med = statistics.median(us)
             print(json.dumps(dict(figure="forward_call", size=size, n=n, device_event_us=round(med, 1), min_us=round(min(us), 1), bytes_moved=int(moved), sclk_mhz=sclk,
                                   gb_per_s=round(moved / med / 1e3, 1), share_of_hbm_peak=round(moved / (med * 1e-6) / HBM_PEAK, 4))), flush=True)
-            del keep, block
+            del job
 
 
 if __name__ == "__main__":

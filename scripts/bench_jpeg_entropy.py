@@ -61,10 +61,11 @@ def main():
 
         for n in (1, 16):
             qt = jpeg.quality_tables(75)
-            call_args, _, keep, (ent_ptr, job) = jpeg._stage_encode(frames[:n], qt, "4:2:0", "rgb", dev, staging, entropy=True)
+            forward = jpeg._stage_encode(frames[:n], qt, "4:2:0", "rgb", dev, staging, entropy=True)
+            job = forward.entropy
             stream = torch.cuda.current_stream(dev)
-            _lib.call("pp_jpeg_forward_batch", *call_args, stream.cuda_stream)
-            ent_args = (ent_ptr, n, max(int(i.coef_count) // 64 for i in job.infos), stream.cuda_stream)
+            _lib.call("pp_jpeg_forward_batch", *forward.args, stream.cuda_stream)
+            ent_args = (job.desc_ptr, n, max(int(i.coef_count) // 64 for i in job.infos), stream.cuda_stream)
             for _ in range(3):
                 _lib.call("pp_jpeg_entropy_encode_batch", *ent_args)
             torch.cuda.synchronize()
@@ -82,7 +83,7 @@ def main():
             print(json.dumps(dict(figure="entropy_call", size=size, n=n, device_event_us=round(statistics.median(us), 1), min_us=round(min(us), 1),
                                   max_us=round(max(us), 1), rounds=args.rounds, stream_bytes=int(res["bytes"].sum()),
                                   coefficient_bytes=int(sum(2 * int(i.coef_count) for i in job.infos)), sclk_mhz=sclk)), flush=True)
-            del keep, job
+            del forward, job
 
         for n in (1, 16):
             for workers in (1, 8):

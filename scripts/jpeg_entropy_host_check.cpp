@@ -1,25 +1,21 @@
 // Stand-alone host check of the device Huffman coder (csrc/pp_jpeg_entropy.hip): its phases restated sequentially on the host
-// with the coder's own __host__ __device__ pieces (block addressing and DC predictor, the code walk, the bit packer, the
-// scratch layout, the byte order of the packed words), compared byte for byte with entropy_encode of csrc/pp_jpeg_enc_host.h
-// on seeded coefficient arrays: seven sizes x three samplings x four densities x two amplitudes x three special forms (plain;
-// a last Cr block ending in 1023 at zigzag 63; single AC values at zigzag 16 / 17 / 33 / 49 / 63 with DC differences of
-// +-2047). What it does not run: the workgroup scans and the grids - those are the GPU tests' (tests/test_jpeg_entropy_gpu.py).
-// No GPU is used; the kernels in the included file are compiled but never launched.
+// around the coder's own core (csrc/pp_jpeg_entropy_core.h: block addressing and DC predictor, the code walk, the bit packer,
+// the scratch layout, the byte order of the packed words - the code the kernels run), compared byte for byte with
+// entropy_encode of csrc/pp_jpeg_enc_host.h on seeded coefficient arrays: seven sizes x three samplings x four densities x
+// two amplitudes x three special forms (plain; a last Cr block ending in 1023 at zigzag 63; single AC values at zigzag
+// 16 / 17 / 33 / 49 / 63 with DC differences of +-2047). What it does not run: the workgroup scans and the grids - those are
+// the GPU tests' (tests/test_jpeg_entropy_gpu.py). A program for a sanitiser build on a CPU machine; no GPU is used:
 //
-//   hipcc -x hip -O1 -g -std=c++17 --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
-//         -Iprobpose_code_amd/csrc scripts/jpeg_entropy_host_check.cpp -o jpeg_entropy_host_check -fsanitize=address,undefined
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all scripts/jpeg_entropy_host_check.cpp -o jpeg_entropy_host_check
 //   ./jpeg_entropy_host_check        ->  "504 cases, 0 failures"
-#include "../probpose_code_amd/csrc/pp_jpeg_entropy.hip"
-
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <random>
 #include <vector>
 
-namespace pp {
-void set_error(const char*, ...) {}
-void count_launch(const char*) {}
-}  // namespace pp
+#include "../probpose_code_amd/csrc/pp_jpeg_enc_host.h"
+#include "../probpose_code_amd/csrc/pp_jpeg_entropy_core.h"
 
 using namespace pp;
 
