@@ -899,8 +899,11 @@ int pp_jpeg_entropy_encode_batch(const pp_jpeg_ent_desc* descriptors, int n, lon
  * stream is cut into subsequences of 128 raw bytes, each decoded by one thread from a guessed state (bit position, block
  * inside the MCU, zigzag index); a decoder started wrongly falls into step with the true one after a short distance, so
  * passes that hand every subsequence its predecessor's exit state converge, and a final check proves it: an image is
- * accepted only if every subsequence's entry equals its predecessor's exit. Files without a restart interval only; an
- * image the passes did not synchronise is PP_ERR_UNSUPPORTED, never wrong data. */
+ * accepted only if every subsequence's entry equals its predecessor's exit. An image the passes did not synchronise is
+ * PP_ERR_UNSUPPORTED, never wrong data. A file with a restart interval decodes as well: a decoder that reaches an RSTn
+ * marker leaves it in the true decoder's state whatever its own entry was, so inside such a file the synchronisation
+ * distance is bounded by the interval's length; the markers' numbers, their count and the blocks between them are checked
+ * on the proven chain (reason 7). */
 
 /* One Huffman table in the form the device reads (the host decoder's own lookup): look[next 9 bits] = length << 8 | symbol
  * for codes of at most 9 bits (0: longer); maxcode[len] the largest code of a length (-1: none; [17] = INT32_MAX);
@@ -924,7 +927,8 @@ typedef struct {
 
 /* What the decoder leaves per image. status: PP_OK, PP_ERR_UNSUPPORTED (reason 1: not synchronised within sync_passes;
  * 2: data ends before the last block; 3: a bit pattern that is no code, a category or a zigzag index no baseline stream
- * holds; 4: a DC coefficient outside int16; 5: data after the last block) or PP_ERR_INVALID_ARG (reason 6: the
+ * holds; 4: a DC coefficient outside int16; 5: data after the last block; 7: a restart marker missing, out of order, in
+ * excess, inside a block or an MCU, or not behind the interval's last MCU) or PP_ERR_INVALID_ARG (reason 6: the
  * descriptor describes no file of the subset). On any status but PP_OK the coefficients are undefined. passes: the
  * synchronisation launches that were needed (1 + the last one in which a subsequence was decoded again); blocks: the
  * blocks counted along the chain. */
@@ -936,7 +940,8 @@ typedef struct {
  * entropy-coded segment, byte stuffing included, only read (fewer than 2^28 bytes); tables: its 2 x ncomp
  * pp_jpeg_huff_table, 4-byte aligned; coef: mcus_x * mcus_y * blocks-per-MCU * 64 int16 out in the layout of
  * pp_jpeg_desc.coef, 16-byte aligned; scratch: the image's share of pp_jpeg_huffman_scratch_bytes, 16-byte aligned,
- * contents undefined before and after; result: the image's slot. */
+ * contents undefined before and after; result: the image's slot; restart_interval: the file's (pp_jpeg_info's), 0: none -
+ * then no byte of the stream is taken for a marker. */
 typedef struct {
     const uint8_t* stream;
     const pp_jpeg_huff_table* tables;
@@ -944,7 +949,7 @@ typedef struct {
     uint8_t* scratch;
     pp_jpeg_hd_result* result;
     int64_t stream_bytes;
-    int32_t hs, vs, mcus_x, mcus_y, ncomp, reserved;
+    int32_t hs, vs, mcus_x, mcus_y, ncomp, restart_interval;
 } pp_jpeg_hd_desc;
 
 /* Host only, re-entrant, no HIP call, no per-bit work: the headers of a file through the parser of pp_jpeg_probe, and the
@@ -952,8 +957,16 @@ typedef struct {
  * pp_jpeg_probe refuses, a file with a restart interval (it keeps the host Huffman decoder), a segment that no EOI marker
  * ends, a segment of 2^28 bytes or more. */
 int pp_jpeg_scan_prepare(const void* data_host, size_t size, pp_jpeg_scan* scan);
+/* The same (added under version 4 as well), but a file with a restart interval is accepted: scan->info.restart_interval is
+ * set and the segment runs from behind the SOS header to the first marker that is no RSTn, which must be EOI - FF D0..D7
+ * and the FF fill bytes in front of them belong to it. Still a search for FF bytes: the markers' order and number are the
+ * device decoder's to check. More than 7 fill bytes in front of an RSTn are PP_ERR_UNSUPPORTED (the device decoder looks
+ * no further; the host decoder takes such a file). Without a restart interval: status, reason and every byte of *scan are
+ * pp_jpeg_scan_prepare's. */
+int pp_jpeg_scan_prepare_restart(const void* data_host, size_t size, pp_jpeg_scan* scan);
 /* Host only. Bytes of scratch for n images with segments of stream_bytes_host[i] bytes (infos_host: their pp_jpeg_info),
- * each image's share a multiple of 256: image i's share starts at the sum of the shares before it. < 0: error. */
+ * each image's share a multiple of 256: image i's share starts at the sum of the shares before it; a file with a restart
+ * interval has a larger one. < 0: error. */
 long long pp_jpeg_huffman_scratch_bytes(const pp_jpeg_info* infos_host, const long long* stream_bytes_host, int n);
 /* The coefficients of n images of any mix of sizes and sampling in sync_passes + 4 launches (sync_passes x "jpeg_hd_sync",
  * "jpeg_hd_scan", "jpeg_hd_zero", "jpeg_hd_write", "jpeg_hd_dc" of pp_launch_count). descriptors: n pp_jpeg_hd_desc on

@@ -176,6 +176,7 @@ SIGNATURES = {
     "pp_jpeg_entropy_scratch_bytes": (c_longlong, [_P, c_int]),
     "pp_jpeg_entropy_encode_batch": (c_int, [_P, c_int, c_longlong, _P]),
     "pp_jpeg_scan_prepare": (c_int, [_P, ctypes.c_size_t, _P]),
+    "pp_jpeg_scan_prepare_restart": (c_int, [_P, ctypes.c_size_t, _P]),
     "pp_jpeg_huffman_scratch_bytes": (c_longlong, [_P, _P, c_int]),
     "pp_jpeg_huffman_decode_batch": (c_int, [_P, c_int, c_longlong, c_longlong, c_int, _P]),
 }

@@ -12,7 +12,9 @@
 // scan_prepare (pp_jpeg_scan_prepare) is the host's share when the Huffman codes are decoded on the device as well
 // (csrc/pp_jpeg_huffdec.hip): the same header parser, the components' tables in the form the device reads, and the bounds of
 // the entropy-coded segment by a search for FF bytes - no bit of it is decoded here. It refuses what the parser refuses,
-// files with a restart interval (they keep entropy_decode) and a segment that no EOI marker ends.
+// files with a restart interval and a segment that no EOI marker ends. scan_prepare_restart (pp_jpeg_scan_prepare_restart)
+// is the same search that takes a file with a restart interval as well: its RSTn markers, and the fill bytes in front of
+// them, belong to the segment, which the first other marker ends. Their order and number are the device decoder's to check.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -50,6 +52,7 @@ static constexpr uint8_t kNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24,
                                      30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 constexpr int LOOK_BITS = 9;
+constexpr int kMaxMarkerFill = 8;  // FF bytes of a restart marker the device decoder recognises (HD_MAX_FILL): the marker's own and seven fill bytes
 
 struct HuffTable {
     bool present = false;
@@ -404,8 +407,10 @@ inline int entropy_decode(const uint8_t* data, size_t size, int16_t* coef, long 
 
 // pp_jpeg_scan_prepare: what the device Huffman decoder (csrc/pp_jpeg_huffdec.hip) needs of a file, read from its headers.
 // No bit of the entropy-coded segment is decoded here: its end is the first FF that no 00 follows, and the marker there
-// must be EOI (what entropy_decode demands behind the last MCU).
-inline int scan_prepare(const uint8_t* data, size_t size, pp_jpeg_scan* scan) {
+// must be EOI (what entropy_decode demands behind the last MCU). restart: a file with a restart interval is taken too; in
+// it an FF run that D0..D7 ends is part of the segment. A run of more than kMaxMarkerFill FF bytes there is refused (the
+// host decoder takes it, the device decoder's reader looks no further).
+inline int scan_prepare(const uint8_t* data, size_t size, pp_jpeg_scan* scan, bool restart = false) {
     if (!data || !scan) {
         std::snprintf(g_reason, sizeof(g_reason), "NULL argument");
         return PP_ERR_INVALID_ARG;
@@ -416,7 +421,7 @@ inline int scan_prepare(const uint8_t* data, size_t size, pp_jpeg_scan* scan) {
     const int st = parse_header(data, size, h, info);
     if (st != PP_OK) return st;
     fill_info(h, info);
-    if (h.restart_interval != 0) return refuse(info, "restart interval: the device Huffman decoder takes files without one");
+    if (h.restart_interval != 0 && !restart) return refuse(info, "restart interval: the device Huffman decoder takes files without one");
     for (int c = 0; c < h.ncomp; ++c) {
         std::memcpy(scan->qtables + 64 * c, h.q[h.comp[c].tq], 64 * sizeof(uint16_t));
         const HuffTable* src[2] = {&h.dc[h.comp[c].td], &h.ac[h.comp[c].ta]};
@@ -433,8 +438,16 @@ inline int scan_prepare(const uint8_t* data, size_t size, pp_jpeg_scan* scan) {
         const void* ff = end < size ? std::memchr(data + end, 0xFF, size - end) : nullptr;
         if (!ff) return refuse(info, "no EOI after the scan");
         end = (size_t)(reinterpret_cast<const uint8_t*>(ff) - data);
-        if (end + 1 < size && data[end + 1] == 0x00) end += 2;  // a stuffed data byte
-        else break;
+        if (end + 1 < size && data[end + 1] == 0x00) {  // a stuffed data byte
+            end += 2;
+            continue;
+        }
+        if (h.restart_interval == 0) break;
+        size_t m = end;
+        while (m < size && data[m] == 0xFF) ++m;
+        if (m >= size || data[m] < 0xD0 || data[m] > 0xD7) break;
+        if (m - end > (size_t)kMaxMarkerFill) return refuse(info, "more than 7 fill bytes in front of a restart marker");
+        end = m + 1;
     }
     size_t p = end;
     while (p < size && data[p] == 0xFF) ++p;

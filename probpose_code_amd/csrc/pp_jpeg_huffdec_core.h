@@ -10,6 +10,16 @@
 // leaves the rest of the state alone. Whatever no valid stream holds - such a pattern, a DC category above 11, an AC
 // category above 10, a zigzag index past 63 - is decoded by a fixed rule and reported in `bad`: a speculative decoder meets
 // these legitimately, on the true chain they refuse the image.
+//
+// With a restart interval (pp_jpeg_hd_desc.restart_interval > 0) the segment holds RSTn markers: an FF whose successor,
+// behind at most HD_MAX_FILL - 1 further FF fill bytes, is D0..D7 (a data FF is always followed by 00, so the raw bytes say
+// which is which). The reader feeds zeros from a marker on. A decoder that stands between two MCUs with fewer than 8 data
+// bits in front of a marker, which are padding (padding() below), jumps to the byte behind it with the state (block 0, DC
+// due) - the true decoder's state there, whatever the decoder's own entry was: a marker is a hard synchronisation point.
+// Everywhere else it decodes on, and one that has read a symbol across the marker - as one inside a block or an MCU must -
+// makes the same jump and reports BAD_RESTART. The sink is told of every jump: on the true chain the j-th marker must be
+// D0 + (j - 1) mod 8 and stand in front of block j * restart_interval * blocks-per-MCU. With restart_interval == 0 no byte
+// is a marker and nothing here differs.
 #pragma once
 #include <cstdint>
 
@@ -24,6 +34,7 @@ constexpr int HD_INNER = 32;       // iterations a workgroup makes over its own 
 constexpr int HD_MAX_PASSES = 64;  // largest sync_passes
 constexpr int HD_DEFAULT_PASSES = 3;  // covers ((3 - 1) * HD_INNER + 2) * HD_S = 8448 bytes of synchronisation distance
 constexpr long long HD_MAX_STREAM = 1ll << 28;  // bytes: bit positions stay below 2^31
+constexpr int HD_MAX_FILL = jpeg::kMaxMarkerFill;  // FF bytes of a marker the reader recognises: the marker's own and seven fill bytes
 constexpr int HD_LOOK_BITS = 9;
 constexpr int HD_TABLE_WORDS = (int)(sizeof(pp_jpeg_huff_table) / 4);
 
@@ -32,9 +43,9 @@ static_assert(sizeof(pp_jpeg_huff_table) == 1424 && sizeof(pp_jpeg_hd_desc) == 7
 static_assert(offsetof(pp_jpeg_hd_desc, stream_bytes) == 40, "five pointers, then the stream's length");
 
 // reasons of a result slot (pp_jpeg_hd_result.reason)
-enum { HD_OK = 0, HD_NOT_SYNCHRONISED = 1, HD_ENDS_EARLY = 2, HD_BAD_CODE = 3, HD_DC_RANGE = 4, HD_TRAILING = 5, HD_BAD_DESC = 6 };
+enum { HD_OK = 0, HD_NOT_SYNCHRONISED = 1, HD_ENDS_EARLY = 2, HD_BAD_CODE = 3, HD_DC_RANGE = 4, HD_TRAILING = 5, HD_BAD_DESC = 6, HD_RESTART = 7 };
 // bits of `bad`
-enum { BAD_CODE = 1u, BAD_CATEGORY = 2u, BAD_INDEX = 4u, BAD_DC_RANGE = 8u };
+enum { BAD_CODE = 1u, BAD_CATEGORY = 2u, BAD_INDEX = 4u, BAD_DC_RANGE = 8u, BAD_RESTART = 16u };
 
 struct State {
     uint32_t pos;  // raw bit position
@@ -56,18 +67,19 @@ PP_HOST_DEVICE uint32_t canonical(const Stream& s, uint32_t pos) {
 // What a descriptor's numbers say: blocks per MCU, luma blocks per MCU, blocks of the scan; valid = 0 for a descriptor that
 // describes no file of the subset.
 struct Geometry {
-    int valid, bpm, lum;
+    int valid, bpm, lum, restart;  // restart: the descriptor's restart interval
     long long nblk, mcus;
 };
 PP_HOST_DEVICE Geometry geometry(const pp_jpeg_hd_desc& d) {
-    Geometry g{0, 1, 1, 0, 0};
+    Geometry g{0, 1, 1, 0, 0, 0};
     const bool sampling = d.ncomp == 1 ? (d.hs == 1 && d.vs == 1)
                                        : (d.ncomp == 3 && ((d.hs == 1 && d.vs == 1) || (d.hs == 2 && d.vs == 1) || (d.hs == 2 && d.vs == 2)));
     if (!sampling || d.mcus_x < 1 || d.mcus_y < 1 || d.mcus_x > 8192 || d.mcus_y > 8192 || !d.stream || !d.tables || !d.coef || !d.scratch ||
-        !d.result || d.stream_bytes < 0 || d.stream_bytes >= HD_MAX_STREAM || ((uintptr_t)d.coef & 15) || ((uintptr_t)d.scratch & 15) ||
+        !d.result || d.restart_interval < 0 || d.restart_interval > 65535 || d.stream_bytes < 0 || d.stream_bytes >= HD_MAX_STREAM || ((uintptr_t)d.coef & 15) || ((uintptr_t)d.scratch & 15) ||
         ((uintptr_t)d.tables & 3) || ((uintptr_t)d.result & 3))
         return g;
     g.valid = 1;
+    g.restart = d.restart_interval;
     g.lum = d.hs * d.vs;
     g.bpm = d.ncomp == 1 ? 1 : g.lum + 2;
     g.mcus = (long long)d.mcus_x * d.mcus_y;
@@ -77,10 +89,12 @@ PP_HOST_DEVICE Geometry geometry(const pp_jpeg_hd_desc& d) {
 
 // An image's share of scratch: byte offsets of its regions.
 struct Layout {
-    long long nsub, nwg, o_entry, o_exit, o_cnt, o_first, o_bexit, o_open, total;
+    long long nsub, nwg, o_entry, o_exit, o_cnt, o_first, o_bexit, o_open, o_mfirst, total;
 };
 PP_HOST_DEVICE long long align16(long long v) { return (v + 15) / 16 * 16; }
-PP_HOST_DEVICE Layout layout(long long stream_bytes) {
+// restart: the share of a file with a restart interval also holds every subsequence's first marker ordinal (o_mfirst);
+// without one the share is what it was (o_mfirst = 0: no such region).
+PP_HOST_DEVICE Layout layout(long long stream_bytes, bool restart = false) {
     Layout L;
     L.nsub = stream_bytes > 0 ? (stream_bytes + HD_S - 1) / HD_S : 1;
     L.nwg = (L.nsub + HD_WG - 1) / HD_WG;
@@ -90,13 +104,16 @@ PP_HOST_DEVICE Layout layout(long long stream_bytes) {
     L.o_first = align16(L.o_cnt + 4 * L.nsub);
     L.o_bexit = align16(L.o_first + 4 * L.nsub);
     L.o_open = align16(L.o_bexit + 2 * 8 * L.nwg);
-    L.total = (L.o_open + 4 * L.nwg + 255) / 256 * 256;
+    L.o_mfirst = restart ? align16(L.o_open + 4 * L.nwg) : 0;
+    L.total = ((restart ? L.o_mfirst + 4 * L.nsub : L.o_open + 4 * L.nwg) + 255) / 256 * 256;
     return L;
 }
 
 struct Header {  // first 64 bytes of the share
-    uint32_t passes, flags, synced, total, endpos, done;
+    uint32_t passes, flags, synced, total, endpos, done, markers;
 };
+// Markers a file of this geometry holds: one in front of every interval but the first.
+PP_HOST_DEVICE long long markers_due(const Geometry& G, int ri) { return ri > 0 ? (G.mcus + ri - 1) / ri - 1 : 0; }
 
 // Index in d.coef (in blocks) of block g of the scan; component <- 0 luma, 1 Cb, 2 Cr.
 PP_HOST_DEVICE long long block_index(const pp_jpeg_hd_desc& d, const Geometry& G, long long g, int& comp) {
@@ -120,14 +137,29 @@ PP_HOST_DEVICE long long component_block(const pp_jpeg_hd_desc& d, const Geometr
     return (my * d.vs + j / d.hs) * ((long long)d.mcus_x * d.hs) + mx * d.hs + j % d.hs;
 }
 
+// The bytes of a marker whose first FF is raw byte i (fill bytes, FF and D0..D7: 2 .. HD_MAX_FILL + 1), 0: no marker starts
+// there. At most HD_MAX_FILL + 1 bytes are looked at.
+PP_HOST_DEVICE int marker_at(const Stream& s, long long i) {
+    if (byte_at(s, i) != 0xFFu) return 0;
+    int f = 1;
+    while (f < HD_MAX_FILL && byte_at(s, i + f) == 0xFFu) ++f;
+    const uint32_t code = byte_at(s, i + f);
+    return i + f < s.len && code >= 0xD0u && code <= 0xD7u ? f + 1 : 0;
+}
+
 // MSB-first reader from a raw bit position on. `limit`: the data bits loaded before the first data byte at or behind raw
-// byte `end_byte`, known as soon as that byte is loaded - the subsequence is done when consumed() reaches it.
+// byte `end_byte`, known as soon as that byte is loaded - the subsequence is done when consumed() reaches it. rst: the
+// stream holds restart markers; at the first one the reader ends its view of the stream (zeros from there on) and keeps
+// where it lies (mark: its first FF), the data bits loaded in front of it (mark_bits) and its length (skip). RST is a
+// template argument so that the reader of a file without a restart interval is the code it was: no test for a marker in its
+// loop.
+template <bool RST>
 struct Reader {
     Stream s;
     long long next, end_byte;
     uint64_t acc = 0;
     uint32_t prev;  // the raw byte in front of `next` (what makes a 00 a stuffed one)
-    int n = 0, loaded = 0, limit = 0x7fffffff;
+    int n = 0, loaded = 0, limit = 0x7fffffff, mark = -1, mark_bits = 0, skip = 0;  // (a stream is shorter than 2^28 bytes)
     PP_HOST_DEVICE Reader(const Stream& s_, uint32_t pos, long long end_byte_)
         : s(s_), next((long long)(pos >> 3)), end_byte(end_byte_), prev(pos >> 3 ? byte_at(s_, (long long)(pos >> 3) - 1) : 0u) {
         fill();
@@ -137,6 +169,16 @@ struct Reader {
         while (n <= 56) {
             uint32_t b = byte_at(s, next);
             if (b == 0u && prev == 0xFFu && next < s.len) b = byte_at(s, ++next);
+            if (RST && b == 0xFFu) {  // (no FF is loaded once the view has ended: at most one marker a reader)
+                const int m = marker_at(s, next);
+                if (m) {
+                    mark = (int)next;
+                    skip = m;
+                    mark_bits = loaded;
+                    s.len = next;
+                    b = 0u;
+                }
+            }
             if (next >= end_byte && limit == 0x7fffffff) limit = loaded;
             acc = (acc << 8) | b;
             prev = b;
@@ -147,18 +189,21 @@ struct Reader {
     }
     PP_HOST_DEVICE uint32_t peek(int k) const { return (uint32_t)(acc >> (n - k)) & ((1u << k) - 1u); }  // k <= 16
     PP_HOST_DEVICE int consumed() const { return loaded - n; }
+    PP_HOST_DEVICE int before_marker() const { return mark_bits - consumed(); }  // data bits in front of the marker (mark >= 0)
     PP_HOST_DEVICE uint32_t position() const {  // of the next unread bit: walk back over the bytes still held
         long long j = next;
         for (int b = (n + 7) >> 3; b > 0; --b) {
             --j;
             if (stuffed(s, j)) --j;
         }
-        return (uint32_t)(j * 8 + ((8 - (n & 7)) & 7));
+        const long long p = j * 8 + ((8 - (n & 7)) & 7);
+        return (uint32_t)(RST && mark >= 0 && p > (long long)mark * 8 ? (long long)mark * 8 : p);  // (the zeros behind a marker are no place)
     }
 };
 
 // One symbol of table t, -1: no such code (nothing consumed).
-PP_HOST_DEVICE int symbol(Reader& r, const pp_jpeg_huff_table& t) {
+template <bool RST>
+PP_HOST_DEVICE int symbol(Reader<RST>& r, const pp_jpeg_huff_table& t) {
     const uint32_t e = t.look[r.peek(HD_LOOK_BITS)];
     const int len9 = (int)(e >> 8);
     if (len9 >= 1 && len9 <= HD_LOOK_BITS) {
@@ -177,26 +222,75 @@ PP_HOST_DEVICE int symbol(Reader& r, const pp_jpeg_huff_table& t) {
     return -1;
 }
 
-PP_HOST_DEVICE int receive_extend(Reader& r, int s) {  // 1 <= s <= 15
+template <bool RST>
+PP_HOST_DEVICE int receive_extend(Reader<RST>& r, int s) {  // 1 <= s <= 15
     const int v = (int)r.peek(s);
     r.n -= s;
     return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
 }
 
+// The reader stands between two MCUs with fewer than 8 data bits in front of a marker: are they the padding of the
+// interval's last byte? Yes if they are all ones (what encoders write, and the prefix of no code), and if no whole MCU
+// can be decoded from them - the host decoder, which knows whether a marker is due, then takes them for padding or refuses
+// the file. (Bits that are no ones and decode as a whole MCU where a marker is due are taken for data: such a file the
+// host accepts and this decoder refuses.) At most 7 symbols.
+PP_HOST_DEVICE bool padding(Reader<true> r, const pp_jpeg_huff_table* tabs, const Geometry& G) {
+    const int b = r.before_marker();
+    if (b == 0 || r.peek(b) == (1u << b) - 1u) return true;
+    int blk = 0, k = 0;
+    for (int it = 0; it < 8; ++it) {
+        const int comp = blk < G.lum ? 0 : 1 + blk - G.lum;
+        const int sym = symbol(r, tabs[2 * comp + (k > 0 ? 1 : 0)]);
+        if (sym < 0) return true;
+        bool end = false;
+        if (k == 0) {
+            if (sym > 11) return true;
+            r.n -= sym;
+            k = 1;
+        } else {
+            const int rr = sym >> 4, s = sym & 15;
+            if (s == 0) {
+                if (rr == 15) k += 16;
+                else end = true;
+            } else {
+                k += rr;
+                r.n -= s;
+                if (s > 10) return true;
+                if (++k == 64) end = true;
+            }
+            if (k > 64 || (k > 63 && !end)) return true;
+        }
+        if (r.before_marker() < 0) return true;
+        if (end) {
+            k = 0;
+            if (++blk == G.bpm) return false;  // a whole MCU in front of the marker: data
+        }
+    }
+    return true;
+}
+
 struct CountSink {
-    uint32_t blocks = 0;
+    uint32_t blocks = 0, markers = 0;
     PP_HOST_DEVICE void coef(int, int) {}
     PP_HOST_DEVICE void block_done() { ++blocks; }
+    PP_HOST_DEVICE void marker(uint32_t, uint32_t&) { ++markers; }
     PP_HOST_DEVICE bool stop() const { return false; }
 };
 
 // Stores every coefficient at kNatural[k] of its block; stops behind the image's last block. Every store is checked.
+// ordinal: the markers the chain jumped in front of this subsequence; every further one must bear the next number and
+// stand in front of the block its ordinal names.
 struct WriteSink {
     const pp_jpeg_hd_desc& d;
     const Geometry& G;
-    long long g, base = -1;
+    long long g, base = -1, ordinal;
     bool finished = false;
-    PP_HOST_DEVICE WriteSink(const pp_jpeg_hd_desc& d_, const Geometry& G_, long long first) : d(d_), G(G_), g(first) {}
+    PP_HOST_DEVICE WriteSink(const pp_jpeg_hd_desc& d_, const Geometry& G_, long long first, long long ordinal_ = 0)
+        : d(d_), G(G_), g(first), ordinal(ordinal_) {}
+    PP_HOST_DEVICE void marker(uint32_t code, uint32_t& bad) {
+        ++ordinal;
+        if (g != ordinal * d.restart_interval * G.bpm || code != 0xD0u + (uint32_t)((ordinal - 1) & 7)) bad |= BAD_RESTART;
+    }
     PP_HOST_DEVICE void coef(int k, int v) {
         if (g >= G.nblk) return;
         if (base < 0) {
@@ -214,16 +308,28 @@ struct WriteSink {
 };
 
 // tabs: the image's 2 * ncomp tables (DC, AC of component 0, 1, 2). Decodes from `in` to the first symbol boundary at or
-// behind raw byte `end_byte` (or until the sink stops). At most 8 HD_S + 64 symbols: bounded whatever the data.
-template <class Sink>
-PP_HOST_DEVICE State run(const Stream& st, const pp_jpeg_huff_table* tabs, State in, long long end_byte, const Geometry& G, Sink& sink, uint32_t& bad) {
-    Reader r(st, in.pos, end_byte);
+// behind raw byte `end_byte` (or until the sink stops). At most 8 HD_S + 64 steps, each a symbol or a jump over a marker:
+// bounded whatever the data.
+template <bool RST, class Sink>
+PP_HOST_DEVICE State run_as(const Stream& st, const pp_jpeg_huff_table* tabs, State in, long long end_byte, const Geometry& G, Sink& sink, uint32_t& bad) {
+    Reader<RST> r(st, in.pos, end_byte);
     int blk = (int)(in.bk >> 8), k = (int)(in.bk & 255u);
     if (blk >= G.bpm) blk = 0;
     if (k > 63) k = 0;
     for (int it = 0; it < 8 * HD_S + 64; ++it) {
         r.fill();
-        if (r.consumed() >= r.limit || sink.stop()) break;
+        if (sink.stop()) break;
+        if constexpr (RST) {
+            if (r.mark >= 0 && (r.before_marker() < 0 || (r.before_marker() < 8 && blk == 0 && k == 0 && padding(r, tabs, G)))) {
+                if (r.before_marker() < 0) bad |= BAD_RESTART;  // a symbol read across the marker
+                const long long after = (long long)r.mark + r.skip;
+                sink.marker(byte_at(st, after - 1), bad);
+                blk = k = 0;
+                r = Reader<RST>(st, (uint32_t)(after << 3), end_byte);
+                continue;
+            }
+        }
+        if (r.consumed() >= r.limit) break;
         const int comp = blk < G.lum ? 0 : 1 + blk - G.lum;
         const int sym = symbol(r, tabs[2 * comp + (k > 0 ? 1 : 0)]);
         if (sym < 0) {
@@ -273,6 +379,12 @@ PP_HOST_DEVICE State run(const Stream& st, const pp_jpeg_huff_table* tabs, State
     return State{r.position(), ((uint32_t)blk << 8) | (uint32_t)k};
 }
 
+// (the branch is uniform: an image has a restart interval or has none)
+template <class Sink>
+PP_HOST_DEVICE State run(const Stream& st, const pp_jpeg_huff_table* tabs, State in, long long end_byte, const Geometry& G, Sink& sink, uint32_t& bad) {
+    return G.restart ? run_as<true>(st, tabs, in, end_byte, G, sink, bad) : run_as<false>(st, tabs, in, end_byte, G, sink, bad);
+}
+
 // The result slot of an image from what the launches left in its header: the host decoder's verdict. The bits in front of
 // the EOI marker are those behind the last block, less a stuffed 00 that ends the segment (the last data byte was FF).
 PP_HOST_DEVICE pp_jpeg_hd_result verdict(const Stream& st, const Geometry& G, const Header& h, bool range_bad) {
@@ -280,6 +392,7 @@ PP_HOST_DEVICE pp_jpeg_hd_result verdict(const Stream& st, const Geometry& G, co
     const long long bits = st.len * 8, data_bits = bits - (stuffed(st, st.len - 1) ? 8 : 0);
     if (!h.synced) r.reason = HD_NOT_SYNCHRONISED;
     else if ((long long)h.total < G.nblk || !h.done || (long long)h.endpos > bits) r.reason = HD_ENDS_EARLY;
+    else if ((h.flags & BAD_RESTART) || (long long)h.markers != markers_due(G, G.restart)) r.reason = HD_RESTART;
     else if (h.flags) r.reason = HD_BAD_CODE;
     else if (range_bad) r.reason = HD_DC_RANGE;
     else if (data_bits - (long long)h.endpos >= 8) r.reason = HD_TRAILING;

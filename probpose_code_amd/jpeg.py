@@ -27,8 +27,12 @@ csrc/pp_jpeg_huffdec.hip: ``sync_passes`` + 4 launches in front of the reconstru
 only reads the headers (``scan_prepare``), a file goes up as its own bytes and the coefficients never cross the bus. The
 stream is decoded in subsequences of 128 bytes by self-synchronising passes; an image the passes did not synchronise, or
 whose stream is damaged, is refused by its result slot - never decoded wrongly - and goes through ``entropy_decode``.
-Files with a restart interval keep the host Huffman decoder. The pixels are those of ``entropy="host"``, which stays
-the default.
+Files with a restart interval decode there as well (``scan_prepare(data, restart=True)``): an RSTn marker is a point where
+the decoder's state is known, so inside such a file the synchronisation distance is bounded by the interval's length; the
+order and number of the markers are checked on the device. (A file with more than 7 fill bytes in front of a marker is
+turned away by the preparation and decodes on the host, uncounted.) The pixels are those of ``entropy="host"``, which stays
+the default. Not done on the device: progressive, arithmetic-coded and 12-bit files (no decoder here takes them), and
+*coding* with a restart interval (``encode_batch(..., entropy="device")`` demands ``restart_interval=0``).
 """
 import ctypes
 from typing import List, NamedTuple, Optional, Sequence, Union
@@ -88,7 +92,7 @@ TABLE_BYTES = ctypes.sizeof(HuffTable)
 assert TABLE_BYTES == 1424
 # pp_jpeg_hd_desc: five pointers, the stream's length, six int32; pp_jpeg_hd_result
 _HD_DESC = np.dtype([("stream", "<u8"), ("tables", "<u8"), ("coef", "<u8"), ("scratch", "<u8"), ("result", "<u8"), ("stream_bytes", "<i8"),
-                     ("hs", "<i4"), ("vs", "<i4"), ("mcus_x", "<i4"), ("mcus_y", "<i4"), ("ncomp", "<i4"), ("reserved", "<i4")])
+                     ("hs", "<i4"), ("vs", "<i4"), ("mcus_x", "<i4"), ("mcus_y", "<i4"), ("ncomp", "<i4"), ("restart_interval", "<i4")])
 assert _HD_DESC.itemsize == 72
 _HD_RESULT = np.dtype([("status", "<i4"), ("passes", "<i4"), ("blocks", "<i4"), ("reason", "<i4")])
 assert _HD_RESULT.itemsize == 16
@@ -99,7 +103,8 @@ MAX_SYNC_PASSES = 64
 DEFAULT_SYNC_PASSES = 3
 assert SUBSEQUENCE_BYTES * (INNER_ITERATIONS * (DEFAULT_SYNC_PASSES - 1) + 2) >= 8192
 HD_REASONS = {0: "", 1: "not synchronised", 2: "data ends before the last MCU", 3: "bad Huffman code, category or coefficient index",
-              4: "DC coefficient out of range", 5: "data after the last MCU", 6: "descriptor outside the subset"}
+              4: "DC coefficient out of range", 5: "data after the last MCU", 6: "descriptor outside the subset",
+              7: "restart markers out of place, order or number"}
 SUBSAMPLING = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}  # pp_jpeg_encode_plan's numbering (Pillow's as well)
 
 
@@ -195,16 +200,19 @@ class JpegScan(NamedTuple):
         return (int(self.info.height), int(self.info.width), 3)
 
 
-def scan_prepare(data) -> JpegScan:
+def scan_prepare(data, restart: bool = False) -> JpegScan:
     """The host's share of ``entropy="device"``: the headers of a file (bytes or a path) and the bounds of its entropy-coded
     segment; no bit of it is decoded. Thread-safe and GIL-free. Raises ``JpegUnsupported`` for what ``entropy_decode`` refuses
-    by the headers, for a file with a restart interval and for a segment no EOI marker ends."""
+    by the headers, for a file with a restart interval and for a segment no EOI marker ends. ``restart=True``
+    (``pp_jpeg_scan_prepare_restart``): a file with a restart interval is accepted too - ``info.restart_interval`` says so and
+    the segment holds its RSTn markers; every other file gives what it gives without the flag."""
     raw = _bytes_of(data)
     scan = _Scan()
-    st = _lib.lib.pp_jpeg_scan_prepare(raw, len(raw), ctypes.byref(scan))
+    name = "pp_jpeg_scan_prepare_restart" if restart else "pp_jpeg_scan_prepare"
+    st = getattr(_lib.lib, name)(raw, len(raw), ctypes.byref(scan))
     if st == _lib.PP_ERR_UNSUPPORTED:
         raise JpegUnsupported(scan.info.reason.decode("utf-8", "replace"))
-    _lib.check("pp_jpeg_scan_prepare", st)
+    _lib.check(name, st)
     ncomp = int(scan.info.ncomp)
     info = JpegInfo.from_buffer_copy(scan.info)
     qt = np.frombuffer(scan, np.uint16, 64 * ncomp, _Scan.qtables.offset).reshape(ncomp, 64).copy()
@@ -282,7 +290,7 @@ def _stage_huffman(scans: Sequence[JpegScan], device, staging, sync_passes: int,
         streams[i][:s.stream.size] = s.stream
         coef_ptr = coef_all.data_ptr() + 2 * o_coef[i]
         desc[i] = (p_streams[i], p_tables[i], coef_ptr, s_at, p_results + 16 * i, s.stream.size, info.hs, info.vs, info.mcus_x, info.mcus_y,
-                   info.ncomp, 0)
+                   info.ncomp, info.restart_interval)
         s_at += shares[i]
         if reconstruct:
             rec[i] = (coef_ptr, p_qtables[i], p_at, out[i].data_ptr(), info.width, info.height, info.ncomp, info.hs, info.vs, info.mcus_x,
@@ -468,7 +476,7 @@ def _host_decode(path_or_bytes) -> np.ndarray:
 def decode_batch(files: Sequence, device="cuda", entropy: str = "host", staging=None, sync_passes: Optional[int] = None) -> List[torch.Tensor]:
     """The (H, W, 3) uint8 BGR device tensors ``imread_device`` gives for a batch of files (paths or bytes) of any mix of sizes
     and sampling. ``entropy="host"``: ``entropy_decode`` per file, one ``reconstruct_batch``. ``entropy="device"``: the host only
-    prepares the files (``scan_prepare``), their bytes go up in one copy, ``pp_jpeg_huffman_decode_batch`` and
+    prepares the files (``scan_prepare(f, restart=True)``), their bytes go up in one copy, ``pp_jpeg_huffman_decode_batch`` and
     ``pp_jpeg_reconstruct_bgr_batch`` run on the current stream, and the result slots come back in one copy. A file the
     preparation refuses goes the ``entropy="host"`` way; an image whose slot is not ``PP_OK`` (not synchronised within
     ``sync_passes``, a damaged stream) goes through ``entropy_decode`` - or, outside its subset, through the host decoder - and
@@ -486,7 +494,7 @@ def decode_batch(files: Sequence, device="cuda", entropy: str = "host", staging=
             if entropy == "device":
                 f = _bytes_of(f)
                 try:
-                    scans.append((i, scan_prepare(f)))
+                    scans.append((i, scan_prepare(f, restart=True)))
                     continue
                 except JpegUnsupported:
                     pass
@@ -503,6 +511,20 @@ def decode_or_host(path: str):
     """A worker's share of the test loop: the file's coefficients, or - outside the subset - its pixels from the host decoder."""
     try:
         return entropy_decode(path)
+    except JpegUnsupported:
+        return _host_decode(path)
+
+
+def prepare_or_host(path: str):
+    """A worker's share of the test loop with ``decode_entropy="device"``: the file's prepared scan (no bit decoded); for a file
+    the preparation refuses its coefficients, or - outside the subset - its pixels from the host decoder."""
+    raw = _bytes_of(path)
+    try:
+        return scan_prepare(raw, restart=True)
+    except JpegUnsupported:
+        pass
+    try:
+        return entropy_decode(raw)
     except JpegUnsupported:
         return _host_decode(path)
 

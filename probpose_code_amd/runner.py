@@ -5,7 +5,9 @@ and ``test_evaluator``): the person instances of a dataset in batches, the model
   * decode: the distinct images of the next batches are decoded on a thread pool (``apis.load_image_bgr``), at least two
     batches ahead; an image is dropped once its last instance has been batched. With ``decode="device"`` the threads run only
     the Huffman half (``jpeg.entropy_decode``) and the images of a batch are reconstructed on the device in ONE
-    ``pp_jpeg_reconstruct_bgr_batch`` call on the producer stream, ahead of the warp that reads them in place;
+    ``pp_jpeg_reconstruct_bgr_batch`` call on the producer stream, ahead of the warp that reads them in place. With
+    ``decode_entropy="device"`` on top the threads only read the file and prepare its scan (``jpeg.scan_prepare``), and the
+    images of a batch go through ONE ``jpeg.decode_scans``: Huffman decoding and reconstruction on the producer stream;
   * crops: the val pipeline through ``Compose.batched`` - box arithmetic on the host, ONE ``pp_warp_affine_u8_batch`` launch
     for the batch, its images uploaded with one copy - on a producer stream, under the model step of the batch before;
   * model: ``test_step_stream`` (full batches replay the captured graph, a partial last batch runs kernel by kernel);
@@ -174,18 +176,24 @@ def _pipeline_of(model, dataset):
 
 
 def test_dataset(model, dataset, evaluator=None, batch_size: int = 64, workers: int = 8, depth: int = 2,
-                 sink: Optional[Callable[[list], None]] = None, decode: str = "host") -> dict:
+                 sink: Optional[Callable[[list], None]] = None, decode: str = "host", decode_entropy: str = "host") -> dict:
     """Run ``model`` over every instance of ``dataset`` (``get_data_info(i)``, i in order) and return the evaluator's metrics
     (``{}`` without one). ``sink``, when given, receives every batch's list of PoseDataSample, in order. ``decode``: "host"
     (``apis.load_image_bgr`` on the threads) or "device" (the split JPEG decoder of ``jpeg``: the same pixels; a file outside
-    its subset is decoded on the host as before)."""
+    its subset is decoded on the host as before). ``decode_entropy`` (with ``decode="device"`` only): "host" (the threads decode
+    the Huffman codes) or "device" (they only prepare the scan; the device decodes the codes as well, and an image it refuses
+    steps down to the host as in ``jpeg.decode_scans``). The samples are the same whatever the choice."""
     from . import jpeg
     from .apis import load_image_bgr
     from .transforms import BatchStaging, pseudo_collate
 
     if decode not in ("host", "device"):
         raise ValueError(f'decode must be "host" or "device", got {decode!r}')
-    decode_fn = jpeg.decode_or_host if decode == "device" else load_image_bgr
+    if decode_entropy not in jpeg.ENTROPY:
+        raise ValueError(f"decode_entropy must be one of {jpeg.ENTROPY}, got {decode_entropy!r}")
+    if decode_entropy == "device" and decode != "device":
+        raise ValueError('decode_entropy="device" needs decode="device"')
+    decode_fn = (jpeg.prepare_or_host if decode_entropy == "device" else jpeg.decode_or_host) if decode == "device" else load_image_bgr
     jpeg_staging = BatchStaging()
 
     n = len(dataset)
@@ -212,12 +220,17 @@ def test_dataset(model, dataset, evaluator=None, batch_size: int = 64, workers: 
     fell_back = set()
 
     def reconstruct(keys):
-        """The pixels of a batch's images; the coefficient sets among them that are not on the device yet in one call."""
+        """The pixels of a batch's images; the coefficient sets among them that are not on the device yet in one call, the
+        prepared scans in one call."""
         results = {key: decoded[key].result() for key in keys if key not in on_device}
         todo = [key for key, r in results.items() if isinstance(r, jpeg.JpegCoefficients)]
-        host = set(results) - set(todo) - fell_back  # files outside the decoder's subset: counted once
+        scans = [key for key, r in results.items() if isinstance(r, jpeg.JpegScan)]
+        host = set(results) - set(todo) - set(scans) - fell_back  # files outside the decoder's subset: counted once
         jpeg.fallbacks += len(host)
         fell_back.update(host)
+        if scans:
+            with torch.cuda.stream(producer):
+                on_device.update(zip(scans, jpeg.decode_scans([results[key] for key in scans], device, jpeg_staging)))
         if todo:
             with torch.cuda.stream(producer):
                 on_device.update(zip(todo, jpeg.reconstruct_batch([results[key] for key in todo], device, jpeg_staging)))

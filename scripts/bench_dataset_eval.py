@@ -11,7 +11,10 @@ written by PIL into a temp directory, 1-8 boxes per image, synthetic weights. On
 
 --decode device runs end_to_end* and decode_only through the split JPEG decoder (Huffman decoding on the threads, the rest
 on the GPU: decode_only then ends with the pixels on the device, the host figure with the pixels in host memory);
---decode both prints the host line, the device line and the host line again (the spread of the host figure)."""
+--decode both prints the host line, the device line and the host line again (the spread of the host figure).
+--decode-entropy device (with --decode device or both) lets the device decode the Huffman codes too: the threads only read
+and prepare the files, the images of a batch go through one jpeg.decode_scans; --decode-entropy both prints the device
+decoder's line with the host's Huffman decoding, with the device's, and the first again."""
 import argparse
 import json
 import os
@@ -36,7 +39,11 @@ def main():
     ap.add_argument("--step", choices=STEPS, action="append")
     ap.add_argument("--data", default=None, help="reuse / keep the generated set in this directory")
     ap.add_argument("--decode", default="host", choices=["host", "device", "both"], help="image decoder of the end_to_end* and decode_only steps")
+    ap.add_argument("--decode-entropy", default="host", choices=["host", "device", "both"],
+                    help="where the device decoder's Huffman codes are decoded (needs --decode device or both)")
     args = ap.parse_args()
+    if args.decode_entropy != "host" and args.decode == "host":
+        ap.error("--decode-entropy device needs --decode device")
 
     import torch
 
@@ -64,7 +71,12 @@ def main():
         torch.cuda.synchronize()
         return time.perf_counter() - t0
 
-    def decode_all_on_device(pool):
+    def decode_all_on_device(pool, entropy):
+        if entropy == "device":  # the threads read and prepare, the images of a batch in one decode_scans
+            futures = [pool.submit(jpeg.scan_prepare, p, True) for p in paths]
+            for lo in range(0, len(futures), 16):
+                jpeg.decode_scans([f.result() for f in futures[lo:lo + 16]], "cuda:0", staging)
+            return
         futures = [pool.submit(jpeg.entropy_decode, p) for p in paths]
         for lo in range(0, len(futures), 16):  # the images of a batch in one reconstruct call
             jpeg.reconstruct_batch([f.result() for f in futures[lo:lo + 16]], "cuda:0", staging)
@@ -73,18 +85,21 @@ def main():
 
     staging = BatchStaging()
     decoded_steps = ("end_to_end", "end_to_end_eval", "decode_only")
-    runs = [(step, mode) for step in args.step or STEPS
-            for mode in ((("host", "device", "host") if args.decode == "both" else (args.decode,)) if step in decoded_steps else ("host",))]
-    for step, mode in runs:
+    entropies = ("host", "device", "host") if args.decode_entropy == "both" else (args.decode_entropy,)
+    runs = [(step, mode, entropy) for step in args.step or STEPS
+            for mode in ((("host", "device", "host") if args.decode == "both" else (args.decode,)) if step in decoded_steps else ("host",))
+            for entropy in (entropies if mode == "device" and step in decoded_steps else ("host",))]
+    for step, mode, entropy in runs:
         if step in ("end_to_end", "end_to_end_eval"):
-            runner.test_dataset(model, dataset, None, args.batch_size, args.workers, decode=mode)  # warm-up: graph capture, pinned buffers
+            kw = dict(decode=mode, decode_entropy=entropy)
+            runner.test_dataset(model, dataset, None, args.batch_size, args.workers, **kw)  # warm-up: graph capture, pinned buffers
             ev = runner.build_evaluator(cfg.test_evaluator, dataset) if step == "end_to_end_eval" else None
-            dt = timed(lambda: runner.test_dataset(model, dataset, ev, args.batch_size, args.workers, decode=mode))
+            dt = timed(lambda: runner.test_dataset(model, dataset, ev, args.batch_size, args.workers, **kw))
         elif step == "decode_only":
             with ThreadPoolExecutor(max_workers=min(16, args.workers)) as pool:
                 if mode == "device":
-                    decode_all_on_device(pool)  # warm-up: pinned buffer, allocator
-                    dt = timed(lambda: decode_all_on_device(pool))
+                    decode_all_on_device(pool, entropy)  # warm-up: pinned buffer, allocator
+                    dt = timed(lambda: decode_all_on_device(pool, entropy))
                 else:
                     dt = timed(lambda: list(pool.map(apis.load_image_bgr, paths)))
         elif step == "model_only":
@@ -116,7 +131,7 @@ def main():
             loop()
             dt = timed(loop)
         print(json.dumps(dict(step=step, instances=n, images=len(paths), seconds=round(dt, 4), instances_per_s=round(n / dt, 1),
-                              batch_size=args.batch_size, workers=args.workers, **(dict(decode=mode) if step in decoded_steps else {}))), flush=True)
+                              batch_size=args.batch_size, workers=args.workers, **(dict(decode=mode, decode_entropy=entropy) if step in decoded_steps else {}))), flush=True)
 
 
 if __name__ == "__main__":

@@ -10,9 +10,11 @@ alternated and medians of --rounds:
     video_demo     demo/video_demo.py on --frames full-HD frames (synthetic checkpoint, --decode device), frames per second of
                    its loop without and with --decode-entropy device (--demo-rounds alternations).
 
-One JSON line per figure.
+--restart-interval R (MCUs, or "row" for one MCU row of the frame) also writes the frames with that restart interval (the
+host coder writes them) and measures them beside the files without one: huffman_call with the two alternated call by
+call, decode_batch for each. One JSON line per figure, ``restart_interval`` in it.
 
-    python scripts/bench_jpeg_huffdec.py [--rounds 7] [--frames 64] [--demo-rounds 3]"""
+    python scripts/bench_jpeg_huffdec.py [--rounds 7] [--frames 64] [--demo-rounds 3] [--restart-interval row]"""
 import argparse
 import json
 import os
@@ -38,7 +40,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--demo-rounds", type=int, default=3)
+    ap.add_argument("--restart-interval", default="0", help='MCUs between restart markers of a second set of files, or "row"; 0: none')
     args = ap.parse_args()
+    if args.restart_interval != "row" and not 0 <= int(args.restart_interval) <= 65535:
+        ap.error("--restart-interval is 0..65535 or row")
 
     import torch
 
@@ -52,62 +57,71 @@ def main():
     for W, H in ((640, 480), (1920, 1080)):
         rng = np.random.default_rng(W)
         frames = [torch.from_numpy(photo_like(rng, H, W)).to(dev) for _ in range(4)]
-        four = jpeg.encode_batch(frames, channel_order="rgb", staging=staging)
-        files = [four[k % 4] for k in range(16)]
+        ri = (W + 15) // 16 if args.restart_interval == "row" else int(args.restart_interval)
+        sets = {}
+        for r in dict.fromkeys((0, ri)):
+            four = jpeg.encode_batch(frames, channel_order="rgb", staging=staging, restart_interval=r)
+            sets[r] = [four[k % 4] for k in range(16)]
+            a = jpeg.decode_batch(four, dev, entropy="host", staging=staging)
+            b = jpeg.decode_batch(four, dev, entropy="device", staging=staging)
+            assert all(torch.equal(x, y) for x, y in zip(a, b)), "the two decoders disagree"
+            print(json.dumps(dict(figure="file", size=f"{W}x{H}", restart_interval=r, file_bytes=[len(f) for f in four])), flush=True)
         size = f"{W}x{H}"
         if W == 1920:
-            hd_files = files
-        a = jpeg.decode_batch(files[:4], dev, entropy="host", staging=staging)
-        b = jpeg.decode_batch(files[:4], dev, entropy="device", staging=staging)
-        assert all(torch.equal(x, y) for x, y in zip(a, b)), "the two decoders disagree"
-        print(json.dumps(dict(figure="file", size=size, file_bytes=[len(f) for f in four])), flush=True)
+            hd_files = sets[ri]
 
         for n in (1, 16):
-            scans = [jpeg.scan_prepare(f) for f in files[:n]]
-            job = jpeg._stage_huffman(scans, dev, staging, jpeg.DEFAULT_SYNC_PASSES, False)
             stream = torch.cuda.current_stream(dev)
-            for _ in range(3):
-                _lib.call("pp_jpeg_huffman_decode_batch", *job.args, stream.cuda_stream)
+            jobs, scans = {}, {}
+            for r, files in sets.items():
+                scans[r] = [jpeg.scan_prepare(f, restart=True) for f in files[:n]]
+                jobs[r] = jpeg._stage_huffman(scans[r], dev, BatchStaging(), jpeg.DEFAULT_SYNC_PASSES, False)
+                for _ in range(3):
+                    _lib.call("pp_jpeg_huffman_decode_batch", *jobs[r].args, stream.cuda_stream)
             torch.cuda.synchronize()
-            us = []
+            us = {r: [] for r in jobs}
             for _ in range(args.rounds):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                _lib.call("pp_jpeg_huffman_decode_batch", *job.args, stream.cuda_stream)
-                e1.record()
-                e1.synchronize()
-                us.append(e0.elapsed_time(e1) * 1e3)
+                for r, job in jobs.items():  # alternated call by call
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    _lib.call("pp_jpeg_huffman_decode_batch", *job.args, stream.cuda_stream)
+                    e1.record()
+                    e1.synchronize()
+                    us[r].append(e0.elapsed_time(e1) * 1e3)
             sclk = shader_clock()  # right behind the timed launches
-            res = job.results.cpu().numpy().view(jpeg._HD_RESULT)
-            assert (res["status"] == 0).all()
-            print(json.dumps(dict(figure="huffman_call", size=size, n=n, device_event_us=round(statistics.median(us), 1), min_us=round(min(us), 1),
-                                  max_us=round(max(us), 1), rounds=args.rounds, sync_passes=jpeg.DEFAULT_SYNC_PASSES,
-                                  passes_used=int(res["passes"].max()), stream_bytes=int(sum(s.stream.size for s in scans)),
-                                  coefficient_bytes=int(sum(2 * int(s.info.coef_count) for s in scans)), sclk_mhz=sclk)), flush=True)
-            del job
+            for r, job in jobs.items():
+                res = job.results.cpu().numpy().view(jpeg._HD_RESULT)
+                assert (res["status"] == 0).all()
+                print(json.dumps(dict(figure="huffman_call", size=size, restart_interval=r, n=n, device_event_us=round(statistics.median(us[r]), 1),
+                                      min_us=round(min(us[r]), 1), max_us=round(max(us[r]), 1), rounds=args.rounds, sync_passes=jpeg.DEFAULT_SYNC_PASSES,
+                                      passes_used=int(res["passes"].max()), stream_bytes=int(sum(s.stream.size for s in scans[r])),
+                                      coefficient_bytes=int(sum(2 * int(s.info.coef_count) for s in scans[r])), sclk_mhz=sclk)), flush=True)
+            del jobs
 
-        for n in (1, 16):
-            for workers in (1, 8):
-                pool = ThreadPoolExecutor(max_workers=workers)
+        for r, files in sets.items():
+            for n in (1, 16):
+                for workers in (1, 8):
+                    pool = ThreadPoolExecutor(max_workers=workers)
 
-                def host(n=n, pool=pool):  # the path as it is: Huffman decoding on the threads, one reconstruct call
-                    return jpeg.reconstruct_batch(list(pool.map(jpeg.entropy_decode, files[:n])), dev, staging)
+                    def host(n=n, pool=pool, files=files):  # the path as it is: Huffman decoding on the threads, one reconstruct call
+                        return jpeg.reconstruct_batch(list(pool.map(jpeg.entropy_decode, files[:n])), dev, staging)
 
-                paths = {"host": host, "device": lambda n=n: jpeg.decode_batch(files[:n], dev, entropy="device", staging=staging)}
-                times = {k: [] for k in paths}
-                for fn in paths.values():
-                    fn()  # warm-up
-                for _ in range(args.rounds):
-                    for name, fn in paths.items():
-                        torch.cuda.synchronize()
-                        t0 = time.perf_counter()
-                        fn()
-                        torch.cuda.synchronize()
-                        times[name].append(time.perf_counter() - t0)
-                pool.shutdown()
-                for name, ts in times.items():
-                    print(json.dumps(dict(figure="decode_batch", size=size, entropy=name, n=n, workers=workers, ms=round(statistics.median(ts) * 1e3, 3),
-                                          min_ms=round(min(ts) * 1e3, 3), max_ms=round(max(ts) * 1e3, 3), rounds=args.rounds)), flush=True)
+                    paths = {"host": host, "device": lambda n=n, files=files: jpeg.decode_batch(files[:n], dev, entropy="device", staging=staging)}
+                    times = {k: [] for k in paths}
+                    for fn in paths.values():
+                        fn()  # warm-up
+                    for _ in range(args.rounds):
+                        for name, fn in paths.items():
+                            torch.cuda.synchronize()
+                            t0 = time.perf_counter()
+                            fn()
+                            torch.cuda.synchronize()
+                            times[name].append(time.perf_counter() - t0)
+                    pool.shutdown()
+                    for name, ts in times.items():
+                        print(json.dumps(dict(figure="decode_batch", size=size, restart_interval=r, entropy=name, n=n, workers=workers,
+                                              ms=round(statistics.median(ts) * 1e3, 3), min_ms=round(min(ts) * 1e3, 3), max_ms=round(max(ts) * 1e3, 3),
+                                              rounds=args.rounds)), flush=True)
 
     if args.frames > 0:
         import video_demo

@@ -9,7 +9,10 @@
 // Every file runs as it is, after the three truncations of tests/golden/make_golden_jpeg.py (half, the last bytes gone with
 // and without EOI), with its entropy-coded segment cut at every one of its last 40 lengths (EOI put back), after each of 32
 // single bit flips at fixed places of the segment (the damaged streams the GPU tests run), and `rounds` times after a
-// seeded single bit flip or byte deletion inside the segment. Stream, tables, coefficients and scratch live
+// seeded single bit flip or byte deletion inside the segment; a file with a restart interval (taken through
+// scan_prepare's restart form) also with a marker deleted, two markers' numbers swapped, a marker doubled (an empty
+// interval) and D7 changed to D0, and for every subsequence that holds a marker run() from five entry states must return
+// one exit state. Stream, tables, coefficients and scratch live
 // in heap blocks of exactly their size, so the sanitiser sees any access outside them. Demanded of every input the
 // preparation accepts: the restated device decoder and the host decoder agree on acceptance - except that the device may
 // say "not synchronised" - and where the device says PP_OK its coefficients are the host's, byte for byte; at sync_passes
@@ -40,12 +43,13 @@ static long long end_of(long long i, long long len) { return (i + 1) * HD_S < le
 static pp_jpeg_hd_result emulate(const pp_jpeg_hd_desc& d, int sync_passes) {
     const Geometry G = geometry(d);
     if (!G.valid) return pp_jpeg_hd_result{PP_ERR_INVALID_ARG, 0, 0, HD_BAD_DESC};
-    const Layout L = layout(d.stream_bytes);
+    const Layout L = layout(d.stream_bytes, G.restart != 0);
     const Stream st{d.stream, d.stream_bytes};
     State* entry_g = reinterpret_cast<State*>(d.scratch + L.o_entry);
     State* exit_g = reinterpret_cast<State*>(d.scratch + L.o_exit);
     uint32_t* cnt_g = reinterpret_cast<uint32_t*>(d.scratch + L.o_cnt);
     uint32_t* first_g = reinterpret_cast<uint32_t*>(d.scratch + L.o_first);
+    uint32_t* mfirst_g = reinterpret_cast<uint32_t*>(d.scratch + L.o_mfirst);  // (restart files only)
     State* bexit = reinterpret_cast<State*>(d.scratch + L.o_bexit);
     uint32_t* open_g = reinterpret_cast<uint32_t*>(d.scratch + L.o_open);
     Header* hdr = reinterpret_cast<Header*>(d.scratch);
@@ -75,7 +79,7 @@ static pp_jpeg_hd_result emulate(const pp_jpeg_hd_desc& d, int sync_passes) {
                     entry[t] = State{canonical(st, (uint32_t)(i * HD_S * 8)), 0u};
                     CountSink c;
                     exit[t] = run(st, d.tables, entry[t], end_of(i, st.len), G, c, unused);
-                    cnt[t] = c.blocks;
+                    cnt[t] = c.blocks | (c.markers << 16);
                 } else {
                     entry[t] = entry_g[i];
                     exit[t] = exit_g[i];
@@ -97,7 +101,7 @@ static pp_jpeg_hd_result emulate(const pp_jpeg_hd_desc& d, int sync_passes) {
                         entry[t] = want;
                         CountSink c;
                         exit[t] = run(st, d.tables, entry[t], end_of(wg * HD_WG + t, st.len), G, c, unused);
-                        cnt[t] = c.blocks;
+                        cnt[t] = c.blocks | (c.markers << 16);
                         dirty[t] = any = true;
                     }
                     ex[cur ^ 1][t] = exit[t];
@@ -118,23 +122,26 @@ static pp_jpeg_hd_result emulate(const pp_jpeg_hd_desc& d, int sync_passes) {
         }
     }
     // jpeg_hd_scan
-    uint32_t carry = 0;
+    uint32_t carry = 0, mcarry = 0;
     bool ok = true;
     for (long long i = 0; i < L.nsub; ++i) {
         const State want = i == 0 ? State{0u, 0u} : exit_g[i - 1];
         if (!same(want, entry_g[i])) ok = false;
         first_g[i] = carry;
-        carry += cnt_g[i];
+        carry += cnt_g[i] & 0xFFFFu;
+        if (G.restart) mfirst_g[i] = mcarry;
+        mcarry += cnt_g[i] >> 16;
     }
     hdr->synced = ok ? 1u : 0u;
     hdr->total = carry;
+    hdr->markers = mcarry;
     // jpeg_hd_zero
     std::memset(d.coef, 0, (size_t)G.nblk * 128);
     // jpeg_hd_write
     if (hdr->synced)
         for (long long i = 0; i < L.nsub; ++i) {
             if ((long long)first_g[i] >= G.nblk) continue;
-            WriteSink sink(d, G, first_g[i]);
+            WriteSink sink(d, G, first_g[i], G.restart ? (long long)mfirst_g[i] : 0);
             uint32_t bad = 0;
             const State out = run(st, d.tables, entry_g[i], end_of(i, st.len), G, sink, bad);
             hdr->flags |= bad;
@@ -152,9 +159,11 @@ static pp_jpeg_hd_result emulate(const pp_jpeg_hd_desc& d, int sync_passes) {
     if (hdr->synced)
         for (int c = 0; c < d.ncomp; ++c) {
             const long long nb = c == 0 ? G.mcus * G.lum : G.mcus;
+            const long long per = G.restart ? (long long)G.restart * (c == 0 ? G.lum : 1) : 0;  // blocks of the component per interval
             long long sum = 0;
             for (long long k = 0; k < nb; ++k) {
                 const long long at = component_block(d, G, c, k) * 64;
+                if (per && k % per == 0) sum = 0;
                 sum += d.coef[at];
                 if (sum < -32768 || sum > 32767) range_bad = true;
                 d.coef[at] = (int16_t)(int32_t)sum;
@@ -163,8 +172,38 @@ static pp_jpeg_hd_result emulate(const pp_jpeg_hd_desc& d, int sync_passes) {
     return verdict(st, G, *hdr, range_bad);
 }
 
-static long g_cases = 0, g_ok = 0, g_refused_prepare = 0, g_refused_both = 0, g_unsync = 0, g_failures = 0;
+static long g_cases = 0, g_ok = 0, g_refused_prepare = 0, g_refused_both = 0, g_unsync = 0, g_failures = 0, g_marker_subs = 0;
 static int g_max_passes = 0;
+
+// A marker is a hard synchronisation point: for every subsequence that holds one (its first FF), run() from five entry
+// states in front of it - the subsequence's first bit and three further bit positions, other places in the MCU and the
+// block - returns one and the same exit state.
+static void marker_exits(const pp_jpeg_hd_desc& d) {
+    const Geometry G = geometry(d);
+    if (!G.valid) return;
+    const Stream st{d.stream, d.stream_bytes};
+    const long long nsub = layout(d.stream_bytes, true).nsub;
+    for (long long i = 0; i < nsub; ++i) {
+        long long m = -1;
+        for (long long b = i * HD_S; b < end_of(i, st.len) && m < 0; ++b)
+            if (marker_at(st, b)) m = b;
+        if (m < 0) continue;
+        ++g_marker_subs;
+        const uint32_t first = canonical(st, (uint32_t)(i * HD_S * 8)), span = (uint32_t)(m * 8) - first;
+        const State in[5] = {State{first, 0u}, State{first + span / 4, (uint32_t)((G.bpm - 1) << 8) | 5u}, State{first + span / 2 + 3, 63u},
+                             State{first + span * 3 / 4 + 1, 1u}, State{first + (span > 3 ? 3u : 0u), (uint32_t)((G.bpm / 2) << 8)}};
+        State out[5];
+        for (int e = 0; e < 5; ++e) {
+            CountSink c;
+            uint32_t bad = 0;
+            out[e] = run(st, d.tables, State{canonical(st, in[e].pos), in[e].bk}, end_of(i, st.len), G, c, bad);
+            if (!same(out[e], out[0])) {
+                ++g_failures;
+                std::printf("MARKER EXIT subsequence %lld: entry %d leaves (%u, %u), entry 0 (%u, %u)\n", i, e, out[e].pos, out[e].bk, out[0].pos, out[0].bk);
+            }
+        }
+    }
+}
 
 // One input through the preparation, the restated device decoder and the host decoder.
 static void check(const std::vector<uint8_t>& bytes, int sync_passes, bool must_sync, const char* what) {
@@ -172,7 +211,7 @@ static void check(const std::vector<uint8_t>& bytes, int sync_passes, bool must_
     uint8_t* data = (uint8_t*)std::malloc(bytes.size() ? bytes.size() : 1);
     if (!bytes.empty()) std::memcpy(data, bytes.data(), bytes.size());
     pp_jpeg_scan* scan = (pp_jpeg_scan*)std::malloc(sizeof(pp_jpeg_scan));
-    const int ps = jpeg::scan_prepare(data, bytes.size(), scan);
+    const int ps = jpeg::scan_prepare(data, bytes.size(), scan, true);
     if (ps != PP_OK) {
         ++g_refused_prepare;
         if (!jpeg::g_reason[0]) {
@@ -193,11 +232,12 @@ static void check(const std::vector<uint8_t>& bytes, int sync_passes, bool must_
         pp_jpeg_huff_table* tabs = (pp_jpeg_huff_table*)std::malloc(2 * (size_t)info.ncomp * sizeof(pp_jpeg_huff_table));
         std::memcpy(tabs, scan->tables, 2 * (size_t)info.ncomp * sizeof(pp_jpeg_huff_table));
         int16_t* coef = (int16_t*)std::aligned_alloc(16, (size_t)info.coef_count * 2);
-        const Layout L = layout(len);
+        const Layout L = layout(len, info.restart_interval != 0);
         uint8_t* scratch = (uint8_t*)std::aligned_alloc(16, (size_t)L.total);
         std::memset(scratch, 0xA5, (size_t)L.total);
         pp_jpeg_hd_result slot;
-        pp_jpeg_hd_desc d{stream, tabs, coef, scratch, &slot, len, info.hs, info.vs, info.mcus_x, info.mcus_y, info.ncomp, 0};
+        pp_jpeg_hd_desc d{stream, tabs, coef, scratch, &slot, len, info.hs, info.vs, info.mcus_x, info.mcus_y, info.ncomp, info.restart_interval};
+        if (info.restart_interval) marker_exits(d);
         const pp_jpeg_hd_result r = emulate(d, sync_passes);
         std::vector<int16_t> want((size_t)info.coef_count);
         uint16_t qt[192];
@@ -266,7 +306,7 @@ int main(int argc, char** argv) {
             check(m, HD_MAX_PASSES, false, "last_mcu_eoi");
         }
         pp_jpeg_scan scan;
-        if (jpeg::scan_prepare(orig.data(), orig.size(), &scan) != PP_OK) continue;
+        if (jpeg::scan_prepare(orig.data(), orig.size(), &scan, true) != PP_OK) continue;
         const size_t off = (size_t)scan.stream_offset, len = (size_t)scan.stream_bytes;
         for (size_t cut = 0; cut < 40 && cut < len; ++cut) {  // the segment without its last bytes, EOI put back
             std::vector<uint8_t> m(orig.begin(), orig.begin() + off + len - 1 - cut);
@@ -279,6 +319,32 @@ int main(int argc, char** argv) {
             m[off + len * k / 32] ^= (uint8_t)(1u << (k % 8));
             check(m, HD_MAX_PASSES, false, "fixed flip");
         }
+        if (scan.info.restart_interval) {  // marker damage: one deleted, two numbers swapped, one doubled (an empty interval), D7 -> D0
+            std::vector<size_t> at;  // the D0..D7 byte of every marker
+            for (size_t b = off; b + 1 < off + len; ++b) {
+                if (orig[b] != 0xFF) continue;
+                if (orig[b + 1] == 0x00) ++b;
+                else if (orig[b + 1] >= 0xD0 && orig[b + 1] <= 0xD7) at.push_back(++b);
+            }
+            for (size_t q = 0; q < at.size(); q += at.size() > 12 ? at.size() / 12 : 1) {
+                std::vector<uint8_t> m = orig;
+                m.erase(m.begin() + at[q] - 1, m.begin() + at[q] + 1);
+                check(m, HD_MAX_PASSES, false, "marker deleted");
+                m = orig;
+                m.insert(m.begin() + at[q] + 1, orig.begin() + at[q] - 1, orig.begin() + at[q] + 1);
+                check(m, HD_MAX_PASSES, false, "marker doubled");
+                if (q + 1 < at.size()) {
+                    m = orig;
+                    std::swap(m[at[q]], m[at[q + 1]]);
+                    check(m, HD_MAX_PASSES, false, "markers swapped");
+                }
+                if (orig[at[q]] == 0xD7) {
+                    m = orig;
+                    m[at[q]] = 0xD0;
+                    check(m, HD_MAX_PASSES, false, "D7 to D0");
+                }
+            }
+        }
         for (int r = 0; r < rounds && len > 0; ++r) {
             std::vector<uint8_t> m = orig;
             const size_t at = off + rnd() % len;
@@ -288,7 +354,7 @@ int main(int argc, char** argv) {
         }
     }
     std::printf("jpeg_huffdec_host_check: %zu files, %ld cases: %ld decoded equal to the host, %ld refused by the preparation, %ld refused by both decoders, "
-                "%ld not synchronised, at most %d passes, %ld failures\n",
-                files.size(), g_cases, g_ok, g_refused_prepare, g_refused_both, g_unsync, g_max_passes, g_failures);
+                "%ld not synchronised, at most %d passes, %ld subsequences with a marker left alike from 5 entries, %ld failures\n",
+                files.size(), g_cases, g_ok, g_refused_prepare, g_refused_both, g_unsync, g_max_passes, g_marker_subs, g_failures);
     return g_failures != 0;
 }

@@ -44,9 +44,13 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--decode", default="host", choices=["host", "device"],
                     help="device: JPEG files are Huffman-decoded on the threads and reconstructed on the GPU (the same pixels)")
+    ap.add_argument("--decode-entropy", default="host", choices=["host", "device"],
+                    help="device (needs --decode device): the files' Huffman codes are decoded on the GPU as well (the same pixels)")
     ap.add_argument("--precision", default=None, choices=[None, "f16x3", "bf16", "f32"],
                     help="overrides model.precision of the config (default there: f16x3)")
     args = ap.parse_args(argv)
+    if args.decode_entropy == "device" and args.decode != "device":
+        ap.error("--decode-entropy device needs --decode device")
 
     from probpose_code_amd import apis, runner, synthetic
     from probpose_code_amd.config import Config
@@ -67,7 +71,8 @@ def main(argv=None):
     evaluator = runner.build_evaluator(cfg["test_evaluator"], dataset, device=args.device)
     batch_size = args.batch_size or int(loader.get("batch_size", 64))
     t0 = time.perf_counter()
-    metrics = runner.test_dataset(model, dataset, evaluator, batch_size=batch_size, workers=args.workers, decode=args.decode)
+    metrics = runner.test_dataset(model, dataset, evaluator, batch_size=batch_size, workers=args.workers, decode=args.decode,
+                                  decode_entropy=args.decode_entropy)
     dt = time.perf_counter() - t0
     for k, v in metrics.items():
         print(f"{k}: {v:.4f}")
