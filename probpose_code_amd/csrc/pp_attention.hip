@@ -18,31 +18,18 @@
 //   * blockIdx is remapped so that the heads of one crop (adjacent columns of the same qkv
 //     rows) land on the same XCD / L2.
 #include "pp_common.h"
+#include "pp_device.h"
 #include "pp_split.h"
 
 namespace pp {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int ATT_THREADS = 256;
 #ifndef ATT_ABL  // dev (scripts/micro/att_ablate.sh): 1 no V transpose, 2 no math, 3 no K / V loads - timing only, wrong results
 #define ATT_ABL 0
 #endif
 
-__device__ __forceinline__ f32x4 att_mma(const u32x4& a, const u32x4& b, f32x4 c, __bf16) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
-                                                   0, 0);
-}
-__device__ __forceinline__ f32x4 att_mma(const u32x4& a, const u32x4& b, f32x4 c, float) {
-    const f32x4 af = __builtin_bit_cast(f32x4, a), bf = __builtin_bit_cast(f32x4, b);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) c = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], bf[j], c, 0, 0, 0);
-    return c;
-}
+__device__ __forceinline__ f32x4 att_mma(const u32x4& a, const u32x4& b, f32x4 c, __bf16) { return mma_bf16(a, b, c); }
+__device__ __forceinline__ f32x4 att_mma(const u32x4& a, const u32x4& b, f32x4 c, float) { return mma_f32(a, b, c); }
 
 template <typename T, int HD, int NT>
 struct AttCfg {

@@ -25,17 +25,11 @@
 // the same wave - the pipe idles while its wave does arithmetic unless ANOTHER wave of the SIMD has MFMAs ready, which is what two workgroups
 // per CU (14 waves) provide and what both attempts gave up.
 #include "pp_common.h"
+#include "pp_device.h"
 #include "pp_split.h"
 
 namespace pp {
 namespace adma {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_t;
 
 constexpr int S = 432, NT = S / 16, QSPLIT = 4, TPW = (NT + QSPLIT - 1) / QSPLIT, THREADS = 64 * TPW;  // 7 waves
 constexpr int SK = 32;                         // keys per stage
@@ -51,11 +45,6 @@ struct Cfg {
     static constexpr int LDS = RING * STAGE;
     static constexpr int DT = HD / 16;
 };
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));  // vmcnt(N) only
-}
 
 template <int HD>
 __global__ __launch_bounds__(THREADS, 4) void attention_split_dma_kernel(const char* __restrict__ qkv, char* __restrict__ out, int n_seq,
@@ -80,7 +69,7 @@ __global__ __launch_bounds__(THREADS, 4) void attention_split_dma_kernel(const c
 
     // ---- DMA: piece j of a stage = sub-tile j / 4 (K blocks 0 .. NB - 1, then V blocks), keys 8 (j % 4) .. + 7; lane (l = lane >> 3,
     // pc = lane & 7) fetches the logical 16-byte chunk pc ^ l of key 8 (j % 4) + l
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(qkv), 0, qkv_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc = buffer_rsrc(qkv, qkv_bytes);
     const int d_l = lane >> 3;
     const unsigned d_sw = (unsigned)(((lane & 7) ^ d_l) << 4);
     auto issue_stage = [&](int st) {
@@ -92,7 +81,7 @@ __global__ __launch_bounds__(THREADS, 4) void attention_split_dma_kernel(const c
                 const int sub = j >> 2, kq = j & 3;
                 const int which = sub / C::NB, blk = sub - which * C::NB;  // 0 = K, 1 = V
                 const unsigned vo = base + (unsigned)(st * SK + kq * 8 + d_l) * row_bytes + (unsigned)((1 + which) * E * 4 + blk * 128) + d_sw;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(dst + j * 1024), 16, vo, 0, 0, 0);
+                dma16(rsrc, dst + j * 1024, vo);
             }
         }
     };
@@ -245,7 +234,7 @@ static int launch(const void* qkv, void* out, int n_seq, int heads, float scale,
     using C = Cfg<HD>;
     auto kern = attention_split_dma_kernel<HD>;
     const size_t bytes = (size_t)n_seq * S * 3 * heads * HD * 4;
-    PP_REQUIRE(bytes < 0x7ffffff0u, PP_ERR_UNSUPPORTED, "pp_attention: qkv tensor exceeds 2 GiB (32-bit buffer offsets)");
+    PP_REQUIRE(bytes < kOob, PP_ERR_UNSUPPORTED, "pp_attention: qkv tensor exceeds 2 GiB (32-bit buffer offsets)");
     PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
     hipLaunchKernelGGL(kern, dim3(n_seq * heads * QSPLIT), dim3(THREADS), C::LDS, s, reinterpret_cast<const char*>(qkv),
                        reinterpret_cast<char*>(out), n_seq, heads, (unsigned)bytes, scale * 1.44269504088896340736f);

@@ -20,16 +20,11 @@
 // Everything else is the single-pass form of pp_attention.hip: one 256-thread workgroup per (sequence, head), K row-major and
 // V transposed in LDS, S^T = K Q^T so that P stays in registers as the B operand of O^T = V^T P^T, softmax statistics in fp32.
 #include "pp_common.h"
+#include "pp_device.h"
 #include "pp_split.h"
 
 namespace pp {
 namespace {
-
-typedef __bf16 h80_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 h80_bf16x4 __attribute__((ext_vector_type(4)));
-typedef float h80_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int h80_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int h80_u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int H80_THREADS = 256;
 constexpr int H80_HD = 80;           // head dim
@@ -39,18 +34,11 @@ constexpr int H80_SPV = H80_S + 8;   // V^T row pitch (elements): 8 * odd -> con
 constexpr int H80_DT = H80_HD / 16;  // output d tiles
 constexpr int H80_QPW = H80_NT / (H80_THREADS / 64);  // query tiles per wave
 
-__device__ __forceinline__ h80_f32x4 h80_mma(const h80_u32x4& a, const h80_u32x4& b, h80_f32x4 c, __bf16) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(h80_bf16x8, a), __builtin_bit_cast(h80_bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ h80_f32x4 h80_mma(const h80_u32x4& a, const h80_u32x4& b, h80_f32x4 c, float) {
-    const h80_f32x4 af = __builtin_bit_cast(h80_f32x4, a), bf = __builtin_bit_cast(h80_f32x4, b);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) c = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], bf[j], c, 0, 0, 0);
-    return c;
-}
+__device__ __forceinline__ f32x4 h80_mma(const u32x4& a, const u32x4& b, f32x4 c, __bf16) { return mma_bf16(a, b, c); }
+__device__ __forceinline__ f32x4 h80_mma(const u32x4& a, const u32x4& b, f32x4 c, float) { return mma_f32(a, b, c); }
 
 // softmax over the 192 keys of this lane's query (fp32); s <- p, returns the row sum
-__device__ __forceinline__ float h80_softmax(h80_f32x4 (&s)[H80_NT], float scale_log2e) {
+__device__ __forceinline__ float h80_softmax(f32x4 (&s)[H80_NT], float scale_log2e) {
     float mx = -__builtin_inff();
 #pragma unroll
     for (int kt = 0; kt < H80_NT; ++kt)
@@ -114,14 +102,14 @@ __global__ __launch_bounds__(H80_THREADS, (sizeof(T) == 2 ? 2 : 1)) void attenti
     const T* base = qkv + (size_t)seq * H80_S * row_stride + (size_t)head * H80_HD;
 
     // ---- Q fragments of this wave's query tiles; a lane whose chunk lies in the padding holds zeros and loads nothing
-    h80_u32x4 qf_all[H80_QPW][C::NG];
+    u32x4 qf_all[H80_QPW][C::NG];
 #pragma unroll
     for (int t = 0; t < H80_QPW; ++t) {
         const T* qrow = base + (size_t)((wave + t * (H80_THREADS / 64)) * 16 + fr) * row_stride;
 #pragma unroll
         for (int g = 0; g < C::NG; ++g) {
-            h80_u32x4 q = {0, 0, 0, 0};
-            if (g * 4 + fg < C::RCG) q = *reinterpret_cast<const h80_u32x4*>(qrow + (g * 4 + fg) * C::CH);
+            u32x4 q = {0, 0, 0, 0};
+            if (g * 4 + fg < C::RCG) q = *reinterpret_cast<const u32x4*>(qrow + (g * 4 + fg) * C::CH);
             qf_all[t][g] = q;
         }
     }
@@ -129,16 +117,16 @@ __global__ __launch_bounds__(H80_THREADS, (sizeof(T) == 2 ? 2 : 1)) void attenti
     // ---- stage K (row-major, padded chunks zero) and V (transposed)
     for (int i = tid; i < H80_S * C::RCL; i += H80_THREADS) {
         const int r = i / C::RCL, c = i - r * C::RCL;
-        h80_u32x4 kv = {0, 0, 0, 0};
+        u32x4 kv = {0, 0, 0, 0};
         if (c < C::RCG) {
-            kv = *reinterpret_cast<const h80_u32x4*>(base + (size_t)r * row_stride + E + c * C::CH);
-            const h80_u32x4 vv = *reinterpret_cast<const h80_u32x4*>(base + (size_t)r * row_stride + 2 * E + c * C::CH);
+            kv = *reinterpret_cast<const u32x4*>(base + (size_t)r * row_stride + E + c * C::CH);
+            const u32x4 vv = *reinterpret_cast<const u32x4*>(base + (size_t)r * row_stride + 2 * E + c * C::CH);
             T ve[C::CH];
-            *reinterpret_cast<h80_u32x4*>(ve) = vv;
+            *reinterpret_cast<u32x4*>(ve) = vv;
 #pragma unroll
             for (int j = 0; j < C::CH; ++j) Vt[(c * C::CH + j) * H80_SPV + r] = ve[j];
         }
-        *reinterpret_cast<h80_u32x4*>(Ks + ((size_t)r * C::RCL + (c ^ ((r >> 2) & 3))) * 16) = kv;
+        *reinterpret_cast<u32x4*>(Ks + ((size_t)r * C::RCL + (c ^ ((r >> 2) & 3))) * 16) = kv;
     }
     __syncthreads();
 
@@ -146,14 +134,14 @@ __global__ __launch_bounds__(H80_THREADS, (sizeof(T) == 2 ? 2 : 1)) void attenti
     for (int t = 0; t < H80_QPW; ++t) {
         const int qt = wave + t * (H80_THREADS / 64);
         // ---- scores: s[kt][i] = q . k for key 16 kt + 4 fg + i
-        h80_f32x4 s[H80_NT];
+        f32x4 s[H80_NT];
 #pragma unroll
         for (int kt = 0; kt < H80_NT; ++kt) {
-            h80_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
             const int r = kt * 16 + fr;
 #pragma unroll
             for (int g = 0; g < C::NG; ++g) {
-                const h80_u32x4 kf = *reinterpret_cast<const h80_u32x4*>(Ks + ((size_t)r * C::RCL + ((g * 4 + fg) ^ ((r >> 2) & 3))) * 16);
+                const u32x4 kf = *reinterpret_cast<const u32x4*>(Ks + ((size_t)r * C::RCL + ((g * 4 + fg) ^ ((r >> 2) & 3))) * 16);
                 acc = h80_mma(kf, qf_all[t][g], acc, T{});
             }
             s[kt] = acc;
@@ -161,31 +149,31 @@ __global__ __launch_bounds__(H80_THREADS, (sizeof(T) == 2 ? 2 : 1)) void attenti
         const float sum = h80_softmax(s, scale_log2e);
 
         // ---- O^T = V^T P^T over the 80 true columns
-        h80_f32x4 o[H80_DT];
+        f32x4 o[H80_DT];
 #pragma unroll
-        for (int dt = 0; dt < H80_DT; ++dt) o[dt] = h80_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int dt = 0; dt < H80_DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
         if constexpr (sizeof(T) == 2) {
 #pragma unroll
             for (int blk = 0; blk < H80_NT / 2; ++blk) {
-                const h80_f32x4 p0 = s[2 * blk], p1 = s[2 * blk + 1];
-                const h80_bf16x8 pf = {(__bf16)p0[0], (__bf16)p0[1], (__bf16)p0[2], (__bf16)p0[3],
+                const f32x4 p0 = s[2 * blk], p1 = s[2 * blk + 1];
+                const bf16x8 pf = {(__bf16)p0[0], (__bf16)p0[1], (__bf16)p0[2], (__bf16)p0[3],
                                        (__bf16)p1[0], (__bf16)p1[1], (__bf16)p1[2], (__bf16)p1[3]};
 #pragma unroll
                 for (int dt = 0; dt < H80_DT; ++dt) {
                     const T* vrow = Vt + (dt * 16 + fr) * H80_SPV + blk * 32 + 4 * fg;
-                    const h80_u32x2 lo = *reinterpret_cast<const h80_u32x2*>(vrow);
-                    const h80_u32x2 hi = *reinterpret_cast<const h80_u32x2*>(vrow + 16);
-                    const h80_u32x4 vf = {lo[0], lo[1], hi[0], hi[1]};
-                    o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(h80_bf16x8, vf), pf, o[dt], 0, 0, 0);
+                    const u32x2 lo = *reinterpret_cast<const u32x2*>(vrow);
+                    const u32x2 hi = *reinterpret_cast<const u32x2*>(vrow + 16);
+                    const u32x4 vf = {lo[0], lo[1], hi[0], hi[1]};
+                    o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vf), pf, o[dt], 0, 0, 0);
                 }
             }
         } else {
 #pragma unroll
             for (int kt = 0; kt < H80_NT; ++kt) {
-                const h80_u32x4 pf = __builtin_bit_cast(h80_u32x4, s[kt]);
+                const u32x4 pf = __builtin_bit_cast(u32x4, s[kt]);
 #pragma unroll
                 for (int dt = 0; dt < H80_DT; ++dt) {
-                    const h80_u32x4 vf = *reinterpret_cast<const h80_u32x4*>(Vt + (dt * 16 + fr) * H80_SPV + kt * 16 + 4 * fg);
+                    const u32x4 vf = *reinterpret_cast<const u32x4*>(Vt + (dt * 16 + fr) * H80_SPV + kt * 16 + 4 * fg);
                     o[dt] = h80_mma(vf, pf, o[dt], T{});
                 }
             }
@@ -195,12 +183,12 @@ __global__ __launch_bounds__(H80_THREADS, (sizeof(T) == 2 ? 2 : 1)) void attenti
         T* orow = out + ((size_t)seq * H80_S + qt * 16 + fr) * E + head * H80_HD;
 #pragma unroll
         for (int dt = 0; dt < H80_DT; ++dt) {
-            const h80_f32x4 v = o[dt] * inv;
+            const f32x4 v = o[dt] * inv;
             if constexpr (sizeof(T) == 2) {
-                const h80_bf16x4 ov = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                *reinterpret_cast<h80_bf16x4*>(orow + dt * 16 + 4 * fg) = ov;
+                const bf16x4 ov = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
+                *reinterpret_cast<bf16x4*>(orow + dt * 16 + 4 * fg) = ov;
             } else {
-                *reinterpret_cast<h80_f32x4*>(orow + dt * 16 + 4 * fg) = v;
+                *reinterpret_cast<f32x4*>(orow + dt * 16 + 4 * fg) = v;
             }
         }
         // one query tile's fragments at a time: without it the K reads of all three tiles are hoisted to the top (256 registers, one workgroup
@@ -241,11 +229,11 @@ __global__ __launch_bounds__(H80_THREADS, 1) void attention_hd80_split_kernel(co
 #pragma unroll
         for (int g = 0; g < H80_NB; ++g) {
             const int j = g * 4 + fg;
-            h80_u32x4 h = {0, 0, 0, 0}, l = {0, 0, 0, 0};
+            u32x4 h = {0, 0, 0, 0}, l = {0, 0, 0, 0};
             if (j < H80_JC) {  // (the padding loads nothing)
                 const char* p = chunk(qr, 0, j);
-                h = *reinterpret_cast<const h80_u32x4*>(p);
-                l = *reinterpret_cast<const h80_u32x4*>(p + 64);
+                h = *reinterpret_cast<const u32x4*>(p);
+                l = *reinterpret_cast<const u32x4*>(p + 64);
             }
             qh_all[t][g] = __builtin_bit_cast(f16x8, h);
             ql_all[t][g] = __builtin_bit_cast(f16x8, l);
@@ -257,11 +245,11 @@ __global__ __launch_bounds__(H80_THREADS, 1) void attention_hd80_split_kernel(co
         const int r = i / H80_JC, j = i - r * H80_JC;
         const char* pk = chunk(r, 1, j);
         const char* pv = chunk(r, 2, j);
-        const h80_u32x4 kh = *reinterpret_cast<const h80_u32x4*>(pk), kl = *reinterpret_cast<const h80_u32x4*>(pk + 64);
-        const h80_u32x4 vh = *reinterpret_cast<const h80_u32x4*>(pv), vl = *reinterpret_cast<const h80_u32x4*>(pv + 64);
+        const u32x4 kh = *reinterpret_cast<const u32x4*>(pk), kl = *reinterpret_cast<const u32x4*>(pk + 64);
+        const u32x4 vh = *reinterpret_cast<const u32x4*>(pv), vl = *reinterpret_cast<const u32x4*>(pv + 64);
         const int c = (j >> 2) * 8 + (j & 3);
-        *reinterpret_cast<h80_u32x4*>(Ks + ((size_t)r * H80_RC + (c ^ (r & 7))) * 16) = kh;
-        *reinterpret_cast<h80_u32x4*>(Ks + ((size_t)r * H80_RC + ((c + 4) ^ (r & 7))) * 16) = kl;
+        *reinterpret_cast<u32x4*>(Ks + ((size_t)r * H80_RC + (c ^ (r & 7))) * 16) = kh;
+        *reinterpret_cast<u32x4*>(Ks + ((size_t)r * H80_RC + ((c + 4) ^ (r & 7))) * 16) = kl;
         const f16x8 eh = __builtin_bit_cast(f16x8, vh), el = __builtin_bit_cast(f16x8, vl);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
@@ -272,7 +260,7 @@ __global__ __launch_bounds__(H80_THREADS, 1) void attention_hd80_split_kernel(co
     // the padding of the third block: chunks 10 and 11, hi and lo, of every key row
     for (int i = tid; i < H80_S * 4; i += H80_THREADS) {
         const int r = i >> 2, c = 16 + 2 + (i & 1) + ((i & 2) ? 4 : 0);
-        *reinterpret_cast<h80_u32x4*>(Ks + ((size_t)r * H80_RC + (c ^ (r & 7))) * 16) = h80_u32x4{0, 0, 0, 0};
+        *reinterpret_cast<u32x4*>(Ks + ((size_t)r * H80_RC + (c ^ (r & 7))) * 16) = u32x4{0, 0, 0, 0};
     }
     __syncthreads();
 
@@ -280,10 +268,10 @@ __global__ __launch_bounds__(H80_THREADS, 1) void attention_hd80_split_kernel(co
     for (int t = 0; t < H80_QPW; ++t) {
         const int qt = wave + t * (H80_THREADS / 64);
         // ---- scores: s[kt][i] = q . k for key 16 kt + 4 fg + i
-        h80_f32x4 s[H80_NT];
+        f32x4 s[H80_NT];
 #pragma unroll
         for (int kt = 0; kt < H80_NT; ++kt) {
-            h80_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
             const int r = kt * 16 + fr;
 #pragma unroll
             for (int g = 0; g < H80_NB; ++g) {
@@ -296,12 +284,12 @@ __global__ __launch_bounds__(H80_THREADS, 1) void attention_hd80_split_kernel(co
         const float sum = h80_softmax(s, scale_log2e);
 
         // ---- O^T = V^T P^T over the 80 true columns; p in [0, 1] is split in registers
-        h80_f32x4 o[H80_DT];
+        f32x4 o[H80_DT];
 #pragma unroll
-        for (int dt = 0; dt < H80_DT; ++dt) o[dt] = h80_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int dt = 0; dt < H80_DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int blk = 0; blk < H80_NT / 2; ++blk) {
-            const h80_f32x4 p0 = s[2 * blk], p1 = s[2 * blk + 1];
+            const f32x4 p0 = s[2 * blk], p1 = s[2 * blk + 1];
             f16x8 ph, pl;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -313,9 +301,9 @@ __global__ __launch_bounds__(H80_THREADS, 1) void attention_hd80_split_kernel(co
 #pragma unroll
             for (int dt = 0; dt < H80_DT; ++dt) {
                 const int off = (dt * 16 + fr) * H80_SPV + blk * 32 + 4 * fg;
-                const h80_u32x2 h0 = *reinterpret_cast<const h80_u32x2*>(Vh + off), h1 = *reinterpret_cast<const h80_u32x2*>(Vh + off + 16);
-                const h80_u32x2 l0 = *reinterpret_cast<const h80_u32x2*>(Vl + off), l1 = *reinterpret_cast<const h80_u32x2*>(Vl + off + 16);
-                const h80_u32x4 vh = {h0[0], h0[1], h1[0], h1[1]}, vl = {l0[0], l0[1], l1[0], l1[1]};
+                const u32x2 h0 = *reinterpret_cast<const u32x2*>(Vh + off), h1 = *reinterpret_cast<const u32x2*>(Vh + off + 16);
+                const u32x2 l0 = *reinterpret_cast<const u32x2*>(Vl + off), l1 = *reinterpret_cast<const u32x2*>(Vl + off + 16);
+                const u32x4 vh = {h0[0], h0[1], h1[0], h1[1]}, vl = {l0[0], l0[1], l1[0], l1[1]};
                 o[dt] = split_mma(__builtin_bit_cast(f16x8, vh), __builtin_bit_cast(f16x8, vl), ph, pl, o[dt]);
             }
         }

@@ -1,5 +1,6 @@
 // Shared host-side helpers of libprobpose_mi355x.so: status codes, thread-local error
-// string, launch checking. gfx950 only -- no dual paths, no CUDA shims.
+// string, launch checking, and the workgroup scan. gfx950 only -- no dual paths, no CUDA shims.
+// (the device-side primitives of the kernels are in pp_device.h)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +9,7 @@
 #include <cstdio>
 
 #include "../../include/probpose_mi355x.h"
+#include "pp_device.h"  // WAVE, lane_id, wave_id (block_scan below) and the matrix kernels' device primitives
 
 namespace pp {
 
@@ -55,11 +57,6 @@ inline int fail(int code, const char* what) {
         ::pp::count_launch(tag);           \
         PP_LAUNCH_CHECK();                 \
     } while (0)
-
-constexpr int WAVE = 64;
-
-__device__ __forceinline__ int lane_id() { return threadIdx.x & (WAVE - 1); }
-__device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 
 // Exclusive prefix of v over the 256 threads of a workgroup; total <- the sum. lds: four words.
 __device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* lds, uint32_t& total) {

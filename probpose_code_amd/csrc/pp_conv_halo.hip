@@ -22,17 +22,12 @@
 //     barrier per K-step, persistent workgroups (one per CU) whose DMA cursors run on across tiles, bias / ReLU /
 //     bf16 epilogue staged through the activation buffer that was just consumed and stored as whole rows.
 #include "pp_common.h"
+#include "pp_device.h"
 #include "pp_gemm.h"
 #include "pp_split.h"
 #include <cstdlib>
 
 namespace pp {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 namespace halo {
 
@@ -51,23 +46,8 @@ constexpr int W_STAGE = BN * 128;            // 16 KiB
 constexpr int OFF_W = 2 * A_BUF;
 constexpr int OFF_DUMP = OFF_W + 2 * W_STAGE; // 1 KiB that takes the DMA instructions which have nothing to fetch
 constexpr int LDS = OFF_DUMP + 1024;         // 159 KiB
-constexpr unsigned OOB = 0x7ffffff0u;
 static_assert(LDS <= 160 * 1024, "LDS map");
 static_assert((BM / 2) * BN * 2 <= A_BUF, "one image of the bf16 output tile is staged through an activation buffer");
-
-#define HSGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
-constexpr int SG_MFMA = 0x008, SG_VMEM = 0x010, SG_DS_READ = 0x100;
-
-__device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
-                                                   0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm_lgkm() {
-    static_assert(N >= 0 && N < 64, "vmcnt immediate");
-    __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (0 << 8) | ((N >> 4) << 14));
-}
 
 // POOL: the towers' MaxPool2d(kernel = stride = (pool_h, pool_w)) + ReLU (probmap_head.py:264,277-278) applied to the staged image in the
 // epilogue - a tile holds whole images, so the pooling windows never leave it; C is then the pooled tensor (N, H / ph, W / pw, Cout)
@@ -102,7 +82,7 @@ __global__ __launch_bounds__(THREADS, 2) void conv3_halo_kernel(const GemmParams
 
     // ---- DMA lanes. An instruction moves 8 LDS rows of 128 B; lane = (row d_l, physical chunk pc).
     const int d_l = lane >> 3, pc = lane & 7;
-    // activation halo rows: tile-invariant part of the address (pixel inside the image pair, swizzled chunk) or OOB
+    // activation halo rows: tile-invariant part of the address (pixel inside the image pair, swizzled chunk) or kOob
     unsigned a_rel[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -111,7 +91,7 @@ __global__ __launch_bounds__(THREADS, 2) void conv3_halo_kernel(const GemmParams
         const int hy = r / PW - 1, hx = r - (r / PW) * PW - 1;
         const bool ok = l < 2 * HR && hy >= 0 && hy < H && hx >= 0 && hx < Wd;
         const int lin = hy * Wd + hx;
-        a_rel[j] = ok ? (unsigned)((img * IMG_PIX + lin) * (p.Cin * 2) + ((pc ^ (lin & 7)) << 4)) : OOB;
+        a_rel[j] = ok ? (unsigned)((img * IMG_PIX + lin) * (p.Cin * 2) + ((pc ^ (lin & 7)) << 4)) : kOob;
     }
     // weight rows: stage row n = 8 (wv + 8 jj) + d_l
     unsigned w_rel[2];
@@ -131,7 +111,7 @@ __global__ __launch_bounds__(THREADS, 2) void conv3_halo_kernel(const GemmParams
         wi_live = wi_tile < ntiles;
         if (wi_live) decode_tile(wi_tile, z, m0, n0);
         const char* Wt = reinterpret_cast<const char*>(p.W) + (size_t)z * p.strideW_z * 2;
-        w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(Wt), 0, p.w_bytes, 0x00020000);
+        w_rsrc = buffer_rsrc(Wt, p.w_bytes);
         wi_base = (unsigned)n0 * (unsigned)(p.ldw * 2);
         wi_chunk = 0;
         wi_tap = 0;
@@ -141,7 +121,7 @@ __global__ __launch_bounds__(THREADS, 2) void conv3_halo_kernel(const GemmParams
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) {
             char* dst = smem + OFF_W + buf * W_STAGE + (wv + 8 * jj) * 1024;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (lds_ptr_t)dst, 16, (wi_live && !(DBG & 1)) ? w_rel[jj] + kb : OOB, 0, 0, 0);
+            dma16(w_rsrc, dst, (wi_live && !(DBG & 1)) ? w_rel[jj] + kb : kOob);
         }
         if (++wi_tap == 9) {
             wi_tap = 0;
@@ -160,7 +140,7 @@ __global__ __launch_bounds__(THREADS, 2) void conv3_halo_kernel(const GemmParams
         pa_live = pa_tile < ntiles;
         if (pa_live) decode_tile(pa_tile, z, m0, n0);
         const char* Act = reinterpret_cast<const char*>(p.A) + (size_t)z * p.strideA_z * 2;
-        a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(Act), 0, p.a_bytes, 0x00020000);
+        a_rsrc = buffer_rsrc(Act, p.a_bytes);
         pa_base = (unsigned)m0 * (unsigned)(p.Cin * 2);  // images past the batch: beyond a_bytes = zeros
         pa_chunk = 0;
     };
@@ -175,8 +155,8 @@ __global__ __launch_bounds__(THREADS, 2) void conv3_halo_kernel(const GemmParams
         }
         const bool real = j < 8 && wv + 8 * j < A_INSTR;
         char* dst = smem + (real ? abuf * A_BUF + (wv + 8 * j) * 1024 : OFF_DUMP);
-        const unsigned va = (real && pa_live && !(DBG & 1)) ? rel + pa_base + (unsigned)(pa_chunk * 128) : OOB;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (lds_ptr_t)dst, 16, va, 0, 0, 0);
+        const unsigned va = (real && pa_live && !(DBG & 1)) ? rel + pa_base + (unsigned)(pa_chunk * 128) : kOob;
+        dma16(a_rsrc, dst, va);
     };
     auto advance_a = [&]() {
         if (++pa_chunk == c64) {
@@ -228,7 +208,7 @@ __global__ __launch_bounds__(THREADS, 2) void conv3_halo_kernel(const GemmParams
         for (int rf = 0; rf < RF; ++rf)
 #pragma unroll
             for (int cf = 0; cf < CF; ++cf) {
-                if (!(DBG & 4)) acc[cf][rf] = mma(w[cf], a[rf], acc[cf][rf]);
+                if (!(DBG & 4)) acc[cf][rf] = mma_bf16(w[cf], a[rf], acc[cf][rf]);
             }
     };
 

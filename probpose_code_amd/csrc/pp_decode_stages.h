@@ -8,13 +8,12 @@
 #include <cmath>
 
 #include "pp_common.h"
+#include "pp_device.h"
 
 // numpy evaluates the fp32 expressions one rounding per operator; keep it so (the including files say the same).
 #pragma clang fp contract(off)
 
 namespace pp {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int PAD = 12;            // x-padding of the LDS map either side: >= the largest radius and a multiple of 4, so that a pixel quad (y, 4 q .. 4 q + 3)
                                    // is a 16-byte aligned slot (ds_write_b128 / ds_read_b128: one conflict-free access per quad)
@@ -132,7 +131,6 @@ __device__ __forceinline__ f32x4 load_quad(const f32x4* base, bool ok, int y, in
     f32x4 r{ninf, ninf, ninf, ninf};
     if (!ok) return r;
     if (!phased) return base[y * W4 + (x0 >> 2)];
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
     const f32x2* pb = reinterpret_cast<const f32x2*>(base) + ((y & 1) * HW4 + (y >> 1) * W4 + (x0 >> 2));  // (in pairs: a phase block is HW4 / 2 pairs)
     const f32x2 a = pb[0], c = pb[HW4 >> 1];
     return f32x4{a[0], c[0], a[1], c[1]};

@@ -23,6 +23,7 @@
 // after a compiler upgrade or a change of the loop structure re-run tests/test_split_fp16.py - its `ffn_form` 1 runs the SAME
 // arithmetic on the builtin-MFMA kernels (hazards handled by the compiler) and both forms are held to the fp64 reference.
 #include "pp_common.h"
+#include "pp_device.h"
 #include "pp_split.h"
 #include "pp_ffn_params.h"
 
@@ -30,9 +31,6 @@ namespace pp {
 namespace ffd {
 
 using ffs::Params;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr int BM = 96, E = 384, CHUNK = 128;
 constexpr int CW = 8, WAVES = 12, THREADS = WAVES * 64;
@@ -56,11 +54,6 @@ static_assert(STEPS % NSLOT == 0 && NPROJ % NSLOT == 0, "ring positions must rep
 #define FFD_STAMP 0  // dev: wave 0 of workgroups 0 and 131 leaves s_memtime stamps at the phase boundaries of the paired proj + FFN kernel (scripts/micro/ffd_stamps.sh)
 #endif
 
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt immediate");
-    __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
-}
 // (n is a compile-time constant after unrolling; the builtin wants a literal)
 __device__ __forceinline__ void wait_vm_n(int n) {
     switch (n) {
@@ -80,10 +73,6 @@ __device__ __forceinline__ void wait_vm_n(int n) {
 // pieces one DMA wave issues for a step of the main loop / of the projection phase
 __host__ __device__ constexpr int n_main(int t) { return (((t % STEPS) + STEPS) % STEPS) < NA ? 7 : 6; }
 __host__ __device__ constexpr int n_proj(int s) { return s < NPROJ ? 6 + ((s & 1) == 0 ? 3 : 0) : 0; }
-
-__device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 
 // In-place MFMA as inline assembly (PAIR form only): acc += a b with the accumulator tied to one register tuple. The builtin form lets the
 // register allocator RENAME the destination of a step's first sweep inside the run-time k-block loop (+24 live registers: 146 spilled);
@@ -120,20 +109,19 @@ __device__ __forceinline__ void dma_role(const Params& p, char* smem, int d, int
     if constexpr (PROJ) {
         auto issue_p = [&](int s) {
             if (s >= NPROJ) return;
-            const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.wproj), 0, p.wproj_bytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rw = buffer_rsrc(p.wproj, p.wproj_bytes);
 #pragma unroll
             for (int u = 0; u < 6; ++u) {
                 const int q = d + 4 * u;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(ring + (s & 3) * SLOTB + q * 1024), 16, v_w, s * B_BLOCK + q * 1024, 0, 0);
+                dma16(rw, ring + (s & 3) * SLOTB + q * 1024, v_w, s * B_BLOCK + q * 1024);
             }
             if ((s & 1) == 0) {
                 const int kb = s >> 1;
-                const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.att), 0, p.att_bytes, 0x00020000);
+                const __amdgpu_buffer_rsrc_t ra = buffer_rsrc(p.att, p.att_bytes);
 #pragma unroll
                 for (int u = 0; u < 3; ++u) {
                     const int q = d + 4 * u;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_ptr_t)(smem + OFF_G + (kb & 3) * G_KB + q * 1024), 16, v_x,
-                                                             kb * 128 + q * 8 * E * 4, 0, 0);
+                    dma16(ra, smem + OFF_G + (kb & 3) * G_KB + q * 1024, v_x, kb * 128 + q * 8 * E * 4);
                 }
             }
         };
@@ -162,27 +150,27 @@ __device__ __forceinline__ void dma_role(const Params& p, char* smem, int d, int
         int c = (live ? ci : 0) + c_rot;
         c = c >= nchunks ? c - nchunks : c;
         const int base = c * CHUNK_BYTES;
-        const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.wpack), 0, live ? p.w_bytes : 0u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rw = buffer_rsrc(p.wpack, live ? p.w_bytes : 0u);
         char* dst = ring + (t & 3) * SLOTB;
         if (t < NA) {
             const int kb = (ci & 1) ? NA - 1 - t : t;  // odd visits walk the k-blocks backwards (pp_ffn_split.hip: the L2 finds the rows)
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int q = d + 4 * u;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(dst + q * 1024), 16, v_w, base + kb * A_BLOCK + q * 1024, 0, 0);
+                dma16(rw, dst + q * 1024, v_w, base + kb * A_BLOCK + q * 1024);
             }
-            const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.h), 0, live ? p.h_bytes : 0u, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rh = buffer_rsrc(p.h, live ? p.h_bytes : 0u);
 #pragma unroll
             for (int u = 0; u < 3; ++u) {
                 const int q = d + 4 * u;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rh, (lds_ptr_t)(dst + X_OFF + q * 1024), 16, v_x, kb * 128 + q * 8 * E * 4, 0, 0);
+                dma16(rh, dst + X_OFF + q * 1024, v_x, kb * 128 + q * 8 * E * 4);
             }
         } else {
             const int sb = t - NA;
 #pragma unroll
             for (int u = 0; u < 6; ++u) {
                 const int q = d + 4 * u;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(dst + q * 1024), 16, v_w, base + B_PART + sb * B_BLOCK + q * 1024, 0, 0);
+                dma16(rw, dst + q * 1024, v_w, base + B_PART + sb * B_BLOCK + q * 1024);
             }
         }
     };
@@ -197,7 +185,7 @@ __device__ __forceinline__ void dma_role(const Params& p, char* smem, int d, int
             asm volatile("" : "+s"(cp));
             const bool live = cp < npairs;
             const int cpl = live ? cp : 0;
-            const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.wpack), 0, live ? p.w_bytes : 0u, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rw = buffer_rsrc(p.wpack, live ? p.w_bytes : 0u);
             char* dst = ring + (t & 3) * SLOTB;
             if (t < 2 * NA) {
                 int c = 2 * cpl + (t & 1) + c_rot;
@@ -206,14 +194,14 @@ __device__ __forceinline__ void dma_role(const Params& p, char* smem, int d, int
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int q = d + 4 * u;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(dst + q * 1024), 16, v_w, c * CHUNK_BYTES + kb * A_BLOCK + q * 1024, 0, 0);
+                    dma16(rw, dst + q * 1024, v_w, c * CHUNK_BYTES + kb * A_BLOCK + q * 1024);
                 }
                 if ((t & 1) == 0) {
-                    const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.h), 0, live ? p.h_bytes : 0u, 0x00020000);
+                    const __amdgpu_buffer_rsrc_t rh = buffer_rsrc(p.h, live ? p.h_bytes : 0u);
 #pragma unroll
                     for (int u = 0; u < 3; ++u) {
                         const int q = d + 4 * u;
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rh, (lds_ptr_t)(dst + X_OFF + q * 1024), 16, v_x, kb * 128 + q * 8 * E * 4, 0, 0);
+                        dma16(rh, dst + X_OFF + q * 1024, v_x, kb * 128 + q * 8 * E * 4);
                     }
                 }
             } else {
@@ -223,7 +211,7 @@ __device__ __forceinline__ void dma_role(const Params& p, char* smem, int d, int
 #pragma unroll
                 for (int u = 0; u < 6; ++u) {
                     const int q = d + 4 * u;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(dst + q * 1024), 16, v_w, c * CHUNK_BYTES + B_PART + sb * B_BLOCK + q * 1024, 0, 0);
+                    dma16(rw, dst + q * 1024, v_w, c * CHUNK_BYTES + B_PART + sb * B_BLOCK + q * 1024);
                 }
             }
         };
@@ -315,7 +303,7 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
     auto step_barrier = [&]() {
         __builtin_amdgcn_sched_barrier(0);
         // lgkmcnt(0): this wave's LDS writes (the G tile) are in before anyone is let through; its reads were consumed by the MFMAs
-        __builtin_amdgcn_s_waitcnt((63 & 15) | (7 << 4) | (0 << 8) | ((63 >> 4) << 14));
+        wait_vm_lgkm<63>();
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
     };
@@ -343,17 +331,17 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
 #pragma unroll
         for (int rf = 0; rf < 3; ++rf)
 #pragma unroll
-            for (int nf = 0; nf < 3; ++nf) acc[rf][half * 3 + nf] = mma(wh[nf], bgh[rf], acc[rf][half * 3 + nf]);
+            for (int nf = 0; nf < 3; ++nf) acc[rf][half * 3 + nf] = mma_f16(wh[nf], bgh[rf], acc[rf][half * 3 + nf]);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int rf = 0; rf < 3; ++rf)
 #pragma unroll
-            for (int nf = 0; nf < 3; ++nf) acc[rf][half * 3 + nf] = mma(wl[nf], bgh[rf], acc[rf][half * 3 + nf]);
+            for (int nf = 0; nf < 3; ++nf) acc[rf][half * 3 + nf] = mma_f16(wl[nf], bgh[rf], acc[rf][half * 3 + nf]);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int nf = 0; nf < 3; ++nf)
 #pragma unroll
-            for (int rf = 0; rf < 3; ++rf) acc[rf][half * 3 + nf] = mma(wh[nf], bgl[rf], acc[rf][half * 3 + nf]);
+            for (int rf = 0; rf < 3; ++rf) acc[rf][half * 3 + nf] = mma_f16(wh[nf], bgl[rf], acc[rf][half * 3 + nf]);
     };
     (void)b_step;  // (not every instantiation takes this path)
     // LayerNorm of the 96 x 384 block in the accumulators (pp_ffn_split.hip layernorm_rows: same operations in the same order)
@@ -379,8 +367,8 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
         const unsigned v_rowh = row_ + (unsigned)fk_ * 8u;                                             // split rows: the lane's four hi halves (lo: + 64)
         const unsigned v_rowh2 = row_ + (unsigned)(fk_ >> 1) * 16u + (unsigned)(fk_ & 1) * 64u;       // row-pair form: 16-byte hi chunk (even f_kg) / lo chunk (odd)
         (void)v_rowh;
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(x_dst, 0, p.h_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc(h_dst, 0, p.h_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rx = buffer_rsrc(x_dst, p.h_bytes);
+        const __amdgpu_buffer_rsrc_t rh = buffer_rsrc(h_dst, p.h_bytes);
         float* stat = reinterpret_cast<float*>(smem + OFF_G);
         float mean[3], rstd[3];
 #pragma unroll
@@ -422,8 +410,7 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
             const float var = ((stat[4 * BM + r] + stat[5 * BM + r]) + (stat[6 * BM + r] + stat[7 * BM + r])) * (1.0f / E);
             rstd[rf] = 1.0f / sqrtf(var + p.eps);
             if (FO && fk_ == 0 && cg == 0 && m0 + r < p.M) {
-                typedef float f32x2_t __attribute__((ext_vector_type(2)));
-                *reinterpret_cast<f32x2_t*>(p.stats_out + (size_t)(m0 + r) * 2) = f32x2_t{mean[rf], rstd[rf]};
+                *reinterpret_cast<f32x2*>(p.stats_out + (size_t)(m0 + r) * 2) = f32x2{mean[rf], rstd[rf]};
             }
         }
         // gamma / beta of all six column fragments in one round trip (48 registers: the operand fragments are dead): inside the store loop every
@@ -441,7 +428,6 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
             const f32x4 g = gs_[cf], b = bs_[cf];
 #pragma unroll
             for (int rf = 0; rf < 3; ++rf) {
-                typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
                 const f32x4 v = acc[rf][cf];
                 float mu = mean[rf];
                 const float rs = rstd[rf];
@@ -453,19 +439,14 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
                 for (int j = 0; j < 4; ++j) { float t = hv[j]; split_pin(t); hv[j] = t; }
                 if (store_x) {
                     const u32x4 vq = __builtin_bit_cast(u32x4, v);
-                    __builtin_amdgcn_raw_buffer_store_b128(vq, rx, v_rowx + rf * (16 * E * 4), cb * 4, 0);
-                    asm volatile("s_nop 3" ::"v"(vq));  // (wait states behind a 16-byte buffer store: scripts/micro/mubuf_store_hazard.hip)
+                    store16_guarded(vq, rx, v_rowx + rf * (16 * E * 4), cb * 4);
                 }
-                // WAIT STATES BEHIND 16-BYTE BUFFER STORES. A buffer_store_dwordx4 reads its data registers one cycle late for lanes
-                // 12 - 15 of every row; an instruction that writes one of them directly behind the store changes what those lanes store.
-                // The hardware wants one wait state (SGPR soffset) or two (immediate) there - scripts/micro/mubuf_store_hazard.hip
-                // shows it in isolation - and the compiler inserts none for the SGPR form, which is the form used here. Seen as a
-                // handful of stale 4-byte words per launch on a full chip (first behind the v_permlane16_swap below and wrongly blamed
-                // on the swap; then in pp_linear_dma.hip's fp32 rows, where no swap is involved). Every 16-byte buffer store of this
-                // file is followed by an explicit s_nop that depends on its data.
+                // Every 16-byte buffer store of this file is a store16_guarded (pp_device.h): without its wait states a handful of stale
+                // 4-byte words per launch on a full chip (first seen behind the v_permlane16_swap below and wrongly blamed on the swap;
+                // then in pp_linear_dma.hip's fp32 rows, where no swap is involved).
                 // (hi, lo) of the four values by split_pair: eight VALU instructions instead of fourteen (the stamps of round 5 found the LayerNorm
                 // epilogues still on the one-value-at-a-time split)
-                u32x2_t hu, lu;
+                u32x2 hu, lu;
                 { unsigned h__, l__; split_pair(hv[0], hv[1], h__, l__); hu[0] = h__; lu[0] = l__; }
                 { unsigned h__, l__; split_pair(hv[2], hv[3], h__, l__); hu[1] = h__; lu[1] = l__; }
                 const int so = (cb >> 5) * 128 + (cb & 16) * 2;
@@ -474,8 +455,7 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
                     const auto s0 = __builtin_amdgcn_permlane16_swap(hu[0], lu[0], false, false);
                     const auto s1 = __builtin_amdgcn_permlane16_swap(hu[1], lu[1], false, false);
                     u32x4 q = {s0[0], s1[0], s0[1], s1[1]};
-                    __builtin_amdgcn_raw_buffer_store_b128(q, rh, v_rowh2 + rf * (16 * E * 4), so, 0);
-                    asm volatile("s_nop 3" ::"v"(q));
+                    store16_guarded(q, rh, v_rowh2 + rf * (16 * E * 4), so);
                 }
             }
         }
@@ -490,7 +470,7 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
             res_mean[rf] = r < p.M ? p.res_stats[(size_t)r * 2] : 0.f;
         }
     }
-    const __amdgpu_buffer_rsrc_t rres = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.residual), 0, p.h_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rres = buffer_rsrc(p.residual, p.h_bytes);
     const unsigned v_rowx = (unsigned)(m0 + rows0) * (unsigned)(E * 4) + (unsigned)f_kg * 16u;  // (dead after these loads)
 #pragma unroll
     for (int rf = 0; rf < 3; ++rf)
@@ -504,8 +484,7 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
                 const u32x4 q = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rres, vsp + rf * (16 * E * 4), (cb >> 5) * 128 + (cb & 16) * 2, 0));
                 const auto s0 = __builtin_amdgcn_permlane16_swap(q[0], q[2], false, false);
                 const auto s1 = __builtin_amdgcn_permlane16_swap(q[1], q[3], false, false);
-                typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-                const f16x4 hh = __builtin_bit_cast(f16x4, u32x2_t{s0[0], s1[0]}), ll = __builtin_bit_cast(f16x4, u32x2_t{s0[1], s1[1]});
+                const f16x4 hh = __builtin_bit_cast(f16x4, u32x2{s0[0], s1[0]}), ll = __builtin_bit_cast(f16x4, u32x2{s0[1], s1[1]});
                 // (centered rows: the row's mean comes back here - after hi + lo, the order the producer's x - mean inverts)
                 const float mu = res_mean[rf];
                 acc[rf][cf] = f32x4{((float)hh[0] + (float)ll[0]) + mu, ((float)hh[1] + (float)ll[1]) + mu, ((float)hh[2] + (float)ll[2]) + mu,
@@ -554,7 +533,7 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
 #pragma unroll
                     for (int i = 0; i < 9; ++i) {  // hi x lo
                         const int rf = i / 3, nf = i % 3;
-                        acc[rf][half * 3 + nf] = mma(pwh[nf], bgl[rf], acc[rf][half * 3 + nf]);
+                        acc[rf][half * 3 + nf] = mma_f16(pwh[nf], bgl[rf], acc[rf][half * 3 + nf]);
                         __builtin_amdgcn_sched_barrier(0);
                         if (i == 1 && nb) step_barrier();
                         if (nf == 2 && newg) bgl[rf] = rd(lane_lo, ug_n, rf * 2048);
@@ -563,7 +542,7 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
 #pragma unroll
                     for (int i = 0; i < 9; ++i) {  // hi x hi
                         const int rf = i / 3, nf = i % 3;
-                        acc[rf][half * 3 + nf] = mma(pwh[nf], bgh[rf], acc[rf][half * 3 + nf]);
+                        acc[rf][half * 3 + nf] = mma_f16(pwh[nf], bgh[rf], acc[rf][half * 3 + nf]);
                         __builtin_amdgcn_sched_barrier(0);
                         if (rf == 2 && nb) pwh[nf] = rd(lane_hi, ub_n, nf * 2048);
                         __builtin_amdgcn_sched_barrier(0);
@@ -571,7 +550,7 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
 #pragma unroll
                     for (int i = 0; i < 9; ++i) {  // lo x hi
                         const int rf = i / 3, nf = i % 3;
-                        acc[rf][half * 3 + nf] = mma(pwl[nf], bgh[rf], acc[rf][half * 3 + nf]);
+                        acc[rf][half * 3 + nf] = mma_f16(pwl[nf], bgh[rf], acc[rf][half * 3 + nf]);
                         __builtin_amdgcn_sched_barrier(0);
                         if (nf == 2 && newg) bgh[rf] = rd(lane_hi, ug_n, rf * 2048);
                         if (rf == 2 && nb) pwl[nf] = rd(lane_lo, ub_n, nf * 2048);
@@ -597,7 +576,7 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
         stamp();  // (fine) ln2 rows stored (issued)
 #endif
         // the rows must be in L2 before the DMA waves ask for them (a store counts in vmcnt until the L2 has acknowledged it)
-        __builtin_amdgcn_s_waitcnt((7 << 4) | (0 << 8) | (0));
+        wait_vm_lgkm<0>();
 #if FFD_STAMP == 2
         stamp();  // (fine) stores acknowledged
 #endif
@@ -645,8 +624,6 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
                 // exp2(-(x sqrt(log2(e) / 2))^2), max(x, 0) = 0.5 x + 0.5 |x| exactly) and the lo half as g - hi by ONE v_fma_mix_f32 that
                 // reads hi straight from the packed fp16 pair (exact: the same difference as convert-back-and-subtract): ~56 instead of ~76
                 // issue cycles per value. |difference to the unpacked form| ~1e-7 relative (rounding of the folded constants).
-                typedef float f32x2 __attribute__((ext_vector_type(2)));
-                typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
                 unsigned hq[2], lq[2];
 #pragma unroll
                 for (int u0 = 0; u0 < 2; ++u0) {
@@ -674,9 +651,8 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
                     hq[u0] = hu;
                     lq[u0] = __builtin_bit_cast(unsigned, __builtin_convertvector(l, f16x2));
                 }
-                typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-                *reinterpret_cast<u32x2_t*>(gs + ((c ^ sw) << 4)) = u32x2_t{hq[0], hq[1]};
-                *reinterpret_cast<u32x2_t*>(gs + (((4 + c) ^ sw) << 4)) = u32x2_t{lq[0], lq[1]};
+                *reinterpret_cast<u32x2*>(gs + ((c ^ sw) << 4)) = u32x2{hq[0], hq[1]};
+                *reinterpret_cast<u32x2*>(gs + (((4 + c) ^ sw) << 4)) = u32x2{lq[0], lq[1]};
             }
     };
 
@@ -691,7 +667,7 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
         // (24 registers) live through the first chunk's GELU and B-steps; the B-steps' fragments leave room for them (72 + 24 + 48 = 144).
         f32x4 pacc1[3][2];  // P of the pair's second chunk (pacc: the first)
         u32x4 wh[2], wl[2], xh[3], xl[3], bwh[3], bwl[3];
-        const __amdgpu_buffer_rsrc_t rb1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.b1), 0, (unsigned)p.F * 4u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rb1 = buffer_rsrc(p.b1, (unsigned)p.F * 4u);
         auto load_b1x = [&](int ci, f32x4 (&dst)[2]) __attribute__((always_inline)) {  // (descriptor + lane & 0x30: no 64-bit address kept alive through the B-steps)
             const int c = chunk_of(ci < nchunks ? ci : 0);
             int vo = lane;
@@ -873,7 +849,7 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
 #pragma unroll
                 for (int i = 0; i < 6; ++i) {  // hi x lo
                     const int rf = i >> 1, nf = i & 1;
-                    pacc[rf][nf] = mma(wh[nf], xl[rf], pacc[rf][nf]);
+                    pacc[rf][nf] = mma_f16(wh[nf], xl[rf], pacc[rf][nf]);
                     __builtin_amdgcn_sched_barrier(0);
                     if (i == 1) step_barrier();  // the barrier of step t + 1
                     if (na && nf == 1) xl[rf] = rd(lane_lo, ux_n, rf * 2048);
@@ -882,7 +858,7 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
 #pragma unroll
                 for (int i = 0; i < 6; ++i) {  // hi x hi
                     const int rf = i >> 1, nf = i & 1;
-                    pacc[rf][nf] = mma(wh[nf], xh[rf], pacc[rf][nf]);
+                    pacc[rf][nf] = mma_f16(wh[nf], xh[rf], pacc[rf][nf]);
                     __builtin_amdgcn_sched_barrier(0);
                     if (rf == 2) { if (na) wh[nf] = rd(lane_hi, ua_n, nf * 2048); else bwh[nf] = rd(lane_hi, ub_n, nf * 2048); }
                     if (!na && i == 5) bwh[2] = rd(lane_hi, ub_n, 2 * 2048);
@@ -891,7 +867,7 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
 #pragma unroll
                 for (int i = 0; i < 6; ++i) {  // lo x hi
                     const int rf = i >> 1, nf = i & 1;
-                    pacc[rf][nf] = mma(wl[nf], xh[rf], pacc[rf][nf]);
+                    pacc[rf][nf] = mma_f16(wl[nf], xh[rf], pacc[rf][nf]);
                     __builtin_amdgcn_sched_barrier(0);
                     if (na && nf == 1) xh[rf] = rd(lane_hi, ux_n, rf * 2048);
                     if (rf == 2) { if (na) wl[nf] = rd(lane_lo, ua_n, nf * 2048); else bwl[nf] = rd(lane_lo, ub_n, nf * 2048); }
@@ -919,7 +895,7 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
 #pragma unroll
                 for (int i = 0; i < 9; ++i) {  // hi x lo
                     const int rf = i / 3, nf = i % 3;
-                    acc[rf][half * 3 + nf] = mma(bwh[nf], bgl[rf], acc[rf][half * 3 + nf]);
+                    acc[rf][half * 3 + nf] = mma_f16(bwh[nf], bgl[rf], acc[rf][half * 3 + nf]);
                     __builtin_amdgcn_sched_barrier(0);
                     if (i == 1 && (nb || ci + 1 < nchunks)) step_barrier();  // (the launch's last step has no successor: the epilogue's E1 is the DMA waves' next barrier)
                     if (nf == 2) { if (newg) bgl[rf] = rd(lane_lo, ug_n, rf * 2048); else if (!nb) xl[rf] = rd(lane_lo, ux_n, rf * 2048); }
@@ -928,7 +904,7 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
 #pragma unroll
                 for (int i = 0; i < 9; ++i) {  // hi x hi
                     const int rf = i / 3, nf = i % 3;
-                    acc[rf][half * 3 + nf] = mma(bwh[nf], bgh[rf], acc[rf][half * 3 + nf]);
+                    acc[rf][half * 3 + nf] = mma_f16(bwh[nf], bgh[rf], acc[rf][half * 3 + nf]);
                     __builtin_amdgcn_sched_barrier(0);
                     if (rf == 2) { if (nb) bwh[nf] = rd(lane_hi, ub_n, nf * 2048); else if (nf < 2) wh[nf] = rd(lane_hi, ua_n, nf * 2048); }
                     __builtin_amdgcn_sched_barrier(0);
@@ -936,7 +912,7 @@ __device__ __forceinline__ void compute_role(const Params& p, char* smem, int wv
 #pragma unroll
                 for (int i = 0; i < 9; ++i) {  // lo x hi
                     const int rf = i / 3, nf = i % 3;
-                    acc[rf][half * 3 + nf] = mma(bwl[nf], bgh[rf], acc[rf][half * 3 + nf]);
+                    acc[rf][half * 3 + nf] = mma_f16(bwl[nf], bgh[rf], acc[rf][half * 3 + nf]);
                     __builtin_amdgcn_sched_barrier(0);
                     if (nf == 2) { if (newg) bgh[rf] = rd(lane_hi, ug_n, rf * 2048); else if (!nb) xh[rf] = rd(lane_hi, ux_n, rf * 2048); }
                     if (rf == 2) { if (nb) bwl[nf] = rd(lane_lo, ub_n, nf * 2048); else if (nf < 2) wl[nf] = rd(lane_lo, ua_n, nf * 2048); }

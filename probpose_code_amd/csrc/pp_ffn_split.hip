@@ -16,15 +16,12 @@
 //     is a linear 1 KiB copy; the x lines are 128-byte segments of the row-major split tensor, swizzled at the source.
 // LDS: 48 KiB G + 4 x 28 KiB ring = 160 KiB.
 #include "pp_common.h"
+#include "pp_device.h"
 #include "pp_split.h"
 #include "pp_ffn_params.h"
 
 namespace pp {
 namespace ffs {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 [[maybe_unused]] constexpr int BM = 96, E = 384, CHUNK = 128, THREADS = 512;
 constexpr int KB = E / 32;                       // 12 k-blocks of the input width
@@ -39,10 +36,8 @@ constexpr int A_BLOCK = CHUNK * 128;             // 16 KiB
 constexpr int B_BLOCK = (E / 2) * 128;           // 24 KiB
 constexpr int B_PART = NA * A_BLOCK;             // 192 KiB: offset of the W2 half blocks inside a chunk's stream
 constexpr int CHUNK_BYTES = B_PART + NB * B_BLOCK;  // 384 KiB
-constexpr unsigned OOB = 0x7ffffff0u;
 static_assert(LDS == 160 * 1024, "LDS map");
 static_assert(NA % NSLOT == 0 && STEPS % NSLOT == 0, "ring positions must repeat per chunk");
-
 
 // Packs W1 (F, 384) and W2 (384, F), both split row-major, into the stream the kernel consumes: per hidden chunk c of 128
 // units 12 blocks [128 units][128 B] (k-block kb of W1 rows 128 c ..) followed by 8 blocks [192 outputs][128 B] (block
@@ -164,7 +159,7 @@ static void fill_proj(pp::ffs::Params& p, const void* att, const void* wproj_pac
 #define PP_FFN_SHAPE_CHECKS(name)                                                                                                          \
     PP_REQUIRE(E == ffs::E, PP_ERR_UNSUPPORTED, name ": built for embed dim 384 (ViT-S)");                                                 \
     PP_REQUIRE(M > 0 && F > 0 && F % ffs::CHUNK == 0, PP_ERR_UNSUPPORTED, name ": hidden width must be a positive multiple of 128");       \
-    PP_REQUIRE((size_t)M * E * 4 < ffs::OOB && (size_t)(F / ffs::CHUNK) * ffs::CHUNK_BYTES < ffs::OOB, PP_ERR_UNSUPPORTED, name ": operand exceeds 2 GiB")
+    PP_REQUIRE((size_t)M * E * 4 < pp::kOob && (size_t)(F / ffs::CHUNK) * ffs::CHUNK_BYTES < pp::kOob, PP_ERR_UNSUPPORTED, name ": operand exceeds 2 GiB")
 
 extern "C" int pp_ffn_split_residual_layernorm_ws(const void* h_in, const void* w_packed, const float* b1, const float* b2, const float* residual,
                                                   float* x_out, const float* gamma, const float* beta, float eps, void* h_out, int M, int E, int F,

@@ -31,6 +31,7 @@
 //   * tile order is XCD-aware: each XCD (private L2) gets a contiguous run of tiles, so the
 //     n-tiles that share one activation panel hit the same L2.
 #include "pp_common.h"
+#include "pp_device.h"
 #include "pp_gemm.h"
 #include "pp_split.h"
 
@@ -38,18 +39,11 @@
 
 namespace pp {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
 constexpr int BM = 128, BN = 128;
 constexpr int GEMM_THREADS = 256;
 constexpr int ROW_BYTES = 128;                  // one K-tile row in LDS
 constexpr int TILE_BYTES = BM * ROW_BYTES;      // 16 KiB per operand per buffer
 constexpr int BUF_BYTES = 2 * TILE_BYTES;       // W tile + Act tile
-constexpr unsigned OOB_OFFSET = 0x7ffffff0u;    // >= num_records of every tensor (< 2 GiB): the DMA writes zeros
 
 template <typename T>
 struct Prec;
@@ -67,21 +61,9 @@ struct Prec<SplitH> {
 };
 enum { FMT_F32 = 0, FMT_BF16 = 1, FMT_SPLIT = 2 };  // GemmParams::out_bf16 carries this code (PP_OUT_*)
 
-__device__ __forceinline__ int swz(int row, int chunk) { return row * ROW_BYTES + ((chunk ^ (row & 7)) << 4); }
-
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-
 // MFMA over one 16x16 fragment pair for a 16-byte chunk of K
-__device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, f32x4 c, __bf16) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
-                                                   0, 0);
-}
-__device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, f32x4 c, float) {
-    const f32x4 af = __builtin_bit_cast(f32x4, a), bf = __builtin_bit_cast(f32x4, b);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) c = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], bf[j], c, 0, 0, 0);
-    return c;
-}
+__device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, f32x4 c, __bf16) { return mma_bf16(a, b, c); }
+__device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, f32x4 c, float) { return mma_f32(a, b, c); }
 
 // Per-tile staging state of one lane: byte offsets of its 4 + 4 source rows (chunk swizzle folded in)
 struct StageRows {
@@ -131,16 +113,16 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(const GemmParams 
         if (GATHER != G_LINEAR) st_tap0 = zs * (p.K / p.Cin);
         const char* Act = reinterpret_cast<const char*>(p.A) + (size_t)zp * p.strideA_z * ESZ;
         const char* Wt = reinterpret_cast<const char*>(p.W) + ((size_t)zp * p.strideW_z + (size_t)zs * p.K) * ESZ;
-        sr.a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(Act), 0, p.a_bytes, 0x00020000);
-        sr.w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(Wt), 0, p.w_bytes, 0x00020000);
+        sr.a_rsrc = buffer_rsrc(Act, p.a_bytes);
+        sr.w_rsrc = buffer_rsrc(Wt, p.w_bytes);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int r = wave * 32 + j * 8 + d_row;
             const int n = n0 + r, m = m0 + r;
-            sr.w_voff[j] = n < p.N ? (unsigned)n * (unsigned)(p.ldw * ESZ) + d_chunk_bytes : OOB_OFFSET;
+            sr.w_voff[j] = n < p.N ? (unsigned)n * (unsigned)(p.ldw * ESZ) + d_chunk_bytes : kOob;
             sr.a_y[j] = sr.a_x[j] = 0;
             if (GATHER == G_LINEAR) {
-                sr.a_voff[j] = m < p.M ? (unsigned)m * (unsigned)(p.lda * ESZ) + d_chunk_bytes : OOB_OFFSET;
+                sr.a_voff[j] = m < p.M ? (unsigned)m * (unsigned)(p.lda * ESZ) + d_chunk_bytes : kOob;
             } else {
                 const int hw = p.H * p.Wd;
                 const int b = m / hw, rr = m - b * hw;
@@ -171,17 +153,17 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(const GemmParams 
         const int tap_off = ((dy * p.Wd + dx) * p.Cin + c0) * ESZ;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const unsigned wv = sr.w_voff[j] == OOB_OFFSET ? OOB_OFFSET : sr.w_voff[j] + kb;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(sr.w_rsrc, (lds_ptr_t)(wdst + j * 1024), 16, wv, 0, 0, 0);
+            const unsigned wv = sr.w_voff[j] == kOob ? kOob : sr.w_voff[j] + kb;
+            dma16(sr.w_rsrc, wdst + j * 1024, wv);
             unsigned av;
             if (GATHER == G_LINEAR) {
-                av = sr.a_voff[j] == OOB_OFFSET ? OOB_OFFSET : sr.a_voff[j] + kb;
+                av = sr.a_voff[j] == kOob ? kOob : sr.a_voff[j] + kb;
             } else {
                 const int yy = sr.a_y[j] + dy, xx = sr.a_x[j] + dx;
                 const bool ok = yy >= 0 && yy < p.H && xx >= 0 && xx < p.Wd;
-                av = ok ? (unsigned)((int)sr.a_voff[j] + tap_off) : OOB_OFFSET;
+                av = ok ? (unsigned)((int)sr.a_voff[j] + tap_off) : kOob;
             }
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(sr.a_rsrc, (lds_ptr_t)(adst + j * 1024), 16, av, 0, 0, 0);
+            dma16(sr.a_rsrc, adst + j * 1024, av);
         }
     };
 
@@ -463,7 +445,7 @@ static int launch_gemm(const GemmParams& p_in, int groups, hipStream_t s) {
     if (p.gather != G_LINEAR)
         PP_REQUIRE(p.Cin % BK == 0 && p.H > 0 && p.Wd > 0, PP_ERR_UNSUPPORTED,
                    "pp gemm: conv gathers need Cin to be a multiple of the K-tile");
-    PP_REQUIRE(p.a_bytes > 0 && p.w_bytes > 0 && p.a_bytes < OOB_OFFSET && p.w_bytes < OOB_OFFSET, PP_ERR_UNSUPPORTED,
+    PP_REQUIRE(p.a_bytes > 0 && p.w_bytes > 0 && p.a_bytes < kOob && p.w_bytes < kOob, PP_ERR_UNSUPPORTED,
                "pp gemm: operand tensors must be smaller than 2 GiB (32-bit buffer offsets)");
     const long long ntiles = (long long)((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM) * groups;
     PP_REQUIRE(ntiles < (1ll << 30), PP_ERR_UNSUPPORTED, "pp gemm: too many output tiles");
@@ -529,7 +511,7 @@ extern "C" int pp_gemm_ws(int prec, const void* act, const void* weight, const f
     const size_t esz = prec == PP_PREC_BF16 ? 2 : 4;
     PP_REQUIRE(M > 0 && N > 0 && K > 0, PP_ERR_INVALID_ARG, "pp_gemm: M, N and K must be positive");
     const size_t ab = ((size_t)(M - 1) * lda + K) * esz, wb = ((size_t)(N - 1) * ldw + K) * esz;
-    PP_REQUIRE(ab < 0x7ffffff0u && wb < 0x7ffffff0u, PP_ERR_UNSUPPORTED, "pp_gemm: operands must be smaller than 2 GiB");
+    PP_REQUIRE(ab < kOob && wb < kOob, PP_ERR_UNSUPPORTED, "pp_gemm: operands must be smaller than 2 GiB");
     p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
     PP_REQUIRE(lda % 8 == 0 && ldw % 8 == 0, PP_ERR_UNSUPPORTED, "pp_gemm: lda/ldw must be multiples of 8 elements");
     if (panel_enabled() && linear_dma_supported(p, prec, 1)) return linear_dma_gemm(p, reinterpret_cast<hipStream_t>(stream));
@@ -565,7 +547,7 @@ extern "C" int pp_conv_gemm(int prec, int kind, const void* act_nhwc, const void
     p.ldres = ldc;
     const size_t esz = prec == PP_PREC_BF16 ? 2 : 4;
     const size_t ab = (size_t)B * H * W * Cin * esz, wb = (size_t)Cout * p.K * esz;
-    PP_REQUIRE(ab < 0x7ffffff0u && wb < 0x7ffffff0u, PP_ERR_UNSUPPORTED, "pp_conv_gemm: operands must be smaller than 2 GiB");
+    PP_REQUIRE(ab < kOob && wb < kOob, PP_ERR_UNSUPPORTED, "pp_conv_gemm: operands must be smaller than 2 GiB");
     p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
     p.strideA_z = stride_act_g; p.strideW_z = stride_w_g; p.strideC_z = stride_out_g; p.strideBias_z = stride_bias_g;
     if (panel_enabled() && panel_split_supported(p, prec, groups)) return panel_split_gemm(p, prec, groups, reinterpret_cast<hipStream_t>(stream));
@@ -592,7 +574,7 @@ extern "C" int pp_conv3x3_splitk(int prec, const void* act_nhwc, const void* wei
     p.ksplit = ksplit;
     const size_t esz = prec == PP_PREC_BF16 ? 2 : 4;
     const size_t ab = (size_t)B * H * W * Cin * esz, wb = (size_t)Cout * 9 * Cin * esz;
-    PP_REQUIRE(ab < 0x7ffffff0u && wb < 0x7ffffff0u, PP_ERR_UNSUPPORTED, "pp_conv3x3_splitk: operands must be smaller than 2 GiB");
+    PP_REQUIRE(ab < kOob && wb < kOob, PP_ERR_UNSUPPORTED, "pp_conv3x3_splitk: operands must be smaller than 2 GiB");
     p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
     p.strideA_z = stride_act_g; p.strideW_z = stride_w_g; p.strideC_z = (long long)p.M * Cout; p.strideBias_z = 0;
     // Channel-range slices (pp_conv3x3_splitk_slices picks them for the split-fp16 4 x 4 tower stage: four quarters of the channels on
@@ -623,7 +605,7 @@ extern "C" int pp_deconv_head(const void* act_nhwc, const void* weight, const fl
     p.act = ACT_RELU; p.out_bf16 = 1; p.gather = G_DECONV; p.ldres = Cout;
     p.head_w = head_w; p.head_b = head_b; p.head_out = logits_phased; p.head_n = K;
     const size_t ab = (size_t)B * H * W * Cin * 2, wb = (size_t)Cout * p.K * 2;
-    PP_REQUIRE(ab < 0x7ffffff0u && wb < 0x7ffffff0u, PP_ERR_UNSUPPORTED, "pp_deconv_head: operands must be smaller than 2 GiB");
+    PP_REQUIRE(ab < kOob && wb < kOob, PP_ERR_UNSUPPORTED, "pp_deconv_head: operands must be smaller than 2 GiB");
     p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
     p.strideA_z = 0; p.strideW_z = (long long)Cout * 4 * Cin; p.strideC_z = 0; p.strideBias_z = 0;
     return panel_gemm(p, 4, reinterpret_cast<hipStream_t>(stream));
@@ -645,7 +627,7 @@ extern "C" int pp_deconv_head_split(const void* act_nhwc, const void* weight, co
     p.act = ACT_RELU; p.out_bf16 = 2; p.gather = G_DECONV; p.ldres = Cout;
     p.head_w = head_w_packed; p.head_b = head_b; p.head_out = logits_phased; p.head_n = K;
     const size_t ab = (size_t)B * H * W * Cin * 4, wb = (size_t)Cout * p.K * 4;
-    PP_REQUIRE(ab < 0x7ffffff0u && wb < 0x7ffffff0u, PP_ERR_UNSUPPORTED, "pp_deconv_head_split: operands must be smaller than 2 GiB");
+    PP_REQUIRE(ab < kOob && wb < kOob, PP_ERR_UNSUPPORTED, "pp_deconv_head_split: operands must be smaller than 2 GiB");
     p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
     p.strideA_z = 0; p.strideW_z = (long long)Cout * 4 * Cin; p.strideC_z = 0; p.strideBias_z = 0;
     PP_REQUIRE(panel_split_supported(p, PP_PREC_F16X3, 4), PP_ERR_UNSUPPORTED,

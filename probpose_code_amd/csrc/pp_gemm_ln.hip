@@ -26,15 +26,10 @@
 // (96-row tiles would be 288 = a second round for 32 workgroups). Replaces GEMM + residual (128 x 128 tiles) followed by a
 // LayerNorm launch that re-reads the fp32 stream.
 #include "pp_common.h"
+#include "pp_device.h"
 #include "pp_split.h"
 
 namespace pp {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 namespace rl {
 
@@ -58,7 +53,6 @@ struct Cfg {
 typedef Cfg<96, 1, 3, 4, 3> C384;    // E = 384: 96 x 384, wave tile 32 x 96 (2 x 6 fragments)
 typedef Cfg<112, 2, 1, 8, 2> C768;   // E = 768: 112 x (2 x 384), eight waves, wave tile 112 x 48 per half (7 x 3 fragments x 2 = 168 accumulator registers;
                                      // twelve waves = three per SIMD leave 168 registers per lane in all: 77 spilled)
-constexpr unsigned OOB_OFFSET = 0x7ffffff0u;
 
 struct Params {
     const void* A;         // [M, lda] activations (bf16 / fp32)
@@ -90,18 +84,8 @@ struct Prec<SplitH> {
     static constexpr int BK = 32;  // split fp16 (pp_split.h): one 128-byte block = 32 hi halves | 32 lo halves
 };
 
-__device__ __forceinline__ int swz(int row, int chunk) { return row * ROW_BYTES + ((chunk ^ (row & 7)) << 4); }
-
-__device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, f32x4 c, __bf16) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
-                                                   0, 0);
-}
-__device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, f32x4 c, float) {
-    const f32x4 af = __builtin_bit_cast(f32x4, a), bf = __builtin_bit_cast(f32x4, b);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) c = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], bf[j], c, 0, 0, 0);
-    return c;
-}
+__device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, f32x4 c, __bf16) { return mma_bf16(a, b, c); }
+__device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, f32x4 c, float) { return mma_f32(a, b, c); }
 
 template <typename T, typename C>
 __global__ __launch_bounds__(C::THREADS, C::MINW) void gemm_res_ln_kernel(const Params p) {
@@ -116,10 +100,8 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void gemm_res_ln_kernel(const 
     const int f_row = lane & 15, f_kg = lane >> 4;
     const int m0 = blockIdx.x * BM;
 
-    const __amdgpu_buffer_rsrc_t a_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.A), 0, p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.W), 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t a_rsrc = buffer_rsrc(p.A, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t w_rsrc = buffer_rsrc(p.W, p.w_bytes);
     const int d_row = lane >> 3;
     const unsigned d_chunk_bytes = (unsigned)(((lane & 7) ^ d_row) << 4);
     // DMA instruction q of a stage (8 rows each): q < 48 weight rows 8 q .. of the current column half, then activation rows
@@ -132,7 +114,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void gemm_res_ln_kernel(const 
             s_voff[j] = (unsigned)n * (unsigned)(p.ldw * ESZ) + d_chunk_bytes;
         } else {
             const int m = m0 + (q - BNH / 8) * 8 + d_row;
-            s_voff[j] = (q < C::DMA_PER_STAGE && m < p.M) ? (unsigned)m * (unsigned)(p.lda * ESZ) + d_chunk_bytes : OOB_OFFSET;
+            s_voff[j] = (q < C::DMA_PER_STAGE && m < p.M) ? (unsigned)m * (unsigned)(p.lda * ESZ) + d_chunk_bytes : kOob;
         }
     }
     const unsigned half_bytes = (unsigned)BNH * (unsigned)(p.ldw * ESZ);  // weight rows of the second column half
@@ -143,11 +125,11 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void gemm_res_ln_kernel(const 
         for (int j = 0; j < DPW; ++j) {
             const int q = wv * DPW + j;
             if (q >= C::DMA_PER_STAGE) continue;  // (wave-uniform: the last wave of a 62-instruction stage has fewer)
-            const unsigned vo = s_voff[j] == OOB_OFFSET ? OOB_OFFSET : s_voff[j] + kb;
+            const unsigned vo = s_voff[j] == kOob ? kOob : s_voff[j] + kb;
             if (q < BNH / 8)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (lds_ptr_t)(dst + j * 1024), 16, vo + (unsigned)half * half_bytes, 0, 0, 0);
+                dma16(w_rsrc, dst + j * 1024, vo + (unsigned)half * half_bytes);
             else
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (lds_ptr_t)(dst + j * 1024), 16, vo, 0, 0, 0);
+                dma16(a_rsrc, dst + j * 1024, vo);
         }
     };
 
@@ -367,7 +349,7 @@ extern "C" int pp_gemm_residual_layernorm_ws(int prec, const void* act, const vo
     PP_REQUIRE(K % bk == 0 && lda % 8 == 0 && ldw % 8 == 0, PP_ERR_UNSUPPORTED,
                "pp_gemm_residual_layernorm: K must be a multiple of the K-tile, lda/ldw multiples of 8");
     const size_t ab = ((size_t)(M - 1) * lda + K) * esz, wb = ((size_t)(N - 1) * ldw + K) * esz;
-    PP_REQUIRE(ab < rl::OOB_OFFSET && wb < rl::OOB_OFFSET, PP_ERR_UNSUPPORTED,
+    PP_REQUIRE(ab < pp::kOob && wb < pp::kOob, PP_ERR_UNSUPPORTED,
                "pp_gemm_residual_layernorm: operands must be smaller than 2 GiB");
     rl::Params p{};
     p.A = act; p.W = weight; p.bias = bias; p.residual = residual; p.x_out = x_out; p.h_out = h_out;

@@ -4,12 +4,10 @@
 // NHWC activations; what is left is MaxPool + ReLU between them and the final
 // Conv1x1 -> Sigmoid/ReLU -> flip-test average on the 1x1 feature.
 #include "pp_common.h"
+#include "pp_device.h"
 #include "pp_split.h"
 
 namespace pp {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 // four consecutive elements at element index idx (idx % 4 == 0) of a tensor in one of the three activation formats
 __device__ __forceinline__ f32x4 load4(const float* base, size_t idx) { return *reinterpret_cast<const f32x4*>(base + idx); }

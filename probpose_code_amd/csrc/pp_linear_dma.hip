@@ -24,16 +24,12 @@
 // SGPRs, and epilogue VALU shares the SIMDs with the MFMAs whichever wave issues it). Step loop alone (scripts/micro/gemm12.hip,
 // M = 55 296): 450 / 583 / 622 us for (N, K) = (2304, 768) / (3072, 768) / (768, 3072).
 #include "pp_common.h"
+#include "pp_device.h"
 #include "pp_gemm.h"
 #include "pp_split.h"
 
 namespace pp {
 namespace ldm {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr int BM = 192, BN = 192, CW = 8, WAVES = 12, THREADS = WAVES * 64, NSTAGE = 3;
 constexpr int STAGE = (BM + BN) * 128, B_OFF = BM * 128, LDS = NSTAGE * STAGE;
@@ -55,14 +51,6 @@ struct Params {
     float w_inv = 1.0f;      // the weights are stored as w * 2^e (weights.py): accumulators * 2^-e in front of bias / activation / residual (exact)
 };
 
-#define LDM_WAITVM(N) __builtin_amdgcn_s_waitcnt(((N) & 15) | (7 << 4) | (15 << 8) | (((N) >> 4) << 14))
-
-__device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-
-
 // K loop of a computing wave with ROLLING fragment reads (pp_ffn_dma.hip, round 5): the 18 fragment registers of a step are re-read for
 // the next stage right behind the last MFMA of this step that uses them - sweeps hi x lo, hi x hi, lo x hi, so the first sweep's operands
 // (weights hi, rows lo) are free earliest - and the barrier of stage k + 1 sits inside step k, behind the first row fragment's six MFMAs:
@@ -74,7 +62,7 @@ __device__ __forceinline__ void k_loop_roll(f32x4 (&acc)[3][6], const char* smem
     auto rd = [&](int lane_off, int uni, int imm) -> u32x4 { return *reinterpret_cast<const u32x4*>(smem + (lane_off + uni) + imm); };
     auto bar = []() {
         __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt((63 & 15) | (7 << 4) | (0 << 8) | ((63 >> 4) << 14));  // lgkmcnt(0): this wave's reads of the stage the barrier frees
+        wait_vm_lgkm<63>();  // lgkmcnt(0): this wave's reads of the stage the barrier frees
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
     };
@@ -100,7 +88,7 @@ __device__ __forceinline__ void k_loop_roll(f32x4 (&acc)[3][6], const char* smem
         for (int i = 0; i < 3; ++i) {  // hi x lo
 #pragma unroll
             for (int j = 0; j < 6; ++j) {
-                acc[i][j] = mma(bh[j], al[i], acc[i][j]);
+                acc[i][j] = mma_f16(bh[j], al[i], acc[i][j]);
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (more) {
@@ -114,7 +102,7 @@ __device__ __forceinline__ void k_loop_roll(f32x4 (&acc)[3][6], const char* smem
         for (int i = 0; i < 3; ++i)  // hi x hi
 #pragma unroll
             for (int j = 0; j < 6; ++j) {
-                acc[i][j] = mma(bh[j], ah[i], acc[i][j]);
+                acc[i][j] = mma_f16(bh[j], ah[i], acc[i][j]);
                 __builtin_amdgcn_sched_barrier(0);
                 if (more && i == 2) bh[j] = rd(lane_hi, ub, j * 2048);
                 __builtin_amdgcn_sched_barrier(0);
@@ -123,7 +111,7 @@ __device__ __forceinline__ void k_loop_roll(f32x4 (&acc)[3][6], const char* smem
         for (int i = 0; i < 3; ++i)  // lo x hi
 #pragma unroll
             for (int j = 0; j < 6; ++j) {
-                acc[i][j] = mma(bl[j], ah[i], acc[i][j]);
+                acc[i][j] = mma_f16(bl[j], ah[i], acc[i][j]);
                 __builtin_amdgcn_sched_barrier(0);
                 if (more && j == 5) ah[i] = rd(lane_hi, ua, i * 2048);
                 if (more && i == 2) bl[j] = rd(lane_lo, ub, j * 2048);
@@ -184,22 +172,22 @@ __global__ __launch_bounds__(THREADS) void linear_dma_kernel(const Params p) {
         const int row8 = 8 * p.K * 4;
         auto rsrc_a = [&](int m0) {
             const int rows_left = p.M - m0 < BM ? p.M - m0 : BM;
-            return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.a) + (size_t)m0 * p.K * 4, 0, (unsigned)rows_left * (unsigned)(p.K * 4), 0x00020000);
+            return buffer_rsrc(p.a + (size_t)m0 * p.K * 4, (unsigned)rows_left * (unsigned)(p.K * 4));
         };
         auto rsrc_w = [&](int n0) {
-            return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.w) + (size_t)n0 * p.K * 4, 0, (unsigned)BN * (unsigned)(p.K * 4), 0x00020000);
+            return buffer_rsrc(p.w + (size_t)n0 * p.K * 4, (unsigned)BN * (unsigned)(p.K * 4));
         };
         auto issue = [&](const __amdgpu_buffer_rsrc_t& ra, const __amdgpu_buffer_rsrc_t& rw, int kk, int st) {
             char* dst = smem + st * STAGE;
 #pragma unroll
             for (int u = 0; u < 6; ++u) {
                 const int q = d + 4 * u;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_ptr_t)(dst + q * 1024), 16, v + (unsigned)(q * row8), kk * 128, 0, 0);
+                dma16(ra, dst + q * 1024, v + (unsigned)(q * row8), kk * 128);
             }
 #pragma unroll
             for (int u = 0; u < 6; ++u) {
                 const int q = d + 4 * u;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(dst + B_OFF + q * 1024), 16, v + (unsigned)(q * row8), kk * 128, 0, 0);
+                dma16(rw, dst + B_OFF + q * 1024, v + (unsigned)(q * row8), kk * 128);
             }
         };
         // (Measured and removed, round 5: pulling the residual tile towards the L2 from here - 18 extra LDS-DMA pieces into a junk KiB over the last
@@ -218,7 +206,7 @@ __global__ __launch_bounds__(THREADS) void linear_dma_kernel(const Params p) {
             const __amdgpu_buffer_rsrc_t ra_n = rsrc_a(m1), rw_n = rsrc_w(n1);
             for (int k = 0; k < ksteps; ++k) {
                 __builtin_amdgcn_sched_barrier(0);
-                LDM_WAITVM(12);  // stage k has landed: this wave's twelve pieces of stage k + 1 may be out
+                wait_vm<12>();  // stage k has landed: this wave's twelve pieces of stage k + 1 may be out
                 __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_sched_barrier(0);
                 // stage k + 2 (all computing waves are past their reads of stage k - 1): of this tile, or the next tile's stage 0 / 1, or - behind
@@ -230,7 +218,7 @@ __global__ __launch_bounds__(THREADS) void linear_dma_kernel(const Params p) {
             }
             ra = ra_n; rw = rw_n; m0 = m1; n0 = n1;
         }
-        LDM_WAITVM(0);
+        wait_vm<0>();
         return;
     }
 
@@ -268,8 +256,7 @@ __global__ __launch_bounds__(THREADS) void linear_dma_kernel(const Params p) {
     float mu[3] = {0.f, 0.f, 0.f}, rs[3] = {1.f, 1.f, 1.f};
     if (MODE == 1) {
         const int parts = p.K / 96;
-        const __amdgpu_buffer_rsrc_t rst = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.ln_stats) + (size_t)m0 * parts * 2, 0,
-                                                                             (unsigned)rows_left * (unsigned)(parts * 8), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rst = buffer_rsrc(p.ln_stats + (size_t)m0 * parts * 2, (unsigned)rows_left * (unsigned)(parts * 8));
         float sm[3] = {0.f, 0.f, 0.f}, m2[3] = {0.f, 0.f, 0.f};
         if (parts <= 8) {  // one round: mean and squared deviations from the same registers
             f32x4 t[3][4];
@@ -332,9 +319,11 @@ __global__ __launch_bounds__(THREADS) void linear_dma_kernel(const Params p) {
     // into w and beta into the bias):  sum_k (a - mean) rstd w = rstd (acc - mean colsum(w)).  With stats_out the wave leaves (mean, sum of
     // squared deviations) of its 96 columns of every output row for the layer that will do the same with THESE rows.
     const size_t ldo = (size_t)p.N * 4;  // bytes per output row in either format
-    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(p.out + (size_t)m0 * ldo, 0, (unsigned)rows_left * (unsigned)ldo, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ro = buffer_rsrc(p.out + (size_t)m0 * ldo, (unsigned)rows_left * (unsigned)ldo);
+    // (the builtin itself, not buffer_rsrc: through the helper the generic MODE 2 kernel comes out with a different SGPR allocation - its
+    //  scalar spills move - and the refactor that introduced pp_device.h held every file's ISA fixed)
     const __amdgpu_buffer_rsrc_t rr_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.residual) + (k_res == 2 ? (size_t)m0 * p.N : 0), 0,
-                                                                          k_res == 2 ? (unsigned)rows_left * (unsigned)ldo : 0u, 0x00020000);
+                                                                          k_res == 2 ? (unsigned)rows_left * (unsigned)ldo : 0u, kRsrcFlags);
     // The residual values of all 18 fragments are fetched FIRST (72 registers: the operand fragments are dead): written inside the store loop
     // each load sits behind the previous fragment's store - `residual` may alias `out`, the compiler must keep that order - and a tile pays 18
     // memory round trips one after the other (measured: ~20 us per tile, as much as the K loop of the proj layer). A lane reads exactly the
@@ -422,21 +411,16 @@ __global__ __launch_bounds__(THREADS) void linear_dma_kernel(const Params p) {
 #if LDM_SKIP_STORES
                 if (i != 0 || j != 0) { asm volatile("" ::"v"(q)); continue; }
 #endif
-                __builtin_amdgcn_raw_buffer_store_b128(q, ro, vrow + (unsigned)(f_kg >> 1) * 16u + (unsigned)(f_kg & 1) * 64u, so, 0);
-                asm volatile("s_nop 3" ::"v"(q));
+                store16_guarded(q, ro, vrow + (unsigned)(f_kg >> 1) * 16u + (unsigned)(f_kg & 1) * 64u, so);
             } else {
-                // (one 16-byte store + the wait states the compiler does not insert behind a buffer_store_dwordx4 with an SGPR offset:
-                //  its data registers are read a cycle late for lanes 12 - 15 of every row, scripts/micro/mubuf_store_hazard.hip)
-                const u32x4 q = __builtin_bit_cast(u32x4, v);
-                __builtin_amdgcn_raw_buffer_store_b128(q, ro, vrow + (unsigned)f_kg * 16u, n * 4, 0);
-                asm volatile("s_nop 3" ::"v"(q));
+                store16_guarded(__builtin_bit_cast(u32x4, v), ro, vrow + (unsigned)f_kg * 16u, n * 4);
             }
         }
     }
     if (k_stats) {
         // two passes (mean, then squared deviations from it): no cancellation whatever the rows' offset is
         const int parts = p.N / 96;
-        const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc(p.stats_out + (size_t)m0 * parts * 2, 0, (unsigned)rows_left * (unsigned)(parts * 8), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rso = buffer_rsrc(p.stats_out + (size_t)m0 * parts * 2, (unsigned)rows_left * (unsigned)(parts * 8));
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             float sm = rsum[i];
@@ -462,7 +446,6 @@ __global__ __launch_bounds__(THREADS) void linear_dma_kernel(const Params p) {
     }  // tiles of this workgroup
 }
 
-
 // grid of the one-tile kernel: the tile count, or - option "linear_loop" - one workgroup per CU, each walking tiles id, id + CUs, ...
 static int loop_grid(int ntiles) {
     if (option("linear_loop") == 0) return ntiles;
@@ -479,7 +462,7 @@ bool linear_dma_supported(const GemmParams& p, int prec, int groups) {
     if (p.out_bf16 != 0 && p.out_bf16 != 2) return false;
     if (p.K % 32 != 0 || p.K < 64 || p.N % ldm::BN != 0 || p.lda != p.K || p.ldw != p.K || p.ldc != p.N) return false;
     if (p.residual && (p.out_bf16 == 2 || ((p.ldres ? p.ldres : p.ldc) % 4) != 0)) return false;
-    if ((size_t)ldm::BM * p.K * 4 >= 0x7ffffff0u || (size_t)ldm::BM * p.N * 4 >= 0x7ffffff0u) return false;
+    if ((size_t)ldm::BM * p.K * 4 >= kOob || (size_t)ldm::BM * p.N * 4 >= kOob) return false;
     const long long ntiles = (long long)(p.N / ldm::BN) * ((p.M + ldm::BM - 1) / ldm::BM);
     // two rounds of the chip at least; smaller problems stay with the 128 x 128 / wide-tile kernels. No lower bound on K beyond two stages: at
     // the ViT-S shapes (K = 384; reached when the fused layer kernels are off or the token count is not 192) it is level with the
@@ -523,7 +506,7 @@ int linear_dma_gemm(const GemmParams& g, hipStream_t s) {
 extern "C" int pp_linear_ln_folded_supported(int M, int N, int K, int with_ln_stats) {
     if (M <= 0 || N <= 0 || K < 64 || K % 32 != 0 || N % pp::ldm::BN != 0) return 0;
     if (with_ln_stats && (K % 192 != 0)) return 0;  // (statistics come in 96-column parts, two per 192-column tile of their producer)
-    if ((size_t)pp::ldm::BM * K * 4 >= 0x7ffffff0u || (size_t)pp::ldm::BM * N * 4 >= 0x7ffffff0u) return 0;
+    if ((size_t)pp::ldm::BM * K * 4 >= pp::kOob || (size_t)pp::ldm::BM * N * 4 >= pp::kOob) return 0;
     const long long ntiles = (long long)(N / pp::ldm::BN) * ((M + pp::ldm::BM - 1) / pp::ldm::BM);
     return ntiles >= 512 ? 2 : 1;  // 2: enough tiles for two rounds of the chip (what pp_gemm asks of this kernel); 1: runs, not recommended
 }

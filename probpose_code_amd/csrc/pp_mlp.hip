@@ -26,18 +26,9 @@
 // GELU uses a clamped odd polynomial for erf (|error| < 1.8e-4 + 1e-6 |x|, a factor 60 under bf16 resolution): libdevice erff costs
 // as many VALU cycles as the MFMAs of the whole block.
 #include "pp_common.h"
+#include "pp_device.h"
 
 namespace pp {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_t;
 
 namespace mlp {
 
@@ -50,8 +41,6 @@ constexpr int DBG = MLP_DBG;
 #ifndef ATT_DBG
 #define ATT_DBG 0  // dev ablations of the attention rounds: 1 no v_exp, 2 no V reads, 4 no K reads, 8 no P V MFMAs (wrong results)
 #endif
-#define SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
-constexpr int SG_VALU = 0x002, SG_MFMA = 0x008, SG_VMEM = 0x010, SG_DS_READ = 0x100;
 constexpr int BM = 96, E = 384, CHUNK = 128;
 constexpr int WAVES = 8, THREADS = 64 * WAVES;
 constexpr int ROW_BYTES = 128;
@@ -63,7 +52,6 @@ constexpr int SLOT = 8192, NSLOT = 8;
 constexpr int LDS = OFF_RING + NSLOT * SLOT;      // 163 840 B
 constexpr int KT1 = 6, KT2 = 4;                   // steps of phase A (k 64) and phase B (k 32)
 constexpr int SLOTS_PER_CHUNK = 2 * KT1 + 3 * KT2;  // 24
-constexpr unsigned OOB = 0x7ffffff0u;
 static_assert(LDS == 160 * 1024, "LDS map");
 static_assert(SLOTS_PER_CHUNK % NSLOT == 0, "ring positions must repeat per chunk");
 
@@ -93,11 +81,6 @@ struct Params {
     float eps;
     unsigned long long* trace;  // dev only (MLP_DBG & 512): per-step time stamps of block 0, waves 0 and 4
 };
-
-__device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
-                                                   0, 0);
-}
 
 // GELU(x) = 0.5 x (1 + erf(x / sqrt 2)) = x (0.5 + t W(t^2)), t = clamp(x, -4.2, 4.2), where t W(t^2) is a degree-15 odd
 // minimax polynomial for 0.5 erf(t / sqrt 2), constrained to reach 0.5 at |t| = 4.2 so that the function saturates to x
@@ -131,13 +114,9 @@ __host__ __device__ constexpr int step_first(int s) { return s < KT1 ? 2 * s : 2
 // then meet the other waves
 template <int N>
 __device__ __forceinline__ void wait_dma_and_barrier() {
-    static_assert(N >= 0 && N < 64, "vmcnt immediate");
     __builtin_amdgcn_sched_barrier(0);  // nothing of the previous step may sink below, nothing of the next may rise above
     if (!(DBG & 32)) {
-        // s_waitcnt vmcnt(N) lgkmcnt(0) as a builtin, not inline asm: the compiler's own wait-count bookkeeping sees it
-        // and does not re-wait for the fragment reads in front of the MFMAs that use them (gfx9 encoding:
-        // vmcnt [3:0] + [15:14], expcnt [6:4] = 7 (none), lgkmcnt [11:8])
-        __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (0 << 8) | ((N >> 4) << 14));
+        wait_vm_lgkm<N>();  // (a builtin: the compiler does not wait again for the fragment reads in front of the MFMAs that use them)
         __builtin_amdgcn_s_barrier();
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -156,7 +135,7 @@ __device__ __forceinline__ int rot_mod(int v, int rot, int n) {  // (v + rot) mo
 __device__ __forceinline__ unsigned wq_slot_offset(int q, unsigned lane_off, int rot) {
     const int t = q / 3;
     const int blk = rot_mod(t / 6, rot, 6);
-    return q < 108 ? (unsigned)(blk * 192 + (q % 3) * 64) * (unsigned)(E * 2) + (unsigned)((t % 6) * 128) + lane_off : OOB;
+    return q < 108 ? (unsigned)(blk * 192 + (q % 3) * 64) * (unsigned)(E * 2) + (unsigned)((t % 6) * 128) + lane_off : kOob;
 }
 
 // PROJ = true puts the attention output projection in front:  x' = x + a Wp^T + bp ;  h = LayerNorm2(x')  and then the
@@ -189,12 +168,9 @@ __global__ __launch_bounds__(THREADS, 2) void mlp_res_ln_kernel(const Params p) 
     if ((gridDim.x & 15) == 0) tile = (tile & 7) * (gridDim.x >> 3) + (tile >> 3);
     const int m0 = tile * BM;
 
-    const __amdgpu_buffer_rsrc_t h_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(p.h), 0, p.h_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w1_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(p.W1), 0, p.w1_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w2_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(p.W2), 0, p.w2_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t h_rsrc = buffer_rsrc(p.h, p.h_bytes);
+    const __amdgpu_buffer_rsrc_t w1_rsrc = buffer_rsrc(p.W1, p.w1_bytes);
+    const __amdgpu_buffer_rsrc_t w2_rsrc = buffer_rsrc(p.W2, p.w2_bytes);
 
     // ---- DMA addressing. One instruction moves 8 lines of 128 B; lane i lands at byte 16 i, so the XOR swizzle is
     // applied to the SOURCE: lane (line l, physical chunk pc) fetches logical chunk pc ^ (l & 7).
@@ -207,10 +183,8 @@ __global__ __launch_bounds__(THREADS, 2) void mlp_res_ln_kernel(const Params p) 
     const unsigned w2_lane = (unsigned)(d_line + 192 * (d_lc >> 2)) * w2_row_bytes + (unsigned)((d_lc & 3) << 4);
     // Wp slot (j, third): the same two-rows-per-line image, row stride 384 elements
     const unsigned wp_lane = (unsigned)(d_line + 192 * (d_lc >> 2)) * (E * 2) + (unsigned)((d_lc & 3) << 4);
-    const __amdgpu_buffer_rsrc_t wp_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(PROJ ? p.Wp : p.W1), 0, PROJ ? p.wp_bytes : p.w1_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wq_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(QKV ? p.Wq : p.W1), 0, QKV ? p.wq_bytes : p.w1_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wp_rsrc = buffer_rsrc(PROJ ? p.Wp : p.W1, PROJ ? p.wp_bytes : p.w1_bytes);
+    const __amdgpu_buffer_rsrc_t wq_rsrc = buffer_rsrc(QKV ? p.Wq : p.W1, QKV ? p.wq_bytes : p.w1_bytes);
 
     const int nchunks = p.F / CHUNK;
     // Every workgroup walks the hidden chunks in a different rotation: all 256 CUs stream the SAME weights, and in
@@ -233,13 +207,13 @@ __global__ __launch_bounds__(THREADS, 2) void mlp_res_ln_kernel(const Params p) 
         if (DBG & 8) return;
         const bool live = ci < nchunks;
         const unsigned vo = (unsigned)(chunk_of(live ? ci : 0) * CHUNK + (q & 1) * 64) * (E * 2) + (unsigned)((q >> 1) * 128) + w1_lane;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(w1_rsrc, (lds_ptr_t)(ring + pos * SLOT + wv * 1024), 16, live ? vo : OOB, 0, 0, 0);
+        dma16(w1_rsrc, ring + pos * SLOT + wv * 1024, live ? vo : kOob);
     };
     auto issue_w2 = [&](int ci, int q, int pos) {
         if (DBG & 8) return;
         const bool live = ci < nchunks;
         const unsigned vo = (unsigned)((q % 3) * 64) * w2_row_bytes + (unsigned)((chunk_of(live ? ci : 0) * CHUNK + 32 * (q / 3)) * 2) + w2_lane;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(w2_rsrc, (lds_ptr_t)(ring + pos * SLOT + wv * 1024), 16, live ? vo : OOB, 0, 0, 0);
+        dma16(w2_rsrc, ring + pos * SLOT + wv * 1024, live ? vo : kOob);
     };
     // The slot stream, in consumption order: A(0) | A(1) B(0) | A(2) B(1) | ... - twelve slots for the peeled first
     // phase A, then 24 per loop iteration it (phase A of chunk it + 1, phase B of chunk it). g is the position in the
@@ -249,15 +223,15 @@ __global__ __launch_bounds__(THREADS, 2) void mlp_res_ln_kernel(const Params p) 
         if (DBG & 8) return;
         const int j = rot_mod(q / 3, p_rot, 12);
         const unsigned vo = (unsigned)((q % 3) * 64) * (E * 2) + (unsigned)(32 * j * 2) + wp_lane;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(wp_rsrc, (lds_ptr_t)(ring + pos * SLOT + wv * 1024), 16, vo, 0, 0, 0);
+        dma16(wp_rsrc, ring + pos * SLOT + wv * 1024, vo);
     };
     // (in the qkv tail only waves 0-3 issue DMA, two of the eight 1 KiB pieces of a slot each: lines 16 w .. 16 w + 15)
     auto issue_wq = [&](int q, int pos, unsigned lane_off) {
         if (DBG & 8) return;
         const unsigned vo = wq_slot_offset(q, lane_off, q_rot);
         char* dst = ring + pos * SLOT + (wv & 3) * 2048;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(wq_rsrc, (lds_ptr_t)dst, 16, vo, 0, 0, 0);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(wq_rsrc, (lds_ptr_t)(dst + 1024), 16, vo == OOB ? OOB : vo + 8 * (E * 2), 0, 0, 0);
+        dma16(wq_rsrc, dst, vo);
+        dma16(wq_rsrc, dst + 1024, vo == kOob ? kOob : vo + 8 * (E * 2));
     };
     auto issue_rel = [&](int it, int g) {
         const int pos = (g + 12 + 24 + 48 + PRE) & (NSLOT - 1);  // PRE + 12 + 24 it + g, multiples of 8 dropped
@@ -346,8 +320,7 @@ __global__ __launch_bounds__(THREADS, 2) void mlp_res_ln_kernel(const Params p) 
         static_assert(HEADS * TILES == NR * WAVES, "72 tasks in nine rounds of eight");
         static_assert(4 * KBYTES + KBYTES <= NSLOT * SLOT && 2 * KBYTES <= 2 * HS_KB && KBYTES == HS_KB, "buffer map");
         const int srow0 = (m0 / SEQ) * SEQ;
-        const __amdgpu_buffer_rsrc_t qkv_rsrc =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(p.qkv_in), 0, (unsigned)p.M * (unsigned)(RS * 2), 0x00020000);
+        const __amdgpu_buffer_rsrc_t qkv_rsrc = buffer_rsrc(p.qkv_in, (unsigned)p.M * (unsigned)(RS * 2));
         // byte offsets inside the LDS allocation of the K and the V half of head hd's buffer
         auto k_off = [](int hd) -> int { const int b = hd & 3; return b == 0 ? OFF_RING + 4 * KBYTES : b == 1 ? OFF_RING : b == 2 ? OFF_RING + 2 * KBYTES : OFF_GS; };
         auto v_off = [](int hd) -> int { const int b = hd & 3; return b == 0 ? OFF_HS + 5 * HS_KB : b == 1 ? OFF_RING + KBYTES : b == 2 ? OFF_RING + 3 * KBYTES : OFF_GS + KBYTES; };
@@ -362,7 +335,7 @@ __global__ __launch_bounds__(THREADS, 2) void mlp_res_ln_kernel(const Params p) 
                 const int c = isv ? (a_pos ^ (2 * ((key >> 2) & 1))) : (a_pos ^ ((key >> 2) & 3));
                 const unsigned vo = (unsigned)(srow0 + key) * (unsigned)(RS * 2) + (unsigned)((isv ? 2 * E : E) * 2 + hd * 64 + c * 16);
                 char* dst = smem + (isv ? v_off(hd) + (i - 12) * 1024 : k_off(hd) + i * 1024);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(qkv_rsrc, (lds_ptr_t)dst, 16, vo, 0, 0, 0);  // rows past M: out of bounds = zeros
+                dma16(qkv_rsrc, dst, vo);  // rows past M: out of bounds = zeros
             }
         };
         // order of the first requests: K / V of heads 0 and 1 (round 0), the Q fragments of this wave's nine tasks, heads 2, 3
@@ -429,7 +402,7 @@ __global__ __launch_bounds__(THREADS, 2) void mlp_res_ln_kernel(const Params p) 
                 f32x4 sc[NKT];
 #pragma unroll
                 for (int kt = 0; kt < NKT; ++kt)  // S^T: lane holds keys 16 kt + 4 f_kg + (0..3) of query f_row
-                    { u32x4 kf; if (ATT_DBG & 4) asm volatile("" : "=v"(kf)); else kf = *reinterpret_cast<const u32x4*>(Ks + kt * 1024 + k_frag_off); sc[kt] = mma(kf, qh, f32x4{0.f, 0.f, 0.f, 0.f}); }
+                    { u32x4 kf; if (ATT_DBG & 4) asm volatile("" : "=v"(kf)); else kf = *reinterpret_cast<const u32x4*>(Ks + kt * 1024 + k_frag_off); sc[kt] = mma_bf16(kf, qh, f32x4{0.f, 0.f, 0.f, 0.f}); }
                 float mx = -__builtin_inff();
 #pragma unroll
                 for (int kt = 0; kt < NKT; ++kt)
@@ -537,8 +510,7 @@ __global__ __launch_bounds__(THREADS, 2) void mlp_res_ln_kernel(const Params p) 
             const int i = wv * 9 + jj;
             const int kb = i / 12, row = (i % 12) * 8 + (lane >> 3);
             const unsigned vo = (unsigned)(m0 + row) * (E * 2) + (unsigned)(kb * 128) + (unsigned)(d_lc << 4);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(h_rsrc, (lds_ptr_t)(smem + OFF_HS + i * 1024), 16,
-                                                     (m0 + row) < p.M ? vo : OOB, 0, 0, 0);
+            dma16(h_rsrc, smem + OFF_HS + i * 1024, (m0 + row) < p.M ? vo : kOob);
         }
     }
 #pragma unroll
@@ -603,25 +575,25 @@ __global__ __launch_bounds__(THREADS, 2) void mlp_res_ln_kernel(const Params p) 
             for (int rf = 0; rf < 3; ++rf)
 #pragma unroll
                 for (int nf = 0; nf < 2; ++nf) {
-                    if (!(DBG & 4)) pacc[rf][nf] = mma(wa[cur][nf][ks], ha[cur][rf][ks], pacc[rf][nf]);
+                    if (!(DBG & 4)) pacc[rf][nf] = mma_bf16(wa[cur][nf][ks], ha[cur][rf][ks], pacc[rf][nf]);
                 }
         if (with_gelu) gelu_frag(kt >> 1, kt & 1);
         // issue order: one MFMA, a few VALU (GELU), one LDS read, ... - VALU and LDS work sits in the MFMA shadows
         if (kt < KT1 - 1 || last_of_peeled) {
 #pragma unroll
             for (int i = 0; i < 12; ++i) {
-                SGB(SG_MFMA, 1);
-                if (with_gelu) SGB(SG_VALU, 4);
-                if (i < 10) SGB(SG_DS_READ, 1);
-                if (i == 1 || i == 5) SGB(SG_VMEM, 1);
+                HSGB(SG_MFMA, 1);
+                if (with_gelu) HSGB(SG_VALU, 4);
+                if (i < 10) HSGB(SG_DS_READ, 1);
+                if (i == 1 || i == 5) HSGB(SG_VMEM, 1);
             }
         } else {
 #pragma unroll
             for (int i = 0; i < 12; ++i) {
-                SGB(SG_MFMA, 1);
-                if (with_gelu) SGB(SG_VALU, 4);
-                if (i < 6) SGB(SG_DS_READ, 1);
-                if (i == 1 || i == 5) SGB(SG_VMEM, 1);
+                HSGB(SG_MFMA, 1);
+                if (with_gelu) HSGB(SG_VALU, 4);
+                if (i < 6) HSGB(SG_DS_READ, 1);
+                if (i == 1 || i == 5) HSGB(SG_VMEM, 1);
             }
         }
     };
@@ -689,11 +661,11 @@ __global__ __launch_bounds__(THREADS, 2) void mlp_res_ln_kernel(const Params p) 
             for (int rf = 0; rf < 3; ++rf)
 #pragma unroll
                 for (int nf = 0; nf < 6; ++nf) {
-                    if (!(DBG & 4)) acc[rf][nf] = mma(wb[cur][nf], gb[cur][rf], acc[rf][nf]);
+                    if (!(DBG & 4)) acc[rf][nf] = mma_bf16(wb[cur][nf], gb[cur][rf], acc[rf][nf]);
                 }
             if (j < 11) {
 #pragma unroll
-                for (int i = 0; i < 9; ++i) { SGB(SG_MFMA, 2); SGB(SG_DS_READ, 1); if (i == 0 || i == 3 || i == 6) SGB(SG_VMEM, 1); }
+                for (int i = 0; i < 9; ++i) { HSGB(SG_MFMA, 2); HSGB(SG_DS_READ, 1); if (i == 0 || i == 3 || i == 6) HSGB(SG_VMEM, 1); }
             }
         }
         // every wave has passed the barrier of step 11, so nobody reads the input rows any more; G is not in use yet
@@ -762,15 +734,15 @@ __global__ __launch_bounds__(THREADS, 2) void mlp_res_ln_kernel(const Params p) 
             for (int rf = 0; rf < 3; ++rf)
 #pragma unroll
                 for (int nf = 0; nf < 6; ++nf) {
-                    if (!(DBG & 4)) acc[rf][nf] = mma(wb[cur][nf], gb[cur][rf], acc[rf][nf]);
+                    if (!(DBG & 4)) acc[rf][nf] = mma_bf16(wb[cur][nf], gb[cur][rf], acc[rf][nf]);
                 }
-            if (j == 0) SGB(SG_DS_READ, 3);
+            if (j == 0) HSGB(SG_DS_READ, 3);
             if (j < KT2 - 1) {
 #pragma unroll
-                for (int i = 0; i < 9; ++i) { SGB(SG_MFMA, 2); SGB(SG_DS_READ, 1); if (i == 0 || i == 3 || i == 6) SGB(SG_VMEM, 1); }
+                for (int i = 0; i < 9; ++i) { HSGB(SG_MFMA, 2); HSGB(SG_DS_READ, 1); if (i == 0 || i == 3 || i == 6) HSGB(SG_VMEM, 1); }
             } else {
 #pragma unroll
-                for (int i = 0; i < 10; ++i) { if (i < 2) SGB(SG_MFMA, 1); else SGB(SG_MFMA, 2); SGB(SG_DS_READ, 1); if (i == 0 || i == 3 || i == 6) SGB(SG_VMEM, 1); }
+                for (int i = 0; i < 10; ++i) { if (i < 2) HSGB(SG_MFMA, 1); else HSGB(SG_MFMA, 2); HSGB(SG_DS_READ, 1); if (i == 0 || i == 3 || i == 6) HSGB(SG_VMEM, 1); }
             }
         }
     }
@@ -941,7 +913,7 @@ __global__ __launch_bounds__(THREADS, 2) void mlp_res_ln_kernel(const Params p) 
                     for (int rf = 0; rf < 3; ++rf)
 #pragma unroll
                         for (int nfr = 0; nfr < 3; ++nfr) {
-                            if (!(DBG & 4)) acc[rf][set * 3 + nfr] = mma(wq_f[cur][nfr][ks], hq_f[cur][rf][ks], acc[rf][set * 3 + nfr]);
+                            if (!(DBG & 4)) acc[rf][set * 3 + nfr] = mma_bf16(wq_f[cur][nfr][ks], hq_f[cur][rf][ks], acc[rf][set * 3 + nfr]);
                         }
             }
             // The previous block leaves in the shadow of this block's MFMAs (which were issued first): rows 0-47 are
@@ -1004,7 +976,7 @@ extern "C" int pp_mlp_residual_layernorm(const void* h_in, const void* w1, const
     PP_REQUIRE(E == mlp::E, PP_ERR_UNSUPPORTED, "pp_mlp_residual_layernorm: built for embed dim 384 (ViT-S)");
     PP_REQUIRE(M > 0 && F > 0 && F % mlp::CHUNK == 0, PP_ERR_UNSUPPORTED,
                "pp_mlp_residual_layernorm: hidden width must be a positive multiple of 128");
-    PP_REQUIRE((size_t)F * E * 2 < 0x7ffffff0u && (size_t)M * E * 2 < 0x7ffffff0u, PP_ERR_UNSUPPORTED,
+    PP_REQUIRE((size_t)F * E * 2 < kOob && (size_t)M * E * 2 < kOob, PP_ERR_UNSUPPORTED,
                "pp_mlp_residual_layernorm: operand exceeds 2 GiB");
     mlp::Params p{};
     p.h = reinterpret_cast<const __bf16*>(h_in);
@@ -1041,7 +1013,7 @@ extern "C" int pp_proj_mlp_residual_layernorm(const void* attn, const void* wp, 
     PP_REQUIRE(E == mlp::E, PP_ERR_UNSUPPORTED, "pp_proj_mlp_residual_layernorm: built for embed dim 384 (ViT-S)");
     PP_REQUIRE(M > 0 && F > 0 && F % mlp::CHUNK == 0, PP_ERR_UNSUPPORTED,
                "pp_proj_mlp_residual_layernorm: hidden width must be a positive multiple of 128");
-    PP_REQUIRE((size_t)F * E * 2 < 0x7ffffff0u && (size_t)M * E * 2 < 0x7ffffff0u, PP_ERR_UNSUPPORTED,
+    PP_REQUIRE((size_t)F * E * 2 < kOob && (size_t)M * E * 2 < kOob, PP_ERR_UNSUPPORTED,
                "pp_proj_mlp_residual_layernorm: operand exceeds 2 GiB");
     mlp::Params p{};
     p.h = reinterpret_cast<const __bf16*>(attn);
@@ -1091,7 +1063,7 @@ extern "C" int pp_vit_layer(const void* qkv_in, int seq_len, int heads, float sc
                "pp_vit_layer: built for ViT-S at 256x192 (embed dim 384, 12 heads x 32, 192 tokens)");
     PP_REQUIRE(M > 0 && M % seq_len == 0 && F > 0 && F % mlp::CHUNK == 0, PP_ERR_UNSUPPORTED,
                "pp_vit_layer: M must be a multiple of the sequence length, the hidden width a multiple of 128");
-    PP_REQUIRE((size_t)F * E * 2 < 0x7ffffff0u && (size_t)M * 3 * E * 2 < 0x7ffffff0u, PP_ERR_UNSUPPORTED,
+    PP_REQUIRE((size_t)F * E * 2 < kOob && (size_t)M * 3 * E * 2 < kOob, PP_ERR_UNSUPPORTED,
                "pp_vit_layer: operand exceeds 2 GiB");
     mlp::Params p{};
     p.qkv_in = reinterpret_cast<const __bf16*>(qkv_in);

@@ -23,15 +23,10 @@
 //   * epilogue: + bias (folded BN), optional ReLU, bf16, staged through a separate 48 KiB LDS region one row half at a
 //     time and written as contiguous 16-byte lane stores (deconv: to the phase-interleaved output pixel).
 #include "pp_common.h"
+#include "pp_device.h"
 #include "pp_gemm.h"
 
 namespace pp {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 namespace panel {
 
@@ -48,24 +43,11 @@ constexpr int STAGE = 56 * 1024, NSTAGE = 2;
 constexpr int OFF_CST = NSTAGE * STAGE;  // 112 KiB
 constexpr int CST_BYTES = 48 * 1024;
 constexpr int LDS = OFF_CST + CST_BYTES;  // 160 KiB
-constexpr unsigned OOB = 0x7ffffff0u;
 static_assert(LDS == 160 * 1024, "LDS map");
 
-#define SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
-constexpr int SG_MFMA = 0x008, SG_VMEM = 0x010, SG_DS_READ = 0x100;
-
-__device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
-                                                   0, 0);
-}
 
 // s_waitcnt vmcnt(N) lgkmcnt(0) + s_barrier as builtins (the compiler's wait-count bookkeeping sees them); gfx9
 // encoding: vmcnt [3:0] + [15:14], expcnt [6:4] = 7 (none), lgkmcnt [11:8]
-template <int N>
-__device__ __forceinline__ void wait_vm_lgkm() {
-    static_assert(N >= 0 && N < 64, "vmcnt immediate");
-    __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (0 << 8) | ((N >> 4) << 14));
-}
 
 template <int GATHER, int RF, int CF>
 __global__ __launch_bounds__(THREADS, 2) void panel_gemm_kernel(const GemmParams p) {
@@ -129,8 +111,8 @@ __global__ __launch_bounds__(THREADS, 2) void panel_gemm_kernel(const GemmParams
         }
         const char* Act = reinterpret_cast<const char*>(p.A) + (size_t)z * p.strideA_z * 2;
         const char* Wt = reinterpret_cast<const char*>(p.W) + (size_t)z * p.strideW_z * 2;
-        a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(Act), 0, p.a_bytes, 0x00020000);
-        w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(Wt), 0, p.w_bytes, 0x00020000);
+        a_rsrc = buffer_rsrc(Act, p.a_bytes);
+        w_rsrc = buffer_rsrc(Wt, p.w_bytes);
         const int hw = p.H * p.Wd;
 #pragma unroll
         for (int j = 0; j < JA; ++j) {
@@ -163,11 +145,11 @@ __global__ __launch_bounds__(THREADS, 2) void panel_gemm_kernel(const GemmParams
             const int yy = (a_yx[j < JA ? j : 0] >> 16) + dy, xx = (a_yx[j < JA ? j : 0] & 0xffff) + dx;
             const bool ok = yy >= 0 && yy < p.H && xx >= 0 && xx < p.Wd;
             const int tap_off = ((dy * p.Wd + dx) * p.Cin + i_c0) * 2;
-            const unsigned va = (ok && !(DBG & (1 | 32))) ? (unsigned)((int)a_voff[j < JA ? j : 0] + tap_off) : OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (lds_ptr_t)dst, 16, va, 0, 0, 0);
+            const unsigned va = (ok && !(DBG & (1 | 32))) ? (unsigned)((int)a_voff[j < JA ? j : 0] + tap_off) : kOob;
+            dma16(a_rsrc, dst, va);
         } else {
             const unsigned kb = (unsigned)((i_tap * p.Cin + i_c0) * 2) + (unsigned)((j - JA) * 64) * (unsigned)(p.ldw * 2);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (lds_ptr_t)dst, 16, (i_live && !(DBG & (1 | 64))) ? w_voff + kb : OOB, 0, 0, 0);
+            dma16(w_rsrc, dst, (i_live && !(DBG & (1 | 64))) ? w_voff + kb : kOob);
         }
     };
     auto advance_cursor = [&]() {
@@ -245,7 +227,7 @@ __global__ __launch_bounds__(THREADS, 2) void panel_gemm_kernel(const GemmParams
         for (int rf = 0; rf < RF; ++rf)  // row-fragment outer: an activation fragment dies after CF MFMAs
 #pragma unroll
             for (int cf = 0; cf < CF; ++cf) {
-                if (!(DBG & 4)) acc[cf][rf] = mma(w[cf], a[rf], acc[cf][rf]);
+                if (!(DBG & 4)) acc[cf][rf] = mma_bf16(w[cf], a[rf], acc[cf][rf]);
             }
     };
 
@@ -265,11 +247,11 @@ __global__ __launch_bounds__(THREADS, 2) void panel_gemm_kernel(const GemmParams
                 __builtin_amdgcn_sched_barrier(0);
                 read_frags(s, 1, af[1], wf[1]);
                 mfmas(acc, af[0], wf[0]);
-                SGB(SG_MFMA, 24 - 2 * (RF + CF) + 2);
+                HSGB(SG_MFMA, 24 - 2 * (RF + CF) + 2);
 #pragma unroll
                 for (int i = 0; i < RF + CF; ++i) {
-                    SGB(SG_DS_READ, 1);
-                    if (i < RF + CF - 1) SGB(SG_MFMA, 2);
+                    HSGB(SG_DS_READ, 1);
+                    if (i < RF + CF - 1) HSGB(SG_MFMA, 2);
                 }
                 // ---- every wave holds the second half in registers -> buffer s is free; the other buffer has landed
                 __builtin_amdgcn_sched_barrier(0);
@@ -282,13 +264,13 @@ __global__ __launch_bounds__(THREADS, 2) void panel_gemm_kernel(const GemmParams
                 advance_cursor();
                 read_frags(s ^ 1, 0, af[0], wf[0]);
                 mfmas(acc, af[1], wf[1]);
-                SGB(SG_MFMA, 24 - 2 * (RF + CF) + 2);
-                SGB(SG_VMEM, 1);
+                HSGB(SG_MFMA, 24 - 2 * (RF + CF) + 2);
+                HSGB(SG_VMEM, 1);
 #pragma unroll
                 for (int i = 0; i < RF + CF; ++i) {
-                    SGB(SG_DS_READ, 1);
-                    if (i < RF + CF - 1) SGB(SG_MFMA, 2);
-                    if (i < 6) SGB(SG_VMEM, 1);
+                    HSGB(SG_DS_READ, 1);
+                    if (i < RF + CF - 1) HSGB(SG_MFMA, 2);
+                    if (i < 6) HSGB(SG_VMEM, 1);
                 }
             }
         }
@@ -376,7 +358,7 @@ __global__ __launch_bounds__(THREADS, 2) void panel_gemm_kernel(const GemmParams
                         for (int nf = 0; nf < 2; ++nf) {
                             const u32x4 b = (DBG & 512) ? u32x4{0x3c003c00u, 0x3c003c00u, 0x3c003c00u, (unsigned)e_row}
                                                         : *reinterpret_cast<const u32x4*>(wfl + (nf * 16 + e_row) * ROWB + (((4 * ks + e_kg) ^ (e_row & 7)) << 4));
-                            hacc[nf] = mma(a, b, hacc[nf]);
+                            hacc[nf] = mma_bf16(a, b, hacc[nf]);
                         }
                     }
                     const int hw = p.H * p.Wd;
@@ -491,7 +473,7 @@ int panel_gemm(const GemmParams& p_in, int groups, hipStream_t s) {
     using namespace panel;
     GemmParams p = p_in;
     p.groups = groups;
-    PP_REQUIRE(p.a_bytes > 0 && p.w_bytes > 0 && p.a_bytes < OOB && p.w_bytes < OOB, PP_ERR_UNSUPPORTED,
+    PP_REQUIRE(p.a_bytes > 0 && p.w_bytes > 0 && p.a_bytes < kOob && p.w_bytes < kOob, PP_ERR_UNSUPPORTED,
                "pp panel gemm: operand tensors must be smaller than 2 GiB (32-bit buffer offsets)");
     void (*kern)(const GemmParams) = nullptr;
     int BM, BN;

@@ -27,6 +27,7 @@
 // pp_panel_gemm.hip (convolutions, bf16 out) does not cover: fc2 of ViT-B (K = 3072) ran at ~550 TFLOP/s on the 128 x 128
 // tiles. Short-K layers stay there (12 K-steps do not amortise this kernel's un-overlapped epilogue).
 #include "pp_common.h"
+#include "pp_device.h"
 #include "pp_gemm.h"
 #include "pp_split.h"
 
@@ -42,32 +43,15 @@ namespace psplit {
 // 128 no epilogue at all
 constexpr int DBG = PSPLIT_DBG;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
 constexpr int THREADS = 512;
 constexpr int CST_BYTES = 48 * 1024;  // epilogue staging of the two-stage form
 // LDS of one instantiation: NST stages of (BM + BN) rows x 128 B; the two-stage form adds a separate staging region, the
 // three-stage form stages the epilogue through the buffer of the stage it has just consumed
 constexpr int lds_bytes(int BM, int BN, int NST) { return NST * (BM + BN) * 128 + (NST == 2 ? CST_BYTES : 0); }
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-constexpr unsigned OOB = 0x7ffffff0u;
-
-template <int N>
-__device__ __forceinline__ void wait_vm_lgkm() {
-    __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (0 << 8) | ((N >> 4) << 14));
-}
-
 template <bool SPLIT>
 __device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, f32x4 c) {
-    if constexpr (SPLIT)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    return SPLIT ? mma_f16(a, b, c) : mma_bf16(a, b, c);
 }
-
-__device__ __forceinline__ float gelu_erf_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
 // NST = 3 (round 2): with two stages exactly ONE stage is in flight - the DMA of stage s + 1 is issued at the barrier of
 // stage s - 1 and must have landed at the barrier of stage s, so a stage can never be shorter than the L2 -> LDS latency
@@ -163,8 +147,8 @@ __global__ __launch_bounds__(THREADS, 2) void panel_split_kernel(const GemmParam
         }
         const char* Act = reinterpret_cast<const char*>(p.A) + (size_t)z * p.strideA_z * ESZ;
         const char* Wt = reinterpret_cast<const char*>(p.W) + (size_t)z * p.strideW_z * ESZ;
-        a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(Act), 0, p.a_bytes, 0x00020000);
-        w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(Wt), 0, p.w_bytes, 0x00020000);
+        a_rsrc = buffer_rsrc(Act, p.a_bytes);
+        w_rsrc = buffer_rsrc(Wt, p.w_bytes);
 #pragma unroll
         for (int j = 0; j < JA; ++j) {
             const int m = m0 + 8 * (wv + 8 * j) + d_l;
@@ -201,11 +185,11 @@ __global__ __launch_bounds__(THREADS, 2) void panel_split_kernel(const GemmParam
             const int yy = a_y[jj] + dy, xx = a_x[jj] + dx;
             const bool ok = GATHER == G_LINEAR ? a_y[jj] >= 0 : (yy >= 0 && yy < p.H && xx >= 0 && xx < p.Wd);
             const int tap_off = GATHER == G_LINEAR ? i_c0 * ESZ : ((dy * p.Wd + dx) * p.Cin + i_c0) * ESZ;
-            const unsigned va = ok ? (unsigned)((int)a_voff[jj] + tap_off) : OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (lds_ptr_t)dst, 16, va, 0, 0, 0);
+            const unsigned va = ok ? (unsigned)((int)a_voff[jj] + tap_off) : kOob;
+            dma16(a_rsrc, dst, va);
         } else {
             const unsigned kb = (unsigned)((i_tap * p.Cin + i_c0) * ESZ) + (unsigned)((j - JA) * 64) * (unsigned)(p.ldw * ESZ);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (lds_ptr_t)dst, 16, i_live ? w_voff + kb : OOB, 0, 0, 0);
+            dma16(w_rsrc, dst, i_live ? w_voff + kb : kOob);
         }
     };
     const int ntaps = p.K / cslice;
@@ -465,7 +449,7 @@ __global__ __launch_bounds__(THREADS, 2) void panel_split_kernel(const GemmParam
                             for (int j = 0; j < 4; ++j) v[j] = SPLIT ? relu_keep_nan(v[j]) : fmaxf(v[j], 0.f);
                         } else if (p.act == ACT_GELU) {
 #pragma unroll
-                            for (int j = 0; j < 4; ++j) v[j] = SPLIT ? gelu_erfc_as(v[j]) : gelu_erf_exact(v[j]);
+                            for (int j = 0; j < 4; ++j) v[j] = SPLIT ? gelu_erfc_as(v[j]) : gelu_erf(v[j]);
                         }
                         const int ml = r2 * 16 + e_row;
                         *reinterpret_cast<f32x4*>(cst + ml * ROWB + ((((nl >> 2)) ^ (ml & 7)) << 4)) = v;
@@ -680,7 +664,7 @@ int panel_split_gemm(const GemmParams& p_in, int prec, int groups, hipStream_t s
     p.tile_order = (p.gather == G_CONV3 && p.tap_inner && option("psplit_conv_weight_major") != 0) ? 1 : 0;
     if (p.gather == G_DECONV && option("psplit_deconv_weight_major") != 0) p.tile_order = 1;  // dev A/B (is deconv2 + 1x1 traffic-bound?)
     if (p.gather == G_LINEAR) p.Cin = p.K;
-    PP_REQUIRE(p.a_bytes > 0 && p.w_bytes > 0 && p.a_bytes < OOB && p.w_bytes < OOB, PP_ERR_UNSUPPORTED,
+    PP_REQUIRE(p.a_bytes > 0 && p.w_bytes > 0 && p.a_bytes < kOob && p.w_bytes < kOob, PP_ERR_UNSUPPORTED,
                "pp panel split gemm: operand tensors must be smaller than 2 GiB (32-bit buffer offsets)");
     void (*kern)(const GemmParams) = nullptr;
     const int shape = panel_split_shape(p, groups);

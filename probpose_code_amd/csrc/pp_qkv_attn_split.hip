@@ -25,15 +25,11 @@
 // runs beside the other's MFMA / fill phase. The twelve heads of a sequence are neighbours on one XCD (block remap), the
 // 288 KiB of its LayerNorm rows are fetched from HBM once and hit in that L2 eleven times; Wqkv (1.7 MB) stays in every L2.
 #include "pp_common.h"
+#include "pp_device.h"
 #include "pp_split.h"
 
 namespace pp {
 namespace qka {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 #ifndef QKA_DBG
 #define QKA_DBG 0  // dev ablations (timing only, wrong results): 1 no attention phase, 2 no GEMM phase MFMAs, 4 no DMA (zeros: the MFMAs then run on
@@ -49,7 +45,6 @@ constexpr int OFF_Q = 0, OFF_K = S * 128, OFF_V = 2 * S * 128;
 constexpr int SPV = S + 4;                        // V^T row pitch in halves: 98 dwords - the 16 rows a ds_read2_b64 group touches fall on 16 distinct bank pairs (mod 32)
 constexpr int V_PLANE = HD * SPV * 2;             // bytes of one plane
 constexpr int LDS = OFF_V + 2 * V_PLANE;          // 74 240 B
-constexpr unsigned OOB = 0x7ffffff0u;
 static_assert(LDS >= 2 * STAGE && 2 * LDS <= 160 * 1024, "two workgroups per CU");
 
 struct Params {
@@ -73,12 +68,7 @@ struct Params {
 
 __device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, f32x4 c) {
     if (DBG & 2) return c;
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm_lgkm() {
-    __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (0 << 8) | ((N >> 4) << 14));
+    return mma_f16(a, b, c);
 }
 
 // (hi, lo) of four values of an accumulator fragment, regrouped by the row swap of split_store4_rowpair: the even-row lane
@@ -152,8 +142,8 @@ __device__ __forceinline__ void qkv_attention_body(const Params& p) {
     // pc = lane & 7) fetches logical chunk pc ^ l: the LDS image is chunk-swizzled by (line & 7).
     const int d_l = lane >> 3;
     const unsigned d_sw = (unsigned)(((lane & 7) ^ d_l) << 4);
-    const __amdgpu_buffer_rsrc_t h_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.h), 0, (DBG & 4) ? 0u : p.h_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, (DBG & 4) ? 0u : p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t h_rsrc = buffer_rsrc(p.h, (DBG & 4) ? 0u : p.h_bytes);
+    const __amdgpu_buffer_rsrc_t w_rsrc = buffer_rsrc(p.w, (DBG & 4) ? 0u : p.w_bytes);
     const unsigned v_h = (unsigned)(seq * S + 8 * wv + d_l) * (unsigned)(E * 4) + d_sw;                    // + 64 j token rows
     const unsigned v_w0 = (unsigned)((wv >> 2) * E + head * HD + (wv & 3) * 8 + d_l) * (unsigned)(E * 4) + d_sw;  // piece 24 + w
     const unsigned v_w1 = (unsigned)(2 * E + head * HD + (wv & 3) * 8 + d_l) * (unsigned)(E * 4) + d_sw;    // piece 32 + w (w < 4)
@@ -162,9 +152,9 @@ __device__ __forceinline__ void qkv_attention_body(const Params& p) {
         const int so = kb * 128;
 #pragma unroll
         for (int j = 0; j < 3; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(h_rsrc, (lds_ptr_t)(dst + j * 8192), 16, v_h + (unsigned)(j * 64 * E * 4), so, 0, 0);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (lds_ptr_t)(dst + 24 * 1024), 16, v_w0, so, 0, 0);
-        if (wv < 4) __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (lds_ptr_t)(dst + 32 * 1024), 16, v_w1, so, 0, 0);
+            dma16(h_rsrc, dst + j * 8192, v_h + (unsigned)(j * 64 * E * 4), so);
+        dma16(w_rsrc, dst + 24 * 1024, v_w0, so);
+        if (wv < 4) dma16(w_rsrc, dst + 32 * 1024, v_w1, so);
     };
 
     // ---- fragment reads: hi halves in 16-byte chunk fg, lo halves in chunk 4 + fg of a line
@@ -241,14 +231,13 @@ __device__ __forceinline__ void qkv_attention_body(const Params& p) {
     };
     // FOLD: (mean, rstd) of the tokens this lane's fragments belong to. Normal fragments: the lane's token 48 rg + 16 rf + fr; transposed ones
     // (V^T, waves of column half 1): four consecutive tokens 48 rg + 16 rf + 4 fg + (0..3) per fragment row
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
     if (cg == 0) k_loop(TagF{}); else k_loop(TagT{});
     // (requested here, all at once: kept through the K loop they cost 6 - 35 spilled registers at the kernel's 128; one pair per fragment inside the
     //  store loop below is a chain of trips to the L2)
-    f32x2_t st_n[3] = {f32x2_t{0.f, 1.f}, f32x2_t{0.f, 1.f}, f32x2_t{0.f, 1.f}};
+    f32x2 st_n[3] = {f32x2{0.f, 1.f}, f32x2{0.f, 1.f}, f32x2{0.f, 1.f}};
     if (FOLD) {
 #pragma unroll
-        for (int rf = 0; rf < 3; ++rf) st_n[rf] = *reinterpret_cast<const f32x2_t*>(p.ln_stats + ((size_t)seq * S + 48 * rg + 16 * rf + fr) * 2);
+        for (int rf = 0; rf < 3; ++rf) st_n[rf] = *reinterpret_cast<const f32x2*>(p.ln_stats + ((size_t)seq * S + 48 * rg + 16 * rf + fr) * 2);
     }
     f32x4 st_t[3][2];
 #pragma unroll
@@ -396,7 +385,6 @@ constexpr int LDS_DEEP = 4 * STAGE;  // 144 KiB: the projection's ring of four s
 static_assert(LDS_DEEP >= LDS && LDS_DEEP <= 160 * 1024, "LDS map of the deep-ring form");
 __global__ __launch_bounds__(THREADS) void qkv_attention_split_deep_kernel(const Params p) { qkv_attention_body<false, 4>(p); }
 
-
 // (Round 3's head-PAIR form - one workgroup per (sequence, two heads), a three-stage ring of 48 KiB stages, one workgroup per CU - measured 80.9 -
 // 87 us per launch against 77.7 - 79 for this kernel and was retired in round 6; `git log -S qkv_attention_split2_kernel` has it, the numbers are in
 // DESIGN_NOTEBOOK.md 4.)
@@ -442,7 +430,7 @@ static int qkv_attention_launch(const void* h_in, const void* wqkv, const float*
     PP_REQUIRE(n_seq > 0, PP_ERR_INVALID_ARG, "pp_qkv_attention_split: n_seq must be positive");
     PP_REQUIRE(seq_len == qka::S && head_dim == qka::HD && heads * head_dim == qka::E, PP_ERR_UNSUPPORTED,
                "pp_qkv_attention_split: built for 192-token sequences, 12 heads of 32 dims (ViT-S at 256x192)");
-    PP_REQUIRE((size_t)n_seq * qka::S * qka::E * 4 < qka::OOB, PP_ERR_UNSUPPORTED, "pp_qkv_attention_split: operand exceeds 2 GiB");
+    PP_REQUIRE((size_t)n_seq * qka::S * qka::E * 4 < pp::kOob, PP_ERR_UNSUPPORTED, "pp_qkv_attention_split: operand exceeds 2 GiB");
     PP_REQUIRE(h_in != out, PP_ERR_INVALID_ARG, "pp_qkv_attention_split: out must not alias h_in (other heads still read the rows)");
     qka::Params p{};
     p.h = h_in;

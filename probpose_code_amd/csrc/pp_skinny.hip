@@ -21,14 +21,11 @@
 //     writes the operand-format rows for the next layer, then puts the counter back to zero. The result does not depend on who arrives last.
 //     A launch costs ~2.7 us of dependency gap in a replayed graph: per layer this saves two of six.
 #include "pp_common.h"
+#include "pp_device.h"
 #include "pp_split.h"
 
 namespace pp {
 namespace sk {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr int THREADS = 256, KS = 2;  // k-blocks (of 32 elements) per stage
 // Stages in the LDS ring per tile edge (32 / 64 / 96): what a workgroup has in flight is what it gets per memory round trip (~2 us from HBM / MALL
@@ -70,12 +67,6 @@ __device__ unsigned long long g_sk_stamps[16];
 #else
 #define SK_T(i) do { } while (0)
 #endif
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt immediate");
-    __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
-}
 
 // ---- LayerNorm of the rows m0 + wave * BM / 4 ... of the fp32 output (device-scope loads: the rows were written inside this launch, possibly behind
 // another XCD's L2), operand-format rows to h_out. LPR lanes per row, G = 64 / LPR rows per group, GC groups requested at once; a lane owns NV8
@@ -229,10 +220,9 @@ __global__ __launch_bounds__(THREADS) void skinny_linear_kernel(const Params p) 
 #endif
     SK_T(0);
 
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.a), 0, p.a_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ra = buffer_rsrc(p.a, p.a_bytes);
     const int phase = DECONV ? (int)blockIdx.y : 0;  // output phase 2 py + px: its own weight matrix
-    const __amdgpu_buffer_rsrc_t rw =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.w) + (DECONV ? (size_t)phase * p.w_bytes : 0), 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rw = buffer_rsrc(p.w + (DECONV ? (size_t)phase * p.w_bytes : 0), p.w_bytes);
     // a DMA instruction moves 8 rows x 128 B: lane (row l = lane >> 3, physical chunk lane & 7) fetches logical chunk (lane & 7) ^ l
     const unsigned d_row = (unsigned)lane >> 3;
     const unsigned d_src = d_row * (unsigned)(p.K * 4) + ((((unsigned)lane & 7u) ^ d_row) << 4);
@@ -275,17 +265,16 @@ __global__ __launch_bounds__(THREADS) void skinny_linear_kernel(const Params p) 
             // (the row part of the address goes into the VGPR offset: the descriptor's range check covers that one, not the scalar offset - rows
             //  past M must fall outside the tensor's extent to read as zeros)
             if (r < BN)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(dst + (kb * ROWS + r) * 128), 16, d_src + (unsigned)((n0 + r) * p.K * 4), koff, 0, 0);
+                dma16(rw, dst + (kb * ROWS + r) * 128, d_src + (unsigned)((n0 + r) * p.K * 4), koff);
             else if constexpr (DECONV) {
                 const int tap = nx_tap[kb], cb = nx_cb[kb];
                 const int dy = (tap >> 1) - 1 + (phase >> 1), dx = (tap & 1) - 1 + (phase & 1);
                 const int yy = pix_y[u] + dy, xx = pix_x[u] + dx;
                 const bool ok = yy >= 0 && yy < p.H && xx >= 0 && xx < p.Wd;
-                const unsigned vo = ok ? (unsigned)((int)pix_off[u] + (dy * p.Wd + dx) * p.Cin * 4) : 0x7ffffff0u;  // outside the map: zeros
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_ptr_t)(dst + (kb * ROWS + r) * 128), 16, vo, (unsigned)(cb * 128), 0, 0);
+                const unsigned vo = ok ? (unsigned)((int)pix_off[u] + (dy * p.Wd + dx) * p.Cin * 4) : kOob;  // outside the map: zeros
+                dma16(ra, dst + (kb * ROWS + r) * 128, vo, (unsigned)(cb * 128));
             } else
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_ptr_t)(dst + (kb * ROWS + r) * 128), 16, d_src + (unsigned)((m0 + r - BN) * p.K * 4), koff, 0,
-                                                         0);
+                dma16(ra, dst + (kb * ROWS + r) * 128, d_src + (unsigned)((m0 + r - BN) * p.K * 4), koff);
         }
         if constexpr (DECONV) {
 #pragma unroll
@@ -383,7 +372,7 @@ __global__ __launch_bounds__(THREADS) void skinny_linear_kernel(const Params p) 
     }
 
     SK_T(1);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (unsigned)((size_t)p.M * p.N * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rout = buffer_rsrc(p.out, (unsigned)((size_t)p.M * p.N * 4));
     // ---- epilogue: lane (f_row, f_kg) of tile (c, r) holds row m0 + 16 (RT wm + r) + f_row, columns n0 + 16 (CT wn + c) + 4 f_kg + (0..3)
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
@@ -431,7 +420,7 @@ __global__ __launch_bounds__(THREADS) void skinny_linear_kernel(const Params p) 
         // ---- LayerNorm tail: the workgroup that completes the row block normalises it
         __shared__ int s_last;
         SK_T(2);
-        __builtin_amdgcn_s_waitcnt((0 & 15) | (7 << 4) | (15 << 8) | ((0 >> 4) << 14));  // vmcnt(0): this thread's device-scope stores are acknowledged
+        wait_vm<0>();  // vmcnt(0): this thread's device-scope stores are acknowledged
         SK_T(3);
         __syncthreads();
         // (every wave is behind its last read of the ring: its first 8 KiB now hold gamma | beta for the tail - LDS reads do not queue behind the
@@ -457,7 +446,7 @@ __global__ __launch_bounds__(THREADS) void skinny_linear_kernel(const Params p) 
         else ln_tail_rows_any<BM>(p, rout, s_gb, m0, wave, lane);
 #if SK_STAMP
         SK_T(5);
-        __builtin_amdgcn_s_waitcnt((0 & 15) | (7 << 4) | (15 << 8) | ((0 >> 4) << 14));
+        wait_vm<0>();
         SK_T(6);
         if (wave == 0 && mt == 0 && lane == 0)
             for (int i = 0; i < 7; ++i) g_sk_stamps[i] = sk_t[i];
@@ -534,7 +523,7 @@ extern "C" int pp_skinny_linear(const void* act, const void* weight, const float
     PP_REQUIRE(act_fn == sk::ACT_NONE || act_fn == sk::ACT_GELU || act_fn == sk::ACT_RELU, PP_ERR_INVALID_ARG, "pp_skinny_linear: unknown act_fn");
     PP_REQUIRE(act != out, PP_ERR_INVALID_ARG, "pp_skinny_linear: act must not alias out (other column tiles still read the rows)");
     PP_REQUIRE(res_mod >= 0 && (!residual || out_format == PP_OUT_F32 || residual != out), PP_ERR_INVALID_ARG, "pp_skinny_linear: bad residual arguments");
-    PP_REQUIRE((size_t)M * K * 4 < 0x7ffffff0u && (size_t)N * K * 4 < 0x7ffffff0u && (size_t)M * N * 4 < 0x7ffffff0u, PP_ERR_UNSUPPORTED,
+    PP_REQUIRE((size_t)M * K * 4 < kOob && (size_t)N * K * 4 < kOob && (size_t)M * N * 4 < kOob, PP_ERR_UNSUPPORTED,
                "pp_skinny_linear: operands must be smaller than 2 GiB");
     {
         unsigned u;
@@ -612,7 +601,7 @@ extern "C" int pp_skinny_conv1x1_planar(const void* act, const void* weight_padd
     PP_REQUIRE(act && weight_padded && out, PP_ERR_INVALID_ARG, "pp_skinny_conv1x1_planar: NULL argument");
     PP_REQUIRE(n_img > 0 && P > 0 && K > 0 && K % 64 == 0 && n_valid > 0, PP_ERR_INVALID_ARG, "pp_skinny_conv1x1_planar: bad shape (K % 64 == 0)");
     const int M = n_img * P, N = 32 * ((n_valid + 31) / 32);
-    PP_REQUIRE((size_t)M * K * 4 < 0x7ffffff0u && (size_t)M * n_valid * 4 < 0x7ffffff0u, PP_ERR_UNSUPPORTED, "pp_skinny_conv1x1_planar: operands must be smaller than 2 GiB");
+    PP_REQUIRE((size_t)M * K * 4 < kOob && (size_t)M * n_valid * 4 < kOob, PP_ERR_UNSUPPORTED, "pp_skinny_conv1x1_planar: operands must be smaller than 2 GiB");
     {
         unsigned u;
         __builtin_memcpy(&u, &w_inv_scale, 4);
@@ -653,7 +642,7 @@ extern "C" int pp_skinny_deconv(const void* act_nhwc, const void* weight, const 
     PP_REQUIRE(Cin > 0 && Cin % 32 == 0 && sk::KS <= Cin / 32 && (4 * Cin) % (32 * sk::KS) == 0 && Cout > 0 && Cout % 32 == 0, PP_ERR_UNSUPPORTED,
                "pp_skinny_deconv: needs Cin % 32 == 0, Cin >= 64 (a stage of two k-blocks within Cin / 32 blocks per tap) and Cout % 32 == 0");
     const long long M = (long long)B * H * W, K = 4ll * Cin;
-    PP_REQUIRE(M * Cin * 4 < 0x7ffffff0ll && (long long)Cout * K * 4 < 0x7ffffff0ll && 4 * M * Cout * 4 < 0x7ffffff0ll, PP_ERR_UNSUPPORTED,
+    PP_REQUIRE(M * Cin * 4 < kOob && (long long)Cout * K * 4 < kOob && 4 * M * Cout * 4 < kOob, PP_ERR_UNSUPPORTED,
                "pp_skinny_deconv: operands must be smaller than 2 GiB");
     sk::Params p{};
     p.a = reinterpret_cast<const char*>(act_nhwc);

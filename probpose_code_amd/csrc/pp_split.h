@@ -14,15 +14,16 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "pp_device.h"
+
 namespace pp {
 
 struct SplitH {
     unsigned raw;  // container only (sizeof == 4); never interpreted as a number
 };
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float split_f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));  // (f16x8, the MFMA operand: pp_device.h)
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ _Float16 split_hi(float x) { return (_Float16)x; }
 __device__ __forceinline__ _Float16 split_lo(float x, _Float16 hi) { return (_Float16)(x - (float)hi); }
@@ -41,15 +42,13 @@ __device__ __forceinline__ void split_pin(float& x) { asm("" : "+v"(x)); }
 // fused product form of the trap described above: g is a finished fp32 value here), packed by a second v_cvt_pk_f16_f32.
 // hi = {fp16(a) | fp16(b) << 16}, lo likewise.
 __device__ __forceinline__ void split_pair(float a, float b, unsigned& hi, unsigned& lo) {
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
-    typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
     asm("" : "+v"(a));
     asm("" : "+v"(b));
-    hi = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{a, b}, f16x2_t));
+    hi = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, f16x2));
     float la, lb;
     asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(la) : "v"(a), "v"(hi));
     asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(lb) : "v"(b), "v"(hi));
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{la, lb}, f16x2_t));
+    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{la, lb}, f16x2));
 }
 
 // address of the hi half of element `idx` of a split tensor (the lo half lives 64 bytes further)
@@ -61,7 +60,7 @@ __device__ __forceinline__ const char* split_addr(const void* base, size_t idx) 
 }
 
 // four consecutive elements (idx % 4 == 0): two 8-byte accesses
-__device__ __forceinline__ void split_store4(void* base, size_t idx, split_f32x4 v) {
+__device__ __forceinline__ void split_store4(void* base, size_t idx, f32x4 v) {
     f16x4 h, l;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -76,45 +75,41 @@ __device__ __forceinline__ void split_store4(void* base, size_t idx, split_f32x4
 // bit 4 clear: elements idx .. idx + 3 with idx % 8 == 0, their partners idx + 4 ..): one row swap per dword
 // (v_permlane16_swap) gives the even-row lane the whole hi chunk and the odd-row lane the whole lo chunk - ONE 16-byte store
 // per lane instead of two 8-byte ones. Every lane of the wave must call it; `store` masks the store itself.
-__device__ __forceinline__ void split_store4_rowpair(void* base, size_t idx, split_f32x4 v, bool store) {
-    typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-    u32x2_t hu, lu;
+__device__ __forceinline__ void split_store4_rowpair(void* base, size_t idx, f32x4 v, bool store) {
+    u32x2 hu, lu;
     { unsigned h__, l__; split_pair(v[0], v[1], h__, l__); hu[0] = h__; lu[0] = l__; }
     { unsigned h__, l__; split_pair(v[2], v[3], h__, l__); hu[1] = h__; lu[1] = l__; }
     // swap(a, b): odd rows of a <-> even rows of b. Even-row lane: (own hi, partner's hi); odd-row lane: (partner's lo, own lo)
     const auto s0 = __builtin_amdgcn_permlane16_swap(hu[0], lu[0], false, false);
     const auto s1 = __builtin_amdgcn_permlane16_swap(hu[1], lu[1], false, false);
-    const u32x4_t q = {s0[0], s1[0], s0[1], s1[1]};
+    const u32x4 q = {s0[0], s1[0], s0[1], s1[1]};
     const bool odd = (threadIdx.x & 16) != 0;
     char* p = split_addr(base, idx & ~(size_t)7) + (odd ? 64 : 0);
-    if (store) *reinterpret_cast<u32x4_t*>(p) = q;
+    if (store) *reinterpret_cast<u32x4*>(p) = q;
 }
-__device__ __forceinline__ void split_store4_rowpair_nt(void* base, size_t idx, split_f32x4 v, bool store) {  // dev: the same, non-temporal
+__device__ __forceinline__ void split_store4_rowpair_nt(void* base, size_t idx, f32x4 v, bool store) {  // dev: the same, non-temporal
     f16x4 h, l;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         h[j] = split_hi(v[j]);
         l[j] = split_lo(v[j], h[j]);
     }
-    typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-    const u32x2_t hu = __builtin_bit_cast(u32x2_t, h), lu = __builtin_bit_cast(u32x2_t, l);
+    const u32x2 hu = __builtin_bit_cast(u32x2, h), lu = __builtin_bit_cast(u32x2, l);
     const auto s0 = __builtin_amdgcn_permlane16_swap(hu[0], lu[0], false, false);
     const auto s1 = __builtin_amdgcn_permlane16_swap(hu[1], lu[1], false, false);
-    const u32x4_t q = {s0[0], s1[0], s0[1], s1[1]};
+    const u32x4 q = {s0[0], s1[0], s0[1], s1[1]};
     const bool odd = (threadIdx.x & 16) != 0;
     char* p = split_addr(base, idx & ~(size_t)7) + (odd ? 64 : 0);
-    if (store) __builtin_nontemporal_store(q, reinterpret_cast<u32x4_t*>(p));
+    if (store) __builtin_nontemporal_store(q, reinterpret_cast<u32x4*>(p));
 }
-__device__ __forceinline__ split_f32x4 split_load4(const void* base, size_t idx) {
+__device__ __forceinline__ f32x4 split_load4(const void* base, size_t idx) {
     const char* p = split_addr(base, idx);
     const f16x4 h = *reinterpret_cast<const f16x4*>(p), l = *reinterpret_cast<const f16x4*>(p + 64);
-    return split_f32x4{(float)h[0] + (float)l[0], (float)h[1] + (float)l[1], (float)h[2] + (float)l[2], (float)h[3] + (float)l[3]};
+    return f32x4{(float)h[0] + (float)l[0], (float)h[1] + (float)l[1], (float)h[2] + (float)l[2], (float)h[3] + (float)l[3]};
 }
 
 // acc += a * b for one K = 32 block given the hi / lo fragments of both operands (small terms first)
-__device__ __forceinline__ split_f32x4 split_mma(const f16x8& ah, const f16x8& al, const f16x8& bh, const f16x8& bl, split_f32x4 c) {
+__device__ __forceinline__ f32x4 split_mma(const f16x8& ah, const f16x8& al, const f16x8& bh, const f16x8& bl, f32x4 c) {
     c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, c, 0, 0, 0);

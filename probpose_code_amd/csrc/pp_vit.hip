@@ -1,14 +1,10 @@
 // Memory-bound pieces of the ViT backbone for gfx950: input preprocessing fused with the
 // patch-embed im2col, and LayerNorm as a wavefront reduction.
 #include "pp_common.h"
+#include "pp_device.h"
 #include "pp_split.h"
 
 namespace pp {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------------------------
 // uint8 BGR CHW crops -> patch matrix for the patch-embed GEMM, both flip-test passes at once.
@@ -144,7 +140,6 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
         const float o0 = (v[i][0] - mean) * rstd * g[0] + b[0];
         const float o1 = (v[i][1] - mean) * rstd * g[1] + b[1];
         if constexpr (__is_same(TO, SplitH)) {
-            typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
             const _Float16 h0 = split_hi(o0), h1 = split_hi(o1);
             char* o = split_addr(y, (size_t)row * E + 2 * (lane + 64 * i));
             *reinterpret_cast<f16x2*>(o) = f16x2{h0, h1};

@@ -26,14 +26,11 @@
 // Numerics: the transforms add at most four values (input) / nine values (output) in fp32; measured against torch fp64 on the
 // unrounded operands the pooled outputs agree to the same 2e-5 the implicit-GEMM kernels meet (tests/test_split_fp16.py).
 #include "pp_common.h"
+#include "pp_device.h"
 #include "pp_split.h"
 
 namespace pp {
 namespace wino {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 #ifndef WINO_DBG
 #define WINO_DBG 0  // dev ablations (timing only, wrong results): 2 no MFMAs, 4 no DMA traffic, 8 no epilogue
@@ -47,7 +44,6 @@ constexpr int STAGE = (BT + BN) * 128;  // 36 KiB: one 128-byte block of K per r
 constexpr int NST = 4;
 constexpr int LDS = NST * STAGE;        // 144 KiB
 constexpr int PITCH = 100;              // floats per pixel of the epilogue staging (16-byte aligned, 2-way conflicts at worst)
-constexpr unsigned OOB = 0x7ffffff0u;
 static_assert(8 * GPX * PITCH * 4 <= LDS, "epilogue staging fits the ring");
 
 struct Params {
@@ -63,12 +59,7 @@ struct Params {
 
 __device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, f32x4 c) {
     if (DBG & 2) return c;
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm_lgkm() {
-    __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (0 << 8) | ((N >> 4) << 14));
+    return mma_f16(a, b, c);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -171,8 +162,8 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_pool_kernel(const Params p) {
     // 32 + w). Lane (line l = lane >> 3, physical chunk pc = lane & 7) fetches logical chunk pc ^ l: chunk-swizzled by (line & 7).
     const int d_l = lane >> 3;
     const unsigned d_sw = (unsigned)(((lane & 7) ^ d_l) << 4);
-    const __amdgpu_buffer_rsrc_t v_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.V), 0, (DBG & 4) ? 0u : p.v_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t u_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.U), 0, (DBG & 4) ? 0u : p.u_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t v_rsrc = buffer_rsrc(p.V, (DBG & 4) ? 0u : p.v_bytes);
+    const __amdgpu_buffer_rsrc_t u_rsrc = buffer_rsrc(p.U, (DBG & 4) ? 0u : p.u_bytes);
     const unsigned rowb = (unsigned)(p.Cin * 4);
     const unsigned v_v = (unsigned)(rb * BT + 8 * wv + d_l) * rowb + d_sw;                                   // + 64 j tile rows
     const unsigned v_u0 = (unsigned)((g * 16) * p.Cout + n0 + 8 * wv + d_l) * rowb + d_sw;                   // piece 24 + w: rows 8 w ..
@@ -182,13 +173,13 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_pool_kernel(const Params p) {
     auto issue_stage = [&]() {
         char* dst = smem + (i_s & (NST - 1)) * STAGE + wv * 1024;
         const bool live = i_s < nstages;  // past the end: zero fillers (every wave's vmcnt arithmetic stays the same)
-        const unsigned so_v = live ? (unsigned)i_p * v_pstride + (unsigned)(i_kb * 128) : OOB;
-        const unsigned so_u = live ? (unsigned)i_p * u_pstride + (unsigned)(i_kb * 128) : OOB;
+        const unsigned so_v = live ? (unsigned)i_p * v_pstride + (unsigned)(i_kb * 128) : kOob;
+        const unsigned so_u = live ? (unsigned)i_p * u_pstride + (unsigned)(i_kb * 128) : kOob;
 #pragma unroll
         for (int j = 0; j < 3; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(v_rsrc, (lds_ptr_t)(dst + j * 8192), 16, live ? v_v + (unsigned)(j * 64) * rowb : OOB, live ? so_v : 0, 0, 0);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(u_rsrc, (lds_ptr_t)(dst + 24 * 1024), 16, live ? v_u0 : OOB, live ? so_u : 0, 0, 0);
-        if (wv < 4) __builtin_amdgcn_raw_ptr_buffer_load_lds(u_rsrc, (lds_ptr_t)(dst + 32 * 1024), 16, live ? v_u1 : OOB, live ? so_u : 0, 0, 0);
+            dma16(v_rsrc, dst + j * 8192, live ? v_v + (unsigned)(j * 64) * rowb : kOob, live ? so_v : 0);
+        dma16(u_rsrc, dst + 24 * 1024, live ? v_u0 : kOob, live ? so_u : 0);
+        if (wv < 4) dma16(u_rsrc, dst + 32 * 1024, live ? v_u1 : kOob, live ? so_u : 0);
         ++i_s;
         if (++i_kb == KB) {
             i_kb = 0;
@@ -382,7 +373,7 @@ extern "C" int pp_conv3x3_winograd_maxpool_relu(const void* act_nhwc, const void
                "pp_conv3x3_winograd_maxpool_relu: Cin must be a multiple of 128, Cout of 96");
     const long long T = (long long)B * (H / 2) * (W / 2);
     const long long vb = 16ll * T * Cin * 4, ub = 16ll * groups * Cout * (long long)Cin * 4;
-    PP_REQUIRE(vb < wino::OOB && ub < wino::OOB && T / wino::GT < (1 << 20), PP_ERR_UNSUPPORTED,
+    PP_REQUIRE(vb < pp::kOob && ub < pp::kOob && T / wino::GT < (1 << 20), PP_ERR_UNSUPPORTED,
                "pp_conv3x3_winograd_maxpool_relu: operands must be smaller than 2 GiB (and fewer than 2^20 tile groups)");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const long long items = T * (Cin / 4);
