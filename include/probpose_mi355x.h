@@ -980,6 +980,92 @@ long long pp_jpeg_huffman_scratch_bytes(const pp_jpeg_info* infos_host, const lo
 int pp_jpeg_huffman_decode_batch(const pp_jpeg_hd_desc* descriptors, int n, long long max_stream_bytes, long long max_blocks,
                                  int sync_passes, void* stream);
 
+/* PNG files written from the device (csrc/pp_png.hip, csrc/pp_png_core.h; added under version 4: purely additive). 8-bit
+ * truecolour, non-interlaced, one IDAT chunk, no ancillary chunk. Each row takes, of the five PNG filters, the one with the
+ * smallest sum of min(b, 256 - b) over its bytes (ties: the lowest number). The filtered stream is cut into tiles of 4096
+ * bytes; a run of equal bytes inside a tile becomes a literal and matches of length 3..258 at distance 1; the tokens are
+ * coded in ONE dynamic deflate block with a Huffman code built on the host from the stream's own histogram. The deflate
+ * stage takes any byte stream: a descriptor without pixels compresses `data` as it stands into a zlib stream. */
+
+/* A stream's Huffman code as the device reads it. sym[s]: the bit-reversed code of literal/length symbol s | its length << 16
+ * (0: unused); header: the first header_bits bits of the zlib stream, LSB first in little-endian words (78 01, BFINAL,
+ * BTYPE, HLIT, HDIST, HCLEN, the code-length code and the lengths). */
+typedef struct {
+    uint32_t sym[288];
+    uint32_t header_bits;
+    uint32_t reserved[3];
+    uint32_t header[76];
+} pp_deflate_code;
+
+/* What the coder leaves per stream: the length of the zlib stream in bytes (also when it did not fit: the capacity it
+ * needs), PP_OK, PP_ERR_INVALID_ARG (a descriptor that describes nothing) or PP_ERR_WORKSPACE (capacity below the need:
+ * nothing written), and the CRC-32 register after crc_init and the stream's bytes (the chunk's CRC is its complement). */
+typedef struct {
+    int64_t bytes;
+    int32_t status;
+    uint32_t crc;
+} pp_deflate_result;
+
+/* One stream of a batch (a device table of these drives every launch). pixels: NULL, or the picture's top-left byte -
+ * (height, width, 3) uint8 with row_stride bytes between rows, rgb: 1 for R,G,B in memory, 0 for B,G,R - only read; then
+ * len = height * (1 + 3 * width) and pp_png_tokens_batch writes the filtered stream to data. Without pixels data is only
+ * read. data: 16-byte aligned; hist: 288 uint32 (the histogram of the 286 symbols, symbol 256 counted once); code: what
+ * pp_deflate_build_code made of hist, read by pp_png_deflate_batch only; scratch: the stream's share of
+ * pp_deflate_scratch_bytes, 16-byte aligned, contents undefined before and after; out / capacity: where the zlib stream
+ * goes (16-byte aligned) and how many bytes fit; crc_init: the CRC-32 register in front of the stream's first byte. */
+typedef struct {
+    const uint8_t* pixels;
+    uint8_t* data;
+    uint32_t* hist;
+    const pp_deflate_code* code;
+    uint8_t* scratch;
+    uint8_t* out;
+    pp_deflate_result* result;
+    int64_t len;
+    int64_t capacity;
+    int32_t width, height;
+    int64_t row_stride;
+    int32_t rgb;
+    uint32_t crc_init;
+    int64_t reserved;
+} pp_deflate_desc;
+
+/* Host only. A capacity no zlib stream of this coder exceeds for len (1 .. 2^31 - 1) input bytes: 15 bits a byte, header,
+ * end-of-block and Adler-32. PP_ERR_INVALID_ARG: len out of range or a bound of 2^31 bytes or more. */
+long long pp_deflate_bound(long long len);
+/* Host only. A capacity no file of a width x height picture exceeds: pp_deflate_bound of its filtered stream and 57 bytes
+ * of framing. PP_ERR_INVALID_ARG: a side outside 1..65535, or a stream bound of 2^31 bytes or more. */
+long long pp_png_encoded_bound(int width, int height);
+/* Host only. Bytes of scratch for one stream of len bytes, a multiple of 256. < 0: error. */
+long long pp_deflate_scratch_bytes(long long len);
+/* Host only, re-entrant: the code of a histogram (hist_host: 286 counts; symbol 256 is taken as used whatever its count).
+ * Lengths of at most 15 bits, a complete code (Kraft sum 1; with fewer than two used symbols an unused one is added), one
+ * distance code of length 1, a code-length code of at most 7 bits that does not use symbols 16..18. The same histogram
+ * gives the same code. */
+int pp_deflate_build_code(const uint32_t* hist_host, pp_deflate_code* code_host);
+/* Host only, re-entrant, no HIP call: the zlib stream of data_host[0, len) into out_host[0, capacity) by the sequential
+ * form of the core the kernels run (the same bytes); *size_out <- its length, *tokens_out (may be NULL) <- the literals and
+ * matches in it. PP_ERR_WORKSPACE: capacity too small (*size_out <- the need). */
+int pp_zlib_compress(const void* data_host, long long len, void* out_host, size_t capacity, size_t* size_out, long long* tokens_out);
+/* Host only, re-entrant, no HIP call: the whole file of a picture in host memory (arguments as pp_deflate_desc's) into
+ * out_host[0, capacity); *size_out <- its length. The sequential form of the same core: the file pp_png_tokens_batch,
+ * pp_deflate_build_code and pp_png_deflate_batch give, byte for byte. */
+int pp_png_encode(const uint8_t* pixels_host, int width, int height, long long row_stride, int rgb, void* out_host, size_t capacity,
+                  size_t* size_out);
+/* The first half on the device, in three launches ("png_filter": a workgroup per row, only with max_height > 0 and only for
+ * descriptors with pixels; "png_clear": the histograms zeroed; "png_hist": a workgroup per tile - the tokens counted into
+ * hist, the tile's Adler-32 partial into scratch). descriptors: n pp_deflate_desc on the device; max_height / max_len: the
+ * largest height and stream length in the table - they size the grids, every stream is bounded by its own entry. The
+ * caller then reads the histograms, builds the codes and uploads them. No allocation, no synchronisation. */
+int pp_png_tokens_batch(const pp_deflate_desc* descriptors, int n, int max_height, long long max_len, void* stream);
+/* The second half, in five launches ("png_bits": a tile's bit count; "png_scan": one workgroup per stream - 64-bit prefix
+ * sums, the Adler-32 combination, size and status into the result slot; "png_zero": the words in use; "png_pack": header,
+ * tokens, end-of-block, padding, Adler-32 ORed into the words; "png_crc": the bytes copied to out and their CRC-32 XORed
+ * into the slot). A stream that does not fit leaves out untouched; one stream's failure leaves the others alone; nothing
+ * is written outside a stream's scratch share, out[0, capacity) and result slot; the same input gives the same bytes
+ * launch after launch. n == 0: PP_OK, nothing is launched. */
+int pp_png_deflate_batch(const pp_deflate_desc* descriptors, int n, long long max_len, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

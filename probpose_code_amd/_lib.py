@@ -179,6 +179,14 @@ SIGNATURES = {
     "pp_jpeg_scan_prepare_restart": (c_int, [_P, ctypes.c_size_t, _P]),
     "pp_jpeg_huffman_scratch_bytes": (c_longlong, [_P, _P, c_int]),
     "pp_jpeg_huffman_decode_batch": (c_int, [_P, c_int, c_longlong, c_longlong, c_int, _P]),
+    "pp_deflate_bound": (c_longlong, [c_longlong]),
+    "pp_png_encoded_bound": (c_longlong, [c_int, c_int]),
+    "pp_deflate_scratch_bytes": (c_longlong, [c_longlong]),
+    "pp_deflate_build_code": (c_int, [_P, _P]),
+    "pp_zlib_compress": (c_int, [_P, c_longlong, _P, ctypes.c_size_t, _P, _P]),
+    "pp_png_encode": (c_int, [_P, c_int, c_int, c_longlong, c_int, _P, ctypes.c_size_t, _P]),
+    "pp_png_tokens_batch": (c_int, [_P, c_int, c_int, c_longlong, _P]),
+    "pp_png_deflate_batch": (c_int, [_P, c_int, c_longlong, _P]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1,5 +1,5 @@
 // Shared host-side helpers of libprobpose_mi355x.so: status codes, thread-local error
-// string, launch checking, and the workgroup scan. gfx950 only -- no dual paths, no CUDA shims.
+// string, launch checking, and the workgroup scans. gfx950 only -- no dual paths, no CUDA shims.
 // (the device-side primitives of the kernels are in pp_device.h)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -78,6 +78,20 @@ __device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* lds, uint32
     }
     __syncthreads();  // (lds is free for the next call)
     return before + incl - v;
+}
+
+// One workgroup: out[i] <- the sum of in[0 .. i) over n entries, in[] read with a stride of `stride` words; returns the total.
+__device__ __forceinline__ unsigned long long scan_u32_to_u64(const uint32_t* in, int stride, long long n, unsigned long long* out, uint32_t* red) {
+    unsigned long long carry = 0;
+    for (long long base = 0; base < n; base += 256) {
+        const long long i = base + threadIdx.x;
+        const uint32_t v = i < n ? in[i * stride] : 0u;
+        uint32_t total;
+        const uint32_t before = block_scan(v, red, total);
+        if (i < n) out[i] = carry + before;
+        carry += total;
+    }
+    return carry;
 }
 
 }  // namespace pp

@@ -67,20 +67,6 @@ __global__ __launch_bounds__(256) void jpeg_ent_bits_kernel(const pp_jpeg_ent_de
     if (threadIdx.x == 0) reinterpret_cast<uint2*>(d.scratch + L.o_csum)[blockIdx.x] = make_uint2(total, any_bad);
 }
 
-// One workgroup: out[i] <- the sum of in[0 .. i) over n entries, in[] read with a stride of `stride` words; returns the total.
-__device__ __forceinline__ unsigned long long scan_u32_to_u64(const uint32_t* in, int stride, long long n, unsigned long long* out, uint32_t* red) {
-    unsigned long long carry = 0;
-    for (long long base = 0; base < n; base += 256) {
-        const long long i = base + threadIdx.x;
-        const uint32_t v = i < n ? in[i * stride] : 0u;
-        uint32_t total;
-        const uint32_t before = block_scan(v, red, total);
-        if (i < n) out[i] = carry + before;
-        carry += total;
-    }
-    return carry;
-}
-
 // blockIdx.x: image.
 __global__ __launch_bounds__(256) void jpeg_ent_scan_kernel(const pp_jpeg_ent_desc* __restrict__ descs) {
     __shared__ uint32_t red[4];

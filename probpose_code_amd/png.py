@@ -1,0 +1,258 @@
+"""PNG files written from the device: 8-bit truecolour (colour type 2), non-interlaced, one ``IDAT`` chunk, no ancillary
+chunk - the lossless counterpart of ``jpeg.encode_batch`` for the pictures the visualizer draws on the GPU.
+
+The format (csrc/pp_png_core.h states it in full). Every row takes, of the five PNG filters, the one with the smallest sum
+of ``min(b, 256 - b)`` over its filtered bytes, the lowest number on a tie. The filtered stream is cut into tiles of 4096
+bytes; a run of equal bytes inside a tile becomes a literal and matches of length 3..258 at distance 1 - the only LZ77
+matches this coder finds. The tokens of a picture are one dynamic deflate block under a Huffman code built from the
+picture's own histogram. Any decoder opens the files; they are not the bytes another encoder would write.
+
+``encode_batch`` runs the filters, the token histogram, the bit packing and both checksums on the device (csrc/pp_png.hip:
+three launches, then five). Between the two halves the host reads the histograms of the whole batch in one copy, builds
+each picture's code and header (``pp_deflate_build_code``) and uploads them in one copy: one synchronisation more than the
+JPEG coder needs. ``encode_host`` is the sequential form of the same core (``pp_png_encode``) and gives the same bytes.
+``zlib_compress_device`` is the deflate stage alone on raw byte strings. Opt-in: ``PoseLocalVisualizer(png_encoder="device")``,
+``--encode-png device`` of demo/image_demo.py.
+
+Not done: alpha, grey, palette, 16-bit and Adam7 pictures; LZ77 matches at distances other than 1 (a picture with repeated
+patterns, such as a drawn demo frame, comes out larger than from zlib); reading PNG files (inflate); building the Huffman
+code on the device.
+"""
+import ctypes
+import struct
+import zlib
+from typing import List, NamedTuple, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from .staging import BatchStaging, StagedBlock, _align
+
+host_calls = 0  # pp_png_encode / pp_zlib_compress calls since import
+tokens_calls = 0  # pp_png_tokens_batch calls since import
+deflate_calls = 0  # pp_png_deflate_batch calls since import
+
+# pp_deflate_desc: seven pointers, len, capacity, width, height, row_stride, rgb, crc_init, eight reserved bytes; pp_deflate_result
+_DESC = np.dtype([("pixels", "<u8"), ("data", "<u8"), ("hist", "<u8"), ("code", "<u8"), ("scratch", "<u8"), ("out", "<u8"), ("result", "<u8"),
+                  ("len", "<i8"), ("capacity", "<i8"), ("width", "<i4"), ("height", "<i4"), ("row_stride", "<i8"), ("rgb", "<i4"),
+                  ("crc_init", "<u4"), ("reserved", "<i8")])
+assert _DESC.itemsize == 104
+_RESULT = np.dtype([("bytes", "<i8"), ("status", "<i4"), ("crc", "<u4")])
+assert _RESULT.itemsize == 16
+HIST_BYTES = 4 * 288
+CODE_BYTES = 1472  # sizeof(pp_deflate_code)
+LAUNCHES_TOKENS = ("png_filter", "png_clear", "png_hist")  # pp_launch_count tags of pp_png_tokens_batch (png_filter: pictures only)
+LAUNCHES_DEFLATE = ("png_bits", "png_scan", "png_zero", "png_pack", "png_crc")  # ... of pp_png_deflate_batch
+_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+_IDAT_REGISTER = ~zlib.crc32(b"IDAT") & 0xFFFFFFFF  # the CRC-32 register in front of the stream's first byte
+
+
+def _check_order(channel_order) -> int:
+    if channel_order not in ("bgr", "rgb"):
+        raise ValueError(f"channel_order must be 'bgr' or 'rgb', got {channel_order!r}")
+    return int(channel_order == "rgb")
+
+
+def _check_picture(im) -> None:
+    """ValueError for anything but an (H, W, 3) uint8 array or tensor that one file holds."""
+    if not isinstance(im, (np.ndarray, torch.Tensor)):
+        raise ValueError(f"the encoder takes (H, W, 3) uint8 images, got {type(im).__name__}")
+    if im.dtype != (np.uint8 if isinstance(im, np.ndarray) else torch.uint8) or len(im.shape) != 3 or im.shape[2] != 3:
+        raise ValueError(f"the encoder takes (H, W, 3) uint8 images, got {tuple(im.shape)} {im.dtype}")
+    if im.shape[0] == 0 or im.shape[1] == 0:
+        raise ValueError("empty image")
+    if im.shape[0] > 65535 or im.shape[1] > 65535:
+        raise ValueError(f"this writer holds at most 65535 pixels a side, got {im.shape[1]} x {im.shape[0]}")
+    if _lib.lib.pp_png_encoded_bound(int(im.shape[1]), int(im.shape[0])) < 0:
+        raise ValueError(f"a {im.shape[1]} x {im.shape[0]} picture needs a stream of 2^31 bytes or more")
+
+
+def _chunk(kind: bytes, data: bytes) -> bytes:
+    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+
+def _frame(width: int, height: int, stream: bytes, register: int) -> bytes:
+    """The file around a zlib stream; ``register``: the CRC-32 register behind "IDAT" and the stream (pp_deflate_result.crc)."""
+    return (_SIGNATURE + _chunk(b"IHDR", struct.pack(">II5B", width, height, 8, 2, 0, 0, 0)) + struct.pack(">I", len(stream)) + b"IDAT" + stream
+            + struct.pack(">I", ~register & 0xFFFFFFFF) + _chunk(b"IEND", b""))
+
+
+def encode_host(image, channel_order: str = "bgr") -> bytes:
+    """The PNG file of one (H, W, 3) uint8 picture, written on the host by the sequential form of the core the kernels run
+    (``pp_png_encode``): the bytes ``encode_batch`` gives. No GPU is used."""
+    global host_calls
+    rgb = _check_order(channel_order)
+    _check_picture(image)
+    px = np.ascontiguousarray(image.cpu().numpy() if isinstance(image, torch.Tensor) else image)
+    h, w = px.shape[:2]
+    out = np.empty(int(_lib.lib.pp_png_encoded_bound(w, h)), np.uint8)
+    size = ctypes.c_size_t(0)
+    _lib.call("pp_png_encode", px.ctypes.data, w, h, 3 * w, rgb, out.ctypes.data, out.size, ctypes.byref(size))
+    host_calls += 1
+    return out[:size.value].tobytes()
+
+
+def _raw(buffer) -> np.ndarray:
+    raw = np.frombuffer(bytes(buffer), np.uint8) if isinstance(buffer, (bytes, bytearray, memoryview)) else buffer
+    if not isinstance(raw, np.ndarray) or raw.dtype != np.uint8 or raw.ndim != 1:
+        raise ValueError("the deflate stage takes bytes or one-dimensional uint8 arrays")
+    if raw.size == 0 or _lib.lib.pp_deflate_bound(raw.size) < 0:
+        raise ValueError(f"the deflate stage takes streams of 1 .. 2^31 - 1 bytes whose bound stays below 2^31, got {raw.size}")
+    return np.ascontiguousarray(raw)
+
+
+def zlib_compress_host(buffer, return_tokens: bool = False):
+    """The zlib stream of a byte string by the host form of the deflate stage (``pp_zlib_compress``); with ``return_tokens``
+    also the number of literals and matches in it."""
+    global host_calls
+    raw = _raw(buffer)
+    out = np.empty(int(_lib.lib.pp_deflate_bound(raw.size)), np.uint8)
+    size, tokens = ctypes.c_size_t(0), ctypes.c_longlong(0)
+    _lib.call("pp_zlib_compress", raw.ctypes.data, raw.size, out.ctypes.data, out.size, ctypes.byref(size), ctypes.byref(tokens))
+    host_calls += 1
+    data = out[:size.value].tobytes()
+    return (data, int(tokens.value)) if return_tokens else data
+
+
+def _size(query: str, value) -> int:
+    if value < 0:
+        raise _lib.ProbPoseLibraryError(query, _lib.lib.pp_status_string(int(value)).decode(), _lib.last_error())
+    return int(value)
+
+
+class _Job(NamedTuple):
+    """One batch on the device: ``block`` (the uploaded ``StagedBlock``: descriptors, result slots, histograms, codes, raw
+    streams), ``lens`` (the stream lengths), ``max_height`` (0 for raw streams), the zlib streams (``out``: stream i's at
+    ``o_out[i]``, ``capacity[i]`` bytes) and ``keep`` (the other tensors the launches use)."""
+
+    block: StagedBlock
+    lens: list
+    max_height: int
+    out: torch.Tensor
+    o_out: list
+    capacity: list
+    keep: tuple
+
+
+def _stage(pictures, raws, rgb: int, dev, staging) -> _Job:
+    """Allocate the buffers of a batch of pictures (device tensors with dense pixel rows) or of raw streams (uint8 arrays),
+    fill the descriptor table and upload it - with the raw streams - in one copy."""
+    n = len(pictures) if pictures is not None else len(raws)
+    lens = [im.shape[0] * (1 + 3 * im.shape[1]) for im in pictures] if pictures is not None else [int(r.size) for r in raws]
+    shares = [_size("pp_deflate_scratch_bytes", _lib.lib.pp_deflate_scratch_bytes(ln)) for ln in lens]
+    capacity = [_align(_size("pp_deflate_bound", _lib.lib.pp_deflate_bound(ln))) for ln in lens]
+    # the block: descriptors (n x 104 bytes) | result slots (n x 16) | histograms (n x 288 u32, written on the device, read
+    # back in one copy) | codes (n x pp_deflate_code, uploaded in one copy once they are built) | per raw stream: its bytes
+    blk = StagedBlock([("desc", 104 * n), ("results", 16 * n), ("hist", HIST_BYTES * n), ("code", CODE_BYTES * n)],
+                      [("data", [0] * n if pictures is not None else lens)])
+    scratch = torch.empty(sum(shares), dtype=torch.uint8, device=dev)
+    out = torch.empty(sum(capacity), dtype=torch.uint8, device=dev)
+    filtered = torch.empty(sum(_align(ln) for ln in lens), dtype=torch.uint8, device=dev) if pictures is not None else None
+    blk.acquire(staging, dev)
+    rows, p_results, p_hist, p_code, p_data = blk.host("desc", _DESC), blk.ptr("results"), blk.ptr("hist"), blk.ptr("code"), blk.ptrs("data")
+    blk.host("results")[:] = 0
+    s_at, o_at, f_at, o_out = scratch.data_ptr(), 0, (filtered.data_ptr() if pictures is not None else 0), []
+    for i in range(n):
+        if pictures is not None:
+            im = pictures[i]
+            pixels, data, w, h, stride = im.data_ptr(), f_at, im.shape[1], im.shape[0], im.stride(0)
+            f_at += _align(lens[i])
+        else:
+            blk.hosts("data")[i][:] = raws[i]
+            pixels, data, w, h, stride = 0, p_data[i], 0, 0, 0
+        rows[i] = (pixels, data, p_hist + HIST_BYTES * i, p_code + CODE_BYTES * i, s_at, out.data_ptr() + o_at, p_results + 16 * i, lens[i],
+                   capacity[i], w, h, stride, rgb, _IDAT_REGISTER, 0)
+        o_out.append(o_at)
+        s_at += shares[i]
+        o_at += capacity[i]
+    blk.upload()
+    return _Job(blk, lens, max(im.shape[0] for im in pictures) if pictures is not None else 0, out, o_out, capacity, (pictures, scratch, filtered))
+
+
+def _launch_tokens(job: _Job, stream) -> None:
+    global tokens_calls
+    _lib.call("pp_png_tokens_batch", job.block.base, len(job.lens), job.max_height, max(job.lens), stream.cuda_stream)
+    tokens_calls += 1
+
+
+def _launch_deflate(job: _Job, stream) -> None:
+    global deflate_calls
+    _lib.call("pp_png_deflate_batch", job.block.base, len(job.lens), max(job.lens), stream.cuda_stream)
+    deflate_calls += 1
+
+
+def _run(job: _Job) -> list:
+    """Both halves of a staged batch on the current stream and the code build between them: (zlib stream, CRC-32 register)
+    per entry."""
+    blk, n = job.block, len(job.lens)
+    staging, stream = blk.staging, torch.cuda.current_stream(blk.dev.device)
+    _launch_tokens(job, stream)
+    # the histograms down (one copy, one synchronisation), the codes built in the pinned buffer, the codes up (one copy)
+    o_h, o_c = blk.offset["hist"], blk.offset["code"]
+    staging.buf[o_h:o_h + HIST_BYTES * n].copy_(blk.dev[o_h:o_h + HIST_BYTES * n], non_blocking=True)
+    stream.synchronize()
+    hist, code = blk.host("hist").ctypes.data, blk.host("code").ctypes.data
+    for i in range(n):
+        _lib.call("pp_deflate_build_code", hist + HIST_BYTES * i, code + CODE_BYTES * i)
+    blk.dev[o_c:o_c + CODE_BYTES * n].copy_(staging.buf[o_c:o_c + CODE_BYTES * n], non_blocking=True)
+    staging.ev.record(stream)  # (the next user of the pinned buffer waits for this copy)
+    _launch_deflate(job, stream)
+    res = blk.device("results").cpu().numpy().view(_RESULT)  # (waits for the stream: the launches have run)
+    for i, r in enumerate(res):
+        if int(r["status"]) != _lib.PP_OK:
+            raise _lib.ProbPoseLibraryError("pp_png_deflate_batch", _lib.lib.pp_status_string(int(r["status"])).decode(),
+                                            f"stream {i}: it needs {int(r['bytes'])} bytes, {job.capacity[i]} were given")
+    sizes = [int(r["bytes"]) for r in res]
+    at, offs = 0, []
+    for sz in sizes:
+        offs.append(at)
+        at += _align(sz)
+    pinned = staging.acquire(max(at, 1))
+    for o, sz, oo in zip(offs, sizes, job.o_out):
+        staging.buf[o:o + sz].copy_(job.out[oo:oo + sz], non_blocking=True)
+    stream.synchronize()
+    return [(pinned[o:o + sz].tobytes(), int(r["crc"])) for o, sz, r in zip(offs, sizes, res)]
+
+
+def encode_batch(images: Sequence, channel_order: str = "bgr", device=None, staging=None) -> List[bytes]:
+    """PNG files of a batch of (H, W, 3) uint8 pictures (device tensors; a host array is uploaded first) of any mix of sizes,
+    ``channel_order`` "bgr" or "rgb" in memory. Filters, tokens, bit packing and checksums run on the device: a batch of n
+    pictures costs one upload (descriptors), the histogram round trip (one download, the codes built on the host, one
+    upload), then 1 + n downloads (the result slots, then the used bytes of each stream) - three synchronisations - and
+    eight launches whatever n is. The files are byte for byte those of ``encode_host``."""
+    from .jpeg import _encoder_images
+
+    rgb = _check_order(channel_order)
+    if isinstance(images, (torch.Tensor, np.ndarray)):
+        raise ValueError("encode_batch takes a sequence of (H, W, 3) images; imwrite_device takes one")
+    images = list(images)
+    for im in images:
+        _check_picture(im)
+    if len(images) == 0:
+        return []
+    images, dev = _encoder_images(images, device)
+    streams = _run(_stage(images, None, rgb, dev, staging if staging is not None else BatchStaging()))
+    return [_frame(im.shape[1], im.shape[0], z, register) for im, (z, register) in zip(images, streams)]
+
+
+def zlib_compress_device(buffers: Sequence, device=None, staging=None) -> List[bytes]:
+    """The deflate stage alone: the zlib streams of a batch of byte strings (bytes or one-dimensional uint8 arrays of at
+    least one byte), coded on the device in seven launches - the streams ``zlib_compress_host`` gives, which
+    ``zlib.decompress`` turns back into the input."""
+    from .jpeg import _cuda_device
+
+    if isinstance(buffers, (bytes, bytearray, memoryview, np.ndarray)):
+        raise ValueError("zlib_compress_device takes a sequence of byte strings")
+    raws = [_raw(b) for b in buffers]
+    if len(raws) == 0:
+        return []
+    dev = _cuda_device(device or "cuda", "zlib_compress_device")
+    return [z for z, _ in _run(_stage(None, raws, 0, dev, staging if staging is not None else BatchStaging()))]
+
+
+def imwrite_device(path: str, image, **kw) -> None:
+    """One picture written as a PNG file by ``encode_batch`` (its keyword arguments)."""
+    data = encode_batch([image], **kw)[0]
+    with open(path, "wb") as f:
+        f.write(data)

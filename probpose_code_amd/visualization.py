@@ -171,10 +171,13 @@ class PoseLocalVisualizer:
     "mmpose" skeleton style, their boxes, and (``draw_heatmap``) the probability areas of the posterior maps on the padded
     canvas, stacked under the pose panel. Everything is drawn on the GPU; ``add_datasample`` copies the image back once."""
 
-    def __init__(self, name="visualizer", radius=3, line_width=1, alpha=0.8, device="cuda:0", image_encoder="host"):
+    def __init__(self, name="visualizer", radius=3, line_width=1, alpha=0.8, device="cuda:0", image_encoder="host", png_encoder="host"):
         if image_encoder not in ("host", "device"):
             raise ValueError(f"image_encoder must be 'host' or 'device', got {image_encoder!r}")
+        if png_encoder not in ("host", "device"):
+            raise ValueError(f"png_encoder must be 'host' or 'device', got {png_encoder!r}")
         self.image_encoder = image_encoder  # "device": a .jpg / .jpeg out_file is written by jpeg.imwrite_device
+        self.png_encoder = png_encoder  # "device": a .png out_file is written by png.imwrite_device
         self.name = name
         self.radius = radius
         self.line_width = line_width
@@ -249,8 +252,9 @@ class PoseLocalVisualizer:
         the (H, W, 3) pose panel, or with ``draw_heatmap`` (and heatmaps in ``pred_fields``) the (2H, W, 3) stack of the pose
         panel over the probability areas resized to (H, W) (:796-865); ``out_file`` is written with Pillow - or, for a visualizer
         built with ``image_encoder="device"`` and a ``.jpg`` / ``.jpeg`` name, by the split JPEG encoder from the frame on the
-        device (Pillow's default quality 75 and 4:2:0: a file that decodes to the same pixels). ``draw_datasample`` plus the
-        copy to the host and the file."""
+        device (Pillow's default quality 75 and 4:2:0: a file that decodes to the same pixels); with ``png_encoder="device"`` a
+        ``.png`` name is written by the device PNG writer (``png.imwrite_device``: the same pixels, other bytes than Pillow's).
+        ``draw_datasample`` plus the copy to the host and the file."""
         if draw_gt:
             raise NotImplementedError("draw_gt: ground-truth drawing is outside ProbPose's demo")
         if show_kpt_idx:
@@ -266,6 +270,10 @@ class PoseLocalVisualizer:
                 from . import jpeg
 
                 jpeg.imwrite_device(out_file, out, quality=75, subsampling="4:2:0", channel_order="rgb")
+            elif self.png_encoder == "device" and str(out_file).lower().endswith(".png"):
+                from . import png
+
+                png.imwrite_device(out_file, out, channel_order="rgb")
             else:
                 from PIL import Image
 

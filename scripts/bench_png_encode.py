@@ -1,0 +1,128 @@
+"""Times and file sizes of the device PNG writer beside what writes a ``.png`` without it, on seeded photo-like frames (smooth
+fields, blobs, mild noise) of 640x480 and 1920x1080 and on one drawn demo frame, all lying on the device as a renderer
+leaves them, in ONE run with the paths alternated:
+
+    (a) host_png       device-to-host copy of the frames + Pillow ``save`` as PNG at its default level (the path without the switch)
+    (b) host_png_l1    the same with ``compress_level=1``
+    (c) device         png.encode_batch: eight launches, the histogram round trip, the used bytes of each stream
+
+for n = 1 and n = 16 frames per call (the host paths at 1 and 8 threads), in ms per call (median of --rounds alternations;
+all end with the file bytes in host memory); the file sizes of the three; then the eight launches alone (both C calls, the
+codes of an earlier run in place) in device-event time, with the shader clock read right behind the timed launches. One JSON
+line per figure.
+
+    python scripts/bench_png_encode.py [--rounds 7]"""
+import argparse
+import io
+import json
+import os
+import statistics
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from scripts.bench_jpeg_decode import photo_like  # noqa: E402
+from scripts.bench_jpeg_encode import shader_clock  # noqa: E402
+
+
+def drawn_demo_frame(dev):
+    """The demo picture with two seeded poses drawn on it by the visualizer: (H, W, 3) uint8 RGB on the host."""
+    from PIL import Image
+
+    from probpose_code_amd.structures import InstanceData, PoseDataSample
+    from probpose_code_amd.visualization import PoseLocalVisualizer
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with Image.open(os.path.join(root, "demo", "resources", "synthetic_person.png")) as im:
+        rgb = np.asarray(im.convert("RGB"), dtype=np.uint8).copy()
+    H, W = rgb.shape[:2]
+    rng = np.random.default_rng(3)
+    ds = PoseDataSample()
+    ds.pred_instances = InstanceData(keypoints=(rng.random((2, 17, 2)) * [W, H]).astype(np.float32), keypoints_visible=np.ones((2, 17), np.float32),
+                                     bboxes=np.array([[10, 10, W * 0.6, H * 0.9], [W * 0.3, 20, W - 10, H - 10]], np.float32))
+    return PoseLocalVisualizer(device=str(dev)).draw_datasample(rgb, ds).cpu().numpy()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    args = ap.parse_args()
+
+    import torch
+    from PIL import Image
+
+    from probpose_code_amd import png
+    from probpose_code_amd.transforms import BatchStaging
+
+    dev = torch.device("cuda:0")
+    staging = BatchStaging()
+
+    def pil_save(arr, level):
+        b = io.BytesIO()
+        Image.fromarray(arr).save(b, "PNG", **({} if level is None else dict(compress_level=level)))
+        return b.getvalue()
+
+    sets = []
+    for W, H in ((640, 480), (1920, 1080)):
+        rng = np.random.default_rng(W)
+        sets.append((f"{W}x{H}", [photo_like(rng, H, W) for _ in range(4)]))
+    demo = drawn_demo_frame(dev)
+    sets.append((f"demo {demo.shape[1]}x{demo.shape[0]}", [demo]))
+    for size, host_frames in sets:
+        frames = [torch.from_numpy(host_frames[k % len(host_frames)]).to(dev) for k in range(16)]
+        ours = png.encode_batch(frames[:1], channel_order="rgb", staging=staging)[0]
+        with Image.open(io.BytesIO(ours)) as a:
+            assert np.array_equal(np.asarray(a), host_frames[0]), "the file does not hold the pixels"
+        default, level1 = len(pil_save(host_frames[0], None)), len(pil_save(host_frames[0], 1))
+        print(json.dumps(dict(figure="file", size=size, device_file_bytes=len(ours), pillow_default_bytes=default, pillow_level1_bytes=level1,
+                              raw_bytes=int(host_frames[0].size), over_default=round(len(ours) / default, 3), over_level1=round(len(ours) / level1, 3))),
+              flush=True)
+        for n in (1, 16):
+            for threads in ((1,) if n == 1 else (1, 8)):
+                with ThreadPoolExecutor(max_workers=threads) as pool:
+                    paths = {
+                        "host_png": lambda: list(pool.map(lambda a: pil_save(a, None), [f.cpu().numpy() for f in frames[:n]])),
+                        "host_png_l1": lambda: list(pool.map(lambda a: pil_save(a, 1), [f.cpu().numpy() for f in frames[:n]])),
+                        "device": lambda: png.encode_batch(frames[:n], channel_order="rgb", staging=staging),
+                    }
+                    times = {k: [] for k in paths}
+                    for fn in paths.values():
+                        fn()  # warm-up
+                    for _ in range(args.rounds):
+                        for name, fn in paths.items():
+                            torch.cuda.synchronize()
+                            t0 = time.perf_counter()
+                            fn()
+                            torch.cuda.synchronize()
+                            times[name].append(time.perf_counter() - t0)
+                for name, ts in times.items():
+                    print(json.dumps(dict(figure="write_call", size=size, path=name, n=n, threads=threads, ms=round(statistics.median(ts) * 1e3, 3),
+                                          min_ms=round(min(ts) * 1e3, 3), max_ms=round(max(ts) * 1e3, 3), rounds=args.rounds)), flush=True)
+        for n in (1, 16):
+            job = png._stage(frames[:n], None, 1, dev, staging)
+            png._run(job)  # (leaves the codes of these frames on the device: the timed launches below need no host in between)
+            stream = torch.cuda.current_stream(dev)
+            us = {"both": [], "tokens": [], "deflate": []}
+            for _ in range(3 + args.rounds):
+                e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                e[0].record()
+                png._launch_tokens(job, stream)
+                e[1].record()
+                png._launch_deflate(job, stream)
+                e[2].record()
+                e[2].synchronize()
+                us["tokens"].append(e[0].elapsed_time(e[1]) * 1e3)
+                us["deflate"].append(e[1].elapsed_time(e[2]) * 1e3)
+                us["both"].append(e[0].elapsed_time(e[2]) * 1e3)
+            sclk = shader_clock()  # right behind the timed launches
+            print(json.dumps(dict(figure="launches", size=size, n=n, device_event_us=round(statistics.median(us["both"][3:]), 1),
+                                  tokens_us=round(statistics.median(us["tokens"][3:]), 1), deflate_us=round(statistics.median(us["deflate"][3:]), 1),
+                                  min_us=round(min(us["both"][3:]), 1), stream_bytes=int(sum(job.lens)), sclk_mhz=sclk, rounds=args.rounds)), flush=True)
+            del job
+
+
+if __name__ == "__main__":
+    main()
