@@ -17,9 +17,12 @@
 //     v_mfma_f32_16x16x4_f32); softmax statistics are fp32 in both;
 //   * blockIdx is remapped so that the heads of one crop (adjacent columns of the same qkv
 //     rows) land on the same XCD / L2.
-#include "pp_common.h"
-#include "pp_device.h"
-#include "pp_split.h"
+//
+// The steps the forms share - block id, MFMA overloads, Q loads, the softmax row and its exp-and-sum step, the packing of P and the bf16
+// P V step, the bf16 / fp32 store, the launch - are pp_attention_core.h. Spelled out here because, shared as an inlined helper, each moved
+// the generated code of its kernel (scripts/gfx950_isa.py): the K / V^T staging loops, the Q loads of the rolled loops of the two
+// stream kernels, and the V^T reads + split_mma of the split-fp16 P V.
+#include "pp_attention_core.h"
 
 namespace pp {
 
@@ -27,9 +30,6 @@ constexpr int ATT_THREADS = 256;
 #ifndef ATT_ABL  // dev (scripts/micro/att_ablate.sh): 1 no V transpose, 2 no math, 3 no K / V loads - timing only, wrong results
 #define ATT_ABL 0
 #endif
-
-__device__ __forceinline__ f32x4 att_mma(const u32x4& a, const u32x4& b, f32x4 c, __bf16) { return mma_bf16(a, b, c); }
-__device__ __forceinline__ f32x4 att_mma(const u32x4& a, const u32x4& b, f32x4 c, float) { return mma_f32(a, b, c); }
 
 template <typename T, int HD, int NT>
 struct AttCfg {
@@ -61,10 +61,7 @@ __global__ __launch_bounds__(ATT_THREADS, (NT <= 12 ? 3 : 1)) void attention_ker
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fr = lane & 15, fg = lane >> 4;
 
-    // XCD-aware remap: hardware round-robins consecutive block ids over the 8 XCDs
-    int id = blockIdx.x;
-    const int nblk = gridDim.x;
-    if ((nblk & 7) == 0) id = (id & 7) * (nblk >> 3) + (id >> 3);
+    const int id = att::xcd_block_id();
     const int seq = id / heads, head = id - seq * heads;
     const int E = heads * HD;
     const size_t row_stride = (size_t)3 * E;
@@ -77,8 +74,7 @@ __global__ __launch_bounds__(ATT_THREADS, (NT <= 12 ? 3 : 1)) void attention_ker
     for (int t = 0; t < QPW; ++t) {
         const int qt = wave + t * (ATT_THREADS / 64);
         const T* qrow = base + (size_t)((qt < NT ? qt : 0) * 16 + fr) * row_stride;
-#pragma unroll
-        for (int g = 0; g < C::NG; ++g) qf_all[t][g] = *reinterpret_cast<const u32x4*>(qrow + (g * 4 + fg) * C::CH);
+        att::load_q<C::CH>(qf_all[t], qrow, fg);
     }
 
     // ---- stage K (row-major, swizzled) and V (transposed); zero the padded key rows
@@ -123,31 +119,12 @@ __global__ __launch_bounds__(ATT_THREADS, (NT <= 12 ? 3 : 1)) void attention_ker
             for (int g = 0; g < C::NG; ++g) {
                 const int r = kt * 16 + fr;
                 const u32x4 kf = *reinterpret_cast<const u32x4*>(Ks + ((size_t)r * C::RC + kswz<C::RC>(r, g * 4 + fg)) * 16);
-                acc = att_mma(kf, qf[g], acc, T{});
+                acc = att::mma(kf, qf[g], acc, T{});
             }
             s[kt] = acc;
         }
         // ---- softmax over the 16 NT keys of this lane's query (fp32)
-        float mx = -__builtin_inff();
-#pragma unroll
-        for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) mx = fmaxf(mx, s[kt][i]);
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float mb = mx * scale_log2e;
-        float sum = 0.f;
-#pragma unroll
-        for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][i], scale_log2e, -mb));  // arg <= 0: raw v_exp_f32
-                s[kt][i] = p;
-                sum += p;
-            }
-        sum += __shfl_xor(sum, 16);
-        sum += __shfl_xor(sum, 32);
-        if (C::NTP > NT) s[C::NTP - 1] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const float sum = att::softmax_row<NT>(s, scale_log2e);  // (the padded tile's fragment: zeros)
 
         // ---- O^T = V^T P^T
         f32x4 o[C::DT];
@@ -156,17 +133,9 @@ __global__ __launch_bounds__(ATT_THREADS, (NT <= 12 ? 3 : 1)) void attention_ker
         if constexpr (sizeof(T) == 2) {
 #pragma unroll
             for (int blk = 0; blk < C::NTP / 2; ++blk) {
-                const f32x4 p0 = s[2 * blk], p1 = s[2 * blk + 1];
-                const bf16x8 pf = {(__bf16)p0[0], (__bf16)p0[1], (__bf16)p0[2], (__bf16)p0[3],
-                                   (__bf16)p1[0], (__bf16)p1[1], (__bf16)p1[2], (__bf16)p1[3]};
+                const bf16x8 pf = att::pack_p(s[2 * blk], s[2 * blk + 1]);
 #pragma unroll
-                for (int dt = 0; dt < C::DT; ++dt) {
-                    const T* vrow = Vt + (dt * 16 + fr) * C::SPV + blk * 32 + 4 * fg;
-                    const u32x2 lo = *reinterpret_cast<const u32x2*>(vrow);
-                    const u32x2 hi = *reinterpret_cast<const u32x2*>(vrow + 16);
-                    const u32x4 vf = {lo[0], lo[1], hi[0], hi[1]};
-                    o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vf), pf, o[dt], 0, 0, 0);
-                }
+                for (int dt = 0; dt < C::DT; ++dt) o[dt] = att::pv_mma(Vt + (dt * 16 + fr) * C::SPV + blk * 32 + 4 * fg, pf, o[dt]);
             }
         } else {
 #pragma unroll
@@ -175,7 +144,7 @@ __global__ __launch_bounds__(ATT_THREADS, (NT <= 12 ? 3 : 1)) void attention_ker
 #pragma unroll
                 for (int dt = 0; dt < C::DT; ++dt) {
                     const u32x4 vf = *reinterpret_cast<const u32x4*>(Vt + (dt * 16 + fr) * C::SPV + kt * 16 + 4 * fg);
-                    o[dt] = att_mma(vf, pf, o[dt], T{});
+                    o[dt] = att::mma(vf, pf, o[dt], T{});
                 }
             }
         }
@@ -183,15 +152,7 @@ __global__ __launch_bounds__(ATT_THREADS, (NT <= 12 ? 3 : 1)) void attention_ker
         const float inv = 1.0f / sum;
         T* orow = out + ((size_t)seq * C::S + qt * 16 + fr) * E + head * HD;
 #pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt) {
-            const f32x4 v = o[dt] * inv;
-            if constexpr (sizeof(T) == 2) {
-                const bf16x4 ov = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                *reinterpret_cast<bf16x4*>(orow + dt * 16 + 4 * fg) = ov;
-            } else {
-                *reinterpret_cast<f32x4*>(orow + dt * 16 + 4 * fg) = v;
-            }
-        }
+        for (int dt = 0; dt < C::DT; ++dt) att::store4(orow + dt * 16 + 4 * fg, o[dt] * inv);
     }
 }
 
@@ -213,10 +174,7 @@ __global__ __launch_bounds__(THREADS, 1) void attention_stream_kernel(const T* _
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fr = lane & 15, fg = lane >> 4;
 
-    // XCD-aware remap: hardware round-robins consecutive block ids over the 8 XCDs
-    int id = blockIdx.x;
-    const int nblk = gridDim.x;
-    if ((nblk & 7) == 0) id = (id & 7) * (nblk >> 3) + (id >> 3);
+    const int id = att::xcd_block_id();
     const int seq = id / heads, head = id - seq * heads;
     const int E = heads * HD;
     const size_t row_stride = (size_t)3 * E;
@@ -232,8 +190,7 @@ __global__ __launch_bounds__(THREADS, 1) void attention_stream_kernel(const T* _
         for (int t = 0; t < QPW; ++t) {
             const int qt = wave + t * (THREADS / 64);
             const T* qrow = base + (size_t)((qt < NT ? qt : 0) * 16 + fr) * row_stride;
-#pragma unroll
-            for (int g = 0; g < C::NG; ++g) qf_all[t][g] = *reinterpret_cast<const u32x4*>(qrow + (g * 4 + fg) * C::CH);
+            att::load_q<C::CH>(qf_all[t], qrow, fg);
         }
     }
 
@@ -278,7 +235,7 @@ __global__ __launch_bounds__(THREADS, 1) void attention_stream_kernel(const T* _
                 for (int g = 0; g < C::NG; ++g) {
                     const int r = (blk0 + kt) * 16 + fr;
                     const u32x4 kf = *reinterpret_cast<const u32x4*>(Ks + ((size_t)r * C::RC + kswz<C::RC>(r, g * 4 + fg)) * 16);
-                    acc = att_mma(kf, qf[g], acc, T{});
+                    acc = att::mma(kf, qf[g], acc, T{});
                 }
                 s[kt] = acc;
             }
@@ -309,12 +266,7 @@ __global__ __launch_bounds__(THREADS, 1) void attention_stream_kernel(const T* _
                     s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};  // padded keys weigh nothing
                     continue;
                 }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][i], scale_log2e, -mb));  // arg <= 0: raw v_exp_f32
-                    s[kt][i] = p;
-                    sum += p;
-                }
+                att::exp_sum(s[kt], scale_log2e, mb, sum);
             }
             l_run += sum;  // (this lane's keys only; the lanes of a query are added up once, at the end)
 
@@ -326,19 +278,10 @@ __global__ __launch_bounds__(THREADS, 1) void attention_stream_kernel(const T* _
             if constexpr (sizeof(T) == 2) {
 #pragma unroll
                 for (int b2 = 0; b2 < KB / 2; ++b2) {
-                    const int blk = blk0 / 2 + b2;
-                    const f32x4 p0 = s[2 * b2], p1 = s[2 * b2 + 1];
-                    const bf16x8 pf = {(__bf16)p0[0], (__bf16)p0[1], (__bf16)p0[2], (__bf16)p0[3],
-                                       (__bf16)p1[0], (__bf16)p1[1], (__bf16)p1[2], (__bf16)p1[3]};
+                const bf16x8 pf = att::pack_p(s[2 * b2], s[2 * b2 + 1]);
 #pragma unroll
-                    for (int dt = 0; dt < C::DT; ++dt) {
-                        const T* vrow = Vt + (dt * 16 + fr) * C::SPV + blk * 32 + 4 * fg;
-                        const u32x2 lo = *reinterpret_cast<const u32x2*>(vrow);
-                        const u32x2 hi = *reinterpret_cast<const u32x2*>(vrow + 16);
-                        const u32x4 vf = {lo[0], lo[1], hi[0], hi[1]};
-                        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vf), pf, o[dt], 0, 0, 0);
-                    }
-                }
+                for (int dt = 0; dt < C::DT; ++dt) o[dt] = att::pv_mma(Vt + (dt * 16 + fr) * C::SPV + (blk0 / 2 + b2) * 32 + 4 * fg, pf, o[dt]);
+            }
             } else {
 #pragma unroll
                 for (int kt = 0; kt < KB; ++kt) {
@@ -347,28 +290,19 @@ __global__ __launch_bounds__(THREADS, 1) void attention_stream_kernel(const T* _
 #pragma unroll
                     for (int dt = 0; dt < C::DT; ++dt) {
                         const u32x4 vf = *reinterpret_cast<const u32x4*>(Vt + (dt * 16 + fr) * C::SPV + (blk0 + kt) * 16 + 4 * fg);
-                        o[dt] = att_mma(vf, pf, o[dt], T{});
+                        o[dt] = att::mma(vf, pf, o[dt], T{});
                     }
                 }
             }
             if (NBLK > 1) __builtin_amdgcn_sched_barrier(0);  // keep the next block's scores from being hoisted up here (registers)
         }
-        float sum = l_run;
-        sum += __shfl_xor(sum, 16);
-        sum += __shfl_xor(sum, 32);
         // ---- normalise and store: lane holds d = 16 dt + 4 fg + (0..3) of query 16 qt + fr
+        float sum = l_run;
+        att::quad_sum(sum);
         const float inv = 1.0f / sum;
         T* orow = out + ((size_t)seq * C::S + qt * 16 + fr) * E + head * HD;
 #pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt) {
-            const f32x4 v = o[dt] * inv;
-            if constexpr (sizeof(T) == 2) {
-                const bf16x4 ov = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                *reinterpret_cast<bf16x4*>(orow + dt * 16 + 4 * fg) = ov;
-            } else {
-                *reinterpret_cast<f32x4*>(orow + dt * 16 + 4 * fg) = v;
-            }
-        }
+        for (int dt = 0; dt < C::DT; ++dt) att::store4(orow + dt * 16 + 4 * fg, o[dt] * inv);
     };
     if (QPRE) {
 #pragma unroll
@@ -382,7 +316,7 @@ __global__ __launch_bounds__(THREADS, 1) void attention_stream_kernel(const T* _
         for (int qt = wave; qt < NT; qt += THREADS / 64) {
             const T* qrow = base + (size_t)(qt * 16 + fr) * row_stride;
 #pragma unroll
-            for (int g = 0; g < C::NG; ++g) qf_all[0][g] = *reinterpret_cast<const u32x4*>(qrow + (g * 4 + fg) * C::CH);
+            for (int g = 0; g < C::NG; ++g) qf_all[0][g] = *reinterpret_cast<const u32x4*>(qrow + (g * 4 + fg) * C::CH);  // (att::load_q, spelled out)
             one_tile(qt, qf_all[0]);
         }
     }
@@ -395,20 +329,12 @@ static int launch_attention(const void* qkv, void* out, int n_seq, int heads, fl
     if constexpr (NT > 12) {
         constexpr int THREADS = 2 * ATT_THREADS;
         constexpr int KB = sizeof(T) == 2 ? C::NTP / 2 : 4;  // 432 tokens: two softmax blocks of 14 key tiles (fp32: seven of 4)
-        auto kern = attention_stream_kernel<T, HD, NT, THREADS, KB>;
-        PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)C::LDS));
-        hipLaunchKernelGGL(kern, dim3(n_seq * heads), dim3(THREADS), C::LDS, s, reinterpret_cast<const T*>(qkv),
-                           reinterpret_cast<T*>(out), n_seq, heads, scale * 1.44269504088896340736f);
+        return att::launch_with_lds(attention_stream_kernel<T, HD, NT, THREADS, KB>, dim3(n_seq * heads), dim3(THREADS), C::LDS, s,
+                                    reinterpret_cast<const T*>(qkv), reinterpret_cast<T*>(out), n_seq, heads, scale * att::kLog2e);
     } else {
-        auto kern = attention_kernel<T, HD, NT>;
-        PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)C::LDS));
-        hipLaunchKernelGGL(kern, dim3(n_seq * heads), dim3(ATT_THREADS), C::LDS, s, reinterpret_cast<const T*>(qkv),
-                           reinterpret_cast<T*>(out), n_seq, heads, scale * 1.44269504088896340736f);
+        return att::launch_with_lds(attention_kernel<T, HD, NT>, dim3(n_seq * heads), dim3(ATT_THREADS), C::LDS, s,
+                                    reinterpret_cast<const T*>(qkv), reinterpret_cast<T*>(out), n_seq, heads, scale * att::kLog2e);
     }
-    PP_LAUNCH_CHECK();
-    return PP_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -442,9 +368,7 @@ __global__ __launch_bounds__(ATT_THREADS, (HD == 32 ? 3 : 1)) void attention_spl
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fr = lane & 15, fg = lane >> 4;
 
-    int id = blockIdx.x;
-    const int nblk = gridDim.x;
-    if ((nblk & 7) == 0) id = (id & 7) * (nblk >> 3) + (id >> 3);  // XCD-aware remap (as above)
+    const int id = att::xcd_block_id();
     const int seq = id / heads, head = id - seq * heads;
     const int E = heads * HD;
     const size_t row_bytes = (size_t)3 * E * 4;
@@ -456,11 +380,7 @@ __global__ __launch_bounds__(ATT_THREADS, (HD == 32 ? 3 : 1)) void attention_spl
     for (int t = 0; t < QPW; ++t) {
         const int qt = wave + t * (ATT_THREADS / 64);
         const char* qrow = base + (size_t)((qt < NT ? qt : 0) * 16 + fr) * row_bytes;
-#pragma unroll
-        for (int g = 0; g < C::NB; ++g) {
-            qh_all[t][g] = *reinterpret_cast<const f16x8*>(qrow + g * 128 + fg * 16);
-            ql_all[t][g] = *reinterpret_cast<const f16x8*>(qrow + g * 128 + 64 + fg * 16);
-        }
+        att::load_q_split(qh_all[t], ql_all[t], qrow, fg);
     }
 
     // ---- stage K (raw blocks, swizzled) and V^T (hi / lo planes); zero the padded key rows
@@ -499,26 +419,7 @@ __global__ __launch_bounds__(ATT_THREADS, (HD == 32 ? 3 : 1)) void attention_spl
             s[kt] = acc;
         }
         // ---- softmax over the 16 NT keys of this lane's query (fp32)
-        float mx = -__builtin_inff();
-#pragma unroll
-        for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) mx = fmaxf(mx, s[kt][i]);
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float mb = mx * scale_log2e;
-        float sum = 0.f;
-#pragma unroll
-        for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][i], scale_log2e, -mb));  // arg <= 0: raw v_exp_f32 (1 ulp)
-                s[kt][i] = p;
-                sum += p;
-            }
-        sum += __shfl_xor(sum, 16);
-        sum += __shfl_xor(sum, 32);
-        if (C::NTP > NT) s[C::NTP - 1] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const float sum = att::softmax_row<NT>(s, scale_log2e);  // (the padded tile's fragment: zeros)
 
         // ---- O^T = V^T P^T
         f32x4 o[C::DT];
@@ -526,15 +427,8 @@ __global__ __launch_bounds__(ATT_THREADS, (HD == 32 ? 3 : 1)) void attention_spl
         for (int dt = 0; dt < C::DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int blk = 0; blk < C::NTP / 2; ++blk) {
-            const f32x4 p0 = s[2 * blk], p1 = s[2 * blk + 1];
             f16x8 ph, pl;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                ph[j] = split_hi(p0[j]);
-                pl[j] = split_lo(p0[j], ph[j]);
-                ph[4 + j] = split_hi(p1[j]);
-                pl[4 + j] = split_lo(p1[j], ph[4 + j]);
-            }
+            att::split_p(s[2 * blk], s[2 * blk + 1], ph, pl);
 #pragma unroll
             for (int dt = 0; dt < C::DT; ++dt) {
                 const int off = (dt * 16 + fr) * C::SPV + blk * 32 + 4 * fg;
@@ -556,12 +450,8 @@ template <int HD, int NT>
 static int launch_attention_split(const void* qkv, void* out, int n_seq, int heads, float scale, hipStream_t s) {
     using C = AttSplitCfg<HD, NT>;
     static_assert(C::LDS <= 160 * 1024, "K/V of one head must fit in one CU's LDS");
-    auto kern = attention_split_kernel<HD, NT>;
-    PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS));
-    hipLaunchKernelGGL(kern, dim3(n_seq * heads), dim3(ATT_THREADS), C::LDS, s, reinterpret_cast<const char*>(qkv),
-                       reinterpret_cast<char*>(out), n_seq, heads, scale * 1.44269504088896340736f);
-    PP_LAUNCH_CHECK();
-    return PP_OK;
+    return att::launch_with_lds(attention_split_kernel<HD, NT>, dim3(n_seq * heads), dim3(ATT_THREADS), C::LDS, s,
+                                reinterpret_cast<const char*>(qkv), reinterpret_cast<char*>(out), n_seq, heads, scale * att::kLog2e);
 }
 
 // Long sequences in the split format (432 tokens @384x288; head dim 64 does not fit K and V^T of all keys in one CU's
@@ -593,9 +483,7 @@ __global__ __launch_bounds__(THREADS, 1) void attention_split_stream_kernel(cons
     _Float16* Vl = Vh + HD * C::SPV;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fr = lane & 15, fg = lane >> 4;
-    int id = blockIdx.x;
-    const int nblk = gridDim.x;
-    if ((nblk & 7) == 0) id = (id & 7) * (nblk >> 3) + (id >> 3);
+    int id = att::xcd_block_id();
     const int qs = id % QSPLIT;  // the QSPLIT workgroups of a (sequence, head) are neighbours: same XCD, same L2 lines
     id /= QSPLIT;
     const int seq = id / heads, head = id - seq * heads;
@@ -640,7 +528,7 @@ __global__ __launch_bounds__(THREADS, 1) void attention_split_stream_kernel(cons
                 const char* qrow = base + (size_t)(qt * 16 + fr) * row_bytes;
                 f16x8 qh[C::NB], ql[C::NB];
 #pragma unroll
-                for (int g = 0; g < C::NB; ++g) {
+                for (int g = 0; g < C::NB; ++g) {  // (att::load_q_split, spelled out)
                     qh[g] = *reinterpret_cast<const f16x8*>(qrow + g * 128 + fg * 16);
                     ql[g] = *reinterpret_cast<const f16x8*>(qrow + g * 128 + 64 + fg * 16);
                 }
@@ -678,26 +566,14 @@ __global__ __launch_bounds__(THREADS, 1) void attention_split_stream_kernel(cons
                         sc[kt] = f32x4{0.f, 0.f, 0.f, 0.f};  // padded keys weigh nothing
                         continue;
                     }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[kt][i], scale_log2e, -mb));
-                        sc[kt][i] = p;
-                        sum += p;
-                    }
+                    att::exp_sum(sc[kt], scale_log2e, mb, sum);
                 }
                 l_run[t] += sum;  // this lane's keys only; the four lanes of a query are added up at the end
 #pragma unroll
                 for (int blk = 0; blk < C::KS / 2; ++blk) {
                     if (st * C::KS + 2 * blk >= NT) continue;
-                    const f32x4 p0 = sc[2 * blk], p1 = sc[2 * blk + 1];
                     f16x8 ph, pl;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        ph[j] = split_hi(p0[j]);
-                        pl[j] = split_lo(p0[j], ph[j]);
-                        ph[4 + j] = split_hi(p1[j]);
-                        pl[4 + j] = split_lo(p1[j], ph[4 + j]);
-                    }
+                    att::split_p(sc[2 * blk], sc[2 * blk + 1], ph, pl);
 #pragma unroll
                     for (int dt = 0; dt < C::DT; ++dt) {
                         const int off = (dt * 16 + fr) * C::SPV + blk * 32 + 4 * fg;
@@ -716,8 +592,7 @@ __global__ __launch_bounds__(THREADS, 1) void attention_split_stream_kernel(cons
         const int qt = qs * TPW + wave + t * NW;
         if (wave + t * NW < TPW && qt < NT) {
             float sum = l_run[t];
-            sum += __shfl_xor(sum, 16);
-            sum += __shfl_xor(sum, 32);
+            att::quad_sum(sum);
             const float inv = 1.0f / sum;
             const size_t oidx = ((size_t)seq * S + qt * 16 + fr) * E + head * HD;
 #pragma unroll
@@ -731,12 +606,8 @@ static int launch_attention_split_stream(const void* qkv, void* out, int n_seq, 
     using C = AttSplitStreamCfg<HD, NT, NSTAGE>;
     static_assert(C::LDS <= 160 * 1024, "one stage of K/V must fit in one CU's LDS");
     constexpr int QSPLIT = 4, THREADS = 64 * ((NT + QSPLIT - 1) / QSPLIT);  // 27 query tiles: 4 workgroups of 7 waves
-    auto kern = attention_split_stream_kernel<HD, NT, NSTAGE, THREADS, QSPLIT>;
-    PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS));
-    hipLaunchKernelGGL(kern, dim3(n_seq * heads * QSPLIT), dim3(THREADS), C::LDS, s, reinterpret_cast<const char*>(qkv),
-                       reinterpret_cast<char*>(out), n_seq, heads, scale * 1.44269504088896340736f);
-    PP_LAUNCH_CHECK();
-    return PP_OK;
+    return att::launch_with_lds(attention_split_stream_kernel<HD, NT, NSTAGE, THREADS, QSPLIT>, dim3(n_seq * heads * QSPLIT), dim3(THREADS),
+                                C::LDS, s, reinterpret_cast<const char*>(qkv), reinterpret_cast<char*>(out), n_seq, heads, scale * att::kLog2e);
 }
 
 int attention_split_dma(const void* qkv, void* out, int n_seq, int heads, int head_dim, float scale, hipStream_t s);  // pp_attention_dma.hip

@@ -24,9 +24,10 @@
 // about as many issue cycles (16 exp2 at quarter rate, the maxima, eight split_pair: ~1.7 k) as the 48 MFMAs do (~1.5 k), and they belong to
 // the same wave - the pipe idles while its wave does arithmetic unless ANOTHER wave of the SIMD has MFMAs ready, which is what two workgroups
 // per CU (14 waves) provide and what both attempts gave up.
-#include "pp_common.h"
-#include "pp_device.h"
-#include "pp_split.h"
+//
+// Block id, the exp-and-sum step, the closing row sum and the launch are pp_attention_core.h; the permlane-swap row maximum, the
+// ballot-skipped rescale, the split_pair packing and the transposing V^T reads below are this kernel's own.
+#include "pp_attention_core.h"
 
 namespace pp {
 namespace adma {
@@ -55,9 +56,7 @@ __global__ __launch_bounds__(THREADS, 4) void attention_split_dma_kernel(const c
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fg = lane >> 4;
 
-    int id = blockIdx.x;
-    const int nblk = gridDim.x;
-    if ((nblk & 7) == 0) id = (id & 7) * (nblk >> 3) + (id >> 3);  // the query quarters and heads of a sequence on one XCD
+    int id = att::xcd_block_id();  // the query quarters and heads of a sequence on one XCD
     const int qs = id % QSPLIT;
     id /= QSPLIT;
     const int seq = id / heads, head = id - seq * heads;
@@ -91,7 +90,7 @@ __global__ __launch_bounds__(THREADS, 4) void attention_split_dma_kernel(const c
     {
         const char* qrow = qkv + base + (size_t)((live ? qt : 0) * 16 + fr) * row_bytes;
 #pragma unroll
-        for (int g = 0; g < C::NB; ++g) {
+        for (int g = 0; g < C::NB; ++g) {  // (att::load_q_split, spelled out: shared, it moves this kernel's schedule)
             qh[g] = *reinterpret_cast<const f16x8*>(qrow + g * 128 + fg * 16);
             ql[g] = *reinterpret_cast<const f16x8*>(qrow + g * 128 + 64 + fg * 16);
         }
@@ -167,13 +166,7 @@ __global__ __launch_bounds__(THREADS, 4) void attention_split_dma_kernel(const c
         const float mb = mx * scale_log2e;
         float sum = 0.f;
 #pragma unroll
-        for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[kt][i], scale_log2e, -mb));  // masked keys: exp2(-inf) = 0
-                sc[kt][i] = e;
-                sum += e;
-            }
+        for (int kt = 0; kt < 4; ++kt) att::exp_sum(sc[kt], scale_log2e, mb, sum);  // masked keys: exp2(-inf) = 0
         l_run += sum;  // this lane's keys only; the four lanes of a query are added up at the end
         // ---- O^T += V^T P^T, one K = 32 block per stage of the pair: keys 4 fg + i and 16 + 4 fg + i per lane on both operands
 #pragma unroll
@@ -221,8 +214,7 @@ __global__ __launch_bounds__(THREADS, 4) void attention_split_dma_kernel(const c
     }
     if (!live) return;
     float sum = l_run;
-    sum += __shfl_xor(sum, 16);
-    sum += __shfl_xor(sum, 32);
+    att::quad_sum(sum);
     const float inv = 1.0f / sum;
     const size_t oidx = ((size_t)seq * S + qt * 16 + fr) * E + head * HD;
 #pragma unroll
@@ -235,11 +227,8 @@ static int launch(const void* qkv, void* out, int n_seq, int heads, float scale,
     auto kern = attention_split_dma_kernel<HD>;
     const size_t bytes = (size_t)n_seq * S * 3 * heads * HD * 4;
     PP_REQUIRE(bytes < kOob, PP_ERR_UNSUPPORTED, "pp_attention: qkv tensor exceeds 2 GiB (32-bit buffer offsets)");
-    PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-    hipLaunchKernelGGL(kern, dim3(n_seq * heads * QSPLIT), dim3(THREADS), C::LDS, s, reinterpret_cast<const char*>(qkv),
-                       reinterpret_cast<char*>(out), n_seq, heads, (unsigned)bytes, scale * 1.44269504088896340736f);
-    PP_LAUNCH_CHECK();
-    return PP_OK;
+    return att::launch_with_lds(kern, dim3(n_seq * heads * QSPLIT), dim3(THREADS), C::LDS, s, reinterpret_cast<const char*>(qkv),
+                                reinterpret_cast<char*>(out), n_seq, heads, (unsigned)bytes, scale * att::kLog2e);
 }
 
 }  // namespace adma

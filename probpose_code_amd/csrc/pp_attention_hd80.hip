@@ -18,10 +18,9 @@
 // which is the layout the score loop of attention_split_kernel reads.
 //
 // Everything else is the single-pass form of pp_attention.hip: one 256-thread workgroup per (sequence, head), K row-major and
-// V transposed in LDS, S^T = K Q^T so that P stays in registers as the B operand of O^T = V^T P^T, softmax statistics in fp32.
-#include "pp_common.h"
-#include "pp_device.h"
-#include "pp_split.h"
+// V transposed in LDS, S^T = K Q^T so that P stays in registers as the B operand of O^T = V^T P^T, softmax statistics in fp32 -
+// block id, MFMA overloads, softmax row, packing of P, the bf16 P V step, the bf16 / fp32 store and the launch from pp_attention_core.h.
+#include "pp_attention_core.h"
 
 namespace pp {
 namespace {
@@ -33,41 +32,6 @@ constexpr int H80_S = H80_NT * 16;
 constexpr int H80_SPV = H80_S + 8;   // V^T row pitch (elements): 8 * odd -> conflict-free reads
 constexpr int H80_DT = H80_HD / 16;  // output d tiles
 constexpr int H80_QPW = H80_NT / (H80_THREADS / 64);  // query tiles per wave
-
-__device__ __forceinline__ f32x4 h80_mma(const u32x4& a, const u32x4& b, f32x4 c, __bf16) { return mma_bf16(a, b, c); }
-__device__ __forceinline__ f32x4 h80_mma(const u32x4& a, const u32x4& b, f32x4 c, float) { return mma_f32(a, b, c); }
-
-// softmax over the 192 keys of this lane's query (fp32); s <- p, returns the row sum
-__device__ __forceinline__ float h80_softmax(f32x4 (&s)[H80_NT], float scale_log2e) {
-    float mx = -__builtin_inff();
-#pragma unroll
-    for (int kt = 0; kt < H80_NT; ++kt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) mx = fmaxf(mx, s[kt][i]);
-    mx = fmaxf(mx, __shfl_xor(mx, 16));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float mb = mx * scale_log2e;
-    float sum = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < H80_NT; ++kt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][i], scale_log2e, -mb));  // arg <= 0: raw v_exp_f32
-            s[kt][i] = p;
-            sum += p;
-        }
-    sum += __shfl_xor(sum, 16);
-    sum += __shfl_xor(sum, 32);
-    return sum;
-}
-
-// XCD-aware remap (hardware round-robins consecutive block ids over the 8 XCDs): the heads of one sequence share an L2
-__device__ __forceinline__ int h80_block_id() {
-    int id = blockIdx.x;
-    const int nblk = gridDim.x;
-    if ((nblk & 7) == 0) id = (id & 7) * (nblk >> 3) + (id >> 3);
-    return id;
-}
 
 // ---------------------------------------------------------------------------------------------
 // PP_PREC_BF16 (K-block 32: contraction padded to 96) and PP_PREC_F32 (K-block 16: 80, no padding)
@@ -95,7 +59,7 @@ __global__ __launch_bounds__(H80_THREADS, (sizeof(T) == 2 ? 2 : 1)) void attenti
     T* Vt = reinterpret_cast<T*>(smem + C::K_BYTES);  // [HD][SPV]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fr = lane & 15, fg = lane >> 4;
-    const int id = h80_block_id();
+    const int id = att::xcd_block_id();
     const int seq = id / heads, head = id - seq * heads;
     const int E = heads * H80_HD;
     const size_t row_stride = (size_t)3 * E;
@@ -142,11 +106,11 @@ __global__ __launch_bounds__(H80_THREADS, (sizeof(T) == 2 ? 2 : 1)) void attenti
 #pragma unroll
             for (int g = 0; g < C::NG; ++g) {
                 const u32x4 kf = *reinterpret_cast<const u32x4*>(Ks + ((size_t)r * C::RCL + ((g * 4 + fg) ^ ((r >> 2) & 3))) * 16);
-                acc = h80_mma(kf, qf_all[t][g], acc, T{});
+                acc = att::mma(kf, qf_all[t][g], acc, T{});
             }
             s[kt] = acc;
         }
-        const float sum = h80_softmax(s, scale_log2e);
+        const float sum = att::softmax_row<H80_NT>(s, scale_log2e);
 
         // ---- O^T = V^T P^T over the 80 true columns
         f32x4 o[H80_DT];
@@ -155,17 +119,9 @@ __global__ __launch_bounds__(H80_THREADS, (sizeof(T) == 2 ? 2 : 1)) void attenti
         if constexpr (sizeof(T) == 2) {
 #pragma unroll
             for (int blk = 0; blk < H80_NT / 2; ++blk) {
-                const f32x4 p0 = s[2 * blk], p1 = s[2 * blk + 1];
-                const bf16x8 pf = {(__bf16)p0[0], (__bf16)p0[1], (__bf16)p0[2], (__bf16)p0[3],
-                                       (__bf16)p1[0], (__bf16)p1[1], (__bf16)p1[2], (__bf16)p1[3]};
+                const bf16x8 pf = att::pack_p(s[2 * blk], s[2 * blk + 1]);
 #pragma unroll
-                for (int dt = 0; dt < H80_DT; ++dt) {
-                    const T* vrow = Vt + (dt * 16 + fr) * H80_SPV + blk * 32 + 4 * fg;
-                    const u32x2 lo = *reinterpret_cast<const u32x2*>(vrow);
-                    const u32x2 hi = *reinterpret_cast<const u32x2*>(vrow + 16);
-                    const u32x4 vf = {lo[0], lo[1], hi[0], hi[1]};
-                    o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vf), pf, o[dt], 0, 0, 0);
-                }
+                for (int dt = 0; dt < H80_DT; ++dt) o[dt] = att::pv_mma(Vt + (dt * 16 + fr) * H80_SPV + blk * 32 + 4 * fg, pf, o[dt]);
             }
         } else {
 #pragma unroll
@@ -174,7 +130,7 @@ __global__ __launch_bounds__(H80_THREADS, (sizeof(T) == 2 ? 2 : 1)) void attenti
 #pragma unroll
                 for (int dt = 0; dt < H80_DT; ++dt) {
                     const u32x4 vf = *reinterpret_cast<const u32x4*>(Vt + (dt * 16 + fr) * H80_SPV + kt * 16 + 4 * fg);
-                    o[dt] = h80_mma(vf, pf, o[dt], T{});
+                    o[dt] = att::mma(vf, pf, o[dt], T{});
                 }
             }
         }
@@ -182,15 +138,7 @@ __global__ __launch_bounds__(H80_THREADS, (sizeof(T) == 2 ? 2 : 1)) void attenti
         const float inv = 1.0f / sum;
         T* orow = out + ((size_t)seq * H80_S + qt * 16 + fr) * E + head * H80_HD;
 #pragma unroll
-        for (int dt = 0; dt < H80_DT; ++dt) {
-            const f32x4 v = o[dt] * inv;
-            if constexpr (sizeof(T) == 2) {
-                const bf16x4 ov = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                *reinterpret_cast<bf16x4*>(orow + dt * 16 + 4 * fg) = ov;
-            } else {
-                *reinterpret_cast<f32x4*>(orow + dt * 16 + 4 * fg) = v;
-            }
-        }
+        for (int dt = 0; dt < H80_DT; ++dt) att::store4(orow + dt * 16 + 4 * fg, o[dt] * inv);
         // one query tile's fragments at a time: without it the K reads of all three tiles are hoisted to the top (256 registers, one workgroup
         // per CU: 115 us per bf16 launch at n_seq 128 x 16 heads); with it 149 registers and the two workgroups a CU's LDS holds (69 KiB each)
         __builtin_amdgcn_sched_barrier(0);
@@ -214,7 +162,7 @@ __global__ __launch_bounds__(H80_THREADS, 1) void attention_hd80_split_kernel(co
     _Float16* Vl = Vh + H80_HD * H80_SPV;                                        // [HD][SPV] lo halves
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fr = lane & 15, fg = lane >> 4;
-    const int id = h80_block_id();
+    const int id = att::xcd_block_id();
     const int seq = id / heads, head = id - seq * heads;
     const int E = heads * H80_HD;
     // the hi halves of chunk j (0 .. 9) of this head in part 0 / 1 / 2 (q / k / v) of token row r of this sequence: flat element index
@@ -281,7 +229,7 @@ __global__ __launch_bounds__(H80_THREADS, 1) void attention_hd80_split_kernel(co
             }
             s[kt] = acc;
         }
-        const float sum = h80_softmax(s, scale_log2e);
+        const float sum = att::softmax_row<H80_NT>(s, scale_log2e);
 
         // ---- O^T = V^T P^T over the 80 true columns; p in [0, 1] is split in registers
         f32x4 o[H80_DT];
@@ -289,15 +237,8 @@ __global__ __launch_bounds__(H80_THREADS, 1) void attention_hd80_split_kernel(co
         for (int dt = 0; dt < H80_DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int blk = 0; blk < H80_NT / 2; ++blk) {
-            const f32x4 p0 = s[2 * blk], p1 = s[2 * blk + 1];
             f16x8 ph, pl;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                ph[j] = split_hi(p0[j]);
-                pl[j] = split_lo(p0[j], ph[j]);
-                ph[4 + j] = split_hi(p1[j]);
-                pl[4 + j] = split_lo(p1[j], ph[4 + j]);
-            }
+            att::split_p(s[2 * blk], s[2 * blk + 1], ph, pl);
 #pragma unroll
             for (int dt = 0; dt < H80_DT; ++dt) {
                 const int off = (dt * 16 + fr) * H80_SPV + blk * 32 + 4 * fg;
@@ -319,12 +260,8 @@ template <typename T>
 int launch_hd80(const void* qkv, void* out, int n_seq, int heads, float scale, hipStream_t s) {
     using C = H80Cfg<T>;
     static_assert(C::LDS <= 160 * 1024, "K/V of one head must fit in one CU's LDS");
-    auto kern = attention_hd80_kernel<T>;
-    PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS));
-    hipLaunchKernelGGL(kern, dim3(n_seq * heads), dim3(H80_THREADS), C::LDS, s, reinterpret_cast<const T*>(qkv), reinterpret_cast<T*>(out), n_seq,
-                       heads, scale * 1.44269504088896340736f);
-    PP_LAUNCH_CHECK();
-    return PP_OK;
+    return att::launch_with_lds(attention_hd80_kernel<T>, dim3(n_seq * heads), dim3(H80_THREADS), C::LDS, s, reinterpret_cast<const T*>(qkv),
+                                reinterpret_cast<T*>(out), n_seq, heads, scale * att::kLog2e);
 }
 
 }  // namespace
@@ -334,12 +271,8 @@ int attention_hd80(int prec, const void* qkv, void* out, int n_seq, int heads, f
     if (prec == PP_PREC_BF16) return launch_hd80<__bf16>(qkv, out, n_seq, heads, scale, s);
     if (prec == PP_PREC_F32) return launch_hd80<float>(qkv, out, n_seq, heads, scale, s);
     static_assert(H80_SPLIT_LDS <= 160 * 1024, "K/V of one head must fit in one CU's LDS");
-    PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_hd80_split_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)H80_SPLIT_LDS));
-    hipLaunchKernelGGL(attention_hd80_split_kernel, dim3(n_seq * heads), dim3(H80_THREADS), H80_SPLIT_LDS, s, reinterpret_cast<const char*>(qkv),
-                       reinterpret_cast<char*>(out), n_seq, heads, scale * 1.44269504088896340736f);
-    PP_LAUNCH_CHECK();
-    return PP_OK;
+    return att::launch_with_lds(attention_hd80_split_kernel, dim3(n_seq * heads), dim3(H80_THREADS), H80_SPLIT_LDS, s,
+                                reinterpret_cast<const char*>(qkv), reinterpret_cast<char*>(out), n_seq, heads, scale * att::kLog2e);
 }
 
 }  // namespace pp

@@ -24,6 +24,20 @@ typedef __attribute__((address_space(3))) s16x4* lds_s16x4_t;  // operand of ds_
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (WAVE - 1); }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
+// the value of lane ^ 16 / lane ^ 32 by v_permlane16_swap / v_permlane32_swap - plain VALU, no trip through the LDS queue (swap(a, a): an
+// even-row lane gets (own, partner's), an odd-row lane (partner's, own))
+__device__ __forceinline__ float xor16(float v) {
+    const unsigned u = __builtin_bit_cast(unsigned, v);
+    const auto s = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    const unsigned own_is_first = ((threadIdx.x >> 4) & 1u) == 0u;
+    return __builtin_bit_cast(float, own_is_first ? (unsigned)s[1] : (unsigned)s[0]);
+}
+__device__ __forceinline__ float xor32(float v) {
+    const unsigned u = __builtin_bit_cast(unsigned, v);
+    const auto s = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    const unsigned own_is_first = ((threadIdx.x >> 5) & 1u) == 0u;
+    return __builtin_bit_cast(float, own_is_first ? (unsigned)s[1] : (unsigned)s[0]);
+}
 
 // ---- MFMA 16x16 over one 16-byte chunk of K per lane: c += a b^T (a, b: lane = row (lane & 15), k-group (lane >> 4))
 __device__ __forceinline__ f32x4 mma_bf16(const u32x4& a, const u32x4& b, f32x4 c) {

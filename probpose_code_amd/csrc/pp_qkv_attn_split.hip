@@ -24,9 +24,7 @@
 // 75 KiB of LDS and <= 128 registers: TWO workgroups per CU (four waves per SIMD), so one workgroup's softmax / LDS phase
 // runs beside the other's MFMA / fill phase. The twelve heads of a sequence are neighbours on one XCD (block remap), the
 // 288 KiB of its LayerNorm rows are fetched from HBM once and hit in that L2 eleven times; Wqkv (1.7 MB) stays in every L2.
-#include "pp_common.h"
-#include "pp_device.h"
-#include "pp_split.h"
+#include "pp_attention_core.h"
 
 namespace pp {
 namespace qka {
@@ -71,30 +69,7 @@ __device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, f32x4 c) {
     return mma_f16(a, b, c);
 }
 
-// (hi, lo) of four values of an accumulator fragment, regrouped by the row swap of split_store4_rowpair: the even-row lane
-// (bit 4 of the lane id clear) gets the 16-byte hi chunk of the pair's eight elements, the odd-row lane the lo chunk
-// the value of lane ^ 16 / lane ^ 32 by v_permlane16_swap / v_permlane32_swap (swap(a, a): an even-row lane gets (own, partner's), an odd-row
-// lane (partner's, own))
-__device__ __forceinline__ float xor16(float v) {
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    const auto s = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    const unsigned own_is_first = ((threadIdx.x >> 4) & 1u) == 0u;
-    return __builtin_bit_cast(float, own_is_first ? (unsigned)s[1] : (unsigned)s[0]);
-}
-__device__ __forceinline__ float xor32(float v) {
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    const auto s = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    const unsigned own_is_first = ((threadIdx.x >> 5) & 1u) == 0u;
-    return __builtin_bit_cast(float, own_is_first ? (unsigned)s[1] : (unsigned)s[0]);
-}
-__device__ __forceinline__ u32x4 split_pair16(f32x4 v) {
-    u32x2 hu, lu;
-    { unsigned h__, l__; split_pair(v[0], v[1], h__, l__); hu[0] = h__; lu[0] = l__; }
-    { unsigned h__, l__; split_pair(v[2], v[3], h__, l__); hu[1] = h__; lu[1] = l__; }
-    const auto s0 = __builtin_amdgcn_permlane16_swap(hu[0], lu[0], false, false);
-    const auto s1 = __builtin_amdgcn_permlane16_swap(hu[1], lu[1], false, false);
-    return u32x4{s0[0], s1[0], s0[1], s1[1]};
-}
+// (xor16 / xor32: pp_device.h; split_pair16: pp_split.h; the block id: pp_attention_core.h)
 
 #ifndef QKA_STAMP
 #define QKA_STAMP 0  // dev: s_memtime stamps of waves 0 and 7 of workgroups 0 and 777 at the phase boundaries (scripts/micro/qka_stamps.py)
@@ -130,9 +105,7 @@ __device__ __forceinline__ void qkv_attention_body(const Params& p) {
     auto stamp = []() {};
 #endif
     stamp();  // 0: start
-    int id = blockIdx.x;
-    const int nblk = gridDim.x;
-    if ((nblk & 7) == 0) id = (id & 7) * (nblk >> 3) + (id >> 3);  // the heads of a sequence on one XCD, one after the other
+    int id = att::xcd_block_id();  // the heads of a sequence on one XCD, one after the other
     const int qh = p.q_split == 2 ? (id & 1) : 0;  // which half of the query tiles
     if (p.q_split == 2) id >>= 1;
     const int seq = id / p.heads, head = id - seq * p.heads;

@@ -71,18 +71,22 @@ __device__ __forceinline__ void split_store4(void* base, size_t idx, f32x4 v) {
     *reinterpret_cast<f16x4*>(p) = h;
     *reinterpret_cast<f16x4*>(p + 64) = l;
 }
-// The same for an MFMA accumulator fragment, where lane and lane ^ 16 hold the two halves of one 8-element chunk (lanes with
-// bit 4 clear: elements idx .. idx + 3 with idx % 8 == 0, their partners idx + 4 ..): one row swap per dword
-// (v_permlane16_swap) gives the even-row lane the whole hi chunk and the odd-row lane the whole lo chunk - ONE 16-byte store
-// per lane instead of two 8-byte ones. Every lane of the wave must call it; `store` masks the store itself.
-__device__ __forceinline__ void split_store4_rowpair(void* base, size_t idx, f32x4 v, bool store) {
+// (hi, lo) of the four values of an MFMA accumulator fragment, regrouped by a row swap: lane and lane ^ 16 hold the two halves of one
+// 8-element chunk (lanes with bit 4 clear: elements idx .. idx + 3 with idx % 8 == 0, their partners idx + 4 ..); one v_permlane16_swap
+// per dword gives the even-row lane the whole 16-byte hi chunk of the pair's eight elements and the odd-row lane the whole lo chunk.
+__device__ __forceinline__ u32x4 split_pair16(f32x4 v) {
     u32x2 hu, lu;
     { unsigned h__, l__; split_pair(v[0], v[1], h__, l__); hu[0] = h__; lu[0] = l__; }
     { unsigned h__, l__; split_pair(v[2], v[3], h__, l__); hu[1] = h__; lu[1] = l__; }
     // swap(a, b): odd rows of a <-> even rows of b. Even-row lane: (own hi, partner's hi); odd-row lane: (partner's lo, own lo)
     const auto s0 = __builtin_amdgcn_permlane16_swap(hu[0], lu[0], false, false);
     const auto s1 = __builtin_amdgcn_permlane16_swap(hu[1], lu[1], false, false);
-    const u32x4 q = {s0[0], s1[0], s0[1], s1[1]};
+    return u32x4{s0[0], s1[0], s0[1], s1[1]};
+}
+// split_store4 for such a fragment: ONE 16-byte store per lane instead of two 8-byte ones. Every lane of the wave must call it; `store`
+// masks the store itself.
+__device__ __forceinline__ void split_store4_rowpair(void* base, size_t idx, f32x4 v, bool store) {
+    const u32x4 q = split_pair16(v);
     const bool odd = (threadIdx.x & 16) != 0;
     char* p = split_addr(base, idx & ~(size_t)7) + (odd ? 64 : 0);
     if (store) *reinterpret_cast<u32x4*>(p) = q;

@@ -61,19 +61,49 @@ def loops(body):
     return found, inner
 
 
+# The closed list of instructions whose two source operands compare() may reorder: IEEE addition, multiplication, maxNum and minNum give
+# the same result for (a, b) and (b, a) - only which NaN payload survives when both are NaN depends on the order. `_e32`, and `_e64`
+# without modifiers (neg / abs, clamp, omod, op_sel would bind to an operand position or follow the operands as further tokens).
+COMMUTATIVE = re.compile(r"^(\s*v_(?:add|mul|max|min)_f32_e(?:32|64)\s+)([^,\s]+), ([^,\s]+), ([^,\s]+)$", re.M)
+_PLAIN_OPERAND = re.compile(r"^(?:[vs]\d+|vcc_lo|vcc_hi|m0|exec_lo|exec_hi|-?\d+|0x[0-9a-f]+|-?\d*\.\d+)$")
+
+
+def canonical_order(code):
+    """code (comments stripped) with the two sources of every COMMUTATIVE instruction sorted; an operand that carries a modifier is left alone"""
+    def one(m):
+        a, b = m.group(3), m.group(4)
+        if not (_PLAIN_OPERAND.match(a) and _PLAIN_OPERAND.match(b)):
+            return m.group(0)
+        a, b = sorted((a, b))
+        return f"{m.group(1)}{m.group(2)}, {a}, {b}"
+    return COMMUTATIVE.sub(one, code)
+
+
+def compare(a, b):
+    """The verdict on two assembly texts of one source file. Three of the four pass:
+      identical;
+      identical but for comments: the assembler's comments carry IR block labels (`; %.preheader194`, `; %_ZN2pp8gelu_erfEf.exit`), which
+        are numbered and named by what was inlined; instructions, directives, kernel descriptors and metadata are outside comments;
+      identical but for commutative operand order: as above once the two source operands of v_add_f32, v_mul_f32, v_max_f32 and v_min_f32
+        are put in a canonical order. Code moved into an inlined helper reaches the instruction selector with the operands of such a node
+        the other way round; IEEE results do not depend on the operand order (a NaN payload aside), so the arithmetic is the same. The
+        list is closed - these four - and everything else must still match line for line."""
+    if a == b:
+        return "identical"
+    code = lambda s: re.sub(r"[ \t]*;.*", "", s)
+    a, b = code(a), code(b)
+    if a == b:
+        return "identical but for comments"
+    return "identical but for commutative operand order" if canonical_order(a) == canonical_order(b) else "DIFFERS"
+
+
 def main(old, new, jobs=8):
     csrc = os.path.join("probpose_code_amd", "csrc")
     names = sorted(f for f in os.listdir(os.path.join(new, csrc)) if f.endswith(".hip"))
     def one(f):
         if not os.path.exists(os.path.join(old, csrc, f)):
             return "new file"
-        a, b = (isa_text(os.path.join(t, csrc, f)) for t in (old, new))
-        if a == b:
-            return "identical"
-        # the assembler's comments carry IR block labels (`; %.preheader194`, `; %_ZN2pp8gelu_erfEf.exit`), which are numbered and named by
-        # what was inlined; instructions, directives, kernel descriptors and metadata are outside comments
-        code = lambda s: re.sub(r"[ \t]*;.*", "", s)
-        return "identical but for comments" if code(a) == code(b) else "DIFFERS"
+        return compare(*(isa_text(os.path.join(t, csrc, f)) for t in (old, new)))
     with ThreadPoolExecutor(max_workers=jobs) as ex:
         results = list(ex.map(one, names))
     for f, r in zip(names, results):

@@ -11,6 +11,7 @@ pytestmark = pytest.mark.gpu
 
 BF16, F32 = 0, 1
 TOL = {F32: dict(rtol=2e-5, atol=2e-5), BF16: dict(rtol=2e-2, atol=2e-2)}
+ATTENTION_TOL = {F32: TOL[F32], BF16: dict(rtol=3e-2, atol=3e-2)}  # (imported by tests/test_attention_forms_gpu.py)
 
 
 def _lib():
@@ -240,8 +241,7 @@ def test_attention_vs_torch(prec, hd, S):
     x = _q(qkv, prec).reshape(n_seq, S, 3, heads, hd).permute(2, 0, 3, 1, 4)
     att = ((x[0] @ x[1].transpose(-2, -1)) * hd ** -0.5).softmax(-1)
     ref = (att @ x[2]).transpose(1, 2).reshape(n_seq * S, E)
-    tol = TOL[prec] if prec == F32 else dict(rtol=3e-2, atol=3e-2)
-    torch.testing.assert_close(out.cpu().double(), ref, **tol)
+    torch.testing.assert_close(out.cpu().double(), ref, **ATTENTION_TOL[prec])
 
 
 @pytest.mark.parametrize("E", [384, 768])
