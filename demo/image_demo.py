@@ -46,7 +46,9 @@ def main():
     ap.add_argument("--encode", default="host", choices=["host", "device"],
                     help="device: a .jpg / .jpeg --out-img is transformed on the GPU and Huffman-coded on the host (a file that decodes to the same pixels)")
     ap.add_argument("--encode-png", default="host", choices=["host", "device"],
-                    help="device: a .png --out-img is filtered, deflated (runs only) and checksummed on the GPU (the same pixels, other bytes)")
+                    help="device: a .png --out-img is filtered, deflated and checksummed on the GPU (the same pixels, other bytes)")
+    ap.add_argument("--png-match", default="runs", choices=["runs", "lz"],
+                    help="with --encode-png device: runs (matches at distance 1 only) or lz (also one pixel and one row back: a smaller file)")
     ap.add_argument("--bboxes", default=None, help="x0,y0,x1,y1;x0,y0,x1,y1;... (default: the whole image)")
     ap.add_argument("--precision", default=None, choices=[None, "f16x3", "bf16", "f32"],
                     help="overrides model.precision of the config (default there: f16x3, the mode within 1e-3 of the fp32 reference)")
@@ -100,7 +102,7 @@ def main():
         from probpose_code_amd.visualization import PoseLocalVisualizer
 
         vis = PoseLocalVisualizer(radius=args.radius, line_width=args.thickness, alpha=args.alpha, device=args.device, image_encoder=args.encode,
-                                  png_encoder=args.encode_png)
+                                  png_encoder=args.encode_png, png_match=args.png_match)
         vis.set_dataset_meta(model.dataset_meta)
         vis.add_datasample("result", load_image_bgr(args.img)[:, :, ::-1], results, draw_heatmap=args.draw_heatmap, kpt_thr=args.kpt_thr,
                            out_file=args.out_img)

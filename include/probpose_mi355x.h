@@ -985,7 +985,13 @@ int pp_jpeg_huffman_decode_batch(const pp_jpeg_hd_desc* descriptors, int n, long
  * smallest sum of min(b, 256 - b) over its bytes (ties: the lowest number). The filtered stream is cut into tiles of 4096
  * bytes; a run of equal bytes inside a tile becomes a literal and matches of length 3..258 at distance 1; the tokens are
  * coded in ONE dynamic deflate block with a Huffman code built on the host from the stream's own histogram. The deflate
- * stage takes any byte stream: a descriptor without pixels compresses `data` as it stands into a zlib stream. */
+ * stage takes any byte stream: a descriptor without pixels compresses `data` as it stands into a zlib stream.
+ *
+ * A second match mode, "lz" (the *_lz functions; opt-in, the unsuffixed ones are unchanged): beside runs (distance 1) a
+ * position may copy from one pixel back (distance 3) and from the row above (distance P = 1 + 3 * width, P - 3, P + 3; for a
+ * raw stream P is the descriptor's `period`, 0 for none), chosen by a greedy rule with a one-byte lookahead; the tokens of a
+ * tile form a chain that the device resolves by pointer doubling. Two Huffman codes, literal/length and distance, both
+ * from the stream's own histograms. csrc/pp_png_core.h states the rule in full. */
 
 /* A stream's Huffman code as the device reads it. sym[s]: the bit-reversed code of literal/length symbol s | its length << 16
  * (0: unused); header: the first header_bits bits of the zlib stream, LSB first in little-endian words (78 01, BFINAL,
@@ -996,6 +1002,13 @@ typedef struct {
     uint32_t reserved[3];
     uint32_t header[76];
 } pp_deflate_code;
+
+/* The code of a stream in lz mode: `base` as above (its header then holds both codes' lengths: at most 2302 bits), and
+ * dist[s]: the bit-reversed code of distance symbol s (0 .. 29) | its length << 16 (0: unused). */
+typedef struct {
+    pp_deflate_code base;
+    uint32_t dist[32];
+} pp_deflate_code_lz;
 
 /* What the coder leaves per stream: the length of the zlib stream in bytes (also when it did not fit: the capacity it
  * needs), PP_OK, PP_ERR_INVALID_ARG (a descriptor that describes nothing) or PP_ERR_WORKSPACE (capacity below the need:
@@ -1012,7 +1025,10 @@ typedef struct {
  * read. data: 16-byte aligned; hist: 288 uint32 (the histogram of the 286 symbols, symbol 256 counted once); code: what
  * pp_deflate_build_code made of hist, read by pp_png_deflate_batch only; scratch: the stream's share of
  * pp_deflate_scratch_bytes, 16-byte aligned, contents undefined before and after; out / capacity: where the zlib stream
- * goes (16-byte aligned) and how many bytes fit; crc_init: the CRC-32 register in front of the stream's first byte. */
+ * goes (16-byte aligned) and how many bytes fit; crc_init: the CRC-32 register in front of the stream's first byte.
+ * period: read in lz mode only - the row period P of a raw stream (0: no far candidates); with pixels it must be 0, P is
+ * 1 + 3 * width. In lz mode hist holds 320 uint32 (the 288 as above, then the counts of the 30 distance symbols), code
+ * points at the `base` of a pp_deflate_code_lz, and scratch is the share pp_deflate_scratch_bytes_lz gives. */
 typedef struct {
     const uint8_t* pixels;
     uint8_t* data;
@@ -1027,7 +1043,7 @@ typedef struct {
     int64_t row_stride;
     int32_t rgb;
     uint32_t crc_init;
-    int64_t reserved;
+    int64_t period;
 } pp_deflate_desc;
 
 /* Host only. A capacity no zlib stream of this coder exceeds for len (1 .. 2^31 - 1) input bytes: 15 bits a byte, header,
@@ -1065,6 +1081,29 @@ int pp_png_tokens_batch(const pp_deflate_desc* descriptors, int n, int max_heigh
  * is written outside a stream's scratch share, out[0, capacity) and result slot; the same input gives the same bytes
  * launch after launch. n == 0: PP_OK, nothing is launched. */
 int pp_png_deflate_batch(const pp_deflate_desc* descriptors, int n, long long max_len, void* stream);
+
+/* lz mode. The host queries, as their unsuffixed counterparts: the bound holds the longer header (both codes), the scratch
+ * share also holds the parse (one uint16 per input byte). */
+long long pp_deflate_bound_lz(long long len);
+long long pp_deflate_scratch_bytes_lz(long long len);
+/* Host only, re-entrant: both codes of a histogram of 320 words (286 literal/length counts at 0, 30 distance counts at 288).
+ * The literal/length code as pp_deflate_build_code's; the distance code likewise at most 15 bits and complete (with fewer
+ * than two used symbols unused ones are added), HDIST the highest symbol with a length. */
+int pp_deflate_build_code_lz(const uint32_t* hist_host, pp_deflate_code_lz* code_host);
+/* Host only, re-entrant, no HIP call: pp_zlib_compress in lz mode with row period `period` (>= 0; 0: near candidates
+ * only), pp_png_encode in lz mode. The sequential run of the same core: the bytes the *_lz kernels give. */
+int pp_zlib_compress_lz(const void* data_host, long long len, long long period, void* out_host, size_t capacity, size_t* size_out,
+                        long long* tokens_out);
+int pp_png_encode_lz(const uint8_t* pixels_host, int width, int height, long long row_stride, int rgb, void* out_host, size_t capacity,
+                     size_t* size_out);
+/* The two halves in lz mode: every stream of the call is coded in lz mode. Arguments, guarantees and error reporting as
+ * pp_png_tokens_batch / pp_png_deflate_batch; eight launches per batch together, no workgroup waits for another. First half:
+ * "png_filter" (as above), "png_clear_lz" (320 histogram words), "png_parse_lz" (a workgroup per tile: the candidates'
+ * match lengths by a running minimum over the workgroup, the choice, the token starts by twelve rounds of pointer doubling
+ * in LDS, the parse - one uint16 per byte - into scratch, both histograms, the tile's Adler-32 partial). Second half:
+ * "png_bits_lz", "png_scan_lz", "png_zero_lz", "png_pack_lz", "png_crc_lz": as above, reading the stored parse. */
+int pp_png_tokens_batch_lz(const pp_deflate_desc* descriptors, int n, int max_height, long long max_len, void* stream);
+int pp_png_deflate_batch_lz(const pp_deflate_desc* descriptors, int n, long long max_len, void* stream);
 
 #ifdef __cplusplus
 }

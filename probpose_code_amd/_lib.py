@@ -187,6 +187,13 @@ SIGNATURES = {
     "pp_png_encode": (c_int, [_P, c_int, c_int, c_longlong, c_int, _P, ctypes.c_size_t, _P]),
     "pp_png_tokens_batch": (c_int, [_P, c_int, c_int, c_longlong, _P]),
     "pp_png_deflate_batch": (c_int, [_P, c_int, c_longlong, _P]),
+    "pp_deflate_bound_lz": (c_longlong, [c_longlong]),
+    "pp_deflate_scratch_bytes_lz": (c_longlong, [c_longlong]),
+    "pp_deflate_build_code_lz": (c_int, [_P, _P]),
+    "pp_zlib_compress_lz": (c_int, [_P, c_longlong, c_longlong, _P, ctypes.c_size_t, _P, _P]),
+    "pp_png_encode_lz": (c_int, [_P, c_int, c_int, c_longlong, c_int, _P, ctypes.c_size_t, _P]),
+    "pp_png_tokens_batch_lz": (c_int, [_P, c_int, c_int, c_longlong, _P]),
+    "pp_png_deflate_batch_lz": (c_int, [_P, c_int, c_longlong, _P]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

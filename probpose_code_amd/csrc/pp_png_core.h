@@ -12,6 +12,25 @@
 // what a byte emits depends on its position, its run's start and its run's end only. One dynamic deflate block per stream:
 // the literal/length code from the stream's own histogram (symbol 256 counted once), one distance code of length 1, zlib
 // header 78 01 in front, Adler-32 behind.
+//
+// The second match mode, "lz" (the *_lz entry points; the run rule above stays the default and gives the same bytes as
+// before). Filters, tiles, one dynamic block, zlib header and Adler-32 as above. Integers only. s[0, len): the stream;
+// E(g) = min(len, PNG_TILE (g / PNG_TILE + 1)): the end of g's tile.
+//   m_d(g)   0 if g < d, else the largest m <= min(258, E(g) - g) with s[g + i] == s[g + i - d] for all i < m: a match never
+//            covers bytes beyond its tile, its source may lie anywhere earlier in the stream and may overlap its output;
+//   N        the near candidates (1, 3); F: the far candidates (P, P - 3, P + 3) in this order, P = 1 + 3 width for a picture
+//            and the descriptor's `period` for a raw stream (0: F is empty); members of F below 4 or above 32768 are dropped;
+//   Ln(g)    the largest m_d(g) over N if that is >= 3, else 0; dn: the first d of N that attains it;
+//   Lf(g)    likewise over F with a minimum of 4; df;
+//   reach(g) max(Ln(g), 1 + Ln(g + 1)), the second term only when g + 1 < E(g) and Ln(g + 1) > 0;
+//   a position g that starts a token emits the match (Lf, df) if Lf(g) > 0 and Lf(g) >= reach(g) + 3, else the match
+//   (Ln, dn) if Ln(g) > 0, else the literal s[g];
+//   a tile's first byte starts a token; behind a token at g of length l (1 for a literal) g + l starts one; tiles are
+//   independent.
+// The literal/length code as above; a distance code over symbols 0 .. 29 built the same way (build_lengths, limit 15; with
+// fewer than two used symbols unused ones are added), HDIST the highest symbol with a length; the code-length code still
+// avoids symbols 16 .. 18. A match takes up to 15 + 5 + 15 + 13 bits: two put calls. The parse is kept as one uint16 per
+// byte: 0 covered by a match, 1 a literal, else length | candidate index << 9 (candidates in the order 1, 3, P, P - 3, P + 3).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -303,6 +322,173 @@ PP_HOST_DEVICE uint32_t crc_shift(const uint32_t* x2n, unsigned long long nbytes
 
 PP_HOST_DEVICE uint32_t crc_byte(const uint32_t* tab, uint32_t reg, uint32_t b) { return tab[(reg ^ b) & 255u] ^ (reg >> 8); }
 
+// ------------------------------------------------------------------------------------------------------------- lz mode
+constexpr int LZ_CANDS = 5;  // distances 1, 3, P, P - 3, P + 3: the parse's candidate index
+constexpr int LZ_NEAR_MIN = 3, LZ_FAR_MIN = 4, LZ_MARGIN = 3;
+constexpr int LZ_DIST_SYMS = 30, LZ_DIST_AT = 288, LZ_HIST_WORDS = 320;  // hist: 288 words as in runs mode, then the distance counts
+constexpr int DEFLATE_HEADER_BITS_LZ = 16 + 3 + 14 + 19 * 3 + (DEFLATE_SYMS + LZ_DIST_SYMS) * 7;
+
+static_assert(sizeof(pp_deflate_code_lz) == 1600 && offsetof(pp_deflate_code_lz, dist) == sizeof(pp_deflate_code), "png.py mirrors these");
+static_assert(DEFLATE_HEADER_BITS_LZ == 2302 && DEFLATE_HEADER_BITS_LZ <= 32 * 76, "pp_deflate_code.header holds the longest lz header");
+
+struct LzDist {
+    int d[LZ_CANDS];  // 0: a dropped candidate
+};
+
+// The candidates of row period P (0: no far candidates).
+PP_HOST_DEVICE LzDist lz_dists(long long P) {
+    LzDist r;
+    r.d[0] = 1, r.d[1] = 3;
+    const long long f[3] = {P, P - 3, P + 3};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) r.d[2 + k] = (P > 0 && f[k] >= 4 && f[k] <= 32768) ? (int)f[k] : 0;
+    return r;
+}
+
+PP_HOST_DEVICE long long lz_period(const pp_deflate_desc& d) { return d.pixels ? 1 + 3ll * d.width : d.period; }
+
+// def_len for a descriptor of lz mode.
+PP_HOST_DEVICE long long def_len_lz(const pp_deflate_desc& d) {
+    if (d.period < 0 || (d.pixels && d.period != 0)) return 0;
+    return def_len(d);
+}
+
+// Distance symbol (0 .. 29), number of extra bits and their value of a distance 1 .. 32768.
+PP_HOST_DEVICE void distance_symbol(int dist, int& sym, int& ebits, uint32_t& extra) {
+    const int v = dist - 1;
+    if (v < 4) {
+        sym = v, ebits = 0, extra = 0;
+    } else {
+        const int nb = 31 - __builtin_clz((unsigned)v);  // floor(log2 v)
+        ebits = nb - 1;
+        sym = 2 * nb + ((v >> ebits) & 1);
+        extra = (uint32_t)v & ((1u << ebits) - 1u);
+    }
+}
+
+// What position g emits if it starts a token, as the parse stores it. m: m_d(g) of the five candidates (0 for a dropped
+// one); ln_next: Ln(g + 1), 0 where g + 1 is past the tile. ln <- Ln(g).
+PP_HOST_DEVICE int lz_token(const int (&m)[LZ_CANDS], int ln_next, int& ln) {
+    const int cn = m[0] >= m[1] ? 0 : 1;
+    ln = m[cn] >= LZ_NEAR_MIN ? m[cn] : 0;
+    int cf = 2;
+    if (m[3] > m[cf]) cf = 3;
+    if (m[4] > m[cf]) cf = 4;
+    const int lf = m[cf] >= LZ_FAR_MIN ? m[cf] : 0;
+    const int reach = (ln_next > 0 && 1 + ln_next > ln) ? 1 + ln_next : ln;
+    if (lf > 0 && lf >= reach + LZ_MARGIN) return lf | (cf << 9);
+    if (ln > 0) return ln | (cn << 9);
+    return 1;
+}
+
+// A span's view of the candidates. eq[c] bit i: byte p0 + i of the tile equals the byte d_c before it in the stream (clear
+// where there is none, for a dropped candidate and at or past the tile's end); nu_next[c]: the first position at or behind
+// the span's end (p0 + cnt) whose bit is clear, n where all are set up to the tile's end.
+struct LzSpan {
+    uint32_t eq[LZ_CANDS];
+    int nu_next[LZ_CANDS];
+};
+
+// tok[i] <- what byte p0 + i (i < cnt) of a tile of n bytes emits if it starts a token.
+PP_HOST_DEVICE void lz_span_tokens(const LzSpan& s, int cnt, int p0, int n, uint16_t (&tok)[PNG_SPAN]) {
+    int nu[LZ_CANDS], m[LZ_CANDS], ln_next = 0;
+#pragma unroll
+    for (int c = 0; c < LZ_CANDS; ++c) {
+        nu[c] = s.nu_next[c];
+        const int left = nu[c] - (p0 + cnt);
+        m[c] = left > 258 ? 258 : left;
+    }
+    if (p0 + cnt < n) (void)lz_token(m, 0, ln_next);
+#pragma unroll
+    for (int i = PNG_SPAN - 1; i >= 0; --i) {
+        tok[i] = 0;
+        if (i < cnt) {
+#pragma unroll
+            for (int c = 0; c < LZ_CANDS; ++c) {
+                if (!((s.eq[c] >> i) & 1u)) nu[c] = p0 + i;
+                const int left = nu[c] - (p0 + i);
+                m[c] = left > 258 ? 258 : left;
+            }
+            int ln;
+            tok[i] = (uint16_t)lz_token(m, ln_next, ln);
+            ln_next = ln;
+        }
+    }
+}
+
+PP_HOST_DEVICE int lz_step(uint32_t tok) { return tok <= 1u ? 1 : (int)(tok & 511u); }
+
+// A stored parse entry to a sink: sink.literal(byte) / sink.match(length, distance).
+template <class Sink>
+PP_HOST_DEVICE void lz_emit(uint32_t v, uint32_t byte, const LzDist& D, Sink& sink) {
+    if (v == 1u) sink.literal(byte);
+    else if (v > 1u) sink.match((int)(v & 511u), D.d[(v >> 9) & 7u]);
+}
+
+struct LzHistSink {  // hist: LZ_HIST_WORDS counts
+    uint32_t* hist;
+    PP_HOST_DEVICE void literal(uint32_t b) { add_word(hist + b, 1u); }
+    PP_HOST_DEVICE void match(int m, int dist) {
+        int sym, ebits;
+        uint32_t extra;
+        length_symbol(m, sym, ebits, extra);
+        add_word(hist + sym, 1u);
+        distance_symbol(dist, sym, ebits, extra);
+        add_word(hist + LZ_DIST_AT + sym, 1u);
+    }
+};
+
+// Tokens to code bits in lz mode. sym: pp_deflate_code.sym, dsym: pp_deflate_code_lz.dist. A match is two puts: the length
+// code with its extra bits (at most 20 bits), the distance code with its extra bits (at most 28).
+template <class Put>
+struct LzCodeSink {
+    const uint32_t* sym;
+    const uint32_t* dsym;
+    Put& out;
+    PP_HOST_DEVICE void literal(uint32_t b) {
+        const uint32_t e = sym[b];
+        out.put(e & 0xFFFFu, (int)(e >> 16));
+    }
+    PP_HOST_DEVICE void match(int m, int dist) {
+        int s, ebits;
+        uint32_t extra;
+        length_symbol(m, s, ebits, extra);
+        uint32_t e = sym[s];
+        int len = (int)(e >> 16);
+        out.put((e & 0xFFFFu) | (extra << len), len + ebits);
+        distance_symbol(dist, s, ebits, extra);
+        e = dsym[s];
+        len = (int)(e >> 16);
+        out.put((e & 0xFFFFu) | (extra << len), len + ebits);
+    }
+};
+
+PP_HOST_DEVICE long long deflate_bound_lz(long long len) {  // a literal takes at most 15 bits; a match of m >= 3 bytes at most 48, never 15 m
+    return (DEFLATE_HEADER_BITS_LZ + 15 * len + 15 + 7) / 8 + 4;
+}
+
+// A stream's share of scratch in lz mode (pp_deflate_scratch_bytes_lz): the regions of runs mode sized by the lz bound, then
+// the parse, PNG_TILE entries a tile.
+struct LzLayout : DefLayout {
+    long long o_parse, parse_entries;
+};
+
+PP_HOST_DEVICE LzLayout def_layout_lz(long long len) {
+    LzLayout L;
+    L.len = len;
+    L.ntiles = (len + PNG_TILE - 1) / PNG_TILE;
+    L.max_bytes = deflate_bound_lz(len);
+    L.nwords = (L.max_bytes + 3) / 4 + 4;
+    L.o_tadler = 64;
+    L.o_tsum = ent_align16(L.o_tadler + 8 * L.ntiles);
+    L.o_toff = ent_align16(L.o_tsum + 4 * L.ntiles);
+    L.o_words = ent_align16(L.o_toff + 8 * L.ntiles);
+    L.o_parse = ent_align16(L.o_words + 4 * L.nwords);
+    L.parse_entries = L.ntiles * PNG_TILE;
+    L.total = (L.o_parse + 2 * L.parse_entries + 255) / 256 * 256;
+    return L;
+}
+
 // =========================================================================================================== host only
 // Code lengths of at most `limit` bits for n symbols with these counts: Huffman's, and where its tree is deeper, the deep
 // leaves are lifted to `limit` and the Kraft sum is brought back to 1 by moving leaves down one level. With fewer than two
@@ -465,6 +651,112 @@ inline int zlib_compress(const uint8_t* data, long long len, uint8_t* out, size_
     return PP_OK;
 }
 
+// pp_deflate_build_code_lz. hist: LZ_HIST_WORDS counts. lengths (may be NULL) <- the 286 + 30 code lengths.
+inline void build_code_lz(const uint32_t* hist, pp_deflate_code_lz* code, uint8_t* lengths = nullptr) {
+    static const uint8_t kOrder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+    uint32_t count[DEFLATE_SYMS];
+    for (int s = 0; s < DEFLATE_SYMS; ++s) count[s] = hist[s];
+    if (!count[256]) count[256] = 1;
+    uint8_t len[DEFLATE_SYMS + LZ_DIST_SYMS];
+    build_lengths(count, DEFLATE_SYMS, 15, len);
+    build_lengths(hist + LZ_DIST_AT, LZ_DIST_SYMS, 15, len + DEFLATE_SYMS);
+    if (lengths) std::memcpy(lengths, len, sizeof(len));
+    int ndist = LZ_DIST_SYMS;
+    while (!len[DEFLATE_SYMS + ndist - 1]) --ndist;  // (at least two symbols have a length)
+    std::memset(code, 0, sizeof(*code));
+    canonical_codes(len, DEFLATE_SYMS, code->base.sym);
+    canonical_codes(len + DEFLATE_SYMS, LZ_DIST_SYMS, code->dist);
+    uint32_t cl_count[19] = {0}, cl_code[19];
+    uint8_t cl_len[19];
+    for (int i = 0; i < DEFLATE_SYMS + ndist; ++i) ++cl_count[len[i]];
+    build_lengths(cl_count, 19, 7, cl_len);
+    canonical_codes(cl_len, 19, cl_code);
+    LsbPacker p(code->base.header, 0, 76);
+    p.put(0x0178u, 16);
+    p.put(1u, 1);
+    p.put(2u, 2);
+    p.put(DEFLATE_SYMS - 257, 5);
+    p.put((uint32_t)(ndist - 1), 5);  // HDIST
+    p.put(15u, 4);
+    for (int i = 0; i < 19; ++i) p.put(cl_len[kOrder[i]], 3);
+    for (int i = 0; i < DEFLATE_SYMS + ndist; ++i) p.put(cl_code[len[i]] & 0xFFFFu, (int)(cl_code[len[i]] >> 16));
+    code->base.header_bits = (uint32_t)(32 * p.widx + p.n);
+    p.finish();
+}
+
+// The parse of one tile on the host: s: the whole stream, t0: the tile's first byte, n: its bytes; parse[0, n).
+inline void lz_parse_tile(const uint8_t* s, long long t0, int n, const LzDist& D, uint16_t* parse) {
+    std::vector<int16_t> nu((size_t)LZ_CANDS * (PNG_TILE + 1));
+    std::vector<uint8_t> eq((size_t)LZ_CANDS * PNG_TILE);
+    for (int c = 0; c < LZ_CANDS; ++c) {
+        int16_t* u = nu.data() + (size_t)c * (PNG_TILE + 1);
+        uint8_t* e = eq.data() + (size_t)c * PNG_TILE;
+        u[n] = (int16_t)n;
+        for (int p = n - 1; p >= 0; --p) {
+            const long long g = t0 + p;
+            e[p] = D.d[c] && g >= D.d[c] && s[g] == s[g - D.d[c]];
+            u[p] = e[p] ? u[p + 1] : (int16_t)p;
+        }
+    }
+    uint16_t tok[PNG_TILE + PNG_SPAN];
+    for (int p0 = 0; p0 < n; p0 += PNG_SPAN) {
+        const int cnt = n - p0 < PNG_SPAN ? n - p0 : PNG_SPAN;
+        LzSpan sp;
+        for (int c = 0; c < LZ_CANDS; ++c) {
+            sp.eq[c] = 0;
+            for (int i = 0; i < cnt; ++i) sp.eq[c] |= (uint32_t)eq[(size_t)c * PNG_TILE + p0 + i] << i;
+            sp.nu_next[c] = nu[(size_t)c * (PNG_TILE + 1) + p0 + cnt];
+        }
+        lz_span_tokens(sp, cnt, p0, n, *reinterpret_cast<uint16_t(*)[PNG_SPAN]>(tok + p0));
+    }
+    for (int p = 0; p < n; ++p) parse[p] = 0;
+    for (int p = 0; p < n; p += lz_step(tok[p])) parse[p] = tok[p];  // (the chain the kernel resolves by pointer doubling)
+}
+
+// pp_zlib_compress_lz: the phases of the kernels one after another.
+inline int zlib_compress_lz(const uint8_t* data, long long len, long long period, uint8_t* out, size_t capacity, size_t* size_out, long long* tokens_out) {
+    const LzLayout L = def_layout_lz(len);
+    const LzDist D = lz_dists(period);
+    uint32_t hist[LZ_HIST_WORDS] = {0};
+    std::vector<uint16_t> parse((size_t)len);
+    unsigned long long lo = 1, hi = (unsigned long long)len % ADLER_MOD;
+    LzHistSink h{hist};
+    for (long long t = 0; t < L.ntiles; ++t) {
+        const long long t0 = t * PNG_TILE;
+        const int n = (int)(len - t0 < PNG_TILE ? len - t0 : PNG_TILE);
+        lz_parse_tile(data, t0, n, D, parse.data() + t0);
+        uint32_t s1 = 0, s2 = 0;
+        for (int p = 0; p < n; ++p) {
+            lz_emit(parse[t0 + p], data[t0 + p], D, h);
+            s1 += data[t0 + p];
+            s2 += (uint32_t)data[t0 + p] * (uint32_t)(n - p);
+        }
+        const long long behind = len - (t + 1) * PNG_TILE;
+        lo += s1;
+        hi += adler_term(s1, s2, behind > 0 ? (unsigned long long)behind : 0ull);
+    }
+    if (tokens_out) {
+        *tokens_out = 0;
+        for (int s = 0; s < DEFLATE_SYMS; ++s) *tokens_out += hist[s];
+    }
+    hist[256] += 1;
+    pp_deflate_code_lz code;
+    build_code_lz(hist, &code);
+    const uint32_t adler = (uint32_t)(hi % ADLER_MOD) << 16 | (uint32_t)(lo % ADLER_MOD);
+    std::vector<uint32_t> words((size_t)L.nwords, 0u);
+    for (int i = 0; i < (int)((code.base.header_bits + 31) / 32); ++i) or_word(words.data() + i, code.base.header[i]);
+    LsbPacker p(words.data(), code.base.header_bits, L.nwords);
+    LzCodeSink<LsbPacker> pack{code.base.sym, code.dist, p};
+    for (long long g = 0; g < len; ++g) lz_emit(parse[g], data[g], D, pack);
+    put_tail(p, code.base.sym, adler);
+    const size_t nbytes = (size_t)((32ull * (unsigned long long)p.widx + (unsigned)p.n) / 8);
+    p.finish();
+    *size_out = nbytes;
+    if (nbytes > capacity) return PP_ERR_WORKSPACE;
+    std::memcpy(out, words.data(), nbytes);
+    return PP_OK;
+}
+
 inline void put_be32(uint8_t* p, uint32_t v) {
     p[0] = (uint8_t)(v >> 24), p[1] = (uint8_t)(v >> 16), p[2] = (uint8_t)(v >> 8), p[3] = (uint8_t)v;
 }
@@ -498,15 +790,17 @@ inline void filter_picture(const uint8_t* pixels, int width, int height, long lo
     }
 }
 
-// pp_png_encode.
-inline int encode_file(const uint8_t* pixels, int width, int height, long long row_stride, int rgb, uint8_t* out, size_t capacity, size_t* size_out) {
+// pp_png_encode; lz: pp_png_encode_lz.
+inline int encode_file(const uint8_t* pixels, int width, int height, long long row_stride, int rgb, uint8_t* out, size_t capacity, size_t* size_out,
+                       bool lz = false) {
     const long long len = (long long)height * (1 + 3ll * width);
     std::vector<uint8_t> stream((size_t)len);
     filter_picture(pixels, width, height, row_stride, rgb, stream.data());
     *size_out = 0;
     if (capacity < PNG_HEAD + PNG_TAIL) return PP_ERR_WORKSPACE;
     size_t z = 0;
-    const int st = zlib_compress(stream.data(), len, out + PNG_HEAD, capacity - PNG_HEAD - PNG_TAIL, &z, nullptr);
+    const int st = lz ? zlib_compress_lz(stream.data(), len, 1 + 3ll * width, out + PNG_HEAD, capacity - PNG_HEAD - PNG_TAIL, &z, nullptr)
+                      : zlib_compress(stream.data(), len, out + PNG_HEAD, capacity - PNG_HEAD - PNG_TAIL, &z, nullptr);
     *size_out = PNG_HEAD + z + PNG_TAIL;
     if (st != PP_OK) return st;
     static const uint8_t kSig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};

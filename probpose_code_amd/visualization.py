@@ -171,13 +171,16 @@ class PoseLocalVisualizer:
     "mmpose" skeleton style, their boxes, and (``draw_heatmap``) the probability areas of the posterior maps on the padded
     canvas, stacked under the pose panel. Everything is drawn on the GPU; ``add_datasample`` copies the image back once."""
 
-    def __init__(self, name="visualizer", radius=3, line_width=1, alpha=0.8, device="cuda:0", image_encoder="host", png_encoder="host"):
+    def __init__(self, name="visualizer", radius=3, line_width=1, alpha=0.8, device="cuda:0", image_encoder="host", png_encoder="host", png_match="runs"):
         if image_encoder not in ("host", "device"):
             raise ValueError(f"image_encoder must be 'host' or 'device', got {image_encoder!r}")
         if png_encoder not in ("host", "device"):
             raise ValueError(f"png_encoder must be 'host' or 'device', got {png_encoder!r}")
+        if png_match not in ("runs", "lz"):
+            raise ValueError(f"png_match must be 'runs' or 'lz', got {png_match!r}")
         self.image_encoder = image_encoder  # "device": a .jpg / .jpeg out_file is written by jpeg.imwrite_device
         self.png_encoder = png_encoder  # "device": a .png out_file is written by png.imwrite_device
+        self.png_match = png_match  # the match mode of that writer: "runs", or "lz" (pixel and row distances: smaller files of drawn frames)
         self.name = name
         self.radius = radius
         self.line_width = line_width
@@ -253,7 +256,8 @@ class PoseLocalVisualizer:
         panel over the probability areas resized to (H, W) (:796-865); ``out_file`` is written with Pillow - or, for a visualizer
         built with ``image_encoder="device"`` and a ``.jpg`` / ``.jpeg`` name, by the split JPEG encoder from the frame on the
         device (Pillow's default quality 75 and 4:2:0: a file that decodes to the same pixels); with ``png_encoder="device"`` a
-        ``.png`` name is written by the device PNG writer (``png.imwrite_device``: the same pixels, other bytes than Pillow's).
+        ``.png`` name is written by the device PNG writer (``png.imwrite_device`` in the visualizer's ``png_match`` mode: the same
+        pixels, other bytes than Pillow's).
         ``draw_datasample`` plus the copy to the host and the file."""
         if draw_gt:
             raise NotImplementedError("draw_gt: ground-truth drawing is outside ProbPose's demo")
@@ -273,7 +277,7 @@ class PoseLocalVisualizer:
             elif self.png_encoder == "device" and str(out_file).lower().endswith(".png"):
                 from . import png
 
-                png.imwrite_device(out_file, out, channel_order="rgb")
+                png.imwrite_device(out_file, out, channel_order="rgb", match=self.png_match)
             else:
                 from PIL import Image
 

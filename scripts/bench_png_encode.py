@@ -11,8 +11,13 @@ all end with the file bytes in host memory); the file sizes of the three; then t
 codes of an earlier run in place) in device-event time, with the shader clock read right behind the timed launches. One JSON
 line per figure.
 
-    python scripts/bench_png_encode.py [--rounds 7]"""
+``--match lz`` measures the ``lz`` match mode in place of the run coder; ``--match both`` alternates the two modes inside every
+round of the same process (path "device" is runs, "device_lz" is lz; the files' sizes and the launches of both). With
+``--parent-lib PATH`` (an earlier build of the library) the runs launches of that build are timed in the same alternation.
+
+    python scripts/bench_png_encode.py [--rounds 7] [--match runs|lz|both] [--parent-lib PATH]"""
 import argparse
+import ctypes
 import io
 import json
 import os
@@ -49,7 +54,11 @@ def drawn_demo_frame(dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--match", default="runs", choices=["runs", "lz", "both"])
+    ap.add_argument("--parent-lib", default=None, help="an earlier build of libprobpose_mi355x.so: its runs launches are timed beside this build's")
     args = ap.parse_args()
+    modes = ("runs", "lz") if args.match == "both" else (args.match,)
+    label = {"runs": "device", "lz": "device_lz"}
 
     import torch
     from PIL import Image
@@ -59,6 +68,12 @@ def main():
 
     dev = torch.device("cuda:0")
     staging = BatchStaging()
+    parent = None
+    if args.parent_lib:
+        parent = ctypes.CDLL(os.path.abspath(args.parent_lib))
+        P = ctypes.c_void_p
+        parent.pp_png_tokens_batch.argtypes = [P, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, P]
+        parent.pp_png_deflate_batch.argtypes = [P, ctypes.c_int, ctypes.c_longlong, P]
 
     def pil_save(arr, level):
         b = io.BytesIO()
@@ -73,20 +88,21 @@ def main():
     sets.append((f"demo {demo.shape[1]}x{demo.shape[0]}", [demo]))
     for size, host_frames in sets:
         frames = [torch.from_numpy(host_frames[k % len(host_frames)]).to(dev) for k in range(16)]
-        ours = png.encode_batch(frames[:1], channel_order="rgb", staging=staging)[0]
-        with Image.open(io.BytesIO(ours)) as a:
-            assert np.array_equal(np.asarray(a), host_frames[0]), "the file does not hold the pixels"
         default, level1 = len(pil_save(host_frames[0], None)), len(pil_save(host_frames[0], 1))
-        print(json.dumps(dict(figure="file", size=size, device_file_bytes=len(ours), pillow_default_bytes=default, pillow_level1_bytes=level1,
-                              raw_bytes=int(host_frames[0].size), over_default=round(len(ours) / default, 3), over_level1=round(len(ours) / level1, 3))),
-              flush=True)
+        for m in modes:
+            ours = png.encode_batch(frames[:1], channel_order="rgb", staging=staging, match=m)[0]
+            with Image.open(io.BytesIO(ours)) as a:
+                assert np.array_equal(np.asarray(a), host_frames[0]), "the file does not hold the pixels"
+            print(json.dumps(dict(figure="file", size=size, match=m, device_file_bytes=len(ours), pillow_default_bytes=default,
+                                  pillow_level1_bytes=level1, raw_bytes=int(host_frames[0].size), over_default=round(len(ours) / default, 3),
+                                  over_level1=round(len(ours) / level1, 3))), flush=True)
         for n in (1, 16):
             for threads in ((1,) if n == 1 else (1, 8)):
                 with ThreadPoolExecutor(max_workers=threads) as pool:
                     paths = {
                         "host_png": lambda: list(pool.map(lambda a: pil_save(a, None), [f.cpu().numpy() for f in frames[:n]])),
                         "host_png_l1": lambda: list(pool.map(lambda a: pil_save(a, 1), [f.cpu().numpy() for f in frames[:n]])),
-                        "device": lambda: png.encode_batch(frames[:n], channel_order="rgb", staging=staging),
+                        **{label[m]: (lambda m=m: png.encode_batch(frames[:n], channel_order="rgb", staging=staging, match=m)) for m in modes},
                     }
                     times = {k: [] for k in paths}
                     for fn in paths.values():
@@ -102,26 +118,36 @@ def main():
                     print(json.dumps(dict(figure="write_call", size=size, path=name, n=n, threads=threads, ms=round(statistics.median(ts) * 1e3, 3),
                                           min_ms=round(min(ts) * 1e3, 3), max_ms=round(max(ts) * 1e3, 3), rounds=args.rounds)), flush=True)
         for n in (1, 16):
-            job = png._stage(frames[:n], None, 1, dev, staging)
-            png._run(job)  # (leaves the codes of these frames on the device: the timed launches below need no host in between)
             stream = torch.cuda.current_stream(dev)
-            us = {"both": [], "tokens": [], "deflate": []}
+            jobs = {m: png._stage(frames[:n], None, 1, dev, staging, m == "lz") for m in modes}
+            for job in jobs.values():
+                png._run(job)  # (leaves the codes of these frames on the device: the timed launches below need no host in between)
+            halves = {label[m]: ((lambda j=j: png._launch_tokens(j, stream)), (lambda j=j: png._launch_deflate(j, stream))) for m, j in jobs.items()}
+            if parent is not None and "runs" in jobs:
+                j = jobs["runs"]
+                halves["parent_runs"] = (
+                    lambda: parent.pp_png_tokens_batch(j.block.base, len(j.lens), j.max_height, max(j.lens), stream.cuda_stream),
+                    lambda: parent.pp_png_deflate_batch(j.block.base, len(j.lens), max(j.lens), stream.cuda_stream))
+            us = {k: {"both": [], "tokens": [], "deflate": []} for k in halves}
             for _ in range(3 + args.rounds):
-                e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-                e[0].record()
-                png._launch_tokens(job, stream)
-                e[1].record()
-                png._launch_deflate(job, stream)
-                e[2].record()
-                e[2].synchronize()
-                us["tokens"].append(e[0].elapsed_time(e[1]) * 1e3)
-                us["deflate"].append(e[1].elapsed_time(e[2]) * 1e3)
-                us["both"].append(e[0].elapsed_time(e[2]) * 1e3)
+                for k, (tokens, deflate) in halves.items():  # the modes (and builds) alternate inside a round
+                    e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                    e[0].record()
+                    tokens()
+                    e[1].record()
+                    deflate()
+                    e[2].record()
+                    e[2].synchronize()
+                    us[k]["tokens"].append(e[0].elapsed_time(e[1]) * 1e3)
+                    us[k]["deflate"].append(e[1].elapsed_time(e[2]) * 1e3)
+                    us[k]["both"].append(e[0].elapsed_time(e[2]) * 1e3)
             sclk = shader_clock()  # right behind the timed launches
-            print(json.dumps(dict(figure="launches", size=size, n=n, device_event_us=round(statistics.median(us["both"][3:]), 1),
-                                  tokens_us=round(statistics.median(us["tokens"][3:]), 1), deflate_us=round(statistics.median(us["deflate"][3:]), 1),
-                                  min_us=round(min(us["both"][3:]), 1), stream_bytes=int(sum(job.lens)), sclk_mhz=sclk, rounds=args.rounds)), flush=True)
-            del job
+            for k, u in us.items():
+                print(json.dumps(dict(figure="launches", size=size, path=k, n=n, device_event_us=round(statistics.median(u["both"][3:]), 1),
+                                      tokens_us=round(statistics.median(u["tokens"][3:]), 1), deflate_us=round(statistics.median(u["deflate"][3:]), 1),
+                                      min_us=round(min(u["both"][3:]), 1), max_us=round(max(u["both"][3:]), 1),
+                                      stream_bytes=int(sum(next(iter(jobs.values())).lens)), sclk_mhz=sclk, rounds=args.rounds)), flush=True)
+            del jobs, halves
 
 
 if __name__ == "__main__":

@@ -8,12 +8,17 @@
 //     every chunk's CRC is crc32()'s, the IDAT inflates to the filtered stream, and that unfilters to the pixels;
 //   - histograms (Fibonacci counts, two symbols, one symbol, all 286 equal, no match): lengths of at most 15 bits, Kraft
 //     sum exactly 1, the same code twice;
-//   - the CRC-32 of a buffer cut into chunks and combined by crc_shift / crc_mul equals crc32().
+//   - the CRC-32 of a buffer cut into chunks and combined by crc_shift / crc_mul equals crc32();
+//   - lz mode (zlib_compress_lz, encode_file with lz, build_code_lz): the same streams with and without a row period, rows
+//     that repeat the row above, far sources in earlier tiles (a period of 4096 and of 5000), a distance with 13 extra bits
+//     (30300), matches cut at a tile border, a last tile of one byte, positions before the first source; pictures whose
+//     filtered rows repeat: uncompress() returns the input, nothing is written behind the size, the size stays inside
+//     deflate_bound_lz, a capacity one byte short is refused with the need; both codes complete and at most 15 bits.
 // What it does not run: the workgroup scans and the grids - those are the GPU tests' (tests/test_png_gpu.py). A program for a
 // sanitiser build on a CPU machine; no GPU is used:
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all scripts/png_host_check.cpp -lz -o png_host_check
-//   ./png_host_check        ->  "146 cases, 0 failures"
+//   ./png_host_check        ->  "609 cases, 0 failures"
 #include <zlib.h>
 
 #include <cmath>
@@ -74,6 +79,43 @@ static void check_stream(const char* name, const std::vector<uint8_t>& d) {
     if (zs > 1 && need != zs) return fail("needed size", name);
 }
 
+static void check_stream_lz(const char* name, const std::vector<uint8_t>& d, long long period) {
+    ++g_cases;
+    const long long bound = deflate_bound_lz((long long)d.size());
+    std::vector<uint8_t> z((size_t)bound + 16, 0xA5);
+    size_t zs = 0;
+    long long tokens = -1;
+    if (zlib_compress_lz(d.data(), (long long)d.size(), period, z.data(), (size_t)bound, &zs, &tokens) != PP_OK) return fail("lz: refused", name);
+    for (size_t i = zs; i < z.size(); ++i)
+        if (z[i] != 0xA5) return fail("lz: wrote behind its size", name);
+    std::vector<uint8_t> back(d.size() + 1);
+    uLongf n = (uLongf)back.size();
+    if (uncompress(back.data(), &n, z.data(), (uLong)zs) != Z_OK) return fail("lz: zlib does not inflate it", name);
+    if (n != d.size() || std::memcmp(back.data(), d.data(), d.size()) != 0) return fail("lz: inflates to other bytes", name);
+    if (tokens < 1 || tokens > (long long)d.size()) return fail("lz: token count", name);
+    if (period == 0 && tokens > tokens_by_runs(d)) return fail("lz: more tokens than the run rule", name);  // (distance 1 is a candidate)
+    size_t need = 0;
+    if (zs > 1 && zlib_compress_lz(d.data(), (long long)d.size(), period, z.data(), zs - 1, &need, nullptr) != PP_ERR_WORKSPACE) return fail("lz: one byte short accepted", name);
+    if (zs > 1 && need != zs) return fail("lz: needed size", name);
+}
+
+static void check_histogram_lz(const char* name, const std::vector<uint32_t>& hist) {
+    ++g_cases;
+    pp_deflate_code_lz a, b;
+    uint8_t len[DEFLATE_SYMS + LZ_DIST_SYMS];
+    build_code_lz(hist.data(), &a, len);
+    build_code_lz(hist.data(), &b);
+    if (std::memcmp(&a, &b, sizeof(a)) != 0) return fail("lz: not deterministic", name);
+    unsigned long long kraft = 0, dkraft = 0;
+    for (int s = 0; s < DEFLATE_SYMS + LZ_DIST_SYMS; ++s) {
+        if (len[s] > 15) return fail("lz: length above 15", name);
+        if (len[s]) (s < DEFLATE_SYMS ? kraft : dkraft) += 1ull << (15 - len[s]);
+        if (s >= DEFLATE_SYMS && hist[LZ_DIST_AT + s - DEFLATE_SYMS] && !len[s]) return fail("lz: used distance without a code", name);
+    }
+    if (kraft != 1ull << 15 || dkraft != 1ull << 15) return fail("lz: Kraft sum is not 1", name);
+    if (a.base.header_bits > (uint32_t)DEFLATE_HEADER_BITS_LZ) return fail("lz: header too long", name);
+}
+
 static std::vector<uint8_t> runs_of(std::initializer_list<int> lengths, int lead = 0) {
     std::vector<uint8_t> d((size_t)lead);
     for (size_t i = 0; i < d.size(); ++i) d[i] = (uint8_t)(i * 7 + 1);
@@ -85,11 +127,12 @@ static std::vector<uint8_t> runs_of(std::initializer_list<int> lengths, int lead
     return d;
 }
 
-static void check_picture(const char* name, const std::vector<uint8_t>& px, int W, int H, long long stride, int rgb) {
+static void check_picture(const char* name, const std::vector<uint8_t>& px, int W, int H, long long stride, int rgb, bool lz = false) {
     ++g_cases;
-    std::vector<uint8_t> file(PNG_HEAD + PNG_TAIL + (size_t)deflate_bound((long long)H * (1 + 3ll * W)));
+    const long long len = (long long)H * (1 + 3ll * W);
+    std::vector<uint8_t> file(PNG_HEAD + PNG_TAIL + (size_t)(lz ? deflate_bound_lz(len) : deflate_bound(len)));
     size_t fs = 0;
-    if (encode_file(px.data(), W, H, stride, rgb, file.data(), file.size(), &fs) != PP_OK) return fail("refused", name);
+    if (encode_file(px.data(), W, H, stride, rgb, file.data(), file.size(), &fs, lz) != PP_OK) return fail("refused", name);
     size_t at = 8;
     std::vector<uint8_t> idat;
     int chunks = 0;
@@ -193,7 +236,60 @@ int main() {
                 }
             check_picture("picture bgr", px, W, H, stride, 0);
             check_picture("picture rgb", px, W, H, stride, 1);
+            check_picture("lz picture rgb", px, W, H, stride, 1, true);
+            for (int y = 1; y < H; ++y)  // every row the row above plus 128: the filtered rows repeat (Sub), the far candidates match
+                for (int i = 0; i < stride; ++i) px[(size_t)(y * stride + i)] = (uint8_t)(px[(size_t)((y - 1) * stride + i)] + 128);
+            check_picture("lz picture of repeating rows", px, W, H, stride, 0, true);
         }
+    }
+    // lz mode: the streams above again, and what only it can get wrong
+    check_stream_lz("runs 258..262", runs_of({258, 259, 260, 261, 262}), 0);
+    check_stream_lz("run 4096 + 1", runs_of({4097}), 7);
+    check_stream_lz("run across a tile border", runs_of({600}, 3800), 100);
+    check_stream_lz("one byte", {42}, 0);
+    check_stream_lz("one byte with a period", {42}, 4);
+    for (int n : {2, 15, 16, 17, 4095, 4096, 4097, 8191, 8192, 8193, 70000}) {
+        std::vector<uint8_t> d((size_t)n);
+        for (long long period : {0ll, 4ll, 100ll, 4096ll, 5000ll, 32768ll, 32771ll, 40000ll}) {
+            for (auto& b : d) b = (uint8_t)rng();
+            check_stream_lz("noise", d, period);
+            for (auto& b : d) b = (uint8_t)((rng() % 16 == 0) ? rng() : 0);
+            check_stream_lz("sparse", d, period);
+            // rows of `period` bytes that repeat the row above but for a few bytes: far matches, sources in earlier tiles
+            for (size_t i = 0; i < d.size(); ++i)
+                d[i] = (period > 0 && i >= (size_t)period && rng() % 40) ? d[i - (size_t)period] : (uint8_t)(rng() % 7 ? rng() : d[i ? i - 1 : 0]);
+            check_stream_lz("repeating rows", d, period);
+            for (size_t i = 3; i < d.size(); ++i)
+                if (rng() % 5) d[i] = d[i - 3];  // equal pixels: distance 3
+            check_stream_lz("pixel runs", d, period);
+        }
+    }
+    {
+        std::vector<uint8_t> d(30300 + 400);  // a repeat 30300 bytes back: distance symbol 29, 13 extra bits
+        for (auto& b : d) b = (uint8_t)rng();
+        std::memcpy(d.data() + 30300, d.data(), 400);
+        check_stream_lz("13 extra bits", d, 30300);
+        check_stream_lz("13 extra bits by P - 3", d, 30303);
+        check_stream_lz("13 extra bits by P + 3", d, 30297);
+        d.resize(2 * PNG_TILE + 1);  // a last tile of one byte; a far match (period 100) that would cross the first border
+        std::memcpy(d.data() + PNG_TILE - 10, d.data() + PNG_TILE - 110, 40);
+        check_stream_lz("a match at a tile border, a last tile of one byte", d, 100);
+    }
+    {
+        std::vector<uint32_t> h(LZ_HIST_WORDS, 0);
+        check_histogram_lz("nothing used", h);
+        h[LZ_DIST_AT + 12] = 5;
+        check_histogram_lz("one distance", h);
+        uint32_t a = 1, b = 1;
+        for (int s = 0; s < 30; ++s) {
+            h[s] = h[LZ_DIST_AT + s] = a;
+            const uint32_t c = a + b;
+            a = b, b = c;
+        }
+        check_histogram_lz("Fibonacci counts in both alphabets", h);
+        for (int s = 0; s < DEFLATE_SYMS; ++s) h[s] = 1 + rng() % 1000;
+        for (int s = 0; s < LZ_DIST_SYMS; ++s) h[LZ_DIST_AT + s] = 1 + rng() % 1000;
+        check_histogram_lz("everything used", h);
     }
     {
         std::vector<uint32_t> h(DEFLATE_SYMS, 0);
