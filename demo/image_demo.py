@@ -45,6 +45,8 @@ def main():
                     help="device (needs --decode device): the file's Huffman codes are decoded on the GPU as well (the same pixels)")
     ap.add_argument("--encode", default="host", choices=["host", "device"],
                     help="device: a .jpg / .jpeg --out-img is transformed on the GPU and Huffman-coded on the host (a file that decodes to the same pixels)")
+    ap.add_argument("--jpeg-optimize", action="store_true",
+                    help="with --encode device: Huffman tables built from the picture itself (Pillow's optimize=True): the same pixels, a smaller file")
     ap.add_argument("--encode-png", default="host", choices=["host", "device"],
                     help="device: a .png --out-img is filtered, deflated and checksummed on the GPU (the same pixels, other bytes)")
     ap.add_argument("--png-match", default="runs", choices=["runs", "lz"],
@@ -102,7 +104,7 @@ def main():
         from probpose_code_amd.visualization import PoseLocalVisualizer
 
         vis = PoseLocalVisualizer(radius=args.radius, line_width=args.thickness, alpha=args.alpha, device=args.device, image_encoder=args.encode,
-                                  png_encoder=args.encode_png, png_match=args.png_match)
+                                  png_encoder=args.encode_png, png_match=args.png_match, jpeg_optimize=args.jpeg_optimize)
         vis.set_dataset_meta(model.dataset_meta)
         vis.add_datasample("result", load_image_bgr(args.img)[:, :, ::-1], results, draw_heatmap=args.draw_heatmap, kpt_thr=args.kpt_thr,
                            out_file=args.out_img)

@@ -57,6 +57,8 @@ def main(argv=None):
                     help="device (needs --decode device): a frame's Huffman codes are decoded on the GPU as well (the same pixels)")
     ap.add_argument("--entropy", default="host", choices=["host", "device"],
                     help="device: the drawn frames are Huffman-coded on the GPU as well (the same files)")
+    ap.add_argument("--jpeg-optimize", action="store_true",
+                    help="every frame gets Huffman tables built from its own statistics (with --entropy device: built on the GPU): the same pixels, smaller frames")
     ap.add_argument("--quality", type=int, default=75, help="JPEG quality of the written frames, 1..100")
     ap.add_argument("--fps", type=float, default=None, help="frame rate of the output (default: the input's, 25 for a directory)")
     ap.add_argument("--workers", type=int, default=8, help="host threads of the Huffman coder with --entropy host")
@@ -120,7 +122,7 @@ def main(argv=None):
         def flush():
             nonlocal written
             for data in jpeg.encode_batch(pending, quality=args.quality, subsampling="4:2:0", channel_order="rgb", workers=args.workers,
-                                          device=args.device, entropy=args.entropy):
+                                          device=args.device, entropy=args.entropy, optimize=args.jpeg_optimize):
                 out.write(data)
                 written += 1
             pending.clear()

@@ -894,6 +894,65 @@ long long pp_jpeg_entropy_scratch_bytes(const pp_jpeg_info* infos_host, int n);
  * outside an image's scratch share, out[0, capacity) and result slot. n == 0: PP_OK, nothing is launched. */
 int pp_jpeg_entropy_encode_batch(const pp_jpeg_ent_desc* descriptors, int n, long long max_blocks, void* stream);
 
+/* Optimised Huffman tables (csrc/pp_jpeg_opt_core.h; added under version 4: purely additive): a file coded with the tables
+ * libjpeg's jpeg_gen_optimal_table builds from the image's own symbol statistics - what Pillow's save(optimize=True) writes
+ * for the same coefficients: the same pixels in fewer bytes. Tables are always in the order of the file's DHT segments: DC
+ * luma, AC luma, DC chroma, AC chroma. Code lengths stay at most 16 bits and no table has more symbols than its annex K
+ * counterpart (12 DC, 162 AC), so pp_jpeg_encoded_bound holds for these files as well. A plan of more than 2^32 / 64 blocks
+ * is refused (PP_ERR_INVALID_ARG): 32-bit frequencies are then exact. */
+
+/* Host only, re-entrant. hist[t][s] <- how often the scan of coef_host codes symbol s with table t: the DC categories,
+ * (run << 4) | size per non-zero AC coefficient, 0xF0 per sixteen zeros in front of one, 0x00 per block whose zigzag position
+ * 63 is zero; hist[t][256] <- 0. restart_interval: the DC prediction restarts with every interval. PP_ERR_INVALID_ARG as
+ * pp_jpeg_entropy_encode. */
+int pp_jpeg_symbol_histogram(const int16_t* coef_host, const pp_jpeg_info* info, int restart_interval, uint32_t hist[4][257]);
+/* Host only, re-entrant. bits[l - 1] (codes of length l = 1..16) and vals (the symbols in code order; *nvals of them, the
+ * rest zero) of libjpeg's optimal table for freq (freq[256] is taken as 1: the pseudo-symbol that keeps the all-ones code
+ * free). PP_ERR_INVALID_ARG: a code tree deeper than 32 (frequencies that grow like the Fibonacci numbers over more than 32
+ * symbols; libjpeg refuses them too). */
+int pp_jpeg_optimal_table(const uint32_t freq[257], uint8_t bits[16], uint8_t vals[256], int* nvals);
+/* pp_jpeg_write_headers with the file's four Huffman tables passed in (bits[t], vals[t]; table t has the sum of bits[t]
+ * symbols): the same segments in the same order, one DHT segment per table immediately in front of DRI / SOS.
+ * PP_ERR_INVALID_ARG also for a table that is no prefix code of at most 256 symbols. */
+int pp_jpeg_write_headers_tables(const uint16_t* qtables_host, const pp_jpeg_info* info, int restart_interval, const uint8_t bits[4][16],
+                                 const uint8_t vals[4][256], void* out_host, size_t capacity, size_t* size_out);
+/* pp_jpeg_entropy_encode with the image's own optimal tables in the DHT segments and in the scan: same arguments, same
+ * error contract, any restart interval. */
+int pp_jpeg_entropy_encode_opt(const int16_t* coef_host, const uint16_t* qtables_host, const pp_jpeg_info* info, int restart_interval,
+                               void* out_host, size_t capacity, size_t* size_out);
+
+/* What pp_jpeg_entropy_encode_opt_batch keeps per image on the device (16-byte aligned, contents undefined before): the
+ * histograms, the tables built from them (the host reads bits / vals back with the result slots and writes them into the
+ * DHT segments), code | length << 16 of every symbol, and PP_OK or PP_ERR_INVALID_ARG (too many blocks, a tree deeper
+ * than 32). */
+typedef struct {
+    uint32_t hist[4][257];
+    uint8_t bits[4][16];
+    uint8_t vals[4][256];
+    uint32_t lookup[4][256];
+    int32_t status;
+    int32_t nvals[4];
+    int32_t reserved[7];
+} pp_jpeg_opt_record;
+
+/* One image of pp_jpeg_entropy_encode_opt_batch: pp_jpeg_ent_desc and the image's record. */
+typedef struct {
+    pp_jpeg_ent_desc ent;
+    pp_jpeg_opt_record* record;
+} pp_jpeg_ent_opt_desc;
+
+/* Host only. As pp_jpeg_entropy_scratch_bytes (the records are the caller's own); PP_ERR_INVALID_ARG for a plan of too many
+ * blocks. */
+long long pp_jpeg_entropy_opt_scratch_bytes(const pp_jpeg_info* infos_host, int n);
+/* pp_jpeg_entropy_encode_batch with every image's own optimal tables, built and used on the device
+ * (csrc/pp_jpeg_entropy_opt.hip): the streams are those of pp_jpeg_entropy_encode_opt, bit for bit. Ten launches:
+ * "jpeg_opt_clear" (the histograms), "jpeg_opt_hist", "jpeg_opt_build" (one wave per image and table), then the coder's
+ * seven phases reading the record's lookup: "jpeg_opt_bits", "jpeg_opt_scan", "jpeg_opt_zero", "jpeg_opt_pack",
+ * "jpeg_opt_ffcount", "jpeg_opt_ffscan", "jpeg_opt_stuff". The rules of pp_jpeg_entropy_encode_batch: no allocation, no
+ * synchronisation, no read-back; an image's failure (its slot's status, PP_ERR_INVALID_ARG also for a refused record) leaves
+ * the others untouched; nothing is written outside an image's scratch share, out[0, capacity), result slot and record. */
+int pp_jpeg_entropy_encode_opt_batch(const pp_jpeg_ent_opt_desc* descriptors, int n, long long max_blocks, void* stream);
+
 /* Huffman decoding on the device (csrc/pp_jpeg_huffdec.hip; added under version 4: purely additive): the coefficients
  * pp_jpeg_entropy_decode gives, bit for bit, from the file's own entropy-coded bytes, by self-synchronising passes. The
  * stream is cut into subsequences of 128 raw bytes, each decoded by one thread from a guessed state (bit position, block

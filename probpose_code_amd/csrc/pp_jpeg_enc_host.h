@@ -9,6 +9,8 @@
 // Every write is checked against the caller's capacity; every coefficient against what a baseline code can express.
 // entropy_encode is also the contract of the device coder (csrc/pp_jpeg_entropy.hip), which writes the bytes between the SOS
 // header and EOI bit for bit and derives its code tables from the arrays below; write_headers gives the bytes in front.
+// The Huffman tables of a file are a parameter (HuffSpec): annex K's by default, the image's own optimal ones in the host form
+// of csrc/pp_jpeg_opt_core.h (entropy_encode_opt), which calls entropy_encode_with and write_headers with the tables it built.
 #pragma once
 #include "pp_jpeg_host.h"
 
@@ -107,6 +109,18 @@ inline long long encoded_bound(const pp_jpeg_info* info) {
     return ENC_HEADER_BOUND + (info->coef_count / 64) * 420 + (long long)info->mcus_x * info->mcus_y * 4;
 }
 
+// The four Huffman tables of a file, in the order of its DHT segments: DC luma, AC luma, DC chroma, AC chroma.
+struct HuffSpec {
+    const uint8_t* bits[4];
+    const uint8_t* vals[4];
+    int nvals[4];
+};
+
+inline const HuffSpec& annex_k_spec() {
+    static const HuffSpec spec = {{kDcLumaBits, kAcLumaBits, kDcChromaBits, kAcChromaBits}, {kDcVals, kAcLumaVals, kDcVals, kAcChromaVals}, {12, 162, 12, 162}};
+    return spec;
+}
+
 struct EncTable {
     uint16_t code[256];
     uint8_t size[256];  // 0: the symbol has no code
@@ -126,11 +140,11 @@ struct EncTables {
             code <<= 1;
         }
     }
-    EncTables() {
-        derive(dc[0], kDcLumaBits, kDcVals);
-        derive(dc[1], kDcChromaBits, kDcVals);
-        derive(ac[0], kAcLumaBits, kAcLumaVals);
-        derive(ac[1], kAcChromaBits, kAcChromaVals);
+    explicit EncTables(const HuffSpec& spec = annex_k_spec()) {
+        derive(dc[0], spec.bits[0], spec.vals[0]);
+        derive(ac[0], spec.bits[1], spec.vals[1]);
+        derive(dc[1], spec.bits[2], spec.vals[2]);
+        derive(ac[1], spec.bits[3], spec.vals[3]);
         for (int k = 0; k < 64; ++k) zigzag_of[kNatural[k]] = (uint8_t)k;
     }
 };
@@ -210,7 +224,8 @@ inline void write_dht(BitWriter& w, int tc_th, const uint8_t* bits, const uint8_
 }
 
 // The marker segments SOI .. SOS of a file into w (the caller checks w.full). Cr gets a table of its own where it differs from Cb's.
-inline void put_headers(BitWriter& w, const uint16_t* qtables, const pp_jpeg_info* info, int restart_interval) {
+// One DHT segment per table of `spec`, immediately before DRI / SOS.
+inline void put_headers(BitWriter& w, const uint16_t* qtables, const pp_jpeg_info* info, int restart_interval, const HuffSpec& spec = annex_k_spec()) {
     w.marker(0xD8);
     static const uint8_t app0[16] = {0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
     w.marker(0xE0);
@@ -235,10 +250,8 @@ inline void put_headers(BitWriter& w, const uint16_t* qtables, const pp_jpeg_inf
         const uint8_t sof[10] = {3, 1, (uint8_t)((info->hs << 4) | info->vs), (uint8_t)tq[0], 2, 0x11, (uint8_t)tq[1], 3, 0x11, (uint8_t)tq[2]};
         w.raw(sof, 10);
     }
-    write_dht(w, 0x00, kDcLumaBits, kDcVals, 12);
-    write_dht(w, 0x10, kAcLumaBits, kAcLumaVals, 162);
-    write_dht(w, 0x01, kDcChromaBits, kDcVals, 12);
-    write_dht(w, 0x11, kAcChromaBits, kAcChromaVals, 162);
+    static const int tc_th[4] = {0x00, 0x10, 0x01, 0x11};
+    for (int t = 0; t < 4; ++t) write_dht(w, tc_th[t], spec.bits[t], spec.vals[t], spec.nvals[t]);
     if (restart_interval) {
         w.marker(0xDD);
         w.u16(4);
@@ -261,27 +274,27 @@ inline int check_file_args(const uint16_t* qtables, const pp_jpeg_info* info, in
 // pp_jpeg_write_headers: the bytes SOI .. SOS of the file entropy_encode writes for these tables, geometry and restart
 // interval, into out[0, capacity); *size_out <- their length. The device coder's stream and FF D9 complete the file.
 inline int write_headers(const uint16_t* qtables, const pp_jpeg_info* info, int restart_interval, uint8_t* out, size_t capacity,
-                         size_t* size_out) {
+                         size_t* size_out, const HuffSpec& spec = annex_k_spec()) {
     if (!qtables || !info || !out || !size_out) return enc_fail(PP_ERR_INVALID_ARG, "NULL argument");
     *size_out = 0;
     if (const int st = check_file_args(qtables, info, restart_interval)) return st;
     BitWriter w{out, out + capacity};
-    put_headers(w, qtables, info, restart_interval);
+    put_headers(w, qtables, info, restart_interval, spec);
     if (w.full) return enc_fail(PP_ERR_WORKSPACE, "output buffer too small");
     *size_out = (size_t)(w.p - out);
     return PP_OK;
 }
 
 // pp_jpeg_entropy_encode: coef (info->coef_count int16, the layout of pp_jpeg_entropy_decode) + qtables (3 x 64 uint16,
-// natural order, values 1..255) -> a baseline JFIF file in out[0, capacity); *size_out <- its length.
-inline int entropy_encode(const int16_t* coef, const uint16_t* qtables, const pp_jpeg_info* info, int restart_interval, uint8_t* out,
-                          size_t capacity, size_t* size_out) {
+// natural order, values 1..255) -> a baseline JFIF file in out[0, capacity); *size_out <- its length. spec / tables: the
+// file's Huffman tables and the codes derived from them (pp_jpeg_entropy_encode: annex K's).
+inline int entropy_encode_with(const int16_t* coef, const uint16_t* qtables, const pp_jpeg_info* info, int restart_interval, uint8_t* out,
+                               size_t capacity, size_t* size_out, const HuffSpec& spec, const EncTables& tables) {
     if (!coef || !qtables || !info || !out || !size_out) return enc_fail(PP_ERR_INVALID_ARG, "NULL argument");
     *size_out = 0;
     if (const int st = check_file_args(qtables, info, restart_interval)) return st;
-    static const EncTables tables;
     BitWriter w{out, out + capacity};
-    put_headers(w, qtables, info, restart_interval);
+    put_headers(w, qtables, info, restart_interval, spec);
     if (w.full) return enc_fail(PP_ERR_WORKSPACE, "output buffer too small");
     // ---- the scan
     const int16_t* plane[3];
@@ -347,6 +360,12 @@ inline int entropy_encode(const int16_t* coef, const uint16_t* qtables, const pp
     if (w.full) return enc_fail(PP_ERR_WORKSPACE, "output buffer too small");
     *size_out = (size_t)(w.p - out);
     return PP_OK;
+}
+
+inline int entropy_encode(const int16_t* coef, const uint16_t* qtables, const pp_jpeg_info* info, int restart_interval, uint8_t* out,
+                          size_t capacity, size_t* size_out) {
+    static const EncTables tables;
+    return entropy_encode_with(coef, qtables, info, restart_interval, out, capacity, size_out, annex_k_spec(), tables);
 }
 
 }  // namespace jpeg

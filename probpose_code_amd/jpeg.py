@@ -22,6 +22,14 @@ seven launches behind the forward call's two, on the same stream): the coefficie
 receives the finished streams and puts ``pp_jpeg_write_headers``' bytes in front and ``FF D9`` behind. The files are byte
 for byte those of the host coder. Restart interval 0 only; the default stays ``entropy="host"``.
 
+``optimize=True`` (``entropy_encode``, ``entropy_encode_device``, ``encode_batch``, ``imwrite_device``) codes every file with the
+Huffman tables libjpeg builds from the image's own symbol statistics - the tables and the scan of Pillow's
+``save(..., optimize=True)`` for the same coefficients: identical pixels in fewer bytes. On the host that is
+``pp_jpeg_entropy_encode_opt``; with ``entropy="device"`` it is ``pp_jpeg_entropy_encode_opt_batch``
+(csrc/pp_jpeg_entropy_opt.hip: histogram, code build and the coder's seven phases in ten launches, no host round trip between
+them), whose per-image records bring the tables back with the result slots. The default, ``optimize=False``, writes the
+annex K tables: every byte as before.
+
 ``decode_batch(..., entropy="device")`` decodes the Huffman codes on the device as well (``pp_jpeg_huffman_decode_batch``,
 csrc/pp_jpeg_huffdec.hip: ``sync_passes`` + 4 launches in front of the reconstruct call's two, on the same stream): the host
 only reads the headers (``scan_prepare``), a file goes up as its own bytes and the coefficients never cross the bus. The
@@ -46,7 +54,8 @@ from .staging import BatchStaging, StagedBlock, _align
 fallbacks = 0  # files imread_device / the test loop handed to the host decoder since import (diagnostics)
 reconstruct_calls = 0  # pp_jpeg_reconstruct_bgr_batch calls since import
 forward_calls = 0  # pp_jpeg_forward_batch calls since import
-entropy_device_calls = 0  # pp_jpeg_entropy_encode_batch calls since import
+entropy_device_calls = 0  # pp_jpeg_entropy_encode_batch / pp_jpeg_entropy_encode_opt_batch calls since import
+entropy_opt_device_calls = 0  # pp_jpeg_entropy_encode_opt_batch calls among them
 huffman_device_calls = 0  # pp_jpeg_huffman_decode_batch calls since import
 unsynchronised = 0  # images the device Huffman decoder refused by their result slot since import (each also counts in fallbacks)
 
@@ -73,6 +82,12 @@ _ENT_DESC = np.dtype([("coef", "<u8"), ("scratch", "<u8"), ("out", "<u8"), ("res
 assert _ENT_DESC.itemsize == 64
 _ENT_RESULT = np.dtype([("bytes", "<i8"), ("status", "<i4"), ("reserved", "<i4")])
 assert _ENT_RESULT.itemsize == 16
+# pp_jpeg_ent_opt_desc: pp_jpeg_ent_desc and the record's address; pp_jpeg_opt_record
+_ENT_OPT_DESC = np.dtype(_ENT_DESC.descr + [("record", "<u8")])
+assert _ENT_OPT_DESC.itemsize == 72
+_OPT_RECORD = np.dtype([("hist", "<u4", (4, 257)), ("bits", "u1", (4, 16)), ("vals", "u1", (4, 256)), ("lookup", "<u4", (4, 256)),
+                        ("status", "<i4"), ("nvals", "<i4", (4,)), ("reserved", "<i4", (7,))])
+assert _OPT_RECORD.itemsize == 9344 and _OPT_RECORD.fields["lookup"][1] == 5200
 ENTROPY = ("host", "device")
 
 
@@ -550,9 +565,39 @@ def encode_plan(width: int, height: int, subsampling: str = "4:2:0") -> JpegInfo
     return info
 
 
-def entropy_encode(coefficients: JpegCoefficients, restart_interval: int = 0) -> bytes:
+def _checked_coefficients(coefficients: JpegCoefficients, restart_interval):
+    info, coef = coefficients.info, np.ascontiguousarray(coefficients.coef, np.int16)
+    if coef.size != info.coef_count:
+        raise ValueError("the encoder takes info.coef_count coefficients")
+    if not 0 <= int(restart_interval) <= 65535:
+        raise ValueError(f"restart_interval must be in 0..65535, got {restart_interval!r}")
+    return info, coef
+
+
+def symbol_histogram(coefficients: JpegCoefficients, restart_interval: int = 0) -> np.ndarray:
+    """(4, 257) uint32: how often the scan of ``coefficients`` codes each symbol with the DC luma, AC luma, DC chroma and AC
+    chroma table (``pp_jpeg_symbol_histogram``); bin 256, libjpeg's pseudo-symbol, is 0."""
+    info, coef = _checked_coefficients(coefficients, restart_interval)
+    hist = np.zeros((4, 257), np.uint32)
+    _lib.call("pp_jpeg_symbol_histogram", coef.ctypes.data, ctypes.byref(info), int(restart_interval), hist.ctypes.data)
+    return hist
+
+
+def optimal_table(freq) -> tuple:
+    """libjpeg's optimal Huffman table for 257 symbol frequencies (``pp_jpeg_optimal_table``; bin 256 is taken as 1):
+    (``bits`` (16,) uint8: codes per length 1..16, ``vals`` uint8: the symbols in code order)."""
+    freq = np.ascontiguousarray(freq, np.uint32)
+    if freq.shape != (257,):
+        raise ValueError("a table is built from 257 frequencies")
+    bits, vals, n = np.zeros(16, np.uint8), np.zeros(256, np.uint8), ctypes.c_int(0)
+    _lib.call("pp_jpeg_optimal_table", freq.ctypes.data, bits.ctypes.data, vals.ctypes.data, ctypes.byref(n))
+    return bits, vals[:n.value].copy()
+
+
+def entropy_encode(coefficients: JpegCoefficients, restart_interval: int = 0, optimize: bool = False) -> bytes:
     """The host half of the encoder: the baseline JFIF file of ``coefficients`` (three components, tables (3, 64) with values
-    1..255). Thread-safe and GIL-free while it codes."""
+    1..255). Thread-safe and GIL-free while it codes. ``optimize``: with the image's own optimal Huffman tables
+    (``pp_jpeg_entropy_encode_opt``) instead of annex K's."""
     info, coef = coefficients.info, np.ascontiguousarray(coefficients.coef, np.int16)
     qt = np.ascontiguousarray(coefficients.qtables, np.uint16)
     if qt.shape != (3, 64) or coef.size != info.coef_count:
@@ -561,8 +606,8 @@ def entropy_encode(coefficients: JpegCoefficients, restart_interval: int = 0) ->
         raise ValueError(f"restart_interval must be in 0..65535, got {restart_interval!r}")
     out = np.empty(_size("pp_jpeg_encoded_bound", _lib.lib.pp_jpeg_encoded_bound(ctypes.byref(info))), np.uint8)
     size = ctypes.c_size_t(0)
-    _lib.call("pp_jpeg_entropy_encode", coef.ctypes.data, qt.ctypes.data, ctypes.byref(info), int(restart_interval), out.ctypes.data,
-              out.size, ctypes.byref(size))
+    _lib.call("pp_jpeg_entropy_encode_opt" if optimize else "pp_jpeg_entropy_encode", coef.ctypes.data, qt.ctypes.data, ctypes.byref(info),
+              int(restart_interval), out.ctypes.data, out.size, ctypes.byref(size))
     return out[:size.value].tobytes()
 
 
@@ -599,7 +644,8 @@ def _encoder_images(images, device):
 class _EntropyJob(NamedTuple):
     """One ``pp_jpeg_entropy_encode_batch`` call and its device buffers: ``desc_ptr`` (the uploaded descriptor table),
     ``results`` (n x 16 bytes, a view of the uploaded block), the streams (``out``: image i's at ``o_out[i]``, ``capacity[i]``
-    bytes), the scratch, the infos and ``block`` (the uploaded ``StagedBlock``)."""
+    bytes), the scratch, the infos, ``block`` (the uploaded ``StagedBlock``) and ``records_at`` (with ``optimize``: where, in
+    ``results``, the n ``pp_jpeg_opt_record`` of ``pp_jpeg_entropy_encode_opt_batch`` begin; None without)."""
 
     desc_ptr: int
     results: torch.Tensor
@@ -609,6 +655,19 @@ class _EntropyJob(NamedTuple):
     scratch: torch.Tensor
     infos: list
     block: StagedBlock
+    records_at: Optional[int] = None
+
+
+def _entropy_regions(name: str, n: int, optimize: bool) -> list:
+    """The head regions of a coded batch: the descriptor table ``name`` and "results" - the result slots and, with ``optimize``,
+    the per-image records behind them (64-byte aligned), so that one copy brings both back."""
+    if not optimize:
+        return [(name, 64 * n), ("results", 16 * n)]
+    return [(name, 72 * n), ("results", _records_at(n) + _OPT_RECORD.itemsize * n)]
+
+
+def _records_at(n: int) -> int:
+    return (16 * n + 63) // 64 * 64
 
 
 class _ForwardJob(NamedTuple):
@@ -624,14 +683,14 @@ class _ForwardJob(NamedTuple):
     entropy: Optional[_EntropyJob]
 
 
-def _stage_encode(images, qt, subsampling, channel_order, dev, staging, entropy=False) -> _ForwardJob:
+def _stage_encode(images, qt, subsampling, channel_order, dev, staging, entropy=False, optimize=False) -> _ForwardJob:
     """Pack the descriptor table and the tables of a batch into the pinned buffer and upload them with one copy. ``entropy``:
     the table and result slots of ``pp_jpeg_entropy_encode_batch`` travel in the same copy."""
     n = len(images)
     infos = [encode_plan(im.shape[1], im.shape[0], subsampling) for im in images]
     # the block: descriptors (n x 64 bytes) | quantisation tables (3 x 64 u16) | with entropy: its descriptors (n x 64 bytes),
     # result slots (n x 16 bytes) | per image: coefficients (int16)
-    blk = StagedBlock([("desc", 64 * n), ("qtables", 384)] + ([("entropy", 64 * n), ("results", 16 * n)] if entropy else []),
+    blk = StagedBlock([("desc", 64 * n), ("qtables", 384)] + (_entropy_regions("entropy", n, optimize) if entropy else []),
                       [("coef", [2 * int(i.coef_count) for i in infos])])
     scratch = torch.empty(sum(_align(int(i.coef_count)) for i in infos), dtype=torch.uint8, device=dev)
     blk.acquire(staging, dev)
@@ -641,63 +700,83 @@ def _stage_encode(images, qt, subsampling, channel_order, dev, staging, entropy=
         desc[i] = (im.data_ptr(), p_qtables, planes, p_coef[i], info.width, info.height, im.stride(0), int(channel_order == "rgb"),
                    info.hs, info.vs, info.mcus_x, info.mcus_y)
         planes += _align(int(info.coef_count))
-    job = _entropy_job(blk, "entropy", infos, p_coef, dev) if entropy else None
+    job = _entropy_job(blk, "entropy", infos, p_coef, dev, optimize) if entropy else None
     blk.upload(before="coef")  # (the coefficient regions are only written on the device)
     args = (blk.base, n, max(int(i.coef_count) // 64 for i in infos), max(int(i.height) for i in infos), max(int(i.width) for i in infos))
     return _ForwardJob(args, blk, infos, qt, (images, scratch), job)
 
 
-def write_headers(qtables: np.ndarray, info: JpegInfo, restart_interval: int = 0) -> bytes:
-    """The bytes SOI .. SOS of the file ``entropy_encode`` writes for these tables and this geometry (one code path)."""
+def write_headers(qtables: np.ndarray, info: JpegInfo, restart_interval: int = 0, tables=None) -> bytes:
+    """The bytes SOI .. SOS of the file ``entropy_encode`` writes for these tables and this geometry (one code path).
+    ``tables``: the file's Huffman tables as (``bits`` (4, 16) uint8, ``vals`` (4, 256) uint8) in the order DC luma, AC luma,
+    DC chroma, AC chroma (``pp_jpeg_write_headers_tables``); None: annex K's."""
     qt = np.ascontiguousarray(qtables, np.uint16)
     if qt.shape != (3, 64):
         raise ValueError("the encoder takes three (64,) tables")
-    out = np.empty(1024, np.uint8)
+    out = np.empty(2048, np.uint8)
     size = ctypes.c_size_t(0)
-    _lib.call("pp_jpeg_write_headers", qt.ctypes.data, ctypes.byref(info), int(restart_interval), out.ctypes.data, out.size, ctypes.byref(size))
+    if tables is None:
+        _lib.call("pp_jpeg_write_headers", qt.ctypes.data, ctypes.byref(info), int(restart_interval), out.ctypes.data, out.size, ctypes.byref(size))
+    else:
+        bits, vals = (np.ascontiguousarray(t, np.uint8) for t in tables)
+        if bits.shape != (4, 16) or vals.shape != (4, 256):
+            raise ValueError("tables are (bits (4, 16), vals (4, 256))")
+        _lib.call("pp_jpeg_write_headers_tables", qt.ctypes.data, ctypes.byref(info), int(restart_interval), bits.ctypes.data, vals.ctypes.data,
+                  out.ctypes.data, out.size, ctypes.byref(size))
     return out[:size.value].tobytes()
 
 
-def _entropy_job(blk: StagedBlock, desc: str, infos, p_coef, dev) -> _EntropyJob:
-    """Allocate the scratch and the stream buffers of a batch, fill the n ``_ENT_DESC`` rows of region ``desc`` of ``blk`` and
-    clear its "results" region; ``p_coef``: the device addresses of the coefficients. The caller uploads the block. A stream
-    gets ``pp_jpeg_encoded_bound`` bytes: no stream of its geometry is longer."""
+def _entropy_job(blk: StagedBlock, desc: str, infos, p_coef, dev, optimize=False) -> _EntropyJob:
+    """Allocate the scratch and the stream buffers of a batch, fill the n ``_ENT_DESC`` rows (with ``optimize``: ``_ENT_OPT_DESC``,
+    the records behind the result slots) of region ``desc`` of ``blk`` and clear its "results" region; ``p_coef``: the device
+    addresses of the coefficients. The caller uploads the block. A stream gets ``pp_jpeg_encoded_bound`` bytes: no stream of
+    its geometry is longer, with annex K's tables or the image's own."""
     shares, capacity = [], []
+    query = "pp_jpeg_entropy_opt_scratch_bytes" if optimize else "pp_jpeg_entropy_scratch_bytes"
     for info in infos:
-        one = int(_lib.lib.pp_jpeg_entropy_scratch_bytes(ctypes.byref(info), 1))
+        one = int(getattr(_lib.lib, query)(ctypes.byref(info), 1))
         bound = int(_lib.lib.pp_jpeg_encoded_bound(ctypes.byref(info)))
-        _size("pp_jpeg_entropy_scratch_bytes", min(one, bound))
+        _size(query, min(one, bound))
         shares.append(one)
         capacity.append(_align(bound))
     scratch = torch.empty(sum(shares), dtype=torch.uint8, device=dev)
     out = torch.empty(sum(capacity), dtype=torch.uint8, device=dev)
-    rows, p_results = blk.host(desc, _ENT_DESC), blk.ptr("results")
+    rows, p_results = blk.host(desc, _ENT_OPT_DESC if optimize else _ENT_DESC), blk.ptr("results")
     blk.host("results")[:] = 0
+    records_at = _records_at(len(infos)) if optimize else None
     o_out, s_at, o_at = [], scratch.data_ptr(), 0
     for i, info in enumerate(infos):
-        rows[i] = (p_coef[i], s_at, out.data_ptr() + o_at, p_results + 16 * i, capacity[i], info.hs, info.vs, info.mcus_x,
-                   info.mcus_y, 0)
+        row = (p_coef[i], s_at, out.data_ptr() + o_at, p_results + 16 * i, capacity[i], info.hs, info.vs, info.mcus_x, info.mcus_y, 0)
+        rows[i] = row + (p_results + records_at + _OPT_RECORD.itemsize * i,) if optimize else row
         o_out.append(o_at)
         s_at += shares[i]
         o_at += capacity[i]
-    return _EntropyJob(blk.ptr(desc), blk.device("results"), out, o_out, capacity, scratch, list(infos), blk)
+    return _EntropyJob(blk.ptr(desc), blk.device("results"), out, o_out, capacity, scratch, list(infos), blk, records_at)
 
 
 def _entropy_launch(job: _EntropyJob, stream) -> None:
-    global entropy_device_calls
-    _lib.call("pp_jpeg_entropy_encode_batch", job.desc_ptr, len(job.infos), max(int(i.coef_count) // 64 for i in job.infos), stream.cuda_stream)
+    global entropy_device_calls, entropy_opt_device_calls
+    name = "pp_jpeg_entropy_encode_batch" if job.records_at is None else "pp_jpeg_entropy_encode_opt_batch"
+    _lib.call(name, job.desc_ptr, len(job.infos), max(int(i.coef_count) // 64 for i in job.infos), stream.cuda_stream)
     entropy_device_calls += 1
+    entropy_opt_device_calls += job.records_at is not None
 
 
 def _entropy_collect(job: "_EntropyJob", qtables, stream, staging) -> List[bytes]:
-    """The files of a coded batch: the result slots first (one copy, one synchronisation), then the used bytes of every
-    stream into the pinned buffer (one copy per image, one synchronisation), each between its headers and ``FF D9``."""
-    res = job.results.cpu().numpy().view(_ENT_RESULT)  # (waits for the stream: the launches have run)
+    """The files of a coded batch: the result slots first (one copy, one synchronisation; with ``optimize`` the records, and
+    in them every image's tables, come in the same copy), then the used bytes of every stream into the pinned buffer (one
+    copy per image, one synchronisation), each between its headers and ``FF D9``."""
+    n, name = len(job.infos), ("pp_jpeg_entropy_encode_batch" if job.records_at is None else "pp_jpeg_entropy_encode_opt_batch")
+    back = job.results.cpu().numpy()  # (waits for the stream: the launches have run)
+    res = back[:16 * n].view(_ENT_RESULT)
+    records = None if job.records_at is None else back[job.records_at:job.records_at + _OPT_RECORD.itemsize * n].view(_OPT_RECORD)
     for i, r in enumerate(res):
         if int(r["status"]) != _lib.PP_OK:
             why = ("a coefficient no baseline code expresses (DC difference outside -2047..2047 or AC outside -1023..1023)"
                    if int(r["status"]) == _lib.PP_ERR_INVALID_ARG else f"the stream needs {int(r['bytes'])} bytes, {job.capacity[i]} were given")
-            raise _lib.ProbPoseLibraryError("pp_jpeg_entropy_encode_batch", _lib.lib.pp_status_string(int(r["status"])).decode(), f"image {i}: {why}")
+            if records is not None and int(records[i]["status"]) != _lib.PP_OK:
+                why = "the image's record was refused (too many blocks, or a code tree deeper than 32)"
+            raise _lib.ProbPoseLibraryError(name, _lib.lib.pp_status_string(int(r["status"])).decode(), f"image {i}: {why}")
     sizes = [int(r["bytes"]) for r in res]
     at, offs = 0, []
     for sz in sizes:
@@ -707,27 +786,29 @@ def _entropy_collect(job: "_EntropyJob", qtables, stream, staging) -> List[bytes
     for o, sz, oo in zip(offs, sizes, job.o_out):
         staging.buf[o:o + sz].copy_(job.out[oo:oo + sz], non_blocking=True)
     stream.synchronize()
-    return [write_headers(qt, info) + blk[o:o + sz].tobytes() + b"\xff\xd9" for qt, info, o, sz in zip(qtables, job.infos, offs, sizes)]
+    tables = [None] * n if records is None else [(r["bits"], r["vals"]) for r in records]
+    return [write_headers(qt, info, 0, t) + blk[o:o + sz].tobytes() + b"\xff\xd9" for qt, info, t, o, sz in zip(qtables, job.infos, tables, offs, sizes)]
 
 
-def _stage_entropy(coefficients, dev, staging) -> _EntropyJob:
+def _stage_entropy(coefficients, dev, staging, optimize=False) -> _EntropyJob:
     """Pack the descriptor table, the result slots and the coefficients of a batch into the pinned buffer and upload them
     with one copy."""
     n = len(coefficients)
     # the block: descriptors (n x 64 bytes) | result slots (n x 16 bytes) | per image: coefficients (int16)
-    blk = StagedBlock([("desc", 64 * n), ("results", 16 * n)], [("coef", [2 * int(c.info.coef_count) for c in coefficients])]).acquire(staging, dev)
+    blk = StagedBlock(_entropy_regions("desc", n, optimize), [("coef", [2 * int(c.info.coef_count) for c in coefficients])]).acquire(staging, dev)
     for view, c in zip(blk.hosts("coef", np.int16), coefficients):
         view[:] = np.asarray(c.coef).reshape(-1)
-    job = _entropy_job(blk, "desc", [c.info for c in coefficients], blk.ptrs("coef"), dev)
+    job = _entropy_job(blk, "desc", [c.info for c in coefficients], blk.ptrs("coef"), dev, optimize)
     blk.upload()
     return job
 
 
-def entropy_encode_device(coefficients: Sequence[JpegCoefficients], device=None, staging=None) -> List[bytes]:
+def entropy_encode_device(coefficients: Sequence[JpegCoefficients], device=None, staging=None, optimize: bool = False) -> List[bytes]:
     """The files ``entropy_encode`` gives for a list of ``JpegCoefficients`` (three components, geometry of ``encode_plan``),
     coded on the device: the coefficient arrays are uploaded with the table in one copy, then ONE
     ``pp_jpeg_entropy_encode_batch`` call (seven launches) on the current stream. Invalid coefficients raise what
-    ``entropy_encode`` raises for them (``ProbPoseLibraryError``, PP_ERR_INVALID_ARG)."""
+    ``entropy_encode`` raises for them (``ProbPoseLibraryError``, PP_ERR_INVALID_ARG). ``optimize``: the files of
+    ``entropy_encode(c, optimize=True)`` from ONE ``pp_jpeg_entropy_encode_opt_batch`` call (ten launches)."""
     coefficients = list(coefficients)
     if len(coefficients) == 0:
         return []
@@ -740,13 +821,13 @@ def entropy_encode_device(coefficients: Sequence[JpegCoefficients], device=None,
             raise ValueError("the encoder takes three (64,) tables and info.coef_count int16 coefficients")
         write_headers(qt, c.info)  # (refuses an info that is no encode_plan result, and tables outside 1..255, before any GPU work)
         qts.append(qt)
-    job = _stage_entropy(coefficients, dev, staging)
+    job = _stage_entropy(coefficients, dev, staging, bool(optimize))
     stream = torch.cuda.current_stream(dev)
     _entropy_launch(job, stream)
     return _entropy_collect(job, qts, stream, staging)
 
 
-def _forward(images, quality, subsampling, channel_order, device, staging, entropy: bool) -> Optional[_ForwardJob]:
+def _forward(images, quality, subsampling, channel_order, device, staging, entropy: bool, optimize: bool = False) -> Optional[_ForwardJob]:
     """What ``forward_batch`` and ``_encode_batch_device`` begin with: the options and images checked, the batch staged and
     ``pp_jpeg_forward_batch`` enqueued on the current stream. None for no images."""
     global forward_calls
@@ -758,7 +839,7 @@ def _forward(images, quality, subsampling, channel_order, device, staging, entro
     images, dev = _encoder_images(list(images), device)
     if len(images) == 0:
         return None
-    job = _stage_encode(images, qt, subsampling, channel_order, dev, staging if staging is not None else BatchStaging(), entropy)
+    job = _stage_encode(images, qt, subsampling, channel_order, dev, staging if staging is not None else BatchStaging(), entropy, optimize)
     _lib.call("pp_jpeg_forward_batch", *job.args, torch.cuda.current_stream(dev).cuda_stream)
     forward_calls += 1
     return job
@@ -781,7 +862,7 @@ def forward_batch(images: Sequence, quality: int = 75, subsampling: str = "4:2:0
 
 
 def encode_batch(images: Sequence, quality: int = 75, subsampling: str = "4:2:0", channel_order: str = "bgr", restart_interval: int = 0,
-                 workers: int = 8, device=None, staging=None, entropy: str = "host") -> List[bytes]:
+                 workers: int = 8, device=None, staging=None, entropy: str = "host", optimize: bool = False) -> List[bytes]:
     """Baseline JPEG files of a batch of (H, W, 3) uint8 images (device tensors; a host array is uploaded first) of any mix
     of sizes: ``forward_batch`` on the device, then Huffman coding on a pool of ``workers`` host threads (at most
     ``runner.MAX_WORKERS``). ``quality`` 1..100, ``subsampling`` "4:4:4" / "4:2:2" / "4:2:0" and ``restart_interval`` (MCUs
@@ -792,7 +873,13 @@ def encode_batch(images: Sequence, quality: int = 75, subsampling: str = "4:2:0"
     ``pp_jpeg_entropy_encode_batch`` on the same stream; the coefficients stay on the device and ``workers`` is not used. A
     batch of n images then costs one upload (tables and descriptors), 1 + n downloads (the result slots, then the used
     bytes of each stream) and two synchronisations, one after each kind of download. The files are byte for byte those
-    of ``entropy="host"``; invalid coefficients raise the same ``ProbPoseLibraryError``."""
+    of ``entropy="host"``; invalid coefficients raise the same ``ProbPoseLibraryError``.
+
+    ``optimize=True`` gives every file the Huffman tables libjpeg builds from its own symbol statistics (Pillow's
+    ``optimize=True``): the same coefficients, so the same pixels, in fewer bytes. With ``entropy="device"`` the statistics,
+    the code build and the coding are ``pp_jpeg_entropy_encode_opt_batch``'s ten launches in place of the seven, the copies
+    and synchronisations stay as they are (the tables come back with the result slots), and the files are byte for byte
+    those of ``entropy="host"``. The default writes annex K's tables, every byte as before."""
     from concurrent.futures import ThreadPoolExecutor
 
     from .runner import MAX_WORKERS
@@ -805,17 +892,18 @@ def encode_batch(images: Sequence, quality: int = 75, subsampling: str = "4:2:0"
     if entropy == "device":
         if int(restart_interval) != 0:
             raise ValueError("entropy='device' codes without restart intervals: restart_interval must be 0")
-        return _encode_batch_device(images, quality, subsampling, channel_order, device, staging)
+        return _encode_batch_device(images, quality, subsampling, channel_order, device, staging, bool(optimize))
     coefs = forward_batch(images, quality, subsampling, channel_order, device, staging, copy=False)  # (coded before staging is used again)
     if len(coefs) <= 1 or int(workers) <= 1:
-        return [entropy_encode(c, restart_interval) for c in coefs]
+        return [entropy_encode(c, restart_interval, optimize) for c in coefs]
     with ThreadPoolExecutor(max_workers=max(1, min(MAX_WORKERS, int(workers), len(coefs)))) as pool:
-        return list(pool.map(lambda c: entropy_encode(c, restart_interval), coefs))
+        return list(pool.map(lambda c: entropy_encode(c, restart_interval, optimize), coefs))
 
 
-def _encode_batch_device(images, quality, subsampling, channel_order, device, staging) -> List[bytes]:
-    """``encode_batch`` with both halves on the device: nine launches on the current stream, no coefficient copy."""
-    job = _forward(images, quality, subsampling, channel_order, device, staging, True)
+def _encode_batch_device(images, quality, subsampling, channel_order, device, staging, optimize=False) -> List[bytes]:
+    """``encode_batch`` with both halves on the device: nine launches on the current stream (twelve with ``optimize``), no
+    coefficient copy."""
+    job = _forward(images, quality, subsampling, channel_order, device, staging, True, optimize)
     if job is None:
         return []
     stream = torch.cuda.current_stream(job.block.dev.device)
@@ -824,7 +912,8 @@ def _encode_batch_device(images, quality, subsampling, channel_order, device, st
 
 
 def imwrite_device(path: str, image, **kw) -> None:
-    """One picture written as a baseline JPEG file by ``encode_batch`` (its keyword arguments, ``entropy`` among them)."""
+    """One picture written as a baseline JPEG file by ``encode_batch`` (its keyword arguments, ``entropy`` and ``optimize``
+    among them)."""
     data = encode_batch([image], **kw)[0]
     with open(path, "wb") as f:
         f.write(data)

@@ -171,7 +171,8 @@ class PoseLocalVisualizer:
     "mmpose" skeleton style, their boxes, and (``draw_heatmap``) the probability areas of the posterior maps on the padded
     canvas, stacked under the pose panel. Everything is drawn on the GPU; ``add_datasample`` copies the image back once."""
 
-    def __init__(self, name="visualizer", radius=3, line_width=1, alpha=0.8, device="cuda:0", image_encoder="host", png_encoder="host", png_match="runs"):
+    def __init__(self, name="visualizer", radius=3, line_width=1, alpha=0.8, device="cuda:0", image_encoder="host", png_encoder="host", png_match="runs",
+                 jpeg_optimize=False):
         if image_encoder not in ("host", "device"):
             raise ValueError(f"image_encoder must be 'host' or 'device', got {image_encoder!r}")
         if png_encoder not in ("host", "device"):
@@ -180,6 +181,7 @@ class PoseLocalVisualizer:
             raise ValueError(f"png_match must be 'runs' or 'lz', got {png_match!r}")
         self.image_encoder = image_encoder  # "device": a .jpg / .jpeg out_file is written by jpeg.imwrite_device
         self.png_encoder = png_encoder  # "device": a .png out_file is written by png.imwrite_device
+        self.jpeg_optimize = bool(jpeg_optimize)  # that writer's optimize=: the picture's own Huffman tables (the same pixels, a smaller file)
         self.png_match = png_match  # the match mode of that writer: "runs", or "lz" (pixel and row distances: smaller files of drawn frames)
         self.name = name
         self.radius = radius
@@ -255,7 +257,8 @@ class PoseLocalVisualizer:
         the (H, W, 3) pose panel, or with ``draw_heatmap`` (and heatmaps in ``pred_fields``) the (2H, W, 3) stack of the pose
         panel over the probability areas resized to (H, W) (:796-865); ``out_file`` is written with Pillow - or, for a visualizer
         built with ``image_encoder="device"`` and a ``.jpg`` / ``.jpeg`` name, by the split JPEG encoder from the frame on the
-        device (Pillow's default quality 75 and 4:2:0: a file that decodes to the same pixels); with ``png_encoder="device"`` a
+        device (Pillow's default quality 75 and 4:2:0: a file that decodes to the same pixels; ``jpeg_optimize=True``: with the
+        Huffman tables of Pillow's ``optimize=True``, the same pixels again in fewer bytes); with ``png_encoder="device"`` a
         ``.png`` name is written by the device PNG writer (``png.imwrite_device`` in the visualizer's ``png_match`` mode: the same
         pixels, other bytes than Pillow's).
         ``draw_datasample`` plus the copy to the host and the file."""
@@ -273,7 +276,7 @@ class PoseLocalVisualizer:
             if self.image_encoder == "device" and str(out_file).lower().endswith((".jpg", ".jpeg")):
                 from . import jpeg
 
-                jpeg.imwrite_device(out_file, out, quality=75, subsampling="4:2:0", channel_order="rgb")
+                jpeg.imwrite_device(out_file, out, quality=75, subsampling="4:2:0", channel_order="rgb", optimize=self.jpeg_optimize)
             elif self.png_encoder == "device" and str(out_file).lower().endswith(".png"):
                 from . import png
 

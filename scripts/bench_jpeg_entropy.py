@@ -9,10 +9,18 @@ alternated and medians of --rounds:
     video_demo     demo/video_demo.py on --frames full-HD frames (synthetic checkpoint, --decode device), frames per second of
                    its loop with --entropy host and --entropy device (--demo-rounds alternations).
 
+With ``--optimize both`` the optimised coder (pp_jpeg_entropy_encode_opt_batch, csrc/pp_jpeg_entropy_opt.hip: the image's own
+Huffman tables, built on the device) is timed in the same alternations - entropy_call and encode_batch carry an ``optimize``
+field - and the ``file`` figures give the sizes of both kinds of file, also for the drawn demo frame of
+scripts/bench_png_encode.py. With ``--parent-lib PATH`` (an earlier build of the library) that build's
+pp_jpeg_entropy_encode_batch is timed in the same alternation as this build's (``lib: "parent"``): the default path must lie
+within the spread two identical builds show.
+
 One JSON line per figure.
 
-    python scripts/bench_jpeg_entropy.py [--rounds 7] [--frames 64] [--demo-rounds 3]"""
+    python scripts/bench_jpeg_entropy.py [--rounds 7] [--frames 64] [--demo-rounds 3] [--optimize off|both] [--parent-lib PATH]"""
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -36,6 +44,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--demo-rounds", type=int, default=3)
+    ap.add_argument("--optimize", default="off", choices=["off", "both"], help="both: the optimised coder beside the default one")
+    ap.add_argument("--parent-lib", default=None, help="an earlier build of libprobpose_mi355x.so: its entropy call is timed beside this build's")
     args = ap.parse_args()
 
     import torch
@@ -47,6 +57,19 @@ def main():
     dev = torch.device("cuda:0")
     staging = BatchStaging()
     hd_frames = None
+    both = args.optimize == "both"
+    parent = None
+    if args.parent_lib:
+        parent = ctypes.CDLL(os.path.abspath(args.parent_lib))
+        parent.pp_jpeg_entropy_encode_batch.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p]
+    if both:
+        from scripts.bench_png_encode import drawn_demo_frame
+
+        drawn = torch.from_numpy(np.ascontiguousarray(drawn_demo_frame(dev))).to(dev)
+        plain, opt = (jpeg.encode_batch([drawn], channel_order="rgb", staging=staging, entropy="device", optimize=o)[0] for o in (False, True))
+        assert opt == jpeg.encode_batch([drawn], channel_order="rgb", staging=staging, entropy="host", optimize=True)[0], "the two coders disagree"
+        print(json.dumps(dict(figure="file", size=f"drawn {drawn.shape[1]}x{drawn.shape[0]}", file_bytes=[len(plain)], optimized_file_bytes=[len(opt)],
+                              ratio=round(len(opt) / len(plain), 4))), flush=True)
     for W, H in ((640, 480), (1920, 1080)):
         rng = np.random.default_rng(W)
         host_frames = [photo_like(rng, H, W) for _ in range(4)]
@@ -57,38 +80,56 @@ def main():
         a = jpeg.encode_batch(frames[:4], channel_order="rgb", staging=staging, entropy="host")
         b = jpeg.encode_batch(frames[:4], channel_order="rgb", staging=staging, entropy="device")
         assert a == b, "the two coders disagree"
-        print(json.dumps(dict(figure="file", size=size, file_bytes=[len(f) for f in a])), flush=True)
+        sizes = dict(figure="file", size=size, file_bytes=[len(f) for f in a])
+        if both:
+            o = jpeg.encode_batch(frames[:4], channel_order="rgb", staging=staging, entropy="device", optimize=True)
+            assert o == jpeg.encode_batch(frames[:4], channel_order="rgb", staging=staging, entropy="host", optimize=True), "the two optimised coders disagree"
+            sizes.update(optimized_file_bytes=[len(f) for f in o], ratio=round(sum(len(f) for f in o) / sum(len(f) for f in a), 4))
+        print(json.dumps(sizes), flush=True)
 
         for n in (1, 16):
             qt = jpeg.quality_tables(75)
-            forward = jpeg._stage_encode(frames[:n], qt, "4:2:0", "rgb", dev, staging, entropy=True)
-            job = forward.entropy
             stream = torch.cuda.current_stream(dev)
-            _lib.call("pp_jpeg_forward_batch", *forward.args, stream.cuda_stream)
-            ent_args = (job.desc_ptr, n, max(int(i.coef_count) // 64 for i in job.infos), stream.cuda_stream)
-            for _ in range(3):
-                _lib.call("pp_jpeg_entropy_encode_batch", *ent_args)
+            # name -> (the call, its staged job): this build's default coder, its optimised coder, the parent build's default coder
+            calls = {}
+            for name in ("default",) + (("optimize",) if both else ()) + (("parent",) if parent is not None else ()):
+                forward = jpeg._stage_encode(frames[:n], qt, "4:2:0", "rgb", dev, staging, entropy=True, optimize=name == "optimize")
+                _lib.call("pp_jpeg_forward_batch", *forward.args, stream.cuda_stream)
+                job = forward.entropy
+                ent_args = (job.desc_ptr, n, max(int(i.coef_count) // 64 for i in job.infos), stream.cuda_stream)
+                if name == "parent":
+                    fn = (lambda a=ent_args: parent.pp_jpeg_entropy_encode_batch(*a))
+                else:
+                    fn = (lambda a=ent_args, f=("pp_jpeg_entropy_encode_opt_batch" if name == "optimize" else "pp_jpeg_entropy_encode_batch"): _lib.call(f, *a))
+                calls[name] = (fn, forward)
+            for fn, _ in calls.values():
+                for _ in range(3):
+                    fn()
             torch.cuda.synchronize()
-            us = []
+            us = {name: [] for name in calls}
             for _ in range(args.rounds):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                _lib.call("pp_jpeg_entropy_encode_batch", *ent_args)
-                e1.record()
-                e1.synchronize()
-                us.append(e0.elapsed_time(e1) * 1e3)
+                for name, (fn, _) in calls.items():  # (alternated)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    fn()
+                    e1.record()
+                    e1.synchronize()
+                    us[name].append(e0.elapsed_time(e1) * 1e3)
             sclk = shader_clock()  # right behind the timed launches
-            res = job.results.cpu().numpy().view(jpeg._ENT_RESULT)
-            assert (res["status"] == 0).all()
-            print(json.dumps(dict(figure="entropy_call", size=size, n=n, device_event_us=round(statistics.median(us), 1), min_us=round(min(us), 1),
-                                  max_us=round(max(us), 1), rounds=args.rounds, stream_bytes=int(res["bytes"].sum()),
-                                  coefficient_bytes=int(sum(2 * int(i.coef_count) for i in job.infos)), sclk_mhz=sclk)), flush=True)
-            del forward, job
+            for name, (_, forward) in calls.items():
+                job = forward.entropy
+                res = job.results.cpu().numpy()[:16 * n].view(jpeg._ENT_RESULT)
+                assert (res["status"] == 0).all()
+                print(json.dumps(dict(figure="entropy_call", size=size, n=n, lib="parent" if name == "parent" else "this", optimize=name == "optimize",
+                                      device_event_us=round(statistics.median(us[name]), 1), min_us=round(min(us[name]), 1),
+                                      max_us=round(max(us[name]), 1), rounds=args.rounds, stream_bytes=int(res["bytes"].sum()),
+                                      coefficient_bytes=int(sum(2 * int(i.coef_count) for i in job.infos)), sclk_mhz=sclk)), flush=True)
+            del calls, forward, job
 
         for n in (1, 16):
             for workers in (1, 8):
-                paths = {e: (lambda e=e: jpeg.encode_batch(frames[:n], channel_order="rgb", workers=workers, staging=staging, entropy=e))
-                         for e in ("host", "device")}
+                paths = {(e, o): (lambda e=e, o=o: jpeg.encode_batch(frames[:n], channel_order="rgb", workers=workers, staging=staging, entropy=e, optimize=o))
+                         for e in ("host", "device") for o in ((False, True) if both else (False,))}
                 times = {k: [] for k in paths}
                 for fn in paths.values():
                     fn()  # warm-up
@@ -99,8 +140,8 @@ def main():
                         fn()
                         torch.cuda.synchronize()
                         times[name].append(time.perf_counter() - t0)
-                for name, ts in times.items():
-                    print(json.dumps(dict(figure="encode_batch", size=size, entropy=name, n=n, workers=workers, ms=round(statistics.median(ts) * 1e3, 3),
+                for (name, o), ts in times.items():
+                    print(json.dumps(dict(figure="encode_batch", size=size, entropy=name, optimize=o, n=n, workers=workers, ms=round(statistics.median(ts) * 1e3, 3),
                                           min_ms=round(min(ts) * 1e3, 3), max_ms=round(max(ts) * 1e3, 3), rounds=args.rounds)), flush=True)
 
     if args.frames > 0:
