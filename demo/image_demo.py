@@ -51,6 +51,9 @@ def main():
                     help="device: a .png --out-img is filtered, deflated and checksummed on the GPU (the same pixels, other bytes)")
     ap.add_argument("--png-match", default="runs", choices=["runs", "lz"],
                     help="with --encode-png device: runs (matches at distance 1 only) or lz (also one pixel and one row back: a smaller file)")
+    ap.add_argument("--png-code", default="host", choices=["host", "device"],
+                    help="with --encode-png device: where the Huffman codes are built - host (a round trip between the writer's halves) or "
+                         "device (one launch more, the same file)")
     ap.add_argument("--bboxes", default=None, help="x0,y0,x1,y1;x0,y0,x1,y1;... (default: the whole image)")
     ap.add_argument("--precision", default=None, choices=[None, "f16x3", "bf16", "f32"],
                     help="overrides model.precision of the config (default there: f16x3, the mode within 1e-3 of the fp32 reference)")
@@ -104,7 +107,8 @@ def main():
         from probpose_code_amd.visualization import PoseLocalVisualizer
 
         vis = PoseLocalVisualizer(radius=args.radius, line_width=args.thickness, alpha=args.alpha, device=args.device, image_encoder=args.encode,
-                                  png_encoder=args.encode_png, png_match=args.png_match, jpeg_optimize=args.jpeg_optimize)
+                                  png_encoder=args.encode_png, png_match=args.png_match, jpeg_optimize=args.jpeg_optimize,
+                                  png_code=args.png_code)
         vis.set_dataset_meta(model.dataset_meta)
         vis.add_datasample("result", load_image_bgr(args.img)[:, :, ::-1], results, draw_heatmap=args.draw_heatmap, kpt_thr=args.kpt_thr,
                            out_file=args.out_img)

@@ -1043,8 +1043,9 @@ int pp_jpeg_huffman_decode_batch(const pp_jpeg_hd_desc* descriptors, int n, long
  * truecolour, non-interlaced, one IDAT chunk, no ancillary chunk. Each row takes, of the five PNG filters, the one with the
  * smallest sum of min(b, 256 - b) over its bytes (ties: the lowest number). The filtered stream is cut into tiles of 4096
  * bytes; a run of equal bytes inside a tile becomes a literal and matches of length 3..258 at distance 1; the tokens are
- * coded in ONE dynamic deflate block with a Huffman code built on the host from the stream's own histogram. The deflate
- * stage takes any byte stream: a descriptor without pixels compresses `data` as it stands into a zlib stream.
+ * coded in ONE dynamic deflate block with a Huffman code built from the stream's own histogram - on the host by default
+ * (pp_deflate_build_code, between the two halves), or on the device by one launch more (pp_png_code_batch, opt-in: the
+ * same code, byte for byte, without the round trip). The deflate stage takes any byte stream: a descriptor without pixels compresses `data` as it stands into a zlib stream.
  *
  * A second match mode, "lz" (the *_lz functions; opt-in, the unsuffixed ones are unchanged): beside runs (distance 1) a
  * position may copy from one pixel back (distance 3) and from the row above (distance P = 1 + 3 * width, P - 3, P + 3; for a
@@ -1082,7 +1083,8 @@ typedef struct {
  * (height, width, 3) uint8 with row_stride bytes between rows, rgb: 1 for R,G,B in memory, 0 for B,G,R - only read; then
  * len = height * (1 + 3 * width) and pp_png_tokens_batch writes the filtered stream to data. Without pixels data is only
  * read. data: 16-byte aligned; hist: 288 uint32 (the histogram of the 286 symbols, symbol 256 counted once); code: what
- * pp_deflate_build_code made of hist, read by pp_png_deflate_batch only; scratch: the stream's share of
+ * pp_deflate_build_code made of hist, read by pp_png_deflate_batch only - and written by pp_png_code_batch(_lz), the one
+ * call that stores through this pointer (the whole struct, in lz mode the whole pp_deflate_code_lz); scratch: the stream's share of
  * pp_deflate_scratch_bytes, 16-byte aligned, contents undefined before and after; out / capacity: where the zlib stream
  * goes (16-byte aligned) and how many bytes fit; crc_init: the CRC-32 register in front of the stream's first byte.
  * period: read in lz mode only - the row period P of a raw stream (0: no far candidates); with pixels it must be 0, P is
@@ -1140,6 +1142,17 @@ int pp_png_tokens_batch(const pp_deflate_desc* descriptors, int n, int max_heigh
  * is written outside a stream's scratch share, out[0, capacity) and result slot; the same input gives the same bytes
  * launch after launch. n == 0: PP_OK, nothing is launched. */
 int pp_png_deflate_batch(const pp_deflate_desc* descriptors, int n, long long max_len, void* stream);
+/* The code build on the device, in one launch ("png_code": one workgroup per stream), called between pp_png_tokens_batch
+ * and pp_png_deflate_batch on the same stream in place of the histogram download, pp_deflate_build_code and the code
+ * upload. It reads each descriptor's hist (288 words) and writes *code: every byte of the pp_deflate_code that
+ * pp_deflate_build_code gives for the same histogram. A descriptor that describes no stream or whose code is NULL is
+ * skipped (pp_png_deflate_batch refuses it into its result slot); nothing else is written. No stored length exceeds 15
+ * and header_bits stays within what pp_deflate_bound counts. No allocation, no synchronisation. n == 0: PP_OK, nothing is
+ * launched. */
+int pp_png_code_batch(const pp_deflate_desc* descriptors, int n, void* stream);
+/* Host only, re-entrant, no HIP call: the steps of the device build (csrc/pp_png_code_core.h) one after another - the code
+ * pp_deflate_build_code gives, byte for byte. For tests of the kernel's logic without a GPU. */
+int pp_deflate_build_code_steps(const uint32_t* hist_host, pp_deflate_code* code_host);
 
 /* lz mode. The host queries, as their unsuffixed counterparts: the bound holds the longer header (both codes), the scratch
  * share also holds the parse (one uint16 per input byte). */
@@ -1163,6 +1176,10 @@ int pp_png_encode_lz(const uint8_t* pixels_host, int width, int height, long lon
  * "png_bits_lz", "png_scan_lz", "png_zero_lz", "png_pack_lz", "png_crc_lz": as above, reading the stored parse. */
 int pp_png_tokens_batch_lz(const pp_deflate_desc* descriptors, int n, int max_height, long long max_len, void* stream);
 int pp_png_deflate_batch_lz(const pp_deflate_desc* descriptors, int n, long long max_len, void* stream);
+/* pp_png_code_batch and pp_deflate_build_code_steps in lz mode ("png_code_lz"): hist holds 320 words, and the whole
+ * pp_deflate_code_lz whose `base` the descriptor's code names is written - what pp_deflate_build_code_lz gives. */
+int pp_png_code_batch_lz(const pp_deflate_desc* descriptors, int n, void* stream);
+int pp_deflate_build_code_steps_lz(const uint32_t* hist_host, pp_deflate_code_lz* code_host);
 
 #ifdef __cplusplus
 }

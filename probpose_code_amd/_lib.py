@@ -200,6 +200,10 @@ SIGNATURES = {
     "pp_png_encode_lz": (c_int, [_P, c_int, c_int, c_longlong, c_int, _P, ctypes.c_size_t, _P]),
     "pp_png_tokens_batch_lz": (c_int, [_P, c_int, c_int, c_longlong, _P]),
     "pp_png_deflate_batch_lz": (c_int, [_P, c_int, c_longlong, _P]),
+    "pp_png_code_batch": (c_int, [_P, c_int, _P]),
+    "pp_png_code_batch_lz": (c_int, [_P, c_int, _P]),
+    "pp_deflate_build_code_steps": (c_int, [_P, _P]),
+    "pp_deflate_build_code_steps_lz": (c_int, [_P, _P]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

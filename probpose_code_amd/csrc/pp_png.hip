@@ -39,6 +39,7 @@
 // and png_bits_lz / png_pack_lz read the stored parse in place of the run scans; png_clear, png_scan, png_zero and png_crc
 // are instantiated a second time for the mode's layout (tags png_clear_lz, png_scan_lz, png_zero_lz, png_crc_lz).
 #include "pp_common.h"
+#include "pp_png_code_core.h"
 #include "pp_png_core.h"
 
 #include <cstdint>
@@ -602,6 +603,48 @@ __global__ __launch_bounds__(256) void png_pack_lz_kernel(const pp_deflate_desc*
     p.finish();
 }
 
+// The executor of the code build's steps (csrc/pp_png_code_core.h) for a workgroup of 256 threads. red: four words.
+struct WgExec {
+    uint32_t* red;
+    template <class F>
+    __device__ __forceinline__ void each(int n, F f) {
+        for (int i = threadIdx.x; i < n; i += 256) f(i);
+        __syncthreads();
+    }
+    template <class F>
+    __device__ __forceinline__ void one(F f) {
+        if (threadIdx.x == 0) f();
+        __syncthreads();
+    }
+    template <class B, class P>
+    __device__ __forceinline__ uint32_t offsets(int n, B bits, P put) {  // two items a thread: n <= 512
+        const int i = 2 * (int)threadIdx.x;
+        const uint32_t b0 = i < n ? bits(i) : 0u, b1 = i + 1 < n ? bits(i + 1) : 0u;
+        uint32_t total;
+        const uint32_t before = block_scan(b0 + b1, red, total);
+        if (i < n) put(i, before);
+        if (i + 1 < n) put(i + 1, before + b0);
+        __syncthreads();
+        return total;
+    }
+};
+
+static_assert(DEFLATE_SYMS + LZ_DIST_SYMS <= 512, "WgExec::offsets takes two items a thread");
+
+// blockIdx.x: stream. Reads hist, writes the whole *code (LZ: the pp_deflate_code_lz whose base it names).
+template <bool LZ>
+__global__ __launch_bounds__(256) void png_code_kernel(const pp_deflate_desc* __restrict__ descs) {
+    __shared__ CodeWork work;
+    __shared__ uint32_t red[4];
+    const pp_deflate_desc d = descs[blockIdx.x];
+    if (mode_len<LZ>(d) == 0 || !d.code) return;
+    WgExec ex{red};
+    code_steps<LZ>(ex, work, d.hist);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(const_cast<pp_deflate_code*>(d.code));
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(&work.out);
+    for (int i = threadIdx.x; i < (LZ ? CODE_WORDS_LZ : CODE_WORDS); i += 256) dst[i] = src[i];
+}
+
 static bool batch_args_ok(const char* fn, const void* descriptors, int n, long long max_len) {
     if (n < 0 || (n > 0 && !descriptors) || n > 65535 || (n > 0 && (max_len < 1 || max_len > 0x7FFFFFFFll))) {
         set_error("%s: at most 65535 descriptors of streams of 1 .. 2^31 - 1 bytes", fn);
@@ -640,6 +683,15 @@ extern "C" int pp_deflate_build_code(const uint32_t* hist_host, pp_deflate_code*
         return PP_ERR_INVALID_ARG;
     }
     pp::png::build_code(hist_host, code_host);
+    return PP_OK;
+}
+
+extern "C" int pp_deflate_build_code_steps(const uint32_t* hist_host, pp_deflate_code* code_host) {
+    if (!hist_host || !code_host) {
+        pp::set_error("pp_deflate_build_code_steps: NULL argument");
+        return PP_ERR_INVALID_ARG;
+    }
+    pp::png::build_code_steps(hist_host, code_host);
     return PP_OK;
 }
 
@@ -709,6 +761,16 @@ extern "C" int pp_png_deflate_batch(const pp_deflate_desc* descriptors, int n, l
     return PP_OK;
 }
 
+extern "C" int pp_png_code_batch(const pp_deflate_desc* descriptors, int n, void* stream) {
+    using namespace pp;
+    if (!batch_args_ok("pp_png_code_batch", descriptors, n, 1)) return PP_ERR_INVALID_ARG;
+    if (n == 0) return PP_OK;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(png_code_kernel<false>, dim3(n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), descriptors);
+    PP_LAUNCH_CHECK_AS("png_code");
+    return PP_OK;
+}
+
 // ------------------------------------------------------------------------------------------------------------- lz mode
 extern "C" long long pp_deflate_bound_lz(long long len) {
     if (len < 1 || len > 0x7FFFFFFFll || pp::png::deflate_bound_lz(len) > 0x7FFFFFFFll) {
@@ -729,6 +791,15 @@ extern "C" int pp_deflate_build_code_lz(const uint32_t* hist_host, pp_deflate_co
         return PP_ERR_INVALID_ARG;
     }
     pp::png::build_code_lz(hist_host, code_host);
+    return PP_OK;
+}
+
+extern "C" int pp_deflate_build_code_steps_lz(const uint32_t* hist_host, pp_deflate_code_lz* code_host) {
+    if (!hist_host || !code_host) {
+        pp::set_error("pp_deflate_build_code_steps_lz: NULL argument");
+        return PP_ERR_INVALID_ARG;
+    }
+    pp::png::build_code_steps_lz(hist_host, code_host);
     return PP_OK;
 }
 
@@ -797,5 +868,15 @@ extern "C" int pp_png_deflate_batch_lz(const pp_deflate_desc* descriptors, int n
     PP_LAUNCH_CHECK_AS("png_pack_lz");
     hipLaunchKernelGGL(png_crc_kernel<true>, crc_grid, tpb, 0, s, descriptors);
     PP_LAUNCH_CHECK_AS("png_crc_lz");
+    return PP_OK;
+}
+
+extern "C" int pp_png_code_batch_lz(const pp_deflate_desc* descriptors, int n, void* stream) {
+    using namespace pp;
+    if (!batch_args_ok("pp_png_code_batch_lz", descriptors, n, 1)) return PP_ERR_INVALID_ARG;
+    if (n == 0) return PP_OK;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(png_code_kernel<true>, dim3(n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), descriptors);
+    PP_LAUNCH_CHECK_AS("png_code_lz");
     return PP_OK;
 }

@@ -31,6 +31,9 @@
 // fewer than two used symbols unused ones are added), HDIST the highest symbol with a length; the code-length code still
 // avoids symbols 16 .. 18. A match takes up to 15 + 5 + 15 + 13 bits: two put calls. The parse is kept as one uint16 per
 // byte: 0 covered by a match, 1 a literal, else length | candidate index << 9 (candidates in the order 1, 3, P, P - 3, P + 3).
+//
+// The code builder below (build_lengths, canonical_codes, build_code, build_code_lz) is host only; csrc/pp_png_code_core.h
+// restates it as steps over fixed-size arrays that a workgroup runs (png_code) and gives the same bytes.
 #pragma once
 #include <algorithm>
 #include <cstddef>

@@ -22,9 +22,16 @@ the tile; the kernel resolves the chain by pointer doubling in LDS and stores th
 (``LAUNCHES_TOKENS_LZ``, ``LAUNCHES_DEFLATE_LZ``), still the host form's bytes. Opt-in: ``png_match="lz"`` of the
 visualizer, ``--png-match lz`` of the demo.
 
+``code="device"`` (``encode_batch``, ``zlib_compress_device``, ``imwrite_device``; ``"host"``, the default, is the round trip
+above) builds the codes on the device instead: one launch more (``LAUNCHES_CODE`` / ``LAUNCHES_CODE_LZ``: a workgroup per
+stream runs the steps of csrc/pp_png_code_core.h in LDS) between the halves, nine launches in all, no histogram download,
+no host build, no code upload, two synchronisations instead of three - and the same bytes, since the kernel gives the
+``pp_deflate_code`` of the host builder byte for byte. Opt-in: ``png_code="device"`` of the visualizer, ``--png-code device``
+of the demo.
+
 Not done: alpha, grey, palette, 16-bit and Adam7 pictures; a hash-table or general-window matcher (``lz`` mode finds a
 repeat only at the pixel and row distances above, so a picture whose repeats lie elsewhere stays larger than from zlib);
-lazy matching beyond one byte; reading PNG files (inflate); building the Huffman code on the device.
+lazy matching beyond one byte; reading PNG files (inflate); choosing ``code=`` by the batch's shape.
 """
 import ctypes
 import struct
@@ -40,6 +47,7 @@ from .staging import BatchStaging, StagedBlock, _align
 host_calls = 0  # pp_png_encode / pp_zlib_compress calls since import
 tokens_calls = 0  # pp_png_tokens_batch calls since import
 deflate_calls = 0  # pp_png_deflate_batch calls since import
+code_calls = 0  # pp_png_code_batch calls since import
 
 # pp_deflate_desc: seven pointers, len, capacity, width, height, row_stride, rgb, crc_init, period (lz mode, raw streams); pp_deflate_result
 _DESC = np.dtype([("pixels", "<u8"), ("data", "<u8"), ("hist", "<u8"), ("code", "<u8"), ("scratch", "<u8"), ("out", "<u8"), ("result", "<u8"),
@@ -56,6 +64,8 @@ HIST_BYTES_LZ = 4 * 320  # lz mode: the 288 words, then the counts of the 30 dis
 CODE_BYTES_LZ = 1600  # sizeof(pp_deflate_code_lz)
 LAUNCHES_TOKENS_LZ = ("png_filter", "png_clear_lz", "png_parse_lz")  # ... of pp_png_tokens_batch_lz
 LAUNCHES_DEFLATE_LZ = ("png_bits_lz", "png_scan_lz", "png_zero_lz", "png_pack_lz", "png_crc_lz")  # ... of pp_png_deflate_batch_lz
+LAUNCHES_CODE = ("png_code",)  # ... of pp_png_code_batch (code="device": between the two halves)
+LAUNCHES_CODE_LZ = ("png_code_lz",)  # ... of pp_png_code_batch_lz
 _SIGNATURE = b"\x89PNG\r\n\x1a\n"
 _IDAT_REGISTER = ~zlib.crc32(b"IDAT") & 0xFFFFFFFF  # the CRC-32 register in front of the stream's first byte
 
@@ -70,6 +80,12 @@ def _check_match(match) -> bool:
     if match not in ("runs", "lz"):
         raise ValueError(f"match must be 'runs' or 'lz', got {match!r}")
     return match == "lz"
+
+
+def _check_code(code) -> bool:
+    if code not in ("host", "device"):
+        raise ValueError(f"code must be 'host' or 'device', got {code!r}")
+    return code == "device"
 
 
 def _check_period(period, lz: bool) -> int:
@@ -223,14 +239,17 @@ def _launch_deflate(job: _Job, stream) -> None:
     deflate_calls += 1
 
 
-def _run(job: _Job) -> list:
-    """Both halves of a staged batch on the current stream and the code build between them: (zlib stream, CRC-32 register)
-    per entry."""
+def _launch_code(job: _Job, stream) -> None:
+    global code_calls
+    _lib.call("pp_png_code_batch_lz" if job.lz else "pp_png_code_batch", job.block.base, len(job.lens), stream.cuda_stream)
+    code_calls += 1
+
+
+def _build_codes_host(job: _Job, stream) -> None:
+    """The histograms down (one copy, one synchronisation), the codes built in the pinned buffer, the codes up (one copy)."""
     blk, n = job.block, len(job.lens)
     hist_bytes, code_bytes, build = (HIST_BYTES_LZ, CODE_BYTES_LZ, "pp_deflate_build_code_lz") if job.lz else (HIST_BYTES, CODE_BYTES, "pp_deflate_build_code")
-    staging, stream = blk.staging, torch.cuda.current_stream(blk.dev.device)
-    _launch_tokens(job, stream)
-    # the histograms down (one copy, one synchronisation), the codes built in the pinned buffer, the codes up (one copy)
+    staging = blk.staging
     o_h, o_c = blk.offset["hist"], blk.offset["code"]
     staging.buf[o_h:o_h + hist_bytes * n].copy_(blk.dev[o_h:o_h + hist_bytes * n], non_blocking=True)
     stream.synchronize()
@@ -239,6 +258,18 @@ def _run(job: _Job) -> list:
         _lib.call(build, hist + hist_bytes * i, code + code_bytes * i)
     blk.dev[o_c:o_c + code_bytes * n].copy_(staging.buf[o_c:o_c + code_bytes * n], non_blocking=True)
     staging.ev.record(stream)  # (the next user of the pinned buffer waits for this copy)
+
+
+def _run(job: _Job, device_code: bool = False) -> list:
+    """Both halves of a staged batch on the current stream and the code build between them - on the host, or with
+    ``device_code`` by one launch more and nothing else: (zlib stream, CRC-32 register) per entry."""
+    blk = job.block
+    staging, stream = blk.staging, torch.cuda.current_stream(blk.dev.device)
+    _launch_tokens(job, stream)
+    if device_code:
+        _launch_code(job, stream)
+    else:
+        _build_codes_host(job, stream)
     _launch_deflate(job, stream)
     res = blk.device("results").cpu().numpy().view(_RESULT)  # (waits for the stream: the launches have run)
     for i, r in enumerate(res):
@@ -257,16 +288,19 @@ def _run(job: _Job) -> list:
     return [(pinned[o:o + sz].tobytes(), int(r["crc"])) for o, sz, r in zip(offs, sizes, res)]
 
 
-def encode_batch(images: Sequence, channel_order: str = "bgr", device=None, staging=None, match: str = "runs") -> List[bytes]:
+def encode_batch(images: Sequence, channel_order: str = "bgr", device=None, staging=None, match: str = "runs", code: str = "host") -> List[bytes]:
     """PNG files of a batch of (H, W, 3) uint8 pictures (device tensors; a host array is uploaded first) of any mix of sizes,
     ``channel_order`` "bgr" or "rgb" in memory. Filters, tokens, bit packing and checksums run on the device: a batch of n
     pictures costs one upload (descriptors), the histogram round trip (one download, the codes built on the host, one
     upload), then 1 + n downloads (the result slots, then the used bytes of each stream) - three synchronisations - and
-    eight launches whatever n is, in either ``match`` mode. The files are byte for byte those of ``encode_host`` in that mode."""
+    eight launches whatever n is, in either ``match`` mode. With ``code="device"`` the codes are built by a ninth launch
+    between the halves: no histogram download, no host build, no code upload, two synchronisations. The files are byte for
+    byte those of ``encode_host`` in that ``match`` mode, whatever ``code`` is."""
     from .jpeg import _encoder_images
 
     rgb = _check_order(channel_order)
     lz = _check_match(match)
+    device_code = _check_code(code)
     if isinstance(images, (torch.Tensor, np.ndarray)):
         raise ValueError("encode_batch takes a sequence of (H, W, 3) images; imwrite_device takes one")
     images = list(images)
@@ -275,17 +309,19 @@ def encode_batch(images: Sequence, channel_order: str = "bgr", device=None, stag
     if len(images) == 0:
         return []
     images, dev = _encoder_images(images, device)
-    streams = _run(_stage(images, None, rgb, dev, staging if staging is not None else BatchStaging(), lz))
+    streams = _run(_stage(images, None, rgb, dev, staging if staging is not None else BatchStaging(), lz), device_code)
     return [_frame(im.shape[1], im.shape[0], z, register) for im, (z, register) in zip(images, streams)]
 
 
-def zlib_compress_device(buffers: Sequence, device=None, staging=None, match: str = "runs", period: int = 0) -> List[bytes]:
+def zlib_compress_device(buffers: Sequence, device=None, staging=None, match: str = "runs", period: int = 0, code: str = "host") -> List[bytes]:
     """The deflate stage alone: the zlib streams of a batch of byte strings (bytes or one-dimensional uint8 arrays of at
-    least one byte), coded on the device in seven launches - the streams ``zlib_compress_host`` gives with the same ``match``
-    and ``period`` (one period for the whole batch), which ``zlib.decompress`` turns back into the input."""
+    least one byte), coded on the device in seven launches (eight with ``code="device"``: the code build on the device, as in
+    ``encode_batch``) - the streams ``zlib_compress_host`` gives with the same ``match`` and ``period`` (one period for the
+    whole batch), which ``zlib.decompress`` turns back into the input."""
     from .jpeg import _cuda_device
 
     lz = _check_match(match)
+    device_code = _check_code(code)
     period = _check_period(period, lz)
     if isinstance(buffers, (bytes, bytearray, memoryview, np.ndarray)):
         raise ValueError("zlib_compress_device takes a sequence of byte strings")
@@ -293,11 +329,11 @@ def zlib_compress_device(buffers: Sequence, device=None, staging=None, match: st
     if len(raws) == 0:
         return []
     dev = _cuda_device(device or "cuda", "zlib_compress_device")
-    return [z for z, _ in _run(_stage(None, raws, 0, dev, staging if staging is not None else BatchStaging(), lz, period))]
+    return [z for z, _ in _run(_stage(None, raws, 0, dev, staging if staging is not None else BatchStaging(), lz, period), device_code)]
 
 
 def imwrite_device(path: str, image, **kw) -> None:
-    """One picture written as a PNG file by ``encode_batch`` (its keyword arguments)."""
+    """One picture written as a PNG file by ``encode_batch`` (its keyword arguments, ``match`` and ``code`` among them)."""
     data = encode_batch([image], **kw)[0]
     with open(path, "wb") as f:
         f.write(data)

@@ -172,17 +172,20 @@ class PoseLocalVisualizer:
     canvas, stacked under the pose panel. Everything is drawn on the GPU; ``add_datasample`` copies the image back once."""
 
     def __init__(self, name="visualizer", radius=3, line_width=1, alpha=0.8, device="cuda:0", image_encoder="host", png_encoder="host", png_match="runs",
-                 jpeg_optimize=False):
+                 jpeg_optimize=False, png_code="host"):
         if image_encoder not in ("host", "device"):
             raise ValueError(f"image_encoder must be 'host' or 'device', got {image_encoder!r}")
         if png_encoder not in ("host", "device"):
             raise ValueError(f"png_encoder must be 'host' or 'device', got {png_encoder!r}")
         if png_match not in ("runs", "lz"):
             raise ValueError(f"png_match must be 'runs' or 'lz', got {png_match!r}")
+        if png_code not in ("host", "device"):
+            raise ValueError(f"png_code must be 'host' or 'device', got {png_code!r}")
         self.image_encoder = image_encoder  # "device": a .jpg / .jpeg out_file is written by jpeg.imwrite_device
         self.png_encoder = png_encoder  # "device": a .png out_file is written by png.imwrite_device
         self.jpeg_optimize = bool(jpeg_optimize)  # that writer's optimize=: the picture's own Huffman tables (the same pixels, a smaller file)
         self.png_match = png_match  # the match mode of that writer: "runs", or "lz" (pixel and row distances: smaller files of drawn frames)
+        self.png_code = png_code  # where that writer builds its Huffman codes: "host" (a round trip between its halves), or "device" (one launch more)
         self.name = name
         self.radius = radius
         self.line_width = line_width
@@ -259,8 +262,8 @@ class PoseLocalVisualizer:
         built with ``image_encoder="device"`` and a ``.jpg`` / ``.jpeg`` name, by the split JPEG encoder from the frame on the
         device (Pillow's default quality 75 and 4:2:0: a file that decodes to the same pixels; ``jpeg_optimize=True``: with the
         Huffman tables of Pillow's ``optimize=True``, the same pixels again in fewer bytes); with ``png_encoder="device"`` a
-        ``.png`` name is written by the device PNG writer (``png.imwrite_device`` in the visualizer's ``png_match`` mode: the same
-        pixels, other bytes than Pillow's).
+        ``.png`` name is written by the device PNG writer (``png.imwrite_device`` in the visualizer's ``png_match`` mode, its codes
+        built where ``png_code`` says: the same pixels, other bytes than Pillow's).
         ``draw_datasample`` plus the copy to the host and the file."""
         if draw_gt:
             raise NotImplementedError("draw_gt: ground-truth drawing is outside ProbPose's demo")
@@ -280,7 +283,7 @@ class PoseLocalVisualizer:
             elif self.png_encoder == "device" and str(out_file).lower().endswith(".png"):
                 from . import png
 
-                png.imwrite_device(out_file, out, channel_order="rgb", match=self.png_match)
+                png.imwrite_device(out_file, out, channel_order="rgb", match=self.png_match, code=self.png_code)
             else:
                 from PIL import Image
 

@@ -13,9 +13,15 @@ line per figure.
 
 ``--match lz`` measures the ``lz`` match mode in place of the run coder; ``--match both`` alternates the two modes inside every
 round of the same process (path "device" is runs, "device_lz" is lz; the files' sizes and the launches of both). With
-``--parent-lib PATH`` (an earlier build of the library) the runs launches of that build are timed in the same alternation.
+``--parent-lib PATH`` (an earlier build of the library) the launches of that build are timed in the same alternation
+(paths "parent_runs", "parent_lz"): its spread across the rounds (min_us .. max_us) is the yardstick for "did not move".
 
-    python scripts/bench_png_encode.py [--rounds 7] [--match runs|lz|both] [--parent-lib PATH]"""
+``--code device`` measures ``code="device"`` (the codes built by a ninth launch, no round trip) in place of the host build;
+``--code both`` alternates the two inside every round: the write calls as paths "device" / "device_lz" (host build) and
+"device_devcode" / "device_lz_devcode", and beside the two halves of the host build the nine launches of the device build
+(tokens, code, deflate) in ONE event pair. ``--device-only`` leaves the Pillow paths out.
+
+    python scripts/bench_png_encode.py [--rounds 7] [--match runs|lz|both] [--code host|device|both] [--parent-lib PATH] [--device-only]"""
 import argparse
 import ctypes
 import io
@@ -55,10 +61,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--match", default="runs", choices=["runs", "lz", "both"])
-    ap.add_argument("--parent-lib", default=None, help="an earlier build of libprobpose_mi355x.so: its runs launches are timed beside this build's")
+    ap.add_argument("--code", default="host", choices=["host", "device", "both"])
+    ap.add_argument("--parent-lib", default=None, help="an earlier build of libprobpose_mi355x.so: its launches are timed beside this build's")
+    ap.add_argument("--device-only", action="store_true", help="leave the Pillow paths out of the write calls")
     args = ap.parse_args()
     modes = ("runs", "lz") if args.match == "both" else (args.match,)
+    codes = ("host", "device") if args.code == "both" else (args.code,)
     label = {"runs": "device", "lz": "device_lz"}
+    suffix = {"host": "", "device": "_devcode"}
 
     import torch
     from PIL import Image
@@ -74,6 +84,8 @@ def main():
         P = ctypes.c_void_p
         parent.pp_png_tokens_batch.argtypes = [P, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, P]
         parent.pp_png_deflate_batch.argtypes = [P, ctypes.c_int, ctypes.c_longlong, P]
+        parent.pp_png_tokens_batch_lz.argtypes = parent.pp_png_tokens_batch.argtypes
+        parent.pp_png_deflate_batch_lz.argtypes = parent.pp_png_deflate_batch.argtypes
 
     def pil_save(arr, level):
         b = io.BytesIO()
@@ -91,6 +103,7 @@ def main():
         default, level1 = len(pil_save(host_frames[0], None)), len(pil_save(host_frames[0], 1))
         for m in modes:
             ours = png.encode_batch(frames[:1], channel_order="rgb", staging=staging, match=m)[0]
+            assert all(png.encode_batch(frames[:1], channel_order="rgb", staging=staging, match=m, code=c)[0] == ours for c in codes), "code= changes the file"
             with Image.open(io.BytesIO(ours)) as a:
                 assert np.array_equal(np.asarray(a), host_frames[0]), "the file does not hold the pixels"
             print(json.dumps(dict(figure="file", size=size, match=m, device_file_bytes=len(ours), pillow_default_bytes=default,
@@ -99,11 +112,15 @@ def main():
         for n in (1, 16):
             for threads in ((1,) if n == 1 else (1, 8)):
                 with ThreadPoolExecutor(max_workers=threads) as pool:
-                    paths = {
+                    paths = {} if args.device_only else {
                         "host_png": lambda: list(pool.map(lambda a: pil_save(a, None), [f.cpu().numpy() for f in frames[:n]])),
                         "host_png_l1": lambda: list(pool.map(lambda a: pil_save(a, 1), [f.cpu().numpy() for f in frames[:n]])),
-                        **{label[m]: (lambda m=m: png.encode_batch(frames[:n], channel_order="rgb", staging=staging, match=m)) for m in modes},
                     }
+                    if args.device_only and threads > 1:
+                        continue  # (the threads are the host paths')
+                    for m in modes:
+                        for c in codes:
+                            paths[label[m] + suffix[c]] = lambda m=m, c=c: png.encode_batch(frames[:n], channel_order="rgb", staging=staging, match=m, code=c)
                     times = {k: [] for k in paths}
                     for fn in paths.values():
                         fn()  # warm-up
@@ -122,13 +139,18 @@ def main():
             jobs = {m: png._stage(frames[:n], None, 1, dev, staging, m == "lz") for m in modes}
             for job in jobs.values():
                 png._run(job)  # (leaves the codes of these frames on the device: the timed launches below need no host in between)
-            halves = {label[m]: ((lambda j=j: png._launch_tokens(j, stream)), (lambda j=j: png._launch_deflate(j, stream))) for m, j in jobs.items()}
-            if parent is not None and "runs" in jobs:
-                j = jobs["runs"]
-                halves["parent_runs"] = (
-                    lambda: parent.pp_png_tokens_batch(j.block.base, len(j.lens), j.max_height, max(j.lens), stream.cuda_stream),
-                    lambda: parent.pp_png_deflate_batch(j.block.base, len(j.lens), max(j.lens), stream.cuda_stream))
-            us = {k: {"both": [], "tokens": [], "deflate": []} for k in halves}
+            halves, nine = {}, {}
+            for m, j in jobs.items():
+                if "host" in codes:
+                    halves[label[m]] = ((lambda j=j: png._launch_tokens(j, stream)), (lambda j=j: png._launch_deflate(j, stream)))
+                if "device" in codes:  # tokens, code, deflate with nothing between them: one event pair
+                    nine[label[m] + "_devcode"] = lambda j=j: (png._launch_tokens(j, stream), png._launch_code(j, stream), png._launch_deflate(j, stream))
+                if parent is not None:
+                    lz = "_lz" if m == "lz" else ""
+                    halves["parent_" + m] = (
+                        lambda j=j, f=getattr(parent, "pp_png_tokens_batch" + lz): f(j.block.base, len(j.lens), j.max_height, max(j.lens), stream.cuda_stream),
+                        lambda j=j, f=getattr(parent, "pp_png_deflate_batch" + lz): f(j.block.base, len(j.lens), max(j.lens), stream.cuda_stream))
+            us = {k: {"both": [], "tokens": [], "deflate": []} for k in list(halves) + list(nine)}
             for _ in range(3 + args.rounds):
                 for k, (tokens, deflate) in halves.items():  # the modes (and builds) alternate inside a round
                     e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
@@ -141,13 +163,20 @@ def main():
                     us[k]["tokens"].append(e[0].elapsed_time(e[1]) * 1e3)
                     us[k]["deflate"].append(e[1].elapsed_time(e[2]) * 1e3)
                     us[k]["both"].append(e[0].elapsed_time(e[2]) * 1e3)
+                for k, all_nine in nine.items():
+                    e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                    e[0].record()
+                    all_nine()
+                    e[1].record()
+                    e[1].synchronize()
+                    us[k]["both"].append(e[0].elapsed_time(e[1]) * 1e3)
             sclk = shader_clock()  # right behind the timed launches
             for k, u in us.items():
-                print(json.dumps(dict(figure="launches", size=size, path=k, n=n, device_event_us=round(statistics.median(u["both"][3:]), 1),
-                                      tokens_us=round(statistics.median(u["tokens"][3:]), 1), deflate_us=round(statistics.median(u["deflate"][3:]), 1),
+                split = dict(tokens_us=round(statistics.median(u["tokens"][3:]), 1), deflate_us=round(statistics.median(u["deflate"][3:]), 1)) if k in halves else {}
+                print(json.dumps(dict(figure="launches", size=size, path=k, n=n, device_event_us=round(statistics.median(u["both"][3:]), 1), **split,
                                       min_us=round(min(u["both"][3:]), 1), max_us=round(max(u["both"][3:]), 1),
                                       stream_bytes=int(sum(next(iter(jobs.values())).lens)), sclk_mhz=sclk, rounds=args.rounds)), flush=True)
-            del jobs, halves
+            del jobs, halves, nine
 
 
 if __name__ == "__main__":
