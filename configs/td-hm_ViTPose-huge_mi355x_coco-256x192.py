@@ -6,10 +6,12 @@
 # head-dim-80 kernel (csrc/pp_attention_hd80.hip).
 #   python tools/test.py configs/td-hm_ViTPose-huge_mi355x_coco-256x192.py CHECKPOINT \
 #       --cfg-options test_dataloader.dataset.data_root=/data/coco/
-# NOT mirrored: the reference evaluates this model on the boxes of a person detector (`bbox_file=...detections_AP_H_56_person.json`).
-# Evaluation on detector boxes is not implemented here (CocoDataset refuses `bbox_file`); this config evaluates on the
-# GROUND-TRUTH boxes of the annotation file, like the ViTPose-small and ProbPose configs - the models are then compared on equal
-# boxes, but the AP is not the number the reference's config reports.
+# The reference evaluates this model on the boxes of a person detector (`bbox_file=...detections_AP_H_56_person.json`). To mirror
+# that evaluation, pass the detections file on the command line (detector score x mean keypoint score, OKS-NMS per image):
+#   python tools/test.py configs/td-hm_ViTPose-huge_mi355x_coco-256x192.py CHECKPOINT --bbox-file COCO_val2017_detections_AP_H_56_person.json [--nms device]
+# The dataset dict below stays without `bbox_file` (CocoDataset still refuses it: the detections enter beside the dataset, as
+# datasets.DetectionBoxes); without the flag this config evaluates on the GROUND-TRUTH boxes of the annotation file, like the
+# ProbPose configs - the models are then compared on equal boxes, but that AP is not the number the reference's config reports.
 custom_imports = dict(imports=["probpose_code_amd"], allow_failed_imports=False)
 default_scope = "mmpose"
 

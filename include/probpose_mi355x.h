@@ -1181,6 +1181,32 @@ int pp_png_deflate_batch_lz(const pp_deflate_desc* descriptors, int n, long long
 int pp_png_code_batch_lz(const pp_deflate_desc* descriptors, int n, void* stream);
 int pp_deflate_build_code_steps_lz(const uint32_t* hist_host, pp_deflate_code_lz* code_host);
 
+/* Greedy OKS suppression (oks_nms with oks_iou, mmpose/evaluation/functional/nms.py:58-170, no vis_thr) of every image of a
+ * dataset at once (csrc/pp_oks_nms.hip; added under version 4: purely additive). The instances of image i are rows
+ * [img_off_host[i], img_off_host[i + 1]) of the flat arrays, ALREADY in that image's suppression order (descending score as
+ * the caller's sort gives it: the tie order is the caller's). img_off_host (n_images + 1) is a HOST array: it starts at 0,
+ * never decreases and ends at n_instances (checked). Device arrays: kpts (n_instances, K, 3) float64 = x, y and a third value
+ * that is not read; areas (n_instances) float64; sigmas (K) float64. Per pair, in fp64 and numpy's operation order,
+ *   e = (dx^2 + dy^2) / (2 sigma)^2 / ((a_i + a_j) / 2 + spacing(1)) / 2,   oks = sum_k exp(-e) / K
+ * (area_f32 != 0: the areas are float32 values and (a_i + a_j) / 2 is formed in float32, as numpy does for a float32 area
+ * array), and a kept row i removes every later row j with float32(oks) > float32(thr); a NaN oks removes.
+ * keep (n_instances) uint8: 1 = kept. status (n_images) int32:
+ *   PP_OKS_NMS_DECIDED    keep is the reference's;
+ *   PP_OKS_NMS_UNDECIDED  some pair's fp64 oks lies within `guard` of the float32 rounding midpoint above float32(thr), where
+ *                         the last bits of exp() decide: the caller runs the image on the host (its keep bytes are a valid
+ *                         greedy result of the device's own values, not relied upon);
+ *   PP_OKS_NMS_HOST       the image holds more than PP_OKS_NMS_MAX_PER_IMAGE instances (its keep bytes are 0).
+ * workspace: pp_oks_nms_workspace_bytes(...) bytes, 8-byte aligned. Two launches (oks_nms_pairs, oks_nms_sweep) behind one
+ * small table upload that is complete when the call returns; the same bytes launch after launch. */
+#define PP_OKS_NMS_MAX_PER_IMAGE 4096
+#define PP_OKS_NMS_DECIDED 0
+#define PP_OKS_NMS_UNDECIDED 1
+#define PP_OKS_NMS_HOST 2
+long long pp_oks_nms_workspace_bytes(const long long* img_off_host, long long n_instances, int n_images);
+int pp_oks_nms_batch(const double* kpts, const double* areas, const long long* img_off_host, const double* sigmas,
+                     long long n_instances, int n_images, int K, double thr, double guard, int area_f32, void* workspace,
+                     long long workspace_bytes, unsigned char* keep, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

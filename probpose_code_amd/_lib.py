@@ -24,6 +24,8 @@ PP_ERR_HIP = -3
 PP_ERR_WORKSPACE = -4
 PP_MAX_RADIUS = 9
 PP_MAX_TAPS = 2 * PP_MAX_RADIUS + 1
+PP_OKS_NMS_MAX_PER_IMAGE = 4096
+PP_OKS_NMS_DECIDED, PP_OKS_NMS_UNDECIDED, PP_OKS_NMS_HOST = 0, 1, 2
 
 
 class ProbPoseLibraryError(RuntimeError):
@@ -204,6 +206,9 @@ SIGNATURES = {
     "pp_png_code_batch_lz": (c_int, [_P, c_int, _P]),
     "pp_deflate_build_code_steps": (c_int, [_P, _P]),
     "pp_deflate_build_code_steps_lz": (c_int, [_P, _P]),
+    "pp_oks_nms_workspace_bytes": (c_longlong, [_P, c_longlong, c_int]),
+    "pp_oks_nms_batch": (
+        c_int, [_P, _P, _P, _P, c_longlong, c_int, c_int, c_double, c_double, c_int, _P, c_longlong, _P, _P, _P]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

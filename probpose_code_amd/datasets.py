@@ -5,7 +5,9 @@
 The instance parsing follows mmpose/datasets/datasets/base/base_coco_style_dataset.py (cited per method) and the sample
 access mmengine's ``BaseDataset`` [3P] (``get_data_info`` = a copy of the parsed instance + ``sample_idx``). ``COCO`` is the
 slice of the ``xtcocotools.COCO`` index [3P] those methods call. Not built (``NotImplementedError``): detector boxes
-(``bbox_file``), bottom-up mode, ``filter_cfg``, ``indices``, ``sample_interval != 1``.
+(``bbox_file``), bottom-up mode, ``filter_cfg``, ``indices``, ``sample_interval != 1``. Detector boxes enter beside the
+dataset instead: ``DetectionBoxes(dataset, bbox_file, bbox_score_thr)`` is a view of a built dataset whose samples are the
+boxes of a detections file.
 """
 import copy
 import json
@@ -342,6 +344,111 @@ class CombinedDataset:
 
     def __getitem__(self, idx: int) -> Optional[dict]:
         return self.pipeline(self.get_data_info(idx))
+
+
+class DetectionBoxes:
+    """The person boxes of a detector in place of a dataset's ground-truth boxes: a view of a built ``CocoDataset`` /
+    ``CocoCropDataset`` whose samples are the reference's ``_load_detection_results`` (base_coco_style_dataset.py:430-486)
+    over ``bbox_file`` followed by ``filter_data``'s ``bbox_score_thr`` rule (:488-514). It offers what the test loop and
+    ``runner.build_evaluator`` read of a dataset (``len``, ``get_data_info``, ``[]``, ``pipeline``, ``metainfo``, ``ann_file``,
+    the class's ``DATASET_NAME``). The dataset constructors themselves still refuse ``bbox_file`` / ``filter_cfg``.
+
+    ``bbox_file``: a JSON list of ``{image_id, category_id, bbox: [x, y, w, h], score[, segmentation]}``. Entries in file
+    order; ``category_id != 1`` skipped; ``bbox`` float32 xyxy, NOT clipped to the image; ``bbox_score`` float32 (1,);
+    keypoints zero, ``keypoints_visible`` one; ``id`` counts the kept entries from 0. An instance with
+    ``bbox_score < bbox_score_thr`` (strict, in the array's dtype) is dropped afterwards, so ids keep their gaps."""
+
+    DATASET_NAME = "coco"
+    _views: Dict[str, type] = {}
+
+    def __new__(cls, dataset=None, *args, **kwargs):
+        if cls is DetectionBoxes and isinstance(dataset, BaseCocoStyleDataset):  # the view class that carries the dataset's name
+            cls = DetectionBoxes._views.get(type(dataset).DATASET_NAME, cls)
+        return super().__new__(cls)
+
+    def __init__(self, dataset, bbox_file: str, bbox_score_thr: Optional[float] = None):
+        if isinstance(dataset, CombinedDataset):
+            raise NotImplementedError("DetectionBoxes: a CombinedDataset is not supported (detector boxes are read for one "
+                                      "CocoDataset / CocoCropDataset; wrap the sub-dataset that has a detections file)")
+        if not isinstance(dataset, BaseCocoStyleDataset):
+            raise TypeError(f"DetectionBoxes wraps a built CocoDataset / CocoCropDataset, got {type(dataset).__name__}")
+        if type(dataset).DATASET_NAME != type(self).DATASET_NAME:
+            raise TypeError(f"{type(self).__name__} views a {type(self).DATASET_NAME!r} dataset, got {type(dataset).DATASET_NAME!r}")
+        dataset.full_init()
+        self.dataset, self.bbox_file, self.bbox_score_thr = dataset, bbox_file, bbox_score_thr
+        self.ann_file, self.pipeline, self.test_mode = dataset.ann_file, dataset.pipeline, dataset.test_mode
+        self.data_list = self._load_detection_results()
+        if bbox_score_thr is not None:  # filter_data (:511-512)
+            self.data_list = [d for d in self.data_list if not d["bbox_score"] < bbox_score_thr]
+
+    @property
+    def metainfo(self) -> dict:
+        return self.dataset.metainfo
+
+    def _load_detection_results(self) -> List[dict]:
+        if not osp.isfile(self.bbox_file):
+            raise FileNotFoundError(f"Bbox file `{self.bbox_file}` does not exist")
+        with open(self.bbox_file) as f:
+            det_results = json.load(f)
+        if not (isinstance(det_results, list) and all(isinstance(d, dict) for d in det_results)):
+            raise TypeError(f"BBox file `{self.bbox_file}` should be a list of dict, but got {type(det_results)}")
+        coco = self.dataset.coco
+        num_keypoints = self.dataset._metainfo["num_keypoints"]
+        data_list = []
+        for n, det in enumerate(det_results):
+            if det["category_id"] != 1:  # non-human instances
+                continue
+            if det["image_id"] not in coco.imgs:
+                raise KeyError(f"BBox file `{self.bbox_file}`: entry {n} names image_id {det['image_id']!r}, which the annotation "
+                               f"file `{self.ann_file}` does not have")
+            img = coco.loadImgs(det["image_id"])[0]
+            bbox = np.array(det["bbox"][:4], dtype=np.float32).reshape(1, 4)
+            bbox[:, 2:] = bbox[:, 2:] + bbox[:, :2]  # bbox_xywh2xyxy, in float32
+            data_list.append({
+                "img_id": det["image_id"],
+                "img_path": osp.join(self.dataset.data_prefix["img"], img["file_name"]),
+                "img_shape": (img["height"], img["width"]),
+                "bbox": bbox,
+                "bbox_score": np.array(det["score"], dtype=np.float32).reshape(1),
+                "keypoints": np.zeros((1, num_keypoints, 2), dtype=np.float32),
+                "keypoints_visible": np.ones((1, num_keypoints), dtype=np.float32),
+                "id": len(data_list),
+                "segmentation": det.get("segmentation", None),
+            })
+        return data_list
+
+    def get_data_info(self, idx: int) -> dict:
+        """As the wrapped dataset's: a copy + ``sample_idx``, then the metainfo keys."""
+        data_info = copy.deepcopy(self.data_list[idx])
+        data_info["sample_idx"] = idx if idx >= 0 else len(self) + idx
+        for key in self.dataset.METAINFO_KEYS:
+            assert key not in data_info, f'"{key}" is a reserved key for `metainfo`, but already exists in the `data_info`.'
+            data_info[key] = copy.deepcopy(self.dataset._metainfo[key])
+        return data_info
+
+    def __len__(self) -> int:
+        return len(self.data_list)
+
+    def __getitem__(self, idx: int) -> Optional[dict]:
+        return self.pipeline(self.get_data_info(idx))
+
+
+@DATASETS.register_module(name="CocoDetectionBoxes", force=True)
+class CocoDetectionBoxes(DetectionBoxes):
+    """``DetectionBoxes`` over a ``CocoDataset`` (what ``DetectionBoxes(dataset, ...)`` returns for one): the class carries the
+    ``DATASET_NAME`` that pairs its samples with their metric."""
+
+    DATASET_NAME = "coco"
+
+
+@DATASETS.register_module(name="CocoCropDetectionBoxes", force=True)
+class CocoCropDetectionBoxes(DetectionBoxes):
+    """``DetectionBoxes`` over a ``CocoCropDataset``."""
+
+    DATASET_NAME = "coco_crop"
+
+
+DetectionBoxes._views.update(coco=CocoDetectionBoxes, coco_crop=CocoCropDetectionBoxes)
 
 
 def build_dataset(cfg):

@@ -411,6 +411,43 @@ def oks_nms(kpts_db, thr, sigmas=None, vis_thr=None, score_per_joint=False):
     return np.array(keep)
 
 
+OKS_NMS_GUARD = 2.0 ** -40  # |fp64 oks - midpoint| at or below this: numpy's last bits decide, the image goes to the host
+
+
+def oks_nms_midpoint(thr) -> float:
+    """``oks_nms`` compares float32(oks) with float32(thr): an fp64 oks above the rounding midpoint between float32(thr) and
+    its float32 successor suppresses, one below does not. That midpoint, as a double."""
+    t = np.float32(thr)
+    return (float(t) + float(np.nextafter(t, np.float32(np.inf)))) / 2
+
+
+def oks_nms_batch(kpts, areas, img_off, thr, sigmas=None, guard=OKS_NMS_GUARD, area_f32=False, device="cuda"):
+    """``oks_nms`` of every image in two launches (pp_oks_nms_batch). ``kpts`` (N, K, 3) and ``areas`` (N,) of all images'
+    instances, each image's rows ALREADY in its suppression order (``scores.argsort()[::-1]``); ``img_off`` (I + 1,) row
+    offsets. ``area_f32``: the areas are float32 values whose pair mean numpy forms in float32. Returns host arrays
+    ``keep`` (N,) uint8 and ``status`` (I,) int32: ``_lib.PP_OKS_NMS_DECIDED`` (keep is ``oks_nms``'s), ``_UNDECIDED`` (a pair lies
+    within ``guard`` of ``oks_nms_midpoint(thr)``) or ``_HOST`` (more than ``_lib.PP_OKS_NMS_MAX_PER_IMAGE`` instances); the caller
+    runs ``oks_nms`` for the latter two."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("probpose_code_amd.evaluation.oks_nms_batch runs on the GPU only (no CPU fallback)")
+    sg = _dev64(COCO_SIGMAS if sigmas is None else sigmas, device)
+    off = np.ascontiguousarray(img_off, np.int64)
+    N, n_img, K = int(off[-1]), len(off) - 1, sg.numel()
+    kp = _dev64(np.asarray(kpts, np.float64).reshape(N, K, 3), device)
+    ar = _dev64(np.asarray(areas).reshape(N), device)
+    size = int(_lib.lib.pp_oks_nms_workspace_bytes(off.ctypes.data, N, n_img))
+    if size < 0:
+        raise _lib.ProbPoseLibraryError("pp_oks_nms_workspace_bytes", _lib.lib.pp_status_string(size).decode(), _lib.last_error())
+    ws = torch.empty(max(size // 8, 1), dtype=torch.int64, device=device)
+    keep = torch.empty(max(N, 1), dtype=torch.uint8, device=device)
+    status = torch.empty(max(n_img, 1), dtype=torch.int32, device=device)
+    _lib.call("pp_oks_nms_batch", kp.data_ptr() if N else None, ar.data_ptr() if N else None, off.ctypes.data, sg.data_ptr(), N, n_img, K,
+              float(thr), float(guard), int(bool(area_f32)), ws.data_ptr(), size, keep.data_ptr(), status.data_ptr(),
+              torch.cuda.current_stream(device).cuda_stream)
+    return keep[:N].cpu().numpy(), status[:n_img].cpu().numpy()
+
+
 def nms(dets, thr):
     """Greedy box suppression of the multi-person demo (mmpose/evaluation/functional/nms.py:16-55): ``dets`` (N, 5)
     [x1, y1, x2, y2, score]; keep the highest score, drop boxes that overlap it by more than ``thr`` (IoU with the
@@ -512,13 +549,18 @@ class CocoMetric:
     def __init__(self, gt_annotations=None, use_area=True, iou_type="keypoints", score_mode="bbox_keypoint", score_thresh_type="score",
                  keypoint_score_thr=0.2, nms_mode="oks_nms", nms_thr=0.9, prefix=None, extended=(False,), match_by_bbox=(False,),
                  ignore_border_points=(False,), ignore_stats=(), padding=1.25, prob_thr=None, sigmas=None, device="cuda",
-                 outfile_prefix=None, format_only=False):
+                 outfile_prefix=None, format_only=False, nms_backend="host", nms_guard=OKS_NMS_GUARD):
         if score_mode not in ("bbox", "bbox_keypoint", "bbox_rle", "keypoint"):
             raise ValueError(f"`score_mode` should be one of 'bbox', 'bbox_keypoint', 'bbox_rle', but got {score_mode}")
         if score_thresh_type not in ("score", "prob"):
             raise ValueError("'score_thresh_type' should be one of 'score' or 'prob'")
         if nms_mode not in ("oks_nms", "soft_oks_nms", "none"):
             raise ValueError("`nms_mode` should be one of 'oks_nms', 'soft_oks_nms', " f"'none', but got {nms_mode}")
+        if nms_backend not in ("host", "device"):
+            raise ValueError(f"`nms_backend` should be 'host' or 'device', but got {nms_backend!r}")
+        if nms_backend == "device" and nms_mode == "soft_oks_nms":
+            raise ValueError("nms_backend='device' does not serve nms_mode='soft_oks_nms': soft suppression re-sorts the decayed scores "
+                             "after every pick, and numpy's tie order cannot be reproduced on the device; it stays on the host")
         if format_only:  # coco_metric.py:156-162
             assert outfile_prefix is not None, ("`outfile_prefix` can not be None when `format_only` is True, otherwise the result "
                                                 "file will be saved to a temp directory which will be cleaned up in the end.")
@@ -543,6 +585,8 @@ class CocoMetric:
         self.device = device
         self.has_probability = True
         self.results = []
+        self.nms_backend, self.nms_guard = nms_backend, nms_guard
+        self.nms_fallbacks = 0  # images of the last device suppression that the host decided (undecided or above the capacity)
 
     def process(self, data_batch, data_samples):
         """One batch of ``PoseDataSample``-like dicts (``to_dict()``) -> ``self.results`` (coco_metric.py:236-358)."""
@@ -591,17 +635,59 @@ class CocoMetric:
             persons = sorted(persons, key=lambda x: x["id"])
             per_img[img_id] = [p for n, p in enumerate(persons) if n == 0 or p["id"] != persons[n - 1]["id"]]
         valid = {}
+        on_device = self.nms_backend == "device" and self.nms_mode == "oks_nms"
         for img_id, persons in per_img.items():  # :541-583
             for p in persons:
                 p["keypoints"] = np.concatenate([p["keypoints"], np.asarray(p["keypoint_probs"])[:, None]], axis=-1)
                 p["score"] = instance_score(p["bbox_score"], p["keypoint_scores"], p["keypoint_probs"], self.score_mode,
                                             self.score_thresh_type, self.keypoint_score_thr)
+            if on_device:
+                continue
             if self.nms_mode == "none":
                 valid[img_id] = persons
             else:
                 nms = oks_nms if self.nms_mode == "oks_nms" else soft_oks_nms  # coco_metric.py:576
                 valid[img_id] = [persons[k] for k in nms(persons, self.nms_thr, sigmas=self.sigmas)]
-        return valid
+        return self._oks_nms_device(per_img) if on_device else valid
+
+    def _oks_nms_device(self, per_img):
+        """``oks_nms`` of every image in one ``oks_nms_batch`` call. Each image's order is numpy's own (the call ``oks_nms`` makes:
+        its tie order is not a stable sort's), the arrays are those ``oks_nms`` builds; an image whose arrays numpy would not
+        process in fp64 (keypoints that are not float64, areas that are neither float32 nor float64), and every image when the
+        threshold is not a plain finite number, is the host's, as is one the device reports undecided or too large."""
+        K = len(self.sigmas)
+        host, batch, kpts, areas, off = set(), [], [], [], [0]
+        f32 = None
+        # (a numpy float64 threshold would make `ovr <= thr` an fp64 comparison: not the rule the device restates)
+        thr_ok = type(self.nms_thr) in (int, float) and bool(np.isfinite(self.nms_thr))
+        for img_id, persons in per_img.items():
+            scores = np.array([p["score"] for p in persons])
+            kp = np.array([np.asarray(p["keypoints"]).flatten() for p in persons])
+            ar = np.array([p["area"] for p in persons])
+            ok = thr_ok and kp.dtype == np.float64 and kp.shape == (len(persons), K * 3) and ar.dtype in (np.float32, np.float64) \
+                and ar.shape == (len(persons),) and scores.ndim == 1
+            if ok and f32 is None:
+                f32 = ar.dtype == np.float32
+            if not ok or (ar.dtype == np.float32) != f32:  # (one area dtype per call)
+                host.add(img_id)
+                continue
+            order = scores.argsort()[::-1]
+            batch.append((img_id, order))
+            kpts.append(kp[order])
+            areas.append(ar[order])
+            off.append(off[-1] + len(persons))
+        if batch:
+            keep, status = oks_nms_batch(np.concatenate(kpts), np.concatenate(areas), off, self.nms_thr, self.sigmas, self.nms_guard,
+                                         bool(f32), self.device)
+        kept = {}
+        for n, (img_id, order) in enumerate(batch):
+            if status[n] == _lib.PP_OKS_NMS_DECIDED:
+                kept[img_id] = order[keep[off[n]:off[n + 1]].astype(bool)]
+            else:
+                host.add(img_id)
+        self.nms_fallbacks = len(host)
+        return {img_id: [persons[k] for k in (oks_nms(persons, self.nms_thr, sigmas=self.sigmas) if img_id in host else kept[img_id])]
+                for img_id, persons in per_img.items()}
 
     def _gt_list(self):
         if hasattr(self.gt, "loadAnns"):

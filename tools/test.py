@@ -6,7 +6,14 @@
         --cfg-options test_dataloader.dataset.datasets.0.data_root=/data/CropCOCO/ \
                       test_dataloader.dataset.datasets.1.data_root=/data/coco/ --out metrics.json
 
-CHECKPOINT may be "synthetic" (seeded random weights: a plumbing check, as in demo/image_demo.py)."""
+CHECKPOINT may be "synthetic" (seeded random weights: a plumbing check, as in demo/image_demo.py).
+
+On the boxes of a person detector instead (the COCO top-down protocol: every box scored detector score x mean keypoint score,
+duplicates removed by OKS-NMS per image), for a single-dataset config:
+
+    python tools/test.py configs/td-hm_ViTPose-base_mi355x_coco-256x192.py CHECKPOINT \
+        --cfg-options test_dataloader.dataset.data_root=/data/coco/ \
+        --bbox-file /data/coco/person_detection_results/COCO_val2017_detections_AP_H_56_person.json --nms device"""
 import ast
 import json
 import os
@@ -48,13 +55,22 @@ def main(argv=None):
                     help="device (needs --decode device): the files' Huffman codes are decoded on the GPU as well (the same pixels)")
     ap.add_argument("--precision", default=None, choices=[None, "f16x3", "bf16", "f32"],
                     help="overrides model.precision of the config (default there: f16x3)")
+    ap.add_argument("--bbox-file", default=None, metavar="FILE",
+                    help="evaluate on the person boxes of this detections file (a JSON list of image_id / category_id / bbox xywh / "
+                         "score) instead of the ground-truth boxes; single-dataset configs")
+    ap.add_argument("--bbox-score-thr", type=float, default=None, metavar="T",
+                    help="with --bbox-file: drop boxes whose score is below T before the model sees them")
+    ap.add_argument("--nms", default="host", choices=["host", "device"],
+                    help="where the metric's OKS-NMS runs (CocoMetric nms_backend); device: all images in two launches, the same kept sets")
     args = ap.parse_args(argv)
+    if args.bbox_score_thr is not None and not args.bbox_file:
+        ap.error("--bbox-score-thr needs --bbox-file")
     if args.decode_entropy == "device" and args.decode != "device":
         ap.error("--decode-entropy device needs --decode device")
 
     from probpose_code_amd import apis, runner, synthetic
     from probpose_code_amd.config import Config
-    from probpose_code_amd.datasets import build_dataset
+    from probpose_code_amd.datasets import DetectionBoxes, build_dataset
 
     cfg = Config.fromfile(args.config)
     opts = parse_cfg_options(args.cfg_options)
@@ -68,7 +84,15 @@ def main(argv=None):
     model = apis.init_model(cfg, ckpt, device=args.device)
     loader = cfg["test_dataloader"]
     dataset = build_dataset(loader["dataset"])
-    evaluator = runner.build_evaluator(cfg["test_evaluator"], dataset, device=args.device)
+    if args.bbox_file:
+        dataset = DetectionBoxes(dataset, args.bbox_file, args.bbox_score_thr)
+    ev_cfg = dict(cfg["test_evaluator"])
+    if args.nms != "host":  # (a metric config's own nms_backend stands when the flag is left at its default)
+        if "metrics" in ev_cfg:
+            ev_cfg["metrics"] = [dict(m, nms_backend=args.nms) if isinstance(m, dict) else m for m in ev_cfg["metrics"]]
+        else:
+            ev_cfg["nms_backend"] = args.nms
+    evaluator = runner.build_evaluator(ev_cfg, dataset, device=args.device)
     batch_size = args.batch_size or int(loader.get("batch_size", 64))
     t0 = time.perf_counter()
     metrics = runner.test_dataset(model, dataset, evaluator, batch_size=batch_size, workers=args.workers, decode=args.decode,
