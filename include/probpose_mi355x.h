@@ -29,7 +29,8 @@ extern "C" {
 #endif
 
 /* 4 (round 6): + pp_warp_affine_u8_batch (additive); + pp_parea_scratch_bytes, pp_parea_thresholds, pp_parea_compose, pp_draw_poses, pp_resize_bilinear_u8 (the --draw-heatmap
- *    picture, csrc/pp_render.hip; added later under the same version: purely additive); the numeric domain of PP_PREC_F16X3 stated and guarded (below); power-of-two WEIGHT SCALES: + pp_gemm_ws, pp_linear_ln_folded_ws,
+ *    picture, csrc/pp_render.hip; added later under the same version: purely additive); + pp_render_batch_scratch_bytes, pp_render_samples_batch (the pictures of a batch of samples in one
+ *    set of launches, csrc/pp_render_batch.hip; additive); the numeric domain of PP_PREC_F16X3 stated and guarded (below); power-of-two WEIGHT SCALES: + pp_gemm_ws, pp_linear_ln_folded_ws,
  *    pp_qkv_attention_split_ws, pp_gemm_residual_layernorm_ws, pp_ffn_split_residual_layernorm_ws, pp_proj_ffn_split_residual_layernorm_ws (the unsuffixed entry points = scale 1);
  *    CHANGED signatures: pp_qkv_attention_split_folded (centered rows, no column sums, + w_inv_scale), pp_proj_ffn_split_folded (+ residual_stats,
  *    + three weight scales; the rows it leaves are centered); pp_probmap_decode_flags writes NaN results for a map with a non-finite logit;
@@ -762,6 +763,60 @@ int pp_draw_poses(const void* image_rgb, int img_h, int img_w, const float* keyp
                   float radius, float thickness, float alpha, void* out_rgb, void* stream);
 /* cv2.resize(src, (dst_w, dst_h), INTER_LINEAR) of an RGB uint8 image, restated in fp32 (half-pixel centres, edge clamp). */
 int pp_resize_bilinear_u8(const void* src_rgb, int src_h, int src_w, void* dst_rgb, int dst_h, int dst_w, void* stream);
+
+/* The pictures of many samples in one set of launches (added under version 4: purely additive), csrc/pp_render_batch.hip:
+ * what pp_revert_heatmaps_max, pp_heatmap_posterior, pp_parea_thresholds, pp_parea_compose, pp_draw_poses and
+ * pp_resize_bilinear_u8 give picture by picture, byte for byte (the same per-pixel and per-part bodies, the same
+ * partitions per picture), in a number of launches that does not depend on the number of pictures: one - the pose panel -
+ * when no picture has a heatmap panel, twelve otherwise. */
+#define PP_RENDER_MAX_KEYPOINTS 32
+#define PP_RENDER_MAX_INSTANCES 255 /* per picture (the presence mean restates a reduction order that holds below 256) */
+/* One picture. image: (height, width, 3) uint8, R G B or (bgr != 0) B G R; out: (height, width, 3) uint8 RGB, with heatmap
+ * != 0 (2 height, width, 3): the pose panel over the probability-area panel resized to the image. pad: left, top, right,
+ * bottom border of the canvas, canvas_h = height + top + bottom, canvas_w = width + left + right (heatmap pictures; else
+ * ignored). Its instances are rows first .. first + count - 1 of the instance table. scratch_offset: where its share of
+ * the scratch starts (bytes, a multiple of 256; pp_render_batch_scratch_bytes of it; the share begins with its (K,
+ * canvas_h, canvas_w) float32 posterior maps). The shares of a call must not overlap, nor its outputs. */
+typedef struct {
+    const uint8_t* image;
+    uint8_t* out;
+    int64_t scratch_offset;
+    int32_t height, width, bgr, heatmap;
+    int32_t pad[4];
+    int32_t canvas_h, canvas_w;
+    int32_t first, count;
+} pp_render_picture;
+/* One instance. maps: its un-reverted (K, hm_h, hm_w) float32 maps (heatmap pictures; else ignored); inverse: the inverse
+ * warp (canvas -> map, six doubles, as pp_revert_heatmaps_max takes it); keypoints (K, 2), visible (K), presence (K): the
+ * first K entries; box: its int pose box x1, y1, x2, y2 in image pixels, drawn when box_valid != 0; rect: its aspect-fixed
+ * rectangle in canvas pixels, drawn on the heatmap panel when rect_valid != 0. */
+typedef struct {
+    const float* maps;
+    double inverse[6];
+    float keypoints[2 * PP_RENDER_MAX_KEYPOINTS];
+    float visible[PP_RENDER_MAX_KEYPOINTS];
+    float presence[PP_RENDER_MAX_KEYPOINTS];
+    int32_t box[4];
+    int32_t rect[4];
+    int32_t box_valid, rect_valid;
+} pp_render_instance;
+/* Host only: bytes of scratch of one heatmap picture with K keypoints and a (canvas_h, canvas_w) canvas, a multiple of 256:
+ * its posterior maps, its canvas, the partial sums, the histogram partials, states, thresholds. < 0: error. */
+long long pp_render_batch_scratch_bytes(int K, int canvas_h, int canvas_w);
+/* pictures / instances / tiles: the tables on the device; *_host: the same bytes in host memory (the caller's staging
+ * buffer), read here for the argument checks - all of which run before any HIP call - and the grid sizes. tiles: 2
+ * (n_pictures + 1) int32, two exclusive prefixes over the pictures with the total last: of the canvas row tiles
+ * canvas_h * ceil(canvas_w / 256) (0 for a picture without heatmap), then of the image row tiles height * ceil(width / 256);
+ * a workgroup finds its picture by a search in them. K keypoints (<= 32; <= 22 when a picture has a heatmap panel) and
+ * (hm_h, hm_w) maps for every instance of the call. skeleton (n_links, 2) int32, link_rgb (n_links, 3), kpt_rgb (K, 3)
+ * uint8, on the device, and kpt_thr, radius, thickness, alpha: as pp_draw_poses takes them. scratch: scratch_bytes bytes on
+ * the device (may be NULL when no picture has a heatmap panel). A picture with no instance and no heatmap panel is legal:
+ * its output is its image, as RGB. */
+int pp_render_samples_batch(const pp_render_picture* pictures_host, const pp_render_instance* instances_host, const int* tiles_host,
+                            const pp_render_picture* pictures, const pp_render_instance* instances, const int* tiles,
+                            int n_pictures, int n_instances, int K, int hm_h, int hm_w, const int* skeleton, const void* link_rgb,
+                            const void* kpt_rgb, int n_links, double kpt_thr, float radius, float thickness, float alpha,
+                            void* scratch, long long scratch_bytes, void* stream);
 
 /* Split JPEG decoder (added under version 4: purely additive). The serial part - markers and Huffman codes - runs on host
  * threads (csrc/pp_jpeg_host.h), the data-parallel rest - dequantisation, 8x8 inverse DCT, chroma upsampling, YCbCr -> BGR,

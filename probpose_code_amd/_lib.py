@@ -165,6 +165,9 @@ SIGNATURES = {
     "pp_draw_poses": (
         c_int, [_P, c_int, c_int, _P, _P, _P, c_int, c_int, _P, _P, _P, c_int, c_double, c_float, c_float, c_float, _P, _P]),
     "pp_resize_bilinear_u8": (c_int, [_P, c_int, c_int, _P, c_int, c_int, _P]),
+    "pp_render_batch_scratch_bytes": (c_longlong, [c_int, c_int, c_int]),
+    "pp_render_samples_batch": (
+        c_int, [_P] * 6 + [c_int] * 5 + [_P, _P, _P, c_int, c_double, c_float, c_float, c_float, _P, c_longlong, _P]),
     "pp_jpeg_probe": (c_int, [_P, ctypes.c_size_t, _P]),
     "pp_jpeg_entropy_decode": (c_int, [_P, ctypes.c_size_t, _P, c_longlong, _P, _P]),
     "pp_jpeg_scratch_bytes": (c_longlong, [_P, c_int]),

@@ -15,15 +15,11 @@
 // One thread per output pixel (all three channels): HBM-bound on the 3 x 48 KiB each crop writes. pp_warp_affine_u8 cuts
 // the crops of one image, pp_warp_affine_u8_batch those of many images (a device table of image pointers) in one launch.
 #include "pp_common.h"
+#include "pp_revert_core.h"  // round_to_int and the bodies shared with pp_render_batch.hip
 
 #include <cstdint>
 
 namespace pp {
-
-__device__ __forceinline__ int round_to_int(double v) {  // saturate_cast<int>(double) = cvRound: nearest, ties to even
-    v = rint(v);
-    return v >= 2147483647.0 ? 2147483647 : (v <= -2147483648.0 ? (int)0x80000000 : (int)v);
-}
 
 // One output pixel (x, y) of one crop, all channels: the fixed-point arithmetic of both warp kernels. img: (ih, iw, ic)
 // HWC; M: the crop's inverse map; out: the crop's (ic, oh, ow) CHW plane. 64-bit offsets into the image.
@@ -76,78 +72,29 @@ __global__ __launch_bounds__(256) void warp_affine_batch_kernel(const uint8_t* c
 // K x H x W floats written. cv2's float path: the same 5-fractional-bit source coordinates as above, the four weights
 // (1 - fy/32)(1 - fx/32), ... in float32 (exact), v = s00 w00 + s01 w01 + s10 w10 + s11 w11.
 // The merge is numpy's np.max: NaN in any person's value stays NaN (fmaxf would drop it), and the maxima start at -inf.
-constexpr int RV_MAXK = 32;
-
-// IEEE 754-2019 maximum (NaN if either operand is): one v_maximum3_f32 on gfx950, where fmaxf is one v_max_f32
-__device__ __forceinline__ float max_keep_nan(float acc, float v) { return __builtin_elementwise_maximum(acc, v); }
-
+// The per-pixel and per-part bodies are in pp_revert_core.h (pp_render_batch.hip runs them over many pictures at once).
 __global__ __launch_bounds__(256) void revert_heatmaps_max_kernel(const float* __restrict__ hm, const double* __restrict__ inv,
                                                                   float* __restrict__ out, int n, int K, int hh, int hw,
                                                                   int H, int W) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= W) return;
-    float acc[RV_MAXK];
-#pragma unroll
-    for (int k = 0; k < RV_MAXK; ++k) acc[k] = -__builtin_huge_valf();
-    for (int b = 0; b < n; ++b) {
-        const double* M = inv + 6 * b;
-        const int X0 = round_to_int((M[1] * y + M[2]) * 1024.0) + 16, Y0 = round_to_int((M[4] * y + M[5]) * 1024.0) + 16;
-        const int X = (X0 + round_to_int(M[0] * x * 1024.0)) >> 5, Y = (Y0 + round_to_int(M[3] * x * 1024.0)) >> 5;
-        int sx = X >> 5, sy = Y >> 5;
-        sx = sx > 32767 ? 32767 : (sx < -32768 ? -32768 : sx);
-        sy = sy > 32767 ? 32767 : (sy < -32768 ? -32768 : sy);
-        const bool x0in = sx >= 0 && sx < hw, x1in = sx + 1 >= 0 && sx + 1 < hw;
-        const bool y0in = sy >= 0 && sy < hh, y1in = sy + 1 >= 0 && sy + 1 < hh;
-        if (!((x0in || x1in) && (y0in || y1in))) {  // this person's map is 0 here (border value)
-#pragma unroll
-            for (int k = 0; k < RV_MAXK; ++k) acc[k] = max_keep_nan(acc[k], 0.f);
-            continue;
-        }
-        const float ax = (float)(X & 31) * (1.f / 32.f), ay = (float)(Y & 31) * (1.f / 32.f);
-        const float w00 = (1.f - ay) * (1.f - ax), w01 = (1.f - ay) * ax, w10 = ay * (1.f - ax), w11 = ay * ax;
-        const float* s = hm + (size_t)b * K * hh * hw + (ptrdiff_t)sy * hw + sx;
-#pragma unroll
-        for (int k = 0; k < RV_MAXK; ++k) {
-            if (k < K) {
-                const float* sk = s + (size_t)k * hh * hw;
-                const float v00 = (x0in && y0in) ? sk[0] : 0.f, v01 = (x1in && y0in) ? sk[1] : 0.f;
-                const float v10 = (x0in && y1in) ? sk[hw] : 0.f, v11 = (x1in && y1in) ? sk[hw + 1] : 0.f;
-                const float v = v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11;
-                acc[k] = max_keep_nan(acc[k], v);
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < RV_MAXK; ++k)
-        if (k < K) out[((size_t)k * H + y) * W + x] = acc[k];
+    const size_t person_stride = (size_t)K * hh * hw;
+    revert_max_pixel([=](int b, const double*& M, const float*& maps) { M = inv + 6 * b, maps = hm + (size_t)b * person_stride; }, n, K, hh,
+                     hw, out, H, W, x, y);
 }
 
-// heatmaps / heatmaps.sum(axis=(1, 2)) * presence[k]   (local_visualizer.py:827-837), two launches: per-channel partial sums
-// in float64 (fixed order), then the scaling
-constexpr int PS_PARTS = 64;
 __global__ __launch_bounds__(256) void channel_partial_sum_kernel(const float* __restrict__ hm, double* __restrict__ parts, int HW) {
     __shared__ double red[256];
     const int k = blockIdx.y, part = blockIdx.x;
-    const size_t per = ((size_t)HW + PS_PARTS - 1) / PS_PARTS, lo = part * per, hi = lo + per < (size_t)HW ? lo + per : (size_t)HW;
-    double s = 0.0;
-    for (size_t i = lo + threadIdx.x; i < hi; i += 256) s += (double)hm[(size_t)k * HW + i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) parts[k * PS_PARTS + part] = red[0];
+    channel_partial_sum(hm + (size_t)k * HW, HW, part, red, parts + k * PS_PARTS + part);
 }
 
 __global__ __launch_bounds__(256) void channel_scale_kernel(float* __restrict__ hm, const double* __restrict__ parts,
                                                             const float* __restrict__ presence, int HW) {
     const int k = blockIdx.y;
-    double s = 0.0;
-    for (int i = 0; i < PS_PARTS; ++i) s += parts[k * PS_PARTS + i];
-    const float total = (float)s, pr = presence[k];
+    const float total = channel_total(parts + k * PS_PARTS), pr = presence[k];
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < (size_t)HW) hm[(size_t)k * HW + i] = hm[(size_t)k * HW + i] / total * pr;
+    if (i < (size_t)HW) hm[(size_t)k * HW + i] = channel_scaled(hm[(size_t)k * HW + i], total, pr);
 }
 
 }  // namespace pp

@@ -27,12 +27,16 @@ from .dist import ResultGather
 
 class StepPipeline:
     def __init__(self, engine, batch: int, flip_indices, flip_test: bool = True, depth: int = 2, world: int = 1, group=None,
-                 use_graph: bool = True, force_collective: bool = False, shift_heatmap: bool = False):
+                 use_graph: bool = True, force_collective: bool = False, shift_heatmap: bool = False, return_heatmaps: bool = False):
         if depth < 1:
             raise ValueError("depth must be >= 1")
         self.engine, self.batch, self.depth = engine, batch, depth
         self.flip_test, self.flip_indices = flip_test, flip_indices
         self._kw = dict(shift_heatmap=True) if shift_heatmap else {}  # (stub engines of the CPU tests take no such keyword)
+        # the engine also leaves the batch's (B, K, h, w) heatmaps in the slot's workspace (device_outputs(ticket)["heatmaps"]); the flag
+        # is part of the key of the slot's captured graph (engine._graph_key), so both kinds of pipeline can share an engine
+        if return_heatmaps:
+            self._kw["return_heatmaps"] = True
         # True: every batch has exactly ``batch`` rows and replays the slot's captured graph (captured here, up front);
         # "full": batches of exactly ``batch`` rows replay the slot's graph (captured when the first one arrives in the slot),
         # smaller ones are launched kernel by kernel; False: always kernel by kernel

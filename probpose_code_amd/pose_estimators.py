@@ -690,19 +690,27 @@ class TopdownPoseEstimator(nn.Module):
         exactly ``max_batch`` crops replays the slot's captured hipGraph (captured when the first such batch arrives - the
         fixed-size batches of a test dataloader), smaller ones are launched kernel by kernel. Results are bit-identical to
         ``test_step``: the records that come back are float64 images of the same float32 / float64 device results
-        (``output_heatmaps`` is not carried by the record: use ``test_step`` for that)."""
+        With ``test_cfg.output_heatmaps`` the engine keeps every batch's heatmaps as well (``StepPipeline(return_heatmaps=True)``):
+        they are not part of the record, so once a ticket's record has landed its ``device_outputs(ticket)["heatmaps"][:n]`` are
+        cloned on the caller's stream - the slot's next step waits for that stream before it overwrites them - and handed to
+        ``head.pack_records`` as ``predict`` hands them over: ``pred_fields.heatmaps`` are device tensors, bit for bit those of
+        ``test_step``. With the flag off the same launches run and the same records come back."""
         from .pipeline import StepPipeline
 
         assert self.with_head, "The model must have head to perform prediction."
-        if bool(self.test_cfg.get("output_heatmaps", False)):
-            raise NotImplementedError("test_step_stream returns the per-keypoint records only; output_heatmaps needs test_step")
+        want_hm = bool(self.test_cfg.get("output_heatmaps", False))
         flip = self._check_flip_cfg()
         pipe, pending = None, []  # pending: (ticket, n, data_samples)
 
         def collect(entry):
             ticket, n, samples = entry
             rec = pipe.result(ticket)[0, :n].numpy().copy()  # (n, K, 7) float64: x, y, conf, prob, vis, oks, err (raw)
-            return self.add_pred_to_datasample(self.head.pack_records(rec, self.test_cfg), None, samples)
+            if not want_hm:
+                return self.add_pred_to_datasample(self.head.pack_records(rec, self.test_cfg), None, samples)
+            # the record has landed, so the slot's step has run; pack_records clones the maps (here: on the caller's stream, which the
+            # slot's next step waits for) - the sample never holds a view of the slot's workspace
+            batch_pred_instances, batch_pred_fields = self.head.pack_records(rec, self.test_cfg, pipe.device_outputs(ticket)["heatmaps"][:n])
+            return self.add_pred_to_datasample(batch_pred_instances, batch_pred_fields, samples)
 
         for data in batches:
             data = self.data_preprocessor(data, False)
@@ -715,7 +723,8 @@ class TopdownPoseEstimator(nn.Module):
             if pipe is None:
                 fi = samples[0].metainfo["flip_indices"] if flip else None
                 pipe = StepPipeline(self.engine, max_batch, fi, flip_test=flip, depth=depth,
-                                    use_graph="full" if self.graph_replay else False, shift_heatmap=self._shift_heatmap)
+                                    use_graph="full" if self.graph_replay else False, shift_heatmap=self._shift_heatmap,
+                                    return_heatmaps=want_hm)
             if inputs.shape[0] > max_batch:
                 raise ValueError(f"batch of {inputs.shape[0]} crops exceeds max_batch={max_batch}")
             while len(pending) >= depth:  # the slot about to be reused must have been read

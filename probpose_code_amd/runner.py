@@ -11,8 +11,13 @@ and ``test_evaluator``): the person instances of a dataset in batches, the model
   * crops: the val pipeline through ``Compose.batched`` - box arithmetic on the host, ONE ``pp_warp_affine_u8_batch`` launch
     for the batch, its images uploaded with one copy - on a producer stream, under the model step of the batch before;
   * model: ``test_step_stream`` (full batches replay the captured graph, a partial last batch runs kernel by kernel);
-  * metric: ``MultiDatasetEvaluator`` routes every sample to the metric of its ``dataset_name``.
+  * metric: ``MultiDatasetEvaluator`` routes every sample to the metric of its ``dataset_name``;
+  * pictures (``show_dir``, the reference's ``tools/test.py --show-dir``: PoseVisualizationHook.after_test_iter): every
+    delivered batch is drawn by ONE ``draw_datasamples`` per scratch chunk - one picture per instance, the pose panel and,
+    with ``test_cfg.output_heatmaps``, the probability-area panel from the heatmaps the engine left on the device - coded on
+    the device (``jpeg.encode_batch`` / ``png.encode_batch``) and written on the thread pool.
 """
+import os
 from concurrent.futures import ThreadPoolExecutor
 from typing import Callable, Dict, List, NamedTuple, Optional, Sequence
 
@@ -161,6 +166,54 @@ def build_evaluator(cfg, dataset=None, device: str = "cuda"):
     return EVALUATORS.build(dict(cfg, type=kind), ann_files=ann_files, device=device)
 
 
+def show_file_names(img_paths: Sequence[str], existing: Sequence[str]) -> List[str]:
+    """The picture names of ``--show-dir`` for the samples of ``img_paths``, in order (visualization_hook.py:152-157):
+    ``<stem>_<index>.<suffix>``, where stem and suffix are the image's base name cut at its last dot and index is the number of
+    names in the directory that START WITH the stem - ``existing`` (the names there when the run began, and those given out
+    earlier in the run) and the names given out before it in this call. As in the reference the stem ``a1`` therefore also
+    counts the names of ``a12``. A pure function: the writes are asynchronous, the directory is not listed again."""
+    names, out = list(existing), []
+    for path in img_paths:
+        base = os.path.basename(path)
+        if "." not in base:
+            raise ValueError(f"{path!r}: a picture name needs the suffix of its image")
+        stem, suffix = base.rsplit(".", 1)
+        name = f"{stem}_{sum(1 for f in names if f.startswith(stem))}.{suffix}"
+        out.append(name)
+        names.append(name)
+    return out
+
+
+def _write_bytes(path: str, data: bytes) -> None:
+    with open(path, "wb") as f:
+        f.write(data)
+
+
+def _write_pillow(path: str, rgb: np.ndarray) -> None:
+    from PIL import Image
+
+    Image.fromarray(rgb).save(path)
+
+
+def _show_sample(sample):
+    """``merge_data_samples([sample])`` without the revert: the sample's instances, ``input_center`` / ``input_scale`` stacked
+    and - with heatmaps in ``pred_fields`` - its un-reverted (1, K, h, w) maps, still on the device (``draw_datasamples``
+    reverts them inside its launches)."""
+    from .structures import PixelData, PoseDataSample
+
+    meta = dict(sample.metainfo)
+    meta["input_center"] = np.array([sample.input_center])
+    meta["input_scale"] = np.array([sample.input_scale])
+    merged = PoseDataSample(metainfo=meta)
+    if "gt_instances" in sample:
+        merged.gt_instances = sample.gt_instances
+    if "pred_instances" in sample:
+        merged.pred_instances = sample.pred_instances
+    if "pred_fields" in sample and "heatmaps" in sample.pred_fields:
+        merged.pred_fields = PixelData(heatmaps=torch.as_tensor(sample.pred_fields.heatmaps)[None])
+    return merged
+
+
 def _pipeline_of(model, dataset):
     from . import apis
     from .transforms import LoadImage, TopdownAffine
@@ -176,13 +229,22 @@ def _pipeline_of(model, dataset):
 
 
 def test_dataset(model, dataset, evaluator=None, batch_size: int = 64, workers: int = 8, depth: int = 2,
-                 sink: Optional[Callable[[list], None]] = None, decode: str = "host", decode_entropy: str = "host") -> dict:
+                 sink: Optional[Callable[[list], None]] = None, decode: str = "host", decode_entropy: str = "host",
+                 show_dir: Optional[str] = None, show_kpt_thr: float = 0.3) -> dict:
     """Run ``model`` over every instance of ``dataset`` (``get_data_info(i)``, i in order) and return the evaluator's metrics
     (``{}`` without one). ``sink``, when given, receives every batch's list of PoseDataSample, in order. ``decode``: "host"
     (``apis.load_image_bgr`` on the threads) or "device" (the split JPEG decoder of ``jpeg``: the same pixels; a file outside
     its subset is decoded on the host as before). ``decode_entropy`` (with ``decode="device"`` only): "host" (the threads decode
     the Huffman codes) or "device" (they only prepare the scan; the device decodes the codes as well, and an image it refuses
-    steps down to the host as in ``jpeg.decode_scans``). The samples are the same whatever the choice."""
+    steps down to the host as in ``jpeg.decode_scans``). The samples are the same whatever the choice.
+
+    ``show_dir``: a directory (created when missing) that receives one picture per instance, named by ``show_file_names``: the
+    sample drawn on its image with its box (``add_datasample(draw_gt=False, draw_bbox=True, draw_heatmap=True,
+    kpt_thr=show_kpt_thr)`` of the reference's hook) - (H, W), or (2H, W) with the probability-area panel when
+    ``model.test_cfg.output_heatmaps`` is on. An image's pixels are then kept until the batches that read it have been DRAWN.
+    ``.jpg`` / ``.jpeg`` names are coded by ``jpeg.encode_batch(entropy="device", quality=75, subsampling="4:2:0")``, ``.png`` names
+    by ``png.encode_batch``, any other suffix by Pillow from a host copy; the files are written on the loop's thread pool.
+    The samples given to ``sink`` and the evaluator are the same with and without it."""
     from . import jpeg
     from .apis import load_image_bgr
     from .transforms import BatchStaging, pseudo_collate
@@ -236,10 +298,41 @@ def test_dataset(model, dataset, evaluator=None, batch_size: int = 64, workers: 
                 on_device.update(zip(todo, jpeg.reconstruct_batch([results[key] for key in todo], device, jpeg_staging)))
         return [on_device[key] if key in on_device else results[key] for key in keys]
 
+    kept: Dict[str, object] = {}  # show_dir: image key -> its pixels (BGR), until the last batch that reads it has been drawn
+    writes = []
+
+    def show(k, samples):
+        """Batch k, delivered: its pictures drawn by one draw_datasamples per chunk, coded per suffix in one call, written on the pool."""
+        from . import png
+
+        paths = [infos[i]["img_path"] for i in plan[k].indices]
+        names = show_file_names(paths, taken)
+        taken.extend(names)
+        frames = visualizer.draw_datasamples([kept[p] for p in paths], [_show_sample(s) for s in samples], draw_bbox=True, draw_heatmap=True,
+                                             kpt_thr=show_kpt_thr, channel_order="bgr", staging=show_staging)
+        for key in plan[k].images:
+            if last[key] == k:
+                del kept[key]
+        kinds = [("jpeg" if n.lower().endswith((".jpg", ".jpeg")) else "png" if n.lower().endswith(".png") else "other") for n in names]
+        for kind in ("jpeg", "png"):
+            sel = [i for i, v in enumerate(kinds) if v == kind]
+            if not sel:
+                continue
+            pics = [frames[i] for i in sel]
+            files = (jpeg.encode_batch(pics, quality=75, subsampling="4:2:0", channel_order="rgb", entropy="device", staging=show_staging)
+                     if kind == "jpeg" else png.encode_batch(pics, channel_order="rgb", staging=show_staging))
+            writes.extend(pool.submit(_write_bytes, os.path.join(show_dir, names[i]), data) for i, data in zip(sel, files))
+        writes.extend(pool.submit(_write_pillow, os.path.join(show_dir, names[i]), frames[i].cpu().numpy()) for i, v in enumerate(kinds) if v == "other")
+
     def batches():
         for k, b in enumerate(plan):
             queue_until(k + 1 + ahead)
             pixels = reconstruct(b.images) if decode == "device" else [decoded[key].result() for key in b.images]
+            if show_dir is not None:
+                for key, px in zip(b.images, pixels):
+                    kept[key] = px
+                    if isinstance(px, torch.Tensor) and px.is_cuda:  # (reconstructed on the producer stream, drawn on the caller's)
+                        px.record_stream(torch.cuda.current_stream(device))
             data_list = []
             for i, j in zip(b.indices, b.crop_image):
                 d = dict(infos[i])
@@ -259,13 +352,25 @@ def test_dataset(model, dataset, evaluator=None, batch_size: int = 64, workers: 
             if packed:
                 yield pseudo_collate(packed)
 
+    if show_dir is not None:
+        from .visualization import PoseLocalVisualizer
+
+        os.makedirs(show_dir, exist_ok=True)
+        taken = sorted(os.listdir(show_dir))  # the names that count towards an index: those on disk now, then those given out
+        visualizer = PoseLocalVisualizer(device=device)
+        visualizer.set_dataset_meta(getattr(model, "dataset_meta", None))
+        show_staging = BatchStaging()
     try:
         with torch.no_grad():
-            for samples in model.test_step_stream(batches(), depth=depth, max_batch=batch_size):
+            for k, samples in enumerate(model.test_step_stream(batches(), depth=depth, max_batch=batch_size)):
+                if show_dir is not None:
+                    show(k, samples)
                 if sink is not None:
                     sink(samples)
                 if evaluator is not None:
                     evaluator.process(samples)
+        for w in writes:
+            w.result()  # (a failed write is this call's failure)
     finally:
         pool.shutdown(wait=True, cancel_futures=True)
     return evaluator.evaluate() if evaluator is not None else {}

@@ -12,6 +12,9 @@ finished image back once. The drawing rules differ from the reference where the 
     outline pixel one pixel outside the mask;
   * the panel resize is bilinear with half-pixel centres in fp32 (cv2.resize uses fixed-point weights).
 cv2 and matplotlib are not available to pin the difference.
+
+``draw_datasamples`` draws the pictures of a whole batch of samples in one set of launches (``csrc/pp_render_batch.hip``, the
+same per-pixel bodies): what ``tools/test.py --show-dir`` dumps. Byte for byte the pictures of ``draw_datasample``.
 """
 import numpy as np
 import torch
@@ -166,6 +169,294 @@ def resize_rgb(src, size_hw, out=None):
     return out
 
 
+# pp_render_picture / pp_render_instance of include/probpose_mi355x.h
+_PICTURE = np.dtype([("image", "<u8"), ("out", "<u8"), ("scratch_offset", "<i8"), ("height", "<i4"), ("width", "<i4"), ("bgr", "<i4"),
+                     ("heatmap", "<i4"), ("pad", "<i4", (4,)), ("canvas_h", "<i4"), ("canvas_w", "<i4"), ("first", "<i4"), ("count", "<i4")])
+RENDER_MAX_KEYPOINTS = 32
+RENDER_MAX_INSTANCES = 255  # per picture (PP_RENDER_MAX_INSTANCES)
+_INSTANCE = np.dtype([("maps", "<u8"), ("inverse", "<f8", (6,)), ("keypoints", "<f4", (2 * RENDER_MAX_KEYPOINTS,)),
+                      ("visible", "<f4", (RENDER_MAX_KEYPOINTS,)), ("presence", "<f4", (RENDER_MAX_KEYPOINTS,)), ("box", "<i4", (4,)),
+                      ("rect", "<i4", (4,)), ("box_valid", "<i4"), ("rect_valid", "<i4")])
+assert _PICTURE.itemsize == 72 and _INSTANCE.itemsize == 608
+RENDER_SCRATCH_DEFAULT = 1 << 30  # a memory bound (64 full-HD pictures would need about 10 GB at once), not a tuned number
+# the stages of one pp_render_samples_batch call with a heatmap panel among its pictures, in launch order (without: the pose panel alone)
+RENDER_BATCH_LAUNCHES = ("revert", "sum", "scale") + ("hist", "select") * 3 + ("compose", "poses", "resize")
+batch_calls = 0  # pp_render_samples_batch calls since import
+batch_uploads = 0  # host-to-device copies of draw_datasamples since import (one per call)
+
+
+def render_share_bytes(K: int, canvas_h: int, canvas_w: int) -> int:
+    """Scratch of one heatmap picture in a batched call, as ``pp_render_batch_scratch_bytes`` gives it: the (K, Hp, Wp) float32
+    posterior maps, the (Hp, Wp, 3) canvas, 64 sum partials, and per keypoint the radix select's state (5), part flags and
+    2048-bin part histograms (float64), thresholds and draw flags; the regions on multiples of 256 bytes where it matters."""
+    from .staging import _align
+
+    hw = int(canvas_h) * int(canvas_w)
+    parts = min(max((hw + 16383) // 16384, 1), 32)
+    at = _align(K * hw * 4)
+    at = _align(at + hw * 3)
+    at += K * 64 * 8 + K * 5 * 8 + K * parts * 8 + K * parts * 2048 * 8 + K * 4 + K * 4
+    return _align(at)
+
+
+def plan_render_chunks(shapes, pads, K: int, budget: int = RENDER_SCRATCH_DEFAULT) -> list:
+    """The host plan of ``draw_datasamples`` (numpy only): ``shapes[i]`` = (H, W) of picture i, ``pads[i]`` = its [left, top,
+    right, bottom] canvas border, or None for a picture without heatmap panel. The pictures are cut, in order, into chunks
+    whose scratch fits ``budget`` bytes (a picture that alone exceeds it goes alone); one ``pp_render_samples_batch`` call draws
+    a chunk. Per chunk a dict: ``pictures`` (their indices), ``canvas`` (n, 2) int (Hp, Wp; the image's for a picture without
+    panel), ``scratch_offset`` (n,) int64 (each share on a multiple of 256, disjoint, in order; 0 without panel),
+    ``scratch_bytes`` (their sum) and ``tiles``, int32 2 (n + 1): the exclusive prefix (total last) of the canvas row tiles
+    Hp * ceil(Wp / 256) of the panel pictures, then that of the image row tiles H * ceil(W / 256) of all pictures - the flat
+    grids of the launches."""
+    if len(shapes) != len(pads):
+        raise ValueError("one pad entry (or None) per picture")
+    if budget < 0:
+        raise ValueError("budget must not be negative")
+    shares, canvas = [], []
+    for (H, W), pad in zip(shapes, pads):
+        H, W = int(H), int(W)
+        if H <= 0 or W <= 0:
+            raise ValueError(f"empty picture {(H, W)}")
+        if pad is None:
+            canvas.append((H, W))
+            shares.append(0)
+        else:
+            p = [int(v) for v in np.asarray(pad).reshape(4)]
+            if min(p) < 0:
+                raise ValueError(f"negative padding {p}")
+            canvas.append((H + p[1] + p[3], W + p[0] + p[2]))
+            shares.append(render_share_bytes(K, *canvas[-1]))
+    chunks, cur, used = [], [], 0
+    for i, share in enumerate(shares):
+        if cur and share and used + share > budget:  # (a picture without panel needs no scratch: it never opens a chunk)
+            chunks.append(cur)
+            cur, used = [], 0
+        cur.append(i)
+        used += share
+    if cur:
+        chunks.append(cur)
+    out = []
+    for idx in chunks:
+        n = len(idx)
+        offsets, tiles, at = np.zeros(n, np.int64), np.zeros(2 * (n + 1), np.int64), 0
+        for j, i in enumerate(idx):
+            H, W = int(shapes[i][0]), int(shapes[i][1])
+            if shares[i]:
+                offsets[j] = at
+                at += shares[i]
+            tiles[j + 1] = tiles[j] + (canvas[i][0] * ((canvas[i][1] + 255) // 256) if shares[i] else 0)
+            tiles[n + 2 + j] = tiles[n + 1 + j] + H * ((W + 255) // 256)
+        if tiles.max() >= 2 ** 31 - 1:
+            raise ValueError("a chunk of 2^31 row tiles or more: lower the scratch budget")
+        out.append(dict(pictures=idx, canvas=np.array([canvas[i] for i in idx], np.int64).reshape(n, 2), scratch_offset=offsets,
+                        scratch_bytes=int(at), tiles=tiles.astype(np.int32)))
+    return out
+
+
+class _Picture:
+    """What ``draw_datasamples`` reads of one merged sample (everything on the host but the image and the maps)."""
+
+    __slots__ = ("key", "image", "host_image", "H", "W", "n", "kpts", "vis", "boxes", "box_ok", "maps", "inv", "pad", "rects", "rect_ok", "presence")
+
+
+def _gather_picture(image, ds, K, draw_bbox, draw_heatmap, device) -> _Picture:
+    """The host half of ``PoseLocalVisualizer.draw_datasample`` for one sample: the same fields, the same conversions, the same
+    padding, inverse maps, int boxes and aspect boxes."""
+    from .structures import _image_padding
+    from .transforms import fix_bbox_aspect_ratio_xyxy, get_warp_matrix, invert_affine
+
+    p = _Picture()
+    p.key = id(image)
+    if isinstance(image, np.ndarray):
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError(f"expected an (H, W, 3) uint8 image, got {image.shape} {image.dtype}")
+        p.host_image, p.image = np.ascontiguousarray(image), None
+        p.H, p.W = image.shape[:2]
+    else:
+        p.host_image, p.image = None, _as_device_image(image, device)
+        p.H, p.W = p.image.shape[:2]
+    pi = ds.pred_instances if "pred_instances" in ds else None
+    with_heatmap = bool(draw_heatmap) and pi is not None and "pred_fields" in ds and "heatmaps" in ds.pred_fields
+    p.n, p.maps, p.pad, p.boxes, p.rects = 0, None, None, None, None
+    if pi is not None and "keypoints" in pi:
+        kpts = pi.get("transformed_keypoints", pi.keypoints)
+        p.kpts = np.ascontiguousarray(np.asarray(kpts, np.float32).reshape(-1, K, 2))
+        p.n = len(p.kpts)
+        vis = pi.keypoints_visible if "keypoints_visible" in pi else np.ones(np.asarray(kpts).shape[:-1], np.float32)
+        p.vis = np.ascontiguousarray(np.asarray(vis, np.float32).reshape(p.n, K))
+        if draw_bbox and "bboxes" in pi:
+            b = np.asarray(pi.bboxes, np.float64).reshape(p.n, 4)
+            p.box_ok = np.isfinite(b).all(axis=1)
+            p.boxes = np.zeros((p.n, 4), np.int32)
+            p.boxes[p.box_ok] = int_boxes(b[p.box_ok])
+    elif with_heatmap:
+        raise ValueError("draw_heatmap needs pred_instances.keypoints")
+    if p.n > RENDER_MAX_INSTANCES:
+        raise ValueError(f"{p.n} instances in one picture: the batched drawing takes at most {RENDER_MAX_INSTANCES} (draw_datasample has no limit)")
+    if not with_heatmap:
+        return p
+    if "keypoints_probs" not in pi:
+        raise ValueError("draw_heatmap needs pred_instances.keypoints_probs (the presence probabilities of ProbPose)")
+    meta = ds.metainfo
+    centers = np.asarray(meta["input_center"], np.float64).reshape(-1, 2)
+    scales = np.asarray(meta["input_scale"], np.float64).reshape(-1, 2)
+    maps = ds.pred_fields.heatmaps
+    maps = maps if isinstance(maps, torch.Tensor) else torch.as_tensor(np.asarray(maps))
+    if maps.dim() != 4 or maps.shape[1] != K or maps.shape[0] != p.n or len(centers) != p.n:
+        raise ValueError(f"draw_datasamples takes the un-reverted (n, K, h, w) maps of a sample's n instances; got {tuple(maps.shape)} for "
+                         f"{p.n} instances of {K} keypoints and {len(centers)} input centers")
+    p.maps = maps.to(device=device, dtype=torch.float32).contiguous()
+    ori_shape = meta["ori_shape"]
+    if (int(ori_shape[0]), int(ori_shape[1])) != (p.H, p.W):
+        raise ValueError(f"ori_shape {tuple(ori_shape)} is not the image {(p.H, p.W)}")
+    p.pad = np.asarray(_image_padding(centers, scales, ori_shape)).reshape(4)
+    h, w = int(maps.shape[2]), int(maps.shape[3])
+    # merge_data_samples: the maps go back on the padded image, each centre shifted by the (left, top) pad
+    p.inv = np.stack([invert_affine(get_warp_matrix(centers[i] + p.pad[:2], scales[i], 0, (w, h), inv=True)) for i in range(p.n)])
+    p.presence = np.ascontiguousarray(np.asarray(pi.keypoints_probs, np.float32).reshape(-1, K))
+    if len(p.presence) != p.n:
+        raise ValueError(f"keypoints_probs of {len(p.presence)} instances for {p.n} instances")
+    if draw_bbox:
+        src = ds.gt_instances if "gt_instances" in ds and "bboxes" in ds.gt_instances else pi
+        if "bboxes" in src:
+            b = np.array(src.bboxes, np.float32).reshape(-1, 4)  # aspect_boxes, row by row
+            if len(b) != p.n:
+                raise ValueError(f"{len(b)} boxes for {p.n} instances")
+            b[:, :2] += p.pad[:2]
+            b[:, 2:] += p.pad[:2]
+            fixed = np.asarray(fix_bbox_aspect_ratio_xyxy(b, aspect_ratio=3 / 4, padding=1.25), np.float64).reshape(-1, 4)
+            p.rect_ok = np.isfinite(fixed).all(axis=1)
+            p.rects = np.zeros((p.n, 4), np.int32)
+            p.rects[p.rect_ok] = int_boxes(fixed[p.rect_ok])
+    return p
+
+
+def draw_datasamples(images, data_samples, draw_bbox=True, draw_heatmap=False, kpt_thr=0.3, channel_order="rgb",
+                     scratch_bytes=RENDER_SCRATCH_DEFAULT, skeleton=COCO_SKELETON, link_colors=COCO_LINK_COLORS,
+                     keypoint_colors=COCO_KEYPOINT_COLORS, radius=3.0, thickness=1.0, alpha=0.8, device="cuda:0", staging=None, out=None,
+                     scratch=None):
+    """The pictures of many merged samples in one set of launches per chunk (pp_render_samples_batch): a list of uint8 RGB
+    device tensors, element i byte for byte ``PoseLocalVisualizer.draw_datasample(images[i], data_samples[i], ...)`` applied
+    to the RGB image - (H, W, 3), or with ``draw_heatmap`` and heatmaps in ``pred_fields`` (2H, W, 3). ``images[i]``: (H, W, 3)
+    uint8, host array (uploaded with the tables) or device tensor, in ``channel_order`` "rgb" or "bgr" (swapped where the
+    kernels read it). ``data_samples[i]``: a merged sample (``merge_data_samples``-shaped: the instances concatenated,
+    ``input_center`` / ``input_scale`` stacked) whose ``pred_fields.heatmaps``, when present, are the UN-REVERTED (n_i, K, h, w)
+    maps of its instances as a device tensor: reverting, merging and the posterior run inside the call. ``draw_bbox`` and
+    ``kpt_thr``: one value, or one per picture.
+
+    A chunk of pictures costs ONE host-to-device copy (picture table, instance table, tile prefixes, skeleton, colours and the
+    host images) and one pp_render_samples_batch call: twelve launches whatever the number of pictures (one - the pose panel -
+    when none of them has a heatmap panel). The batch is cut into chunks whose scratch (the posterior maps of every picture of
+    the chunk at once) fits ``scratch_bytes``; the default, 1 GiB, is a memory bound and was not tuned. ``kpt_thr`` is an
+    argument of the call, so a list of differing values cuts the batch at every change as well. ``out``: a list of dense uint8
+    device tensors to draw into; ``scratch``: a uint8 device tensor to use when it is large enough for a chunk."""
+    global batch_calls, batch_uploads
+    from .staging import BatchStaging, StagedBlock, _align
+
+    if channel_order not in ("rgb", "bgr"):
+        raise ValueError(f"channel_order must be 'rgb' or 'bgr', got {channel_order!r}")
+    device = _check_device(device)
+    images, data_samples = list(images), list(data_samples)
+    n_all = len(images)
+    if len(data_samples) != n_all:
+        raise ValueError(f"{n_all} images for {len(data_samples)} samples")
+    if n_all == 0:
+        return []
+    K = len(keypoint_colors)
+    if K > RENDER_MAX_KEYPOINTS:
+        raise ValueError(f"{K} keypoints: the batched drawing takes at most {RENDER_MAX_KEYPOINTS}")
+    sk = np.ascontiguousarray(np.asarray(skeleton, np.int32).reshape(-1, 2))
+    L = len(sk)
+    if L and (sk.min() < 0 or sk.max() >= K):
+        raise ValueError(f"skeleton links name keypoints outside 0..{K - 1}")
+    lc = np.ascontiguousarray(np.asarray(link_colors, np.uint8).reshape(L, 3))
+    kc = np.ascontiguousarray(np.asarray(keypoint_colors, np.uint8).reshape(K, 3))
+    per = lambda v: list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * n_all  # noqa: E731
+    bbox_of, thr_of = [bool(v) for v in per(draw_bbox)], [float(v) for v in per(kpt_thr)]
+    if len(bbox_of) != n_all or len(thr_of) != n_all:
+        raise ValueError("draw_bbox / kpt_thr: one value, or one per picture")
+    pics = [_gather_picture(im, ds, K, bb, draw_heatmap, device) for im, ds, bb in zip(images, data_samples, bbox_of)]
+    if any(p.maps is not None for p in pics) and K > PAREA_MAX_KEYPOINTS:
+        raise ValueError(f"{K} keypoints: the probability areas have {PAREA_MAX_KEYPOINTS} colours")
+    hm_hw = {tuple(p.maps.shape[2:]) for p in pics if p.maps is not None}
+    if len(hm_hw) > 1:
+        raise ValueError(f"the maps of one call share their shape, got {sorted(hm_hw)}")
+    hm_h, hm_w = hm_hw.pop() if hm_hw else (0, 0)
+    shapes = [(p.H, p.W) for p in pics]
+    if out is not None:
+        out = list(out)
+        if len(out) != n_all:
+            raise ValueError(f"{len(out)} outputs for {n_all} pictures")
+        out = [_output(o, ((2 * p.H if p.maps is not None else p.H), p.W, 3), device) for o, p in zip(out, pics)]
+    results = [None] * n_all
+    staging = staging if staging is not None else BatchStaging()
+    stream = _stream(device)
+    # kpt_thr is one value per call: pictures are planned in runs of one value (a run is a whole batch unless the caller varies it)
+    lo = 0
+    while lo < n_all:
+        hi = lo + 1
+        while hi < n_all and thr_of[hi] == thr_of[lo]:
+            hi += 1
+        for chunk in plan_render_chunks(shapes[lo:hi], [p.pad if p.maps is not None else None for p in pics[lo:hi]], K, int(scratch_bytes)):
+            mine = [pics[lo + j] for j in chunk["pictures"]]
+            n, m = len(mine), sum(p.n for p in mine)
+            first_of = {}  # a host array given for several pictures (the instances of one image) is uploaded once
+            owner = [first_of.setdefault(p.key, j) for j, p in enumerate(mine)]
+            blk = StagedBlock([("pictures", 72 * n), ("instances", 608 * max(m, 1)), ("tiles", 4 * len(chunk["tiles"])), ("skeleton", 8 * max(L, 1)),
+                               ("link_rgb", 3 * max(L, 1)), ("kpt_rgb", 3 * K)],
+                              [("image", [p.H * p.W * 3 if (p.host_image is not None and owner[j] == j) else 0 for j, p in enumerate(mine)])])
+            sizes = [(2 * p.H if p.maps is not None else p.H) * p.W * 3 for p in mine]
+            if out is None:
+                o_at = np.concatenate([[0], np.cumsum([_align(s) for s in sizes])])
+                obuf = torch.empty(int(o_at[-1]), dtype=torch.uint8, device=device)
+                outs = [obuf[int(o_at[j]):int(o_at[j]) + sizes[j]].view(-1, mine[j].W, 3) for j in range(n)]
+            else:
+                outs = [out[lo + j] for j in chunk["pictures"]]
+            need = chunk["scratch_bytes"]
+            scr = scratch if (scratch is not None and scratch.numel() >= need) else (torch.empty(need, dtype=torch.uint8, device=device) if need else None)
+            blk.acquire(staging, device)
+            rows, inst = blk.host("pictures", _PICTURE), blk.host("instances", _INSTANCE)
+            inst[:] = 0
+            blk.host("tiles", np.int32)[:] = chunk["tiles"]
+            if L:
+                blk.host("skeleton", np.int32)[:] = sk.reshape(-1)
+                blk.host("link_rgb")[:] = lc.reshape(-1)
+            blk.host("kpt_rgb")[:] = kc.reshape(-1)
+            first, img_ptrs, img_hosts = 0, blk.ptrs("image"), blk.hosts("image")
+            for j, p in enumerate(mine):
+                if p.host_image is not None and owner[j] == j:
+                    img_hosts[j][:] = p.host_image.reshape(-1)
+                heat = p.maps is not None
+                rows[j] = (img_ptrs[owner[j]] if p.host_image is not None else p.image.data_ptr(), outs[j].data_ptr(), int(chunk["scratch_offset"][j]),
+                           p.H, p.W, int(channel_order == "bgr"), int(heat), tuple(int(v) for v in p.pad) if heat else (0, 0, 0, 0),
+                           int(chunk["canvas"][j][0]), int(chunk["canvas"][j][1]), first, p.n)
+                r = inst[first:first + p.n]
+                if p.n:
+                    r["keypoints"][:, :2 * K] = p.kpts.reshape(p.n, 2 * K)
+                    r["visible"][:, :K] = p.vis
+                    if p.boxes is not None:
+                        r["box"], r["box_valid"] = p.boxes, p.box_ok
+                    if heat:
+                        r["maps"] = [p.maps.data_ptr() + 4 * i * K * hm_h * hm_w for i in range(p.n)]
+                        r["inverse"] = p.inv.reshape(p.n, 6)
+                        r["presence"][:, :K] = p.presence
+                        if p.rects is not None:
+                            r["rect"], r["rect_valid"] = p.rects, p.rect_ok
+                first += p.n
+            blk.upload()
+            batch_uploads += 1
+            host = blk.pinned.ctypes.data
+            _lib.call("pp_render_samples_batch", host + blk.offset["pictures"], host + blk.offset["instances"] if m else None,
+                      host + blk.offset["tiles"], blk.ptr("pictures"), blk.ptr("instances") if m else None, blk.ptr("tiles"), n, m, K, hm_h, hm_w,
+                      blk.ptr("skeleton") if L else None, blk.ptr("link_rgb") if L else None, blk.ptr("kpt_rgb"), L, thr_of[lo], float(radius),
+                      float(thickness), float(alpha), _lib.ptr(scr), int(scr.numel()) if scr is not None else 0, stream)
+            batch_calls += 1
+            for j, o in zip(chunk["pictures"], outs):
+                results[lo + j] = o
+        lo = hi
+    return results
+
+
 class PoseLocalVisualizer:
     """mmpose/visualization/local_visualizer.py:PoseLocalVisualizer for what ProbPose's demo draws: predictions in the
     "mmpose" skeleton style, their boxes, and (``draw_heatmap``) the probability areas of the posterior maps on the padded
@@ -254,6 +545,16 @@ class PoseLocalVisualizer:
             resize_rgb(panel, (H, W), out=out[H:])
         return out
 
+    def draw_datasamples(self, images, data_samples, draw_bbox=True, draw_heatmap=False, kpt_thr=0.3, channel_order="rgb",
+                         scratch_bytes=RENDER_SCRATCH_DEFAULT, **kw):
+        """``draw_datasample`` for a batch in one set of launches per chunk (``visualization.draw_datasamples`` with this
+        visualizer's skeleton, colours, radius, line width and alpha): a list of device tensors, each byte for byte what
+        ``draw_datasample`` gives for its sample. The samples carry the un-reverted (n, K, h, w) maps of their instances."""
+        return draw_datasamples(images, data_samples, draw_bbox=draw_bbox, draw_heatmap=draw_heatmap, kpt_thr=kpt_thr,
+                                channel_order=channel_order, scratch_bytes=scratch_bytes, skeleton=self.skeleton,
+                                link_colors=self.link_color, keypoint_colors=self.kpt_color, radius=self.radius, thickness=self.line_width,
+                                alpha=self.alpha, device=self.device, **kw)
+
     def add_datasample(self, name, image, data_sample, draw_gt=False, draw_bbox=True, draw_heatmap=False, kpt_thr=0.3,
                        out_file=None, show_kpt_idx=False, skeleton_style="mmpose", show=False, wait_time=0, step=0):
         """Draw the predictions of one merged sample on ``image`` ((H, W, 3) uint8 RGB, host array or device tensor). Returns
@@ -292,4 +593,4 @@ class PoseLocalVisualizer:
 
 
 __all__ = ["PoseLocalVisualizer", "probability_area_thresholds", "render_probability_areas", "draw_poses", "resize_rgb", "aspect_boxes",
-           "int_boxes", "COCO_SKELETON", "COCO_LINK_COLORS", "COCO_KEYPOINT_COLORS", "PAREA_MAX_KEYPOINTS"]
+           "int_boxes", "draw_datasamples", "plan_render_chunks", "render_share_bytes", "COCO_SKELETON", "COCO_LINK_COLORS", "COCO_KEYPOINT_COLORS", "PAREA_MAX_KEYPOINTS"]

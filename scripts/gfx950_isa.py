@@ -14,6 +14,7 @@ EXTRA_FLAGS = {
     "pp_ffn_dma.hip": ["-fno-slp-vectorize"],
     "pp_render.hip": ["-ffp-contract=off"],
     "pp_warp.hip": ["-ffp-contract=off"],
+    "pp_render_batch.hip": ["-ffp-contract=off"],
     "pp_jpeg.hip": ["-fwrapv"],
 }
 

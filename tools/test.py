@@ -13,7 +13,10 @@ duplicates removed by OKS-NMS per image), for a single-dataset config:
 
     python tools/test.py configs/td-hm_ViTPose-base_mi355x_coco-256x192.py CHECKPOINT \
         --cfg-options test_dataloader.dataset.data_root=/data/coco/ \
-        --bbox-file /data/coco/person_detection_results/COCO_val2017_detections_AP_H_56_person.json --nms device"""
+        --bbox-file /data/coco/person_detection_results/COCO_val2017_detections_AP_H_56_person.json --nms device
+
+``--show-dir DIR`` dumps one picture per evaluated instance (the reference's PoseVisualizationHook); add
+``--cfg-options model.test_cfg.output_heatmaps=True`` for the probability-area panel under the pose."""
 import ast
 import json
 import os
@@ -62,6 +65,9 @@ def main(argv=None):
                     help="with --bbox-file: drop boxes whose score is below T before the model sees them")
     ap.add_argument("--nms", default="host", choices=["host", "device"],
                     help="where the metric's OKS-NMS runs (CocoMetric nms_backend); device: all images in two launches, the same kept sets")
+    ap.add_argument("--show-dir", default=None, metavar="DIR",
+                    help="write one picture per evaluated instance into DIR, named <image stem>_<index>.<suffix>: the pose on the image and, with "
+                         "model.test_cfg.output_heatmaps=True, the probability areas under it; drawn and coded (.jpg, .png) on the GPU")
     args = ap.parse_args(argv)
     if args.bbox_score_thr is not None and not args.bbox_file:
         ap.error("--bbox-score-thr needs --bbox-file")
@@ -96,7 +102,7 @@ def main(argv=None):
     batch_size = args.batch_size or int(loader.get("batch_size", 64))
     t0 = time.perf_counter()
     metrics = runner.test_dataset(model, dataset, evaluator, batch_size=batch_size, workers=args.workers, decode=args.decode,
-                                  decode_entropy=args.decode_entropy)
+                                  decode_entropy=args.decode_entropy, show_dir=args.show_dir)
     dt = time.perf_counter() - t0
     for k, v in metrics.items():
         print(f"{k}: {v:.4f}")
