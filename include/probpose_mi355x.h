@@ -589,7 +589,8 @@ int pp_probmap_decode_flags(const float* maps, const float* maps_flip, const int
  * from the seven-point fp32 derivative / Hessian, (H + eps32 I)^+ in fp64, the result rounded to fp32 and rescaled:
  * `keypoints` (B, K, 2) f64 = loc / (W - 1, H - 1) * (in_w, in_h). A map with maximum <= 0 takes three of its seven points from the
  * map of keypoint k - 1 (K - 1 for k = 0) of the same sample, as the reference's flat index does. blur_kernel_size odd, 1 .. 19;
- * H, W >= 2, H * W <= 12288 and the two LDS images ((W + ks) H + (H + ks - 1) W floats) within 160 KiB, else PP_ERR_UNSUPPORTED.
+ * H, W >= 2, H * W <= 12288 and the two LDS images ((W + ks) H + (H + ks - 1) W floats) within 160 KiB less
+ * the 256 bytes the kernel holds statically, else PP_ERR_UNSUPPORTED.
  * avg_out (optional) takes the averaged maps, row-major (B, K, H, W). A map with a non-finite value (or, for a map with maximum
  * <= 0, such a neighbour) yields NaN locs / keypoints / scores. */
 int pp_udp_heatmap_decode(const float* maps, const float* maps_flip, const int32_t* flip_indices, int B, int K, int H, int W,
@@ -606,7 +607,12 @@ int pp_udp_heatmap_decode(const float* maps, const float* maps_flip, const int32
  * on: flip-back, channel permutation and fp32 average; separable OKS-kernel convolution in fp64, one rounding to fp32; first-occurrence
  * argmax; one fp32 sub-pixel step; rescale in fp64; `scores` = the raw averaged map at the integer argmax. Row-major maps, or with
  * PP_DECODE_PHASED the phase-separated layout of pp_deconv_head (even H, W % 8 == 0); PP_DECODE_SHIFT_HEATMAP honoured; any other
- * flag is PP_ERR_INVALID_ARG. taps / radius as pp_probmap_decode takes them; K <= 17 (the reference's table of sigmas), else
+ * flag is PP_ERR_INVALID_ARG. conv_out against scipy.ndimage.convolve (a raster sum over the 2-D kernel, a product and a sum per tap): both
+ * are fp64 sums rounded once to fp32, and differ in fp64 by at most (d^2 + 2 d + 130) 2^-53 times the same convolution of |map|
+ * (d = 2 r + 1: the two orders of summation, and the 1-D taps against the 2-D weights). On a result that does not cancel that is far
+ * below half an fp32 spacing and the bits are equal; on a signed map whose result is a cancellation residue (or an exact 0.0 of
+ * scipy's) conv_out is within that bound, not equal, and the argmax may move between pixels scipy ties to within it. locs,
+ * keypoints and scores are always the reference's steps applied to conv_out as returned. taps / radius as pp_probmap_decode takes them; K <= 17 (the reference's table of sigmas), else
  * PP_ERR_UNSUPPORTED. Shape limits are pp_probmap_decode's. A map holding a non-finite value (in either pass) gives NaN locs /
  * keypoints / scores (and NaN avg_out / conv_out maps) for that (crop, keypoint) only. Tallied as "pp_expmax_heatmap_decode". */
 int pp_expmax_heatmap_decode(const float* maps, const float* maps_flip, const int32_t* flip_indices, const double* taps,
@@ -621,7 +627,7 @@ int pp_expmax_heatmap_decode(const float* maps, const float* maps_flip, const in
  * for bit those of pp_probmap_decode_flags(PP_DECODE_LOGITS | flags, avg_out = maps) followed by pp_udp_heatmap_decode(maps): both
  * halves are the same device code (csrc/pp_decode_stages.h). logits row-major or PP_DECODE_PHASED (even H, W % 8 == 0);
  * PP_DECODE_SHIFT_HEATMAP honoured; any other flag is PP_ERR_INVALID_ARG. W % 4 == 0, H * W <= 12288, blur_kernel_size odd,
- * 1 .. 19, and the LDS above (512 B + max(H (W + 24) + 32, 2048, (H + ks - 1) W) + H ((W + ks - 1) | 1) floats) within 160 KiB, else
+ * 1 .. 19, and the LDS above (512 B + max(H (W + 24) + 32, 2048, (H + ks - 1) W) + H ((W + ks - 1) | 1) floats) within 160 KiB less the 256 bytes the kernel holds statically, else
  * PP_ERR_UNSUPPORTED. A non-finite logit gives NaN locs / keypoints / scores (and a NaN avg_out map) for that (crop, keypoint), and
  * for one whose map has maximum <= 0 and takes points from that neighbour (see pp_udp_heatmap_decode). Tallied as
  * "pp_argmax_probmap_decode". */

@@ -122,7 +122,7 @@ extern "C" int pp_argmax_probmap_decode(const float* logits, const float* logits
     const int r = (blur_kernel_size - 1) / 2;
     const size_t region = argmax_region_floats(H, W, r);
     const size_t lds = RED_BYTES + (region + (size_t)H * ((W + 2 * r) | 1)) * 4;
-    PP_REQUIRE(lds <= (size_t)160 * 1024, PP_ERR_UNSUPPORTED,
+    PP_REQUIRE(lds <= UDP_MAX_DYNAMIC_LDS, PP_ERR_UNSUPPORTED,
                "pp_argmax_probmap_decode: the Sparsemax map and the blur's map image exceed one CU's LDS");
     if (B == 0) return PP_OK;  // empty batch: nothing to read or write (buffers may be NULL)
     PP_REQUIRE(logits && locs && keypoints && scores, PP_ERR_INVALID_ARG,

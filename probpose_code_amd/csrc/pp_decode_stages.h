@@ -358,6 +358,10 @@ constexpr int UDP_THREADS = 256;
 constexpr int UDP_MAX_R = PP_MAX_RADIUS;  // blur_kernel_size <= 19
 constexpr int UDP_RED_FLOATS = 64;        // cross-wave reduction scratch, from UDP_TAPS_AT the taps of the runtime-radius kernel
 constexpr int UDP_TAPS_AT = 32;
+// __syncthreads_or (udp_blur) reduces through LDS the compiler allocates statically, 256 bytes per kernel: the dynamic region a launch
+// may ask for is one CU's 160 KiB less that (hipFuncSetAttribute refuses more with an error, not with PP_ERR_UNSUPPORTED)
+constexpr size_t UDP_STATIC_LDS = 256;
+constexpr size_t UDP_MAX_DYNAMIC_LDS = (size_t)160 * 1024 - UDP_STATIC_LDS;
 
 struct UdpTaps {
     float t[2 * UDP_MAX_R + 1];

@@ -119,7 +119,7 @@ extern "C" int pp_udp_heatmap_decode(const float* maps, const float* maps_flip, 
     PP_REQUIRE((long)H * W <= 12288, PP_ERR_UNSUPPORTED, "pp_udp_heatmap_decode: H*W exceeds 12288 pixels");
     const int r = (blur_kernel_size - 1) / 2;
     const size_t lds = ((size_t)UDP_RED_FLOATS + (size_t)H * ((W + 2 * r) | 1) + (size_t)(H + 2 * r) * W) * 4;
-    PP_REQUIRE(lds <= (size_t)160 * 1024, PP_ERR_UNSUPPORTED, "pp_udp_heatmap_decode: the map and its blur halo exceed one CU's LDS");
+    PP_REQUIRE(lds <= UDP_MAX_DYNAMIC_LDS, PP_ERR_UNSUPPORTED, "pp_udp_heatmap_decode: the map and its blur halo exceed one CU's LDS");
     const UdpTaps taps = udp_gaussian_taps(blur_kernel_size);
     UdpKernel kern = udp_kernel(r, maps_flip != nullptr);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
