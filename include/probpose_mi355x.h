@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-/* 4 (round 6): + pp_warp_affine_u8_batch (additive); + pp_parea_scratch_bytes, pp_parea_thresholds, pp_parea_compose, pp_draw_poses, pp_resize_bilinear_u8 (the --draw-heatmap
+/* 4 (later, additive): + pp_relu_operand, pp_taps_upsample4_conv3x3 (the ViTPose "-simple" head, csrc/pp_simple_head.hip).
+ * 4 (round 6): + pp_warp_affine_u8_batch (additive); + pp_parea_scratch_bytes, pp_parea_thresholds, pp_parea_compose, pp_draw_poses, pp_resize_bilinear_u8 (the --draw-heatmap
  *    picture, csrc/pp_render.hip; added later under the same version: purely additive); + pp_render_batch_scratch_bytes, pp_render_samples_batch (the pictures of a batch of samples in one
  *    set of launches, csrc/pp_render_batch.hip; additive); the numeric domain of PP_PREC_F16X3 stated and guarded (below); power-of-two WEIGHT SCALES: + pp_gemm_ws, pp_linear_ln_folded_ws,
  *    pp_qkv_attention_split_ws, pp_gemm_residual_layernorm_ws, pp_ffn_split_residual_layernorm_ws, pp_proj_ffn_split_residual_layernorm_ws (the unsuffixed entry points = scale 1);
@@ -634,6 +635,39 @@ int pp_expmax_heatmap_decode(const float* maps, const float* maps_flip, const in
 int pp_argmax_probmap_decode(const float* logits, const float* logits_flip, const int32_t* flip_indices, int B, int K, int H, int W,
                              double in_w, double in_h, float temperature, float normalize, int blur_kernel_size, float* avg_out,
                              float* locs, double* keypoints, float* scores, int flags, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * The head of the ViTPose "-simple" variants (csrc/pp_simple_head.hip): FeatureMapProcessor(scale_factor=4.0, apply_relu=True)
+ * (mmpose/models/necks/fmap_proc_neck.py:52-92; resize = F.interpolate(x, None, 4.0, "bilinear", align_corners=False),
+ * mmpose/models/utils/ops.py:60) in front of HeatmapHead(deconv_out_channels=[], final_layer=dict(kernel_size=3, padding=1))
+ * (heatmap_head.py:198-213). Behind the ReLU everything is linear, so the 3x3 convolution runs at the backbone's resolution as nine
+ * 1x1 "tap" convolutions - ONE pp_gemm_ws with the (9 K, E) tap matrix and planar_P = h * w - and the upsampling gathers from the tap
+ * planes; the (n_img, 4h, 4w, E) upsampled map is never built. Three launches: pp_relu_operand, pp_gemm_ws, pp_taps_upsample4_conv3x3.
+ *
+ * pp_relu_operand: out = relu(in) for n_rows x row_len elements of an activation tensor in the operand format `format` (PP_OUT_F32,
+ *   PP_OUT_BF16, PP_OUT_SPLIT), dense rows, row_len % 32 == 0, both buffers 16-byte aligned, out distinct from in (the input stays as it
+ *   is). fp32 / bf16: an element becomes +0 unless it is > 0 or NaN. Split fp16: an element becomes (+0, +0)
+ *   unless float(hi) + float(lo) > 0 or that sum is NaN. Every other element is copied bit for bit - a NaN (an out-of-range operand,
+ *   "numeric domain" above) reaches the logits and the decode behind them writes NaN results. n_rows == 0 returns PP_OK at once.
+ *
+ * pp_taps_upsample4_conv3x3:
+ *   out[i, k, Y, X] = bias[k] + sum over dy, dx in {-1, 0, 1} with 0 <= Y + dy < 4h and 0 <= X + dx < 4w
+ *                               of bil(taps[i, (3 (dy + 1) + dx + 1) K + k], Y + dy, X + dx)
+ *   bil(P, Y', X'): sy = max((Y' + 0.5) / 4 - 0.5, 0), y0 = floor(sy), y1 = min(y0 + 1, h - 1), ly = sy - y0; x likewise;
+ *                   = (1 - ly) ((1 - lx) P[y0, x0] + lx P[y0, x1]) + ly ((1 - lx) P[y1, x0] + lx P[y1, x1])
+ *   taps (n_img, 9 K, h * w) fp32: plane t K + k = tap t = 3 (dy + 1) + (dx + 1) of keypoint k WITHOUT bias - what
+ *        pp_gemm_ws(act = relu'd NHWC features (n_img h w, E), weight row t K + k = W[k, :, dy + 1, dx + 1], bias = NULL, N = 9 K,
+ *        planar_P = h * w) stores; bias (K) fp32; out (n_img, K, 4h * 4w) fp32, plain planar (not PP_DECODE_PHASED): what
+ *        pp_udp_heatmap_decode / pp_expmax_heatmap_decode read.
+ *   A tap outside the upsampled map is the convolution's zero padding: it is left out by selection (not sampled at a clamped position, not
+ *   multiplied by zero). The weights ly, lx and their products are exact in fp32; the sum is fp32 in a fixed order (bit-identical from
+ *   launch to launch), within 41 * 2^-24 * (|bias| + sum of weight * |tap|) of the exact value.
+ *   K >= 1, h, w >= 1 (at most 2^20 each), n_img >= 0 (0 returns PP_OK at once; n_img K ceil(h / 16) ceil(w / 16) < 2^31 workgroups, else
+ *   PP_ERR_UNSUPPORTED). 16-byte stores when out is 16-byte aligned, scalar ones otherwise.
+ * Both are tallied under "pp_simple_head.hip" (pp_launch_count).
+ * ---------------------------------------------------------------------------------- */
+int pp_relu_operand(int format, const void* in, void* out, int n_rows, int row_len, void* stream);
+int pp_taps_upsample4_conv3x3(const float* taps, const float* bias, float* out, int n_img, int K, int h, int w, void* stream);
 
 /* Split-K form of the towers' 3x3 convolution for stages with few output pixels: the contraction is cut into ksplit slices -
  * 1, 3 or 9: whole taps (any precision); any other count with Cin % (32 ksplit) == 0: channel ranges [s Cin / ksplit, ...) of all nine

@@ -13,6 +13,7 @@ from .config import Config  # noqa: F401
 from .engine import ProbPoseEngine, domain_report  # noqa: F401
 from .pipeline import StepPipeline  # noqa: F401
 from .pose_estimators import (  # noqa: F401
+    FeatureMapProcessor,
     HeatmapHead,
     PoseDataPreprocessor,
     ProbMapHead,

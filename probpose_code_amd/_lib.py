@@ -92,6 +92,8 @@ SIGNATURES = {
         c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_double, c_double, _P, _P, _P, _P, _P, c_int, _P]),
     "pp_argmax_probmap_decode": (
         c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_double, c_double, c_float, c_float, c_int, _P, _P, _P, _P, c_int, _P]),
+    "pp_relu_operand": (c_int, [c_int, _P, _P, c_int, c_int, _P]),
+    "pp_taps_upsample4_conv3x3": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "pp_deconv_head": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "pp_deconv_head_split": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "pp_gemm": (

@@ -8,6 +8,7 @@ comes from torch, that is all torch does here) and enqueues the hand-written HIP
   preprocess + flip copy + patch im2col -> patch-embed GEMM (+bias +pos_embed)
   -> L x [LN -> qkv GEMM -> attention -> proj GEMM (+residual) -> LN -> fc1 GEMM (GELU) -> fc2 GEMM (+residual)]
   -> final LN -> deconv x2 (4 phase GEMMs each, BN folded, ReLU) -> 1x1 conv (planar logits)
+     (the ViTPose "-simple" head instead: ReLU -> the 3x3 final layer as nine taps at the backbone's resolution -> x4 upsampling gather)
   -> fused Sparsemax + flip-average + OKS-conv + argmax + sub-pixel decode
   and, from the same features, the four scalar towers (grouped implicit-GEMM 3x3 convs,
   MaxPool+ReLU, final 1x1 + sigmoid/ReLU + flip-average).
@@ -97,7 +98,7 @@ class ProbPoseEngine:
                  bgr_to_rgb: bool = True, temperature: float = 0.5, normalize: Optional[float] = 1.0,
                  input_size: Optional[Sequence[int]] = None, ln_eps: float = 1e-6, precision: str = "f16x3",
                  device="cuda", plan: Optional[Dict[str, object]] = None, head_kind: Optional[str] = None,
-                 blur_kernel_size: int = 11, decode: Optional[str] = None):
+                 blur_kernel_size: int = 11, decode: Optional[str] = None, neck_relu: bool = True):
         if precision not in PREC:
             raise ValueError(f"precision must be one of {list(PREC)}, got {precision!r}")
         self.device = torch.device(device)
@@ -144,7 +145,11 @@ class ProbPoseEngine:
         self.E = self.w.embed_dims
         self.hd = self.E // num_heads
         self.K = self.w.num_keypoints
-        self.up = 2 ** len(self.w.deconv_channels)
+        # the ViTPose "-simple" head (weights.pack: no deconvolutions, a 3x3 final layer): FeatureMapProcessor's ReLU (`neck_relu` = its apply_relu)
+        # and bilinear x4 upsampling run inside the head's launches (heatmap_logits), the heatmap is 4 Hp x 4 Wp
+        self.simple_head = self.w.final_upsample == 4
+        self.neck_relu = bool(neck_relu)
+        self.up = 4 if self.simple_head else 2 ** len(self.w.deconv_channels)
         if precision == "bf16":
             # every bf16 convolution kernel walks K in tiles of 64 channels of one tap (pp_conv_gemm, pp_deconv_head): a deconvolution whose
             # input width is no multiple of 64 has no bf16 kernel. Said here, by name, and not as PP_ERR_UNSUPPORTED at the first batch
@@ -346,6 +351,10 @@ class ProbPoseEngine:
             keypoints=e(B, self.K, 2, dt=torch.float64), scores=e(B, self.K, dt=f32),
             heatmaps=e(B, self.K, self.Hh, self.Wh, dt=f32),
         )
+        if self.simple_head:
+            # the ReLU'd features (the features themselves stay: extract_feat and the callers of run_backbone get them) and the nine tap planes per keypoint
+            ws["relu"] = buf("feat", (M, E)) if self.neck_relu else None
+            ws["taps"] = e(nb, 9 * self.K, self.Np, dt=f32)
         hh, ww = self.Hp, self.Wp
         for j, c in enumerate(dc):
             hh, ww = hh * 2, ww * 2
@@ -619,6 +628,17 @@ class ProbPoseEngine:
         ob = self.fmt
         src, cin, hh, ww = feat, self.E, self.Hp, self.Wp
         self._logits_phased = False
+        if self.simple_head:
+            # FeatureMapProcessor(scale_factor=4, apply_relu) + the 3x3 final layer, composed (csrc/pp_simple_head.hip): ReLU, the nine taps of every
+            # keypoint as ONE Linear layer at the backbone's resolution (planar: (nb, 9 K, Hp Wp), no bias), then the gather that upsamples and sums them
+            if self.neck_relu:
+                self._call("neck_relu", "pp_relu_operand", ob, feat.data_ptr(), ws["relu"].data_ptr(), nb * self.Np, self.E, st)
+                src = ws["relu"]
+            self._gemm(st, src, w["final.taps"], None, ws["taps"], nb * self.Np, 9 * self.K, self.E, planar=self.Np, out_bf16=0,
+                       winv=w.inv("final.taps"))
+            self._call("taps_upsample", "pp_taps_upsample4_conv3x3", ws["taps"].data_ptr(), w["final.b"].data_ptr(), ws["logits"].data_ptr(), nb,
+                       self.K, self.Hp, self.Wp, st)
+            return ws["logits"]
         nd = len(w.deconv_channels)
         for j, cout in enumerate(w.deconv_channels):
             dst = ws[f"d{j}"]

@@ -6,6 +6,8 @@ Same registry names, constructor arguments, method names and outputs as
 * ``VisionTransformer``     -- mmpretrain 1.2.0 [3P], ctor args at
   configs/body_2d_keypoint/topdown_probmap/coco/td-pm_ProbPose-small_8xb64-210e_coco-256x192.py:56-67
 * ``ProbMapHead``           -- mmpose/models/heads/hybrid_heads/probmap_head.py:25-804 (inference methods)
+* ``HeatmapHead``           -- mmpose/models/heads/heatmap_heads/heatmap_head.py:22-370 (inference methods)
+* ``FeatureMapProcessor``   -- mmpose/models/necks/fmap_proc_neck.py:13-92 (the neck of the ViTPose ``-simple`` variants)
 * ``TopdownPoseEstimator``  -- mmpose/models/pose_estimators/topdown.py:12-194, base.py:17-243
 
 but every ``forward`` / ``predict`` lands in ``ProbPoseEngine`` (hand-written HIP through the C ABI).
@@ -165,6 +167,42 @@ class VisionTransformer(nn.Module):
         eng = self._owner().engine
         feat = eng.export_features(eng.run_backbone(x, flip_test=False))
         return (feat.permute(0, 3, 1, 2),)
+
+
+# =================================================================================================
+@register(MODELS, reference_name="FeatureMapProcessor", mi355x_name="FeatureMapProcessorMI355X")
+class FeatureMapProcessor(nn.Module):
+    """fmap_proc_neck.py:13-92 with the reference's constructor: the neck of the ViTPose ``-simple`` variants,
+    ``FeatureMapProcessor(scale_factor=4.0, apply_relu=True)`` - ReLU, then ``F.interpolate(x, None, 4.0, "bilinear", align_corners=False)``
+    (models/utils/ops.py:60). It has no parameters. Inside a ``TopdownPoseEstimator`` its output is never built: the estimator's engine applies
+    the ReLU and composes the upsampling with the head's 3x3 final layer (csrc/pp_simple_head.hip; INTEGRATION.md, deviations), so
+    ``extract_feat`` keeps returning the backbone's maps. ``forward`` is the plain torch form for a caller of ``model.neck(x)``.
+    What the device path runs: ``scale_factor=4.0``, ``apply_relu`` either way, ``align_corners=False``, no ``select_index``, no ``concat``;
+    anything else is refused here, by name."""
+
+    def __init__(self, select_index: Optional[Union[int, Tuple[int]]] = None, concat: bool = False, scale_factor: float = 1.0,
+                 apply_relu: bool = False, align_corners: bool = False):
+        super().__init__()
+        assert scale_factor > 0, f"the argument `scale_factor` must be positive, but got {scale_factor}"
+        if select_index is not None:
+            raise NotImplementedError(f"FeatureMapProcessor on MI355X: select_index={select_index!r} is not implemented (the backbone returns one map)")
+        if concat:
+            raise NotImplementedError("FeatureMapProcessor on MI355X: concat=True is not implemented (the backbone returns one map)")
+        if float(scale_factor) != 4.0:
+            raise NotImplementedError(f"FeatureMapProcessor on MI355X: scale_factor={scale_factor!r} is not implemented; the x4 upsampling of the "
+                                      "ViTPose '-simple' configs is (scale_factor=4.0)")
+        if align_corners:
+            raise NotImplementedError("FeatureMapProcessor on MI355X: align_corners=True is not implemented (the '-simple' configs use False)")
+        self.select_index, self.concat = None, False
+        self.scale_factor, self.apply_relu, self.align_corners = float(scale_factor), bool(apply_relu), False
+
+    def forward(self, inputs):
+        many = isinstance(inputs, (tuple, list))
+        maps = list(inputs) if many else [inputs]
+        if self.apply_relu:
+            maps = [torch.relu(x) for x in maps]
+        maps = [nn.functional.interpolate(x, None, self.scale_factor, "bilinear", align_corners=False) for x in maps]
+        return maps if many else maps[0]
 
 
 # =================================================================================================
@@ -362,8 +400,15 @@ class HeatmapHead(nn.Module):
     """heatmap_head.py:22-370, inference side: the head of the ViTPose baseline - ProbMapHead's heatmap branch without Sparsemax and
     without the scalar towers (deconvolutions + BN + ReLU, a 1x1 conv), decoded by the ``UDPHeatmap`` codec. Constructor
     arguments are the reference's; ``loss`` is accepted and ignored (training is out of scope). What the kernels do not cover is
-    refused: deconvolution kernels 3 / 2, intermediate conv layers, a final layer that is not the 1x1 conv (the ``-simple``
-    ViTPose variants, whose head is an upsample + 3x3 conv), no deconvolution at all."""
+    refused: deconvolution kernels 3 / 2, intermediate conv layers, a final layer that is not the 1x1 conv, no deconvolution at all.
+
+    The head of the ``-simple`` ViTPose variants - no deconvolutions, ``final_layer=dict(kernel_size=3, padding=1)`` - runs behind the x4
+    upsampling of a ``FeatureMapProcessor`` neck and only there: the 3x3 convolution is composed with that upsampling
+    (csrc/pp_simple_head.hip). The head learns of it through the MI355X-only keyword ``upsampled_input=4``, which ``TopdownPoseEstimator``
+    adds to its copy of the head's config when it has the neck; with it the head accepts exactly that pairing (no deconvolutions: ``None``,
+    ``[]``, ``()``; no intermediate conv layers; the 3x3 / padding 1 / stride 1 final layer, built as ``nn.Conv2d(in_channels, K, 3,
+    padding=1)`` so that checkpoint keys load under the reference's names). Without the keyword nothing changes: built on its own, such a
+    head is refused as before."""
 
     _version = 2
 
@@ -371,10 +416,15 @@ class HeatmapHead(nn.Module):
                  deconv_out_channels: Optional[Sequence[int]] = (256, 256, 256),
                  deconv_kernel_sizes: Optional[Sequence[int]] = (4, 4, 4),
                  conv_out_channels: Optional[Sequence[int]] = None, conv_kernel_sizes: Optional[Sequence[int]] = None,
-                 final_layer: dict = dict(kernel_size=1), loss=None, decoder=None, init_cfg=None):
+                 final_layer: dict = dict(kernel_size=1), loss=None, decoder=None, init_cfg=None,
+                 upsampled_input: Optional[int] = None):
         super().__init__()
         self.in_channels, self.out_channels = in_channels, out_channels
         self.decoder = KEYPOINT_CODECS.build(decoder) if decoder is not None else None
+        self.upsampled_input = upsampled_input
+        if upsampled_input is not None:
+            self._init_behind_upsampling(upsampled_input, deconv_out_channels, conv_out_channels, final_layer)
+            return
         if not deconv_out_channels:
             raise NotImplementedError("HeatmapHead on MI355X needs at least one deconv layer (ViTPose's classic head has two; the "
                                       "'-simple' variants upsample instead and are not implemented)")
@@ -401,6 +451,27 @@ class HeatmapHead(nn.Module):
             raise NotImplementedError("final_layer must be the plain 1x1 conv of the ViTPose config (the '-simple' variants end in a "
                                       "3x3 conv behind an upsample: not implemented)")
         self.final_layer = nn.Conv2d(cin, out_channels, 1)
+        self._register_load_state_dict_pre_hook(self._load_state_dict_pre_hook)
+        self._owner = None
+        self.init_weights()
+
+    def _init_behind_upsampling(self, factor, deconv_out_channels, conv_out_channels, final_layer):
+        """The ``-simple`` head behind ``FeatureMapProcessor(scale_factor=4.0)`` (``upsampled_input=4``, set by the estimator)."""
+        pairing = ("the pairing that runs behind a FeatureMapProcessor(scale_factor=4.0) neck is the '-simple' head: deconv_out_channels=[] "
+                   "(or None), no conv_out_channels, final_layer=dict(kernel_size=3, padding=1)")
+        if factor != 4:
+            raise NotImplementedError(f"HeatmapHead on MI355X: upsampled_input={factor!r}; " + pairing)
+        if deconv_out_channels:
+            raise NotImplementedError(f"HeatmapHead on MI355X: deconv_out_channels={tuple(deconv_out_channels)} behind an upsampling neck (a neck "
+                                      "in front of the classic deconvolution head) has no kernel; " + pairing)
+        if conv_out_channels:
+            raise NotImplementedError("intermediate conv layers (conv_out_channels) have no MI355X kernel; " + pairing)
+        fl = dict(final_layer) if final_layer is not None else None
+        if fl is None or fl.get("kernel_size", 1) != 3 or fl.get("padding", 0) != 1 or fl.get("stride", 1) != 1:
+            raise NotImplementedError(f"HeatmapHead on MI355X: final_layer={fl!r} behind an upsampling neck; " + pairing)
+        self.deconv_layers = nn.Identity()
+        self.conv_layers = nn.Identity()
+        self.final_layer = nn.Conv2d(self.in_channels, self.out_channels, 3, padding=1)
         self._register_load_state_dict_pre_hook(self._load_state_dict_pre_hook)
         self._owner = None
         self.init_weights()
@@ -506,8 +577,7 @@ class TopdownPoseEstimator(nn.Module):
                  data_preprocessor: Optional[dict] = None, init_cfg=None, metainfo: Optional[dict] = None,
                  precision: str = "f16x3", graph_replay: bool = True, graph_capture_after: int = 3, max_graphs: int = 8):
         super().__init__()
-        if neck is not None:
-            raise NotImplementedError("the ProbPose config has no neck")
+        head = self._pair_neck_and_head(neck, head)
         self.metainfo = metainfo
         self.train_cfg = train_cfg if train_cfg else {}
         self.test_cfg = test_cfg if test_cfg else {}
@@ -525,6 +595,7 @@ class TopdownPoseEstimator(nn.Module):
         self._sizes_seen: Dict[tuple, int] = {}
         self._gather = None  # ResultGather of ``predict``: pinned host record buffer, grown to the largest batch met
         self.backbone = MODELS.build(backbone)
+        self.neck = MODELS.build(neck) if neck is not None else None
         self.head = MODELS.build(head) if head is not None else None
         self.data_preprocessor = MODELS.build(data_preprocessor) if data_preprocessor is not None else PoseDataPreprocessor()
         import weakref
@@ -539,7 +610,39 @@ class TopdownPoseEstimator(nn.Module):
     # -- properties of the reference
     @property
     def with_neck(self) -> bool:
-        return False
+        return self.neck is not None
+
+    @staticmethod
+    def _pair_neck_and_head(neck: Optional[dict], head: Optional[dict]) -> Optional[dict]:
+        """The one neck that runs is ``FeatureMapProcessor(scale_factor=4.0)`` in front of the ``-simple`` ``HeatmapHead`` (no deconvolutions, a
+        3x3 final layer): its output is never built, the engine composes it with the head's convolution. Returns the head's config - a copy
+        with the MI355X-only ``upsampled_input=4`` when the neck is there. Every other pairing is refused here, with the pairing that runs."""
+        def cls_of(cfg):
+            t = dict(cfg).get("type")
+            return MODELS.get(t) if isinstance(t, str) else t
+
+        runs = ("the pairing that runs is neck=dict(type='FeatureMapProcessor', scale_factor=4.0, apply_relu=True) with head=dict(type='HeatmapHead', "
+                "deconv_out_channels=[], deconv_kernel_sizes=[], final_layer=dict(kernel_size=3, padding=1)) - the ViTPose '-simple' configs")
+        head_cls = cls_of(head) if head is not None else None
+        is_heatmap = isinstance(head_cls, type) and issubclass(head_cls, HeatmapHead)
+        if neck is None:
+            if is_heatmap and dict(head).get("upsampled_input") is not None:
+                raise NotImplementedError("head.upsampled_input is set by the estimator when it has the FeatureMapProcessor neck; without a neck "
+                                          "there is no upsampling in front of the head; " + runs)
+            if is_heatmap and not dict(head).get("deconv_out_channels", (256, 256, 256)):
+                raise NotImplementedError("HeatmapHead without deconv layers under an estimator without a neck: the head's 3x3 final layer has a "
+                                          "kernel only behind the x4 upsampling; " + runs)
+            return head
+        neck_cls = cls_of(neck)
+        if not (isinstance(neck_cls, type) and issubclass(neck_cls, FeatureMapProcessor)):
+            raise NotImplementedError(f"neck={dict(neck).get('type')!r} is not implemented on MI355X (the ProbPose and classic ViTPose configs have no "
+                                      "neck); " + runs)
+        if not is_heatmap:
+            raise NotImplementedError(f"head={dict(head).get('type') if head is not None else None!r} behind a FeatureMapProcessor neck is not "
+                                      "implemented (a ProbMapHead behind a neck is out of scope); " + runs)
+        head = dict(head)
+        head.setdefault("upsampled_input", 4)
+        return head
 
     @property
     def with_head(self) -> bool:
@@ -569,7 +672,8 @@ class TopdownPoseEstimator(nn.Module):
             bgr_to_rgb=dp.channel_conversion, temperature=getattr(hd, "temperature", 1.0), normalize=getattr(hd, "normalize", None),
             input_size=tuple(codec.input_size), ln_eps=bb.ln_eps, precision=self.precision,
             head_kind="heatmap" if heatmap else "probmap", decode=decode,
-            blur_kernel_size=int(getattr(codec, "blur_kernel_size", 11)) if decode == "dark" else 11)
+            blur_kernel_size=int(getattr(codec, "blur_kernel_size", 11)) if decode == "dark" else 11,
+            neck_relu=self.neck.apply_relu if self.neck is not None else True)
 
     @property
     def engine(self) -> ProbPoseEngine:
@@ -624,6 +728,8 @@ class TopdownPoseEstimator(nn.Module):
         raise NotImplementedError("training is outside the MI355X inference hot path")
 
     def extract_feat(self, inputs: Tensor) -> Tuple[Tensor]:
+        """The backbone's maps - with a neck too (deviation from topdown.py:72-84): the x4 upsampled map of the ``-simple``
+        variants is never built, the engine applies the neck inside the head's launches (``head.forward`` / ``head.predict`` take these maps)."""
         return self.backbone(inputs)
 
     def _forward(self, inputs: Tensor, data_samples=None):

@@ -113,9 +113,12 @@ def synthetic_state_dict(arch: str = "small", img_size=(256, 192), num_keypoints
     """``stats="unit"``: activations O(1) everywhere (the weights every round-1..5 parity figure was taken on);
     ``stats="trained"``: the same network re-parametrised to a trained ViT's statistics (``_trained_like``).
     ``head="heatmap"``: the state dict of a ``HeatmapHead`` model (the ViTPose baseline) - the same backbone and heatmap branch
-    (the same tensors as ``head="probmap"`` at equal seed, the final layer's weights centred per keypoint), no scalar-tower keys."""
-    if head not in ("probmap", "heatmap"):
-        raise ValueError(f"head must be 'probmap' or 'heatmap', got {head!r}")
+    (the same tensors as ``head="probmap"`` at equal seed, the final layer's weights centred per keypoint), no scalar-tower keys.
+    ``head="heatmap-simple"``: the head of the ViTPose ``-simple`` variants - the same backbone, no deconvolution keys,
+    ``head.final_layer.weight`` (K, E, 3, 3) at std ``logit_scale / sqrt(9 E)``, centred per keypoint, drawn from a generator stream of its
+    own (the other heads' tensors do not move); ``deconv_out_channels`` is ignored."""
+    if head not in ("probmap", "heatmap", "heatmap-simple"):
+        raise ValueError(f"head must be 'probmap', 'heatmap' or 'heatmap-simple', got {head!r}")
     if stats not in ("unit", "trained"):
         raise ValueError(f"stats must be 'unit' or 'trained', got {stats!r}")
     a = ARCHS[arch] if isinstance(arch, str) else arch
@@ -161,6 +164,13 @@ def synthetic_state_dict(arch: str = "small", img_size=(256, 192), num_keypoints
         cin = cout
     sd["head.final_layer.weight"] = n(num_keypoints, cin, 1, 1, std=logit_scale / math.sqrt(cin))
     sd["head.final_layer.bias"] = n(num_keypoints, std=0.1)
+    if head == "heatmap-simple":
+        for k in [k for k in sd if k.startswith("head.deconv_layers.")]:
+            del sd[k]
+        gs = torch.Generator().manual_seed(seed + 7919)  # its own stream: nothing the other heads draw moves
+        w = torch.randn(num_keypoints, E, 3, 3, generator=gs) * (logit_scale / math.sqrt(9 * E))
+        # centred per keypoint, for the reason given below: the 3x3 conv reads ReLU'd (non-negative) features
+        sd["head.final_layer.weight"] = w - w.mean(dim=(1, 2, 3), keepdim=True)
     if head == "heatmap":
         # HeatmapHead's maps are decoded as they are (no Sparsemax in front). A 1x1 conv of random sign on ReLU'd (non-negative) maps gives every
         # keypoint's map an offset of either sign, large against its peaks; with the flip-test average of two unrelated passes a map then often has
@@ -180,10 +190,13 @@ def synthetic_state_dict(arch: str = "small", img_size=(256, 192), num_keypoints
 
 
 def head_kind_of(cfg) -> str:
-    """``head=`` of ``synthetic_state_dict`` for a config's ``model.head.type``: "heatmap" for ``HeatmapHead`` (the ViTPose baseline),
-    "probmap" otherwise."""
-    head_type = str(dict(dict(cfg["model"]).get("head") or {}).get("type", "ProbMapHead"))
-    return "heatmap" if head_type.split(".")[-1] in ("HeatmapHead", "HeatmapHeadMI355X") else "probmap"
+    """``head=`` of ``synthetic_state_dict`` for a config's ``model.head.type``: "heatmap" for ``HeatmapHead`` (the ViTPose baseline) -
+    "heatmap-simple" when it has no deconvolutions (the ``-simple`` variants) -, "probmap" otherwise."""
+    head_cfg = dict(dict(cfg["model"]).get("head") or {})
+    head_type = str(head_cfg.get("type", "ProbMapHead"))
+    if head_type.split(".")[-1] not in ("HeatmapHead", "HeatmapHeadMI355X"):
+        return "probmap"
+    return "heatmap" if head_cfg.get("deconv_out_channels", (256, 256, 256)) else "heatmap-simple"
 
 
 def arch_of(cfg) -> Dict[str, int]:

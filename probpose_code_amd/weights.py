@@ -12,7 +12,10 @@ Packing (all on the host, once, in fp32; then cast to the operand precision):
   * ConvTranspose2d(k4, s2, p1, bias=False) + BatchNorm (eval) -> BN folded, then split into the
     four output phases: Wph[py, px][n, (ty*2+tx)*Cin + c] = w[c, n, 3-2ty-py, 3-2tx-px] * scale[n];
   * tower Conv2d(k3, p1) + BatchNorm -> folded, [tower][n, (ky*3+kx)*Cin + c];
-  * tower Conv1x1 -> [tower][K, C] fp32.
+  * tower Conv1x1 -> [tower][K, C] fp32;
+  * the 3x3 final layer of a head WITHOUT deconvolutions (the ViTPose "-simple" variants: it runs behind a bilinear x4 upsampling
+    of the ReLU'd features) -> the tap matrix [(ky*3+kx)*K + k, c], a Linear weight applied at the backbone's resolution
+    (csrc/pp_simple_head.hip gathers the upsampled sum from the nine tap planes).
 """
 import math
 from dataclasses import dataclass, field
@@ -147,6 +150,9 @@ class PackedWeights:
     # name -> 2^-e of the split-fp16 Linear weight tensors stored as w * 2^e (weight_scale_exponent); absent = 1.0
     inv_scale: Dict[str, float] = field(default_factory=dict)
     head_kind: str = "probmap"  # "probmap": heatmap branch + four scalar towers; "heatmap": the heatmap branch alone (HeatmapHead)
+    # > 0: the final layer is a 3x3 convolution behind a bilinear upsampling by this factor (4: the ViTPose "-simple" head, no deconvolutions);
+    # its weights are packed as the (9 K, E) tap matrix "final.taps" (csrc/pp_simple_head.hip). 0: the 1x1 final layer "final.w"
+    final_upsample: int = 0
 
     def __getitem__(self, k):
         return self.t[k]
@@ -289,9 +295,23 @@ def pack(sd: Dict[str, torch.Tensor], dtype: torch.dtype, device, split: bool = 
         t[f"deconv{j}.b"] = f32(shift)
         deconv_channels.append(cout)
         j += 1
-    t["final.w"] = op(sd["head.final_layer.weight"].reshape(K, -1), "final.w")
+    fw = sd["head.final_layer.weight"]
+    final_upsample = 0
+    if fw.dim() == 4 and tuple(fw.shape[2:]) == (3, 3):
+        # the ViTPose "-simple" head: no deconvolutions, a 3x3 final layer behind FeatureMapProcessor's x4 upsampling (the estimator pairs them).
+        # Behind the neck's ReLU the head is linear, so the convolution runs at the backbone's resolution: row t K + k of the tap matrix is
+        # W[k, :, dy + 1, dx + 1], t = 3 (dy + 1) + (dx + 1) - a Linear weight like any other (scaled by a power of two in f16x3)
+        if deconv_channels:
+            raise NotImplementedError("a 3x3 final layer behind deconvolutions has no MI355X kernel: the 3x3 final layer runs behind the x4 "
+                                      "upsampling of the '-simple' head (no head.deconv_layers.* keys), the deconvolutions end in a 1x1 final layer")
+        if fw.shape[1] != E:
+            raise ValueError(f"head.final_layer.weight is {tuple(fw.shape)}: the 3x3 final layer of the '-simple' head reads the backbone's {E} channels")
+        t["final.taps"] = op(fw.float().permute(2, 3, 0, 1).reshape(9 * K, E), "final.taps", scaled=True)
+        final_upsample = 4
+    else:
+        t["final.w"] = op(fw.reshape(K, -1), "final.w")
     t["final.b"] = f32(sd["head.final_layer.bias"])
-    if K <= 32:  # zero-padded to 32 rows: the MFMA operand of the 1x1 conv fused into the last deconvolution (pp_deconv_head)
+    if K <= 32 and not final_upsample:  # zero-padded to 32 rows: the MFMA operand of the 1x1 conv fused into the last deconvolution (pp_deconv_head)
         wpad = torch.zeros((32, t["final.w"].shape[1]), dtype=torch.float32)
         wpad[:K] = sd["head.final_layer.weight"].reshape(K, -1).float()
         t["final.w_pad"] = op(wpad, "final.w_pad")
@@ -320,4 +340,4 @@ def pack(sd: Dict[str, torch.Tensor], dtype: torch.dtype, device, split: bool = 
         t["tower_out.w"] = f32(torch.stack([sd[f"head.{tw}_layers.12.weight"].float().reshape(K, -1) for tw in TOWERS]))
         t["tower_out.b"] = f32(torch.stack([sd[f"head.{tw}_layers.12.bias"].float() for tw in TOWERS]))
     return PackedWeights(dtype=dtype, embed_dims=E, num_layers=L, ffn_dims=Fd, num_keypoints=K,
-                         deconv_channels=deconv_channels, t=t, inv_scale=inv_scale, head_kind=head_kind)
+                         deconv_channels=deconv_channels, t=t, inv_scale=inv_scale, head_kind=head_kind, final_upsample=final_upsample)
