@@ -47,6 +47,8 @@ def main():
                     help="device: a .jpg / .jpeg --out-img is transformed on the GPU and Huffman-coded on the host (a file that decodes to the same pixels)")
     ap.add_argument("--jpeg-optimize", action="store_true",
                     help="with --encode device: Huffman tables built from the picture itself (Pillow's optimize=True): the same pixels, a smaller file")
+    ap.add_argument("--restart-rows", type=int, default=0,
+                    help="with --encode device: a restart marker every N MCU rows of the file (cjpeg -restart N; 0: none): the same pixels")
     ap.add_argument("--encode-png", default="host", choices=["host", "device"],
                     help="device: a .png --out-img is filtered, deflated and checksummed on the GPU (the same pixels, other bytes)")
     ap.add_argument("--png-match", default="runs", choices=["runs", "lz"],
@@ -70,6 +72,8 @@ def main():
         ap.error("--draw-heatmap draws into --out-img")
     if args.decode_entropy == "device" and args.decode != "device":
         ap.error("--decode-entropy device needs --decode device")
+    if not 0 <= args.restart_rows <= 65535:
+        ap.error("--restart-rows is in 0..65535")
 
     from probpose_code_amd import apis, synthetic
     from probpose_code_amd.structures import merge_data_samples
@@ -108,7 +112,7 @@ def main():
 
         vis = PoseLocalVisualizer(radius=args.radius, line_width=args.thickness, alpha=args.alpha, device=args.device, image_encoder=args.encode,
                                   png_encoder=args.encode_png, png_match=args.png_match, jpeg_optimize=args.jpeg_optimize,
-                                  png_code=args.png_code)
+                                  png_code=args.png_code, jpeg_restart_rows=args.restart_rows)
         vis.set_dataset_meta(model.dataset_meta)
         vis.add_datasample("result", load_image_bgr(args.img)[:, :, ::-1], results, draw_heatmap=args.draw_heatmap, kpt_thr=args.kpt_thr,
                            out_file=args.out_img)

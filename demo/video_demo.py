@@ -59,6 +59,8 @@ def main(argv=None):
                     help="device: the drawn frames are Huffman-coded on the GPU as well (the same files)")
     ap.add_argument("--jpeg-optimize", action="store_true",
                     help="every frame gets Huffman tables built from its own statistics (with --entropy device: built on the GPU): the same pixels, smaller frames")
+    ap.add_argument("--restart-rows", type=int, default=0,
+                    help="a restart marker every N MCU rows of the written frames (cjpeg -restart N; 0: none), with --entropy host or device: the same files")
     ap.add_argument("--quality", type=int, default=75, help="JPEG quality of the written frames, 1..100")
     ap.add_argument("--fps", type=float, default=None, help="frame rate of the output (default: the input's, 25 for a directory)")
     ap.add_argument("--workers", type=int, default=8, help="host threads of the Huffman coder with --entropy host")
@@ -86,6 +88,8 @@ def main(argv=None):
         ap.error("--decode-entropy device needs --decode device")
     if args.depth < 1 or args.encode_batch < 1 or not 1 <= args.quality <= 100:
         ap.error("--depth and --encode-batch are at least 1, --quality is in 1..100")
+    if not 0 <= args.restart_rows <= 65535:
+        ap.error("--restart-rows is in 0..65535")
     frames, fps = frame_source(args.input)
     fps = args.fps if args.fps is not None else (fps or 25.0)
 
@@ -122,7 +126,7 @@ def main(argv=None):
         def flush():
             nonlocal written
             for data in jpeg.encode_batch(pending, quality=args.quality, subsampling="4:2:0", channel_order="rgb", workers=args.workers,
-                                          device=args.device, entropy=args.entropy, optimize=args.jpeg_optimize):
+                                          device=args.device, entropy=args.entropy, optimize=args.jpeg_optimize, restart_rows=args.restart_rows):
                 out.write(data)
                 written += 1
             pending.clear()

@@ -953,7 +953,8 @@ int pp_jpeg_write_headers(const uint16_t* qtables_host, const pp_jpeg_info* info
 
 /* Huffman coding on the device (csrc/pp_jpeg_entropy.hip; added under version 4: purely additive): the bytes
  * pp_jpeg_entropy_encode writes between the SOS header and the EOI marker, bit for bit, from coefficients that stay where
- * pp_jpeg_forward_batch left them. Restart interval 0 only. */
+ * pp_jpeg_forward_batch left them. pp_jpeg_entropy_encode_batch and pp_jpeg_entropy_encode_opt_batch code without restart
+ * intervals; the *_restart_batch calls further down honour every image's own. */
 
 /* What the coder leaves per image: the length of the stream in bytes (also when it did not fit: the capacity it needs) and
  * PP_OK, PP_ERR_INVALID_ARG (a DC difference outside -2047..2047 or an AC value outside -1023..1023: the stream is
@@ -967,7 +968,9 @@ typedef struct {
 /* One image of a batched entropy coding (a device table of these drives every launch). coef: info.coef_count int16 in the
  * layout of pp_jpeg_desc.coef, 16-byte aligned, only read; scratch: the image's share of pp_jpeg_entropy_scratch_bytes,
  * 16-byte aligned, contents undefined before and after; out / capacity: where the stream goes and how many bytes fit;
- * result: the image's slot; hs / vs / mcus_x / mcus_y: as pp_jpeg_encode_plan gives them. */
+ * result: the image's slot; hs / vs / mcus_x / mcus_y: as pp_jpeg_encode_plan gives them; restart_interval: MCUs between
+ * RSTn markers, 0: none - read by the *_restart_batch calls only (the calls without "restart" in their name code without
+ * intervals whatever it holds). */
 typedef struct {
     const int16_t* coef;
     uint8_t* scratch;
@@ -975,7 +978,8 @@ typedef struct {
     pp_jpeg_ent_result* result;
     int64_t capacity;
     int32_t hs, vs, mcus_x, mcus_y;
-    int64_t reserved;
+    int32_t restart_interval;
+    int32_t reserved;
 } pp_jpeg_ent_desc;
 
 /* Host only. Bytes of scratch for n images (infos_host: n pp_jpeg_encode_plan results), each image's share a multiple of
@@ -1047,6 +1051,29 @@ long long pp_jpeg_entropy_opt_scratch_bytes(const pp_jpeg_info* infos_host, int 
  * synchronisation, no read-back; an image's failure (its slot's status, PP_ERR_INVALID_ARG also for a refused record) leaves
  * the others untouched; nothing is written outside an image's scratch share, out[0, capacity), result slot and record. */
 int pp_jpeg_entropy_encode_opt_batch(const pp_jpeg_ent_opt_desc* descriptors, int n, long long max_blocks, void* stream);
+
+/* The device coder with restart intervals (added under version 4: purely additive). Every image of a batch has its own
+ * descriptor field restart_interval, 0 included: the stream is what pp_jpeg_entropy_encode resp. pp_jpeg_entropy_encode_opt
+ * writes between the SOS header and the EOI marker for that interval, bit for bit - the DC prediction restarts with every
+ * interval, every interval is padded with ones to a whole byte (a padding byte FF gets its 00), and FF D0 .. FF D7, never
+ * stuffed, stand between the intervals. An image with interval 0, or one of at least its MCU count, gets the bytes of the
+ * calls above. An interval outside 0..65535 fails that image alone (PP_ERR_INVALID_ARG). result->bytes counts the markers,
+ * also when the stream does not fit (PP_ERR_WORKSPACE, nothing written). */
+
+/* Host only. As pp_jpeg_entropy_scratch_bytes, for the two calls below: an image's share for any interval (sized for one MCU
+ * per interval: sixteen bytes per MCU for the interval table, seven padding bits per MCU in the bit buffer). Never below
+ * pp_jpeg_entropy_scratch_bytes of the same plans. < 0: error. */
+long long pp_jpeg_entropy_restart_scratch_bytes(const pp_jpeg_info* infos_host, int n);
+/* pp_jpeg_entropy_encode_batch with the intervals of the descriptors, its rules and its arguments; scratch shares of
+ * pp_jpeg_entropy_restart_scratch_bytes. Seven launches: "jpeg_ent_rst_bits", "jpeg_ent_rst_scan" (which also lays the
+ * intervals out: one workgroup per image), "jpeg_ent_rst_zero", "jpeg_ent_rst_pack", "jpeg_ent_rst_ffcount",
+ * "jpeg_ent_rst_ffscan", "jpeg_ent_rst_stuff" of pp_launch_count. */
+int pp_jpeg_entropy_encode_restart_batch(const pp_jpeg_ent_desc* descriptors, int n, long long max_blocks, void* stream);
+/* pp_jpeg_entropy_encode_opt_batch with the intervals of the descriptors (descriptors[i].ent.restart_interval): the tables
+ * are built from the statistics of the restarted DC differences, as pp_jpeg_symbol_histogram counts them. Ten launches:
+ * "jpeg_opt_clear", "jpeg_opt_rst_hist", "jpeg_opt_build", "jpeg_opt_rst_bits", "jpeg_opt_rst_scan", "jpeg_opt_rst_zero",
+ * "jpeg_opt_rst_pack", "jpeg_opt_rst_ffcount", "jpeg_opt_rst_ffscan", "jpeg_opt_rst_stuff". */
+int pp_jpeg_entropy_encode_opt_restart_batch(const pp_jpeg_ent_opt_desc* descriptors, int n, long long max_blocks, void* stream);
 
 /* Huffman decoding on the device (csrc/pp_jpeg_huffdec.hip; added under version 4: purely additive): the coefficients
  * pp_jpeg_entropy_decode gives, bit for bit, from the file's own entropy-coded bytes, by self-synchronising passes. The

@@ -188,6 +188,9 @@ SIGNATURES = {
     "pp_jpeg_entropy_encode_opt": (c_int, [_P, _P, _P, c_int, _P, ctypes.c_size_t, _P]),
     "pp_jpeg_entropy_opt_scratch_bytes": (c_longlong, [_P, c_int]),
     "pp_jpeg_entropy_encode_opt_batch": (c_int, [_P, c_int, c_longlong, _P]),
+    "pp_jpeg_entropy_restart_scratch_bytes": (c_longlong, [_P, c_int]),
+    "pp_jpeg_entropy_encode_restart_batch": (c_int, [_P, c_int, c_longlong, _P]),
+    "pp_jpeg_entropy_encode_opt_restart_batch": (c_int, [_P, c_int, c_longlong, _P]),
     "pp_jpeg_scan_prepare": (c_int, [_P, ctypes.c_size_t, _P]),
     "pp_jpeg_scan_prepare_restart": (c_int, [_P, ctypes.c_size_t, _P]),
     "pp_jpeg_huffman_scratch_bytes": (c_longlong, [_P, _P, c_int]),

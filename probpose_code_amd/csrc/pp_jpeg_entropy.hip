@@ -2,8 +2,9 @@
 // (per component [block_row][block_col][64], natural order) to the entropy-coded bytes entropy_encode of
 // csrc/pp_jpeg_enc_host.h writes between the SOS header and the EOI marker - one interleaved scan, annex K tables, ZRL for
 // runs above 15, EOB unless zigzag position 63 is non-zero, bits MSB first, the last byte padded with ones, every data byte
-// FF followed by 00. Restart interval 0 only. A batch of images of any mix of sizes and sampling per call, driven by a
-// device table of pp_jpeg_ent_desc.
+// FF followed by 00. A batch of images of any mix of sizes and sampling per call, driven by a device table of
+// pp_jpeg_ent_desc. pp_jpeg_entropy_encode_batch codes without restart intervals; pp_jpeg_entropy_encode_restart_batch (at
+// the end of this comment) honours every image's own.
 //
 // Encoding has no serial dependency: a block's code depends on its own 64 coefficients and on the DC value of the block
 // before it in scan order, which is read in place. So it is a map, a prefix sum and a scatter, twice - once for the bits,
@@ -27,6 +28,25 @@
 // which the sequential host check (scripts/jpeg_entropy_host_check.cpp) runs as well. The kernels are the templates of
 // csrc/pp_jpeg_entropy_phases.h, instantiated here with annex K's tables (csrc/pp_jpeg_entropy_opt.hip instantiates them
 // with an image's own).
+//
+// Restart intervals (pp_jpeg_entropy_encode_restart_batch; every image its own interval R, 0 included) keep that shape and
+// add a second, segmented level. The same seven launches, the phase templates instantiated with RST:
+//   jpeg_ent_rst_bits     load_block returns predictor 0 for the first block of each component of an interval; the thread of
+//                         an interval's first block also leaves its bit offset inside the chunk in irel[];
+//   jpeg_ent_rst_scan     behind the chunk scan, still one workgroup per image: interval j has P[start j+1] - P[start j]
+//                         bits (P: chunk offset + irel), ilen[j] = its bytes rounded up, ioff[] = their prefix sums - the
+//                         unstuffed stream is the byte-aligned intervals back to back;
+//   jpeg_ent_rst_pack     block s of interval j packs at bit 8 ioff[j] + P[s] - P[start j]; the last block of EVERY interval
+//                         pads with ones;
+//   jpeg_ent_rst_ffcount  as before: a padding byte FF is a data byte and is stuffed;
+//   jpeg_ent_rst_ffscan   need = unstuffed bytes + FF bytes + 2 (intervals - 1);
+//   jpeg_ent_rst_stuff    a byte's place grows by 2 x (intervals before it) - one binary search in ioff[] per thread - and the
+//                         thread that holds the last byte of interval j < last writes FF, D0 + (j & 7) behind it, unstuffed
+//                         (ent_stuff_restart: a thread's eight bytes may cross several interval ends).
+// ioff[] is strictly increasing (an interval holds three blocks of two bits at least), so every byte has one interval.
+// The scratch share is ent_rst_layout's (pp_jpeg_entropy_restart_scratch_bytes): ent_layout's regions, the bit buffer longer
+// by seven padding bits per MCU, and sixteen bytes of interval table per MCU - any interval down to one MCU fits. The
+// instantiations without RST compile to the instructions they had before the argument existed.
 #include "pp_common.h"
 #include "pp_jpeg_entropy_core.h"
 #include "pp_jpeg_entropy_phases.h"
@@ -94,5 +114,49 @@ extern "C" int pp_jpeg_entropy_encode_batch(const pp_jpeg_ent_desc* descriptors,
     PP_LAUNCH_CHECK_AS("jpeg_ent_ffscan");
     hipLaunchKernelGGL(jpeg_ent_stuff_kernel<AnnexKSource>, g.stuff, tpb, 0, s, descriptors);
     PP_LAUNCH_CHECK_AS("jpeg_ent_stuff");
+    return PP_OK;
+}
+
+extern "C" long long pp_jpeg_entropy_restart_scratch_bytes(const pp_jpeg_info* infos_host, int n) {
+    if (!infos_host || n < 0) {
+        pp::set_error("pp_jpeg_entropy_restart_scratch_bytes: bad argument");
+        return PP_ERR_INVALID_ARG;
+    }
+    long long total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!pp::jpeg::plan_consistent(infos_host[i])) {
+            pp::set_error("pp_jpeg_entropy_restart_scratch_bytes: entry %d is not a pp_jpeg_encode_plan result", i);
+            return PP_ERR_INVALID_ARG;
+        }
+        total += pp::ent_rst_layout(infos_host[i].coef_count / 64, (long long)infos_host[i].mcus_x * infos_host[i].mcus_y).total;
+    }
+    return total;
+}
+
+extern "C" int pp_jpeg_entropy_encode_restart_batch(const pp_jpeg_ent_desc* descriptors, int n, long long max_blocks, void* stream) {
+    using namespace pp;
+    PP_REQUIRE(n >= 0, PP_ERR_INVALID_ARG, "pp_jpeg_entropy_encode_restart_batch: n < 0");
+    if (n == 0) return PP_OK;
+    PP_REQUIRE(descriptors, PP_ERR_INVALID_ARG, "pp_jpeg_entropy_encode_restart_batch: NULL argument");
+    PP_REQUIRE(max_blocks > 0, PP_ERR_INVALID_ARG, "pp_jpeg_entropy_encode_restart_batch: bad shape");
+    PP_REQUIRE(n <= 65535 && max_blocks <= 3ll * 8192 * 8192, PP_ERR_INVALID_ARG,
+               "pp_jpeg_entropy_encode_restart_batch: at most 65535 images of sides up to 65535");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const EntGrids g(max_blocks, n, true);
+    const dim3 tpb(256);
+    hipLaunchKernelGGL((jpeg_ent_bits_kernel<AnnexKSource, true>), g.per_chunk, tpb, 0, s, descriptors);
+    PP_LAUNCH_CHECK_AS("jpeg_ent_rst_bits");
+    hipLaunchKernelGGL((jpeg_ent_scan_kernel<AnnexKSource, true>), g.per_image, tpb, 0, s, descriptors);
+    PP_LAUNCH_CHECK_AS("jpeg_ent_rst_scan");
+    hipLaunchKernelGGL((jpeg_ent_zero_kernel<AnnexKSource, true>), g.zero, tpb, 0, s, descriptors);
+    PP_LAUNCH_CHECK_AS("jpeg_ent_rst_zero");
+    hipLaunchKernelGGL((jpeg_ent_pack_kernel<AnnexKSource, true>), g.per_chunk, tpb, 0, s, descriptors);
+    PP_LAUNCH_CHECK_AS("jpeg_ent_rst_pack");
+    hipLaunchKernelGGL((jpeg_ent_ffcount_kernel<AnnexKSource, true>), g.stuff, tpb, 0, s, descriptors);
+    PP_LAUNCH_CHECK_AS("jpeg_ent_rst_ffcount");
+    hipLaunchKernelGGL((jpeg_ent_ffscan_kernel<AnnexKSource, true>), g.per_image, tpb, 0, s, descriptors);
+    PP_LAUNCH_CHECK_AS("jpeg_ent_rst_ffscan");
+    hipLaunchKernelGGL((jpeg_ent_stuff_kernel<AnnexKSource, true>), g.stuff, tpb, 0, s, descriptors);
+    PP_LAUNCH_CHECK_AS("jpeg_ent_rst_stuff");
     return PP_OK;
 }

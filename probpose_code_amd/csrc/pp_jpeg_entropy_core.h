@@ -16,6 +16,7 @@ constexpr int ENT_BLOCK_BITS = 1665;  // 16 + 11 bits of DC, 63 x (16 + 10) bits
 // what probpose_code_amd/jpeg.py mirrors (_ENT_DESC, _ENT_RESULT)
 static_assert(sizeof(pp_jpeg_ent_desc) == 64 && sizeof(pp_jpeg_ent_result) == 16, "jpeg.py mirrors these");
 static_assert(offsetof(pp_jpeg_ent_desc, capacity) == 32, "four pointers, then the capacity");
+static_assert(offsetof(pp_jpeg_ent_desc, restart_interval) == 56, "the interval in the first four of the eight bytes once reserved");
 
 // code | size << 16 of every symbol: [0] luma, [1] chroma
 struct EntTables {
@@ -71,6 +72,69 @@ PP_HOST_DEVICE EntLayout ent_layout(long long nblk) {
     L.total = (L.o_soff + 8 * L.nstuff + 255) / 256 * 256;
     return L;
 }
+
+// The restart intervals of an image as the *_restart_batch calls see them. per: MCUs per interval (the whole image for
+// interval 0 and for one of at least the MCU count: no marker in the scan); count: intervals; bpi: blocks per interval.
+struct EntIntervals {
+    long long per, count, bpi;
+    int R;  // what load_block takes: the interval, 0 for none
+};
+
+PP_HOST_DEVICE bool ent_interval_ok(const pp_jpeg_ent_desc& d) { return d.restart_interval >= 0 && d.restart_interval <= 65535; }
+
+PP_HOST_DEVICE EntIntervals ent_intervals(const pp_jpeg_ent_desc& d) {
+    EntIntervals v;
+    const long long mcus = (long long)d.mcus_x * d.mcus_y;
+    v.R = d.restart_interval;
+    v.per = (v.R <= 0 || v.R >= mcus) ? mcus : v.R;
+    v.count = v.per > 0 ? (mcus + v.per - 1) / v.per : 0;
+    v.bpi = v.per * (d.hs * d.vs + 2);
+    return v;
+}
+
+// An image's share of scratch with restart intervals (pp_jpeg_entropy_restart_scratch_bytes): ent_layout's regions - the bit
+// buffer and what follows it longer by seven padding bits per MCU - and behind them, per interval (at most one per MCU):
+// irel[j] (u32: the bit offset of the interval's first block inside its chunk of ENT_CHUNK blocks), ilen[j] (u32: its bytes,
+// padding included) and ioff[j] (u64: the byte offset of the interval in the unstuffed stream; ioff[count] is the stream's
+// length). ent_layout's own result is not changed by any of this.
+struct EntRstLayout : EntLayout {
+    long long nint, o_irel, o_ilen, o_ioff;
+};
+
+PP_HOST_DEVICE EntRstLayout ent_rst_layout(long long nblk, long long mcus) {
+    EntRstLayout L;
+    if (nblk <= 0) mcus = 0;
+    L.nblk = nblk;
+    L.nint = mcus;
+    L.nchunks = (nblk + ENT_CHUNK - 1) / ENT_CHUNK;
+    const long long max_bits = nblk * ENT_BLOCK_BITS + 7 * (mcus > 0 ? mcus : 1);  // (every interval pads its last byte)
+    L.max_bytes = (max_bits + 7) / 8;
+    L.nwords = (max_bits + 31) / 32 + 4;
+    L.nstuff = (L.max_bytes + STUFF_CHUNK - 1) / STUFF_CHUNK;
+    L.o_len = 64;
+    L.o_csum = ent_align16(L.o_len + 4 * nblk);
+    L.o_coff = ent_align16(L.o_csum + 8 * L.nchunks);
+    L.o_words = ent_align16(L.o_coff + 8 * L.nchunks);
+    L.o_sff = ent_align16(L.o_words + 4 * L.nwords);
+    L.o_soff = ent_align16(L.o_sff + 4 * L.nstuff);
+    L.o_irel = ent_align16(L.o_soff + 8 * L.nstuff);
+    L.o_ilen = ent_align16(L.o_irel + 4 * L.nint);
+    L.o_ioff = ent_align16(L.o_ilen + 4 * L.nint);
+    L.total = (L.o_ioff + 8 * (L.nint + 1) + 255) / 256 * 256;
+    return L;
+}
+
+// The layout a phase runs with: ent_layout without restart handling, ent_rst_layout with it.
+template <bool RST>
+struct EntPhaseLayout {
+    using type = EntLayout;
+    static PP_HOST_DEVICE EntLayout of(const pp_jpeg_ent_desc&, long long nblk) { return ent_layout(nblk); }
+};
+template <>
+struct EntPhaseLayout<true> {
+    using type = EntRstLayout;
+    static PP_HOST_DEVICE EntRstLayout of(const pp_jpeg_ent_desc& d, long long nblk) { return ent_rst_layout(nblk, (long long)d.mcus_x * d.mcus_y); }
+};
 
 // Blocks of the scan, 0 for a descriptor that holds no pp_jpeg_encode_plan geometry (its status becomes PP_ERR_INVALID_ARG).
 PP_HOST_DEVICE long long ent_blocks(const pp_jpeg_ent_desc& d) {
@@ -166,7 +230,9 @@ struct alignas(16) EntQuad {
 #endif
 
 // Block s of the scan: loads its coefficients, finds its component (0 luma, 1 chroma tables) and its DC predictor.
-PP_HOST_DEVICE void load_block(const pp_jpeg_ent_desc& d, long long s, uint32_t (&w)[32], int& pred, int& chroma) {
+// RST: R is the restart interval in MCUs, 0 for none - the first block of each component in an interval has predictor 0.
+template <bool RST = false>
+PP_HOST_DEVICE void load_block(const pp_jpeg_ent_desc& d, long long s, uint32_t (&w)[32], int& pred, int& chroma, int R = 0) {
     const int lum = d.hs * d.vs, bpm = lum + 2;
     const long long mcu = s / bpm, mcus = (long long)d.mcus_x * d.mcus_y;
     const int j = (int)(s - mcu * bpm);
@@ -195,10 +261,79 @@ PP_HOST_DEVICE void load_block(const pp_jpeg_ent_desc& d, long long s, uint32_t 
         w[4 * q + 2] = v.z;
         w[4 * q + 3] = v.w;
     }
+    if constexpr (RST) {  // no predictor comes over from the MCU before an interval's first
+        if (R > 0 && (j == 0 || j >= lum) && (unsigned)mcu % (unsigned)R == 0u) prev = -1;
+    }
     pred = prev >= 0 ? (int)d.coef[prev * 64] : 0;
 }
 
 // Byte k of the unstuffed stream out of its words (word k / 4 holds it at bits 31 - 8 (k % 4) and down).
 PP_HOST_DEVICE uint32_t stream_byte(uint32_t word, int k) { return (word >> (24 - 8 * k)) & 255u; }
+
+// ------------------------------------------------------------------------------------------------ restart intervals
+// With P[s] the exclusive prefix of the block lengths (a chunk's offset + the prefix inside the chunk), interval j holds
+// P[start of j + 1] - P[start of j] bits and ilen[j] = ceil(that / 8) bytes; ioff[] is the exclusive prefix of ilen[]. The
+// unstuffed stream is the byte-aligned intervals back to back: block s of interval j packs at bit 8 ioff[j] + P[s] -
+// P[start of j], and the last block of every interval pads its byte with ones. An interval is at least one byte (three
+// blocks of at least two bits), so ioff[] is strictly increasing and a byte lies in exactly one interval.
+
+// P[start of interval j]; j == count: the total.
+PP_HOST_DEVICE unsigned long long ent_interval_bits_before(const EntIntervals& iv, long long j, const unsigned long long* coff, const uint32_t* irel,
+                                                           unsigned long long total_bits) {
+    return j >= iv.count ? total_bits : coff[(j * iv.bpi) / ENT_CHUNK] + irel[j];
+}
+
+PP_HOST_DEVICE uint32_t ent_interval_bytes(const EntIntervals& iv, long long j, const unsigned long long* coff, const uint32_t* irel,
+                                           unsigned long long total_bits) {
+    return (uint32_t)((ent_interval_bits_before(iv, j + 1, coff, irel, total_bits) - ent_interval_bits_before(iv, j, coff, irel, total_bits) + 7) >> 3);
+}
+
+// Where block s (bit offset P[s] = `before`) packs, and whether it pads.
+PP_HOST_DEVICE unsigned long long ent_pack_start(const EntIntervals& iv, long long s, unsigned long long before, const unsigned long long* coff,
+                                                 const uint32_t* irel, const unsigned long long* ioff) {
+    const long long j = s / iv.bpi;
+    return 8ull * ioff[j] + (before - ent_interval_bits_before(iv, j, coff, irel, 0));
+}
+PP_HOST_DEVICE bool ent_pads(const EntIntervals& iv, long long s, long long nblk) { return s == nblk - 1 || (s + 1) % iv.bpi == 0; }
+
+// The interval that holds byte `b` of the unstuffed stream (b < ioff[count]): the last j with ioff[j] <= b. It is also the
+// number of markers in front of the byte.
+PP_HOST_DEVICE long long ent_interval_at(const unsigned long long* ioff, long long count, unsigned long long b) {
+    long long lo = 0, hi = count;  // ioff[lo] <= b < ioff[hi]
+    while (hi - lo > 1) {
+        const long long mid = lo + (hi - lo) / 2;
+        if (ioff[mid] <= b) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// A thread's `valid` bytes (v: two words) from byte `byte0` of the unstuffed stream to their places in the output; pos: the
+// place of the first with the FF bytes in front of it counted, the markers not. A 00 behind every FF, and FF D0 + (j & 7)
+// behind the last byte of interval j unless it is the image's last - eight bytes may cross several interval ends.
+PP_HOST_DEVICE void ent_stuff_restart(const uint32_t (&v)[2], int valid, long long byte0, long long pos, const unsigned long long* ioff, long long count,
+                                      uint8_t* out, long long capacity) {
+    if (valid <= 0) return;
+    long long j = ent_interval_at(ioff, count, (unsigned long long)byte0);
+    long long end = (long long)ioff[j + 1];
+    pos += 2 * j;
+    for (int k = 0; k < 8; ++k) {
+        if (k >= valid) break;
+        const uint32_t b = stream_byte(v[k >> 2], k & 3);
+        if (pos < capacity) out[pos] = (uint8_t)b;
+        ++pos;
+        if (b == 255u) {
+            if (pos < capacity) out[pos] = 0;
+            ++pos;
+        }
+        if (byte0 + k + 1 == end && j + 1 < count) {
+            if (pos < capacity) out[pos] = 0xFF;
+            if (pos + 1 < capacity) out[pos + 1] = (uint8_t)(0xD0 + (j & 7));
+            pos += 2;
+            ++j;
+            end = (long long)ioff[j + 1];
+        }
+    }
+}
 
 }  // namespace pp

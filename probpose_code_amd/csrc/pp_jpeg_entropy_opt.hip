@@ -18,6 +18,9 @@
 // record pointer that is NULL or not 16-byte aligned, for more than OPT_MAX_BLOCKS blocks (32-bit frequencies would not be
 // exact) and for a code tree deeper than 32 (the record's status says so too). Every store goes to a fixed place of the
 // image's record or, in the phases, is checked against its region as before.
+// pp_jpeg_entropy_encode_opt_restart_batch honours every image's restart interval (see csrc/pp_jpeg_entropy.hip): the same ten
+// launches with jpeg_opt_hist counting the restarted DC differences (what pp_jpeg_symbol_histogram(..., restart_interval)
+// counts on the host) and the seven phases instantiated with RST.
 #include "pp_common.h"
 #include "pp_jpeg_entropy_phases.h"
 #include "pp_jpeg_opt_core.h"
@@ -63,8 +66,9 @@ struct LdsHistSink {
     __device__ __forceinline__ void ac(int rs) { atomicAdd(ac_bins + rs, 1u); }
 };
 
-// blockIdx.y: image; blockIdx.x: chunk of ENT_CHUNK blocks.
-__global__ __launch_bounds__(256) void jpeg_opt_hist_kernel(const pp_jpeg_ent_opt_desc* __restrict__ descs) {
+// blockIdx.y: image; blockIdx.x: chunk of ENT_CHUNK blocks. RST: the DC prediction restarts with the image's interval.
+template <bool RST>
+__device__ __forceinline__ void opt_hist_body(const pp_jpeg_ent_opt_desc* __restrict__ descs) {
     __shared__ uint32_t bins[536];  // AC luma (256), AC chroma (256), DC luma (12), DC chroma (12)
     const pp_jpeg_ent_opt_desc src = descs[blockIdx.y];
     const EntLayout L = ent_layout(OptSource::plan_blocks(src));
@@ -75,7 +79,7 @@ __global__ __launch_bounds__(256) void jpeg_opt_hist_kernel(const pp_jpeg_ent_op
     if (s < L.nblk) {
         uint32_t w[32];
         int pred, chroma;
-        load_block(src.ent, s, w, pred, chroma);
+        load_block<RST>(src.ent, s, w, pred, chroma, src.ent.restart_interval);
         LdsHistSink sink{bins + 512 + 12 * chroma, bins + 256 * chroma};
         block_symbols(w, pred, sink);  // (a coefficient outside the codes is the coder's to report)
     }
@@ -89,6 +93,9 @@ __global__ __launch_bounds__(256) void jpeg_opt_hist_kernel(const pp_jpeg_ent_op
         atomicAdd(bin, v);
     }
 }
+
+__global__ __launch_bounds__(256) void jpeg_opt_hist_kernel(const pp_jpeg_ent_opt_desc* __restrict__ descs) { opt_hist_body<false>(descs); }
+__global__ __launch_bounds__(256) void jpeg_opt_hist_rst_kernel(const pp_jpeg_ent_opt_desc* __restrict__ descs) { opt_hist_body<true>(descs); }
 
 __device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
 #pragma unroll
@@ -245,6 +252,40 @@ extern "C" int pp_jpeg_entropy_encode_opt_batch(const pp_jpeg_ent_opt_desc* desc
     PP_LAUNCH_CHECK_AS("jpeg_opt_ffscan");
     hipLaunchKernelGGL(jpeg_ent_stuff_kernel<OptSource>, g.stuff, tpb, 0, s, descriptors);
     PP_LAUNCH_CHECK_AS("jpeg_opt_stuff");
+    return PP_OK;
+}
+
+extern "C" int pp_jpeg_entropy_encode_opt_restart_batch(const pp_jpeg_ent_opt_desc* descriptors, int n, long long max_blocks, void* stream) {
+    using namespace pp;
+    PP_REQUIRE(n >= 0, PP_ERR_INVALID_ARG, "pp_jpeg_entropy_encode_opt_restart_batch: n < 0");
+    if (n == 0) return PP_OK;
+    PP_REQUIRE(descriptors, PP_ERR_INVALID_ARG, "pp_jpeg_entropy_encode_opt_restart_batch: NULL argument");
+    PP_REQUIRE(max_blocks > 0, PP_ERR_INVALID_ARG, "pp_jpeg_entropy_encode_opt_restart_batch: bad shape");
+    PP_REQUIRE(n <= 65535 && max_blocks <= OPT_MAX_BLOCKS, PP_ERR_INVALID_ARG,
+               "pp_jpeg_entropy_encode_opt_restart_batch: at most 65535 images of at most 2^32 / 64 blocks");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const EntGrids g(max_blocks, n, true);
+    const dim3 tpb(256);
+    hipLaunchKernelGGL(jpeg_opt_clear_kernel, g.per_image, tpb, 0, s, descriptors);
+    PP_LAUNCH_CHECK_AS("jpeg_opt_clear");
+    hipLaunchKernelGGL(jpeg_opt_hist_rst_kernel, g.per_chunk, tpb, 0, s, descriptors);
+    PP_LAUNCH_CHECK_AS("jpeg_opt_rst_hist");
+    hipLaunchKernelGGL(jpeg_opt_build_kernel, dim3(4, n), dim3(WAVE), 0, s, descriptors);
+    PP_LAUNCH_CHECK_AS("jpeg_opt_build");
+    hipLaunchKernelGGL((jpeg_ent_bits_kernel<OptSource, true>), g.per_chunk, tpb, 0, s, descriptors);
+    PP_LAUNCH_CHECK_AS("jpeg_opt_rst_bits");
+    hipLaunchKernelGGL((jpeg_ent_scan_kernel<OptSource, true>), g.per_image, tpb, 0, s, descriptors);
+    PP_LAUNCH_CHECK_AS("jpeg_opt_rst_scan");
+    hipLaunchKernelGGL((jpeg_ent_zero_kernel<OptSource, true>), g.zero, tpb, 0, s, descriptors);
+    PP_LAUNCH_CHECK_AS("jpeg_opt_rst_zero");
+    hipLaunchKernelGGL((jpeg_ent_pack_kernel<OptSource, true>), g.per_chunk, tpb, 0, s, descriptors);
+    PP_LAUNCH_CHECK_AS("jpeg_opt_rst_pack");
+    hipLaunchKernelGGL((jpeg_ent_ffcount_kernel<OptSource, true>), g.stuff, tpb, 0, s, descriptors);
+    PP_LAUNCH_CHECK_AS("jpeg_opt_rst_ffcount");
+    hipLaunchKernelGGL((jpeg_ent_ffscan_kernel<OptSource, true>), g.per_image, tpb, 0, s, descriptors);
+    PP_LAUNCH_CHECK_AS("jpeg_opt_rst_ffscan");
+    hipLaunchKernelGGL((jpeg_ent_stuff_kernel<OptSource, true>), g.stuff, tpb, 0, s, descriptors);
+    PP_LAUNCH_CHECK_AS("jpeg_opt_rst_stuff");
     return PP_OK;
 }
 

@@ -20,7 +20,7 @@ of demo/image_demo.py.
 ``encode_batch(..., entropy="device")`` codes on the device as well (``pp_jpeg_entropy_encode_batch``, csrc/pp_jpeg_entropy.hip:
 seven launches behind the forward call's two, on the same stream): the coefficients never leave the device, the host
 receives the finished streams and puts ``pp_jpeg_write_headers``' bytes in front and ``FF D9`` behind. The files are byte
-for byte those of the host coder. Restart interval 0 only; the default stays ``entropy="host"``.
+for byte those of the host coder. With restart intervals: ``restart_rows``, at the end of this text; the default stays ``entropy="host"``.
 
 ``optimize=True`` (``entropy_encode``, ``entropy_encode_device``, ``encode_batch``, ``imwrite_device``) codes every file with the
 Huffman tables libjpeg builds from the image's own symbol statistics - the tables and the scan of Pillow's
@@ -39,8 +39,15 @@ Files with a restart interval decode there as well (``scan_prepare(data, restart
 the decoder's state is known, so inside such a file the synchronisation distance is bounded by the interval's length; the
 order and number of the markers are checked on the device. (A file with more than 7 fill bytes in front of a marker is
 turned away by the preparation and decodes on the host, uncounted.) The pixels are those of ``entropy="host"``, which stays
-the default. Not done on the device: progressive, arithmetic-coded and 12-bit files (no decoder here takes them), and
-*coding* with a restart interval (``encode_batch(..., entropy="device")`` demands ``restart_interval=0``).
+the default. Not done on the device: progressive, arithmetic-coded and 12-bit files (no decoder here takes them).
+
+Restart intervals are coded on the device too: ``entropy_encode_device(..., restart_interval=R)`` (an int, or one per image)
+and ``encode_batch(..., entropy="device", restart_rows=N)`` (a marker every N MCU rows of each image's own width, libjpeg's
+``restart_in_rows``) run ``pp_jpeg_entropy_encode_restart_batch`` resp. ``pp_jpeg_entropy_encode_opt_restart_batch`` - the
+same seven resp. ten launches with a segmented level: the DC prediction cut at every interval start, every interval padded
+to a byte, unstuffed RSTn markers between them - and give the files of ``entropy="host"`` at the same interval byte for
+byte. Without either keyword every path makes the calls it made before. (``encode_batch(entropy="device",
+restart_interval=R)`` with R != 0 is still refused: one MCU count means another thing for every width of a mixed batch.)
 """
 import ctypes
 from typing import List, NamedTuple, Optional, Sequence, Union
@@ -56,6 +63,7 @@ reconstruct_calls = 0  # pp_jpeg_reconstruct_bgr_batch calls since import
 forward_calls = 0  # pp_jpeg_forward_batch calls since import
 entropy_device_calls = 0  # pp_jpeg_entropy_encode_batch / pp_jpeg_entropy_encode_opt_batch calls since import
 entropy_opt_device_calls = 0  # pp_jpeg_entropy_encode_opt_batch calls among them
+entropy_restart_device_calls = 0  # the *_restart_batch forms among both
 huffman_device_calls = 0  # pp_jpeg_huffman_decode_batch calls since import
 unsynchronised = 0  # images the device Huffman decoder refused by their result slot since import (each also counts in fallbacks)
 
@@ -76,15 +84,22 @@ assert _DESC.itemsize == 64
 _ENC_DESC = np.dtype([("src", "<u8"), ("qtables", "<u8"), ("planes", "<u8"), ("coef", "<u8"), ("width", "<i4"), ("height", "<i4"),
                       ("row_stride", "<i4"), ("rgb", "<i4"), ("hs", "<i4"), ("vs", "<i4"), ("mcus_x", "<i4"), ("mcus_y", "<i4")])
 assert _ENC_DESC.itemsize == 64
-# pp_jpeg_ent_desc: four pointers, the capacity, four int32, eight reserved bytes; pp_jpeg_ent_result
+# pp_jpeg_ent_desc: four pointers, the capacity, four int32, the restart interval, four reserved bytes; pp_jpeg_ent_result.
+# _ENT_DESC keeps the shape its users fill row by row, ten values: its last field is the interval and the reserved word as
+# one little-endian int64 (an interval 0..65535 written there lands in restart_interval, 0 in reserved); _ENT_RESTART_DESC
+# names the two fields of the header.
 _ENT_DESC = np.dtype([("coef", "<u8"), ("scratch", "<u8"), ("out", "<u8"), ("result", "<u8"), ("capacity", "<i8"), ("hs", "<i4"),
                       ("vs", "<i4"), ("mcus_x", "<i4"), ("mcus_y", "<i4"), ("reserved", "<i8")])
 assert _ENT_DESC.itemsize == 64
+_ENT_RESTART_DESC = np.dtype(_ENT_DESC.descr[:-1] + [("restart_interval", "<i4"), ("reserved", "<i4")])
+assert _ENT_RESTART_DESC.itemsize == 64 and _ENT_RESTART_DESC.fields["restart_interval"][1] == 56
 _ENT_RESULT = np.dtype([("bytes", "<i8"), ("status", "<i4"), ("reserved", "<i4")])
 assert _ENT_RESULT.itemsize == 16
 # pp_jpeg_ent_opt_desc: pp_jpeg_ent_desc and the record's address; pp_jpeg_opt_record
 _ENT_OPT_DESC = np.dtype(_ENT_DESC.descr + [("record", "<u8")])
 assert _ENT_OPT_DESC.itemsize == 72
+_ENT_OPT_RESTART_DESC = np.dtype(_ENT_RESTART_DESC.descr + [("record", "<u8")])
+assert _ENT_OPT_RESTART_DESC.itemsize == 72
 _OPT_RECORD = np.dtype([("hist", "<u4", (4, 257)), ("bits", "u1", (4, 16)), ("vals", "u1", (4, 256)), ("lookup", "<u4", (4, 256)),
                         ("status", "<i4"), ("nvals", "<i4", (4,)), ("reserved", "<i4", (7,))])
 assert _OPT_RECORD.itemsize == 9344 and _OPT_RECORD.fields["lookup"][1] == 5200
@@ -645,7 +660,8 @@ class _EntropyJob(NamedTuple):
     """One ``pp_jpeg_entropy_encode_batch`` call and its device buffers: ``desc_ptr`` (the uploaded descriptor table),
     ``results`` (n x 16 bytes, a view of the uploaded block), the streams (``out``: image i's at ``o_out[i]``, ``capacity[i]``
     bytes), the scratch, the infos, ``block`` (the uploaded ``StagedBlock``) and ``records_at`` (with ``optimize``: where, in
-    ``results``, the n ``pp_jpeg_opt_record`` of ``pp_jpeg_entropy_encode_opt_batch`` begin; None without)."""
+    ``results``, the n ``pp_jpeg_opt_record`` of ``pp_jpeg_entropy_encode_opt_batch`` begin; None without) and ``restart``
+    (every image's restart interval: the ``*_restart_batch`` form of the call; None: the call without intervals)."""
 
     desc_ptr: int
     results: torch.Tensor
@@ -656,6 +672,11 @@ class _EntropyJob(NamedTuple):
     infos: list
     block: StagedBlock
     records_at: Optional[int] = None
+    restart: Optional[list] = None
+
+
+def _entropy_call(job: "_EntropyJob") -> str:
+    return "pp_jpeg_entropy_encode" + ("" if job.records_at is None else "_opt") + ("" if job.restart is None else "_restart") + "_batch"
 
 
 def _entropy_regions(name: str, n: int, optimize: bool) -> list:
@@ -683,7 +704,7 @@ class _ForwardJob(NamedTuple):
     entropy: Optional[_EntropyJob]
 
 
-def _stage_encode(images, qt, subsampling, channel_order, dev, staging, entropy=False, optimize=False) -> _ForwardJob:
+def _stage_encode(images, qt, subsampling, channel_order, dev, staging, entropy=False, optimize=False, restart=None) -> _ForwardJob:
     """Pack the descriptor table and the tables of a batch into the pinned buffer and upload them with one copy. ``entropy``:
     the table and result slots of ``pp_jpeg_entropy_encode_batch`` travel in the same copy."""
     n = len(images)
@@ -700,7 +721,7 @@ def _stage_encode(images, qt, subsampling, channel_order, dev, staging, entropy=
         desc[i] = (im.data_ptr(), p_qtables, planes, p_coef[i], info.width, info.height, im.stride(0), int(channel_order == "rgb"),
                    info.hs, info.vs, info.mcus_x, info.mcus_y)
         planes += _align(int(info.coef_count))
-    job = _entropy_job(blk, "entropy", infos, p_coef, dev, optimize) if entropy else None
+    job = _entropy_job(blk, "entropy", infos, p_coef, dev, optimize, restart) if entropy else None
     blk.upload(before="coef")  # (the coefficient regions are only written on the device)
     args = (blk.base, n, max(int(i.coef_count) // 64 for i in infos), max(int(i.height) for i in infos), max(int(i.width) for i in infos))
     return _ForwardJob(args, blk, infos, qt, (images, scratch), job)
@@ -726,13 +747,16 @@ def write_headers(qtables: np.ndarray, info: JpegInfo, restart_interval: int = 0
     return out[:size.value].tobytes()
 
 
-def _entropy_job(blk: StagedBlock, desc: str, infos, p_coef, dev, optimize=False) -> _EntropyJob:
+def _entropy_job(blk: StagedBlock, desc: str, infos, p_coef, dev, optimize=False, restart=None) -> _EntropyJob:
     """Allocate the scratch and the stream buffers of a batch, fill the n ``_ENT_DESC`` rows (with ``optimize``: ``_ENT_OPT_DESC``,
     the records behind the result slots) of region ``desc`` of ``blk`` and clear its "results" region; ``p_coef``: the device
     addresses of the coefficients. The caller uploads the block. A stream gets ``pp_jpeg_encoded_bound`` bytes: no stream of
-    its geometry is longer, with annex K's tables or the image's own."""
+    its geometry is longer, with annex K's tables or the image's own, at any restart interval. ``restart``: every image's
+    interval for the ``*_restart_batch`` form (its scratch query, the interval in the rows); None: the form without."""
     shares, capacity = [], []
     query = "pp_jpeg_entropy_opt_scratch_bytes" if optimize else "pp_jpeg_entropy_scratch_bytes"
+    if restart is not None:
+        query = "pp_jpeg_entropy_restart_scratch_bytes"
     for info in infos:
         one = int(getattr(_lib.lib, query)(ctypes.byref(info), 1))
         bound = int(_lib.lib.pp_jpeg_encoded_bound(ctypes.byref(info)))
@@ -741,32 +765,39 @@ def _entropy_job(blk: StagedBlock, desc: str, infos, p_coef, dev, optimize=False
         capacity.append(_align(bound))
     scratch = torch.empty(sum(shares), dtype=torch.uint8, device=dev)
     out = torch.empty(sum(capacity), dtype=torch.uint8, device=dev)
-    rows, p_results = blk.host(desc, _ENT_OPT_DESC if optimize else _ENT_DESC), blk.ptr("results")
+    if restart is None:
+        rows = blk.host(desc, _ENT_OPT_DESC if optimize else _ENT_DESC)
+    else:
+        rows = blk.host(desc, _ENT_OPT_RESTART_DESC if optimize else _ENT_RESTART_DESC)
+    p_results = blk.ptr("results")
     blk.host("results")[:] = 0
     records_at = _records_at(len(infos)) if optimize else None
     o_out, s_at, o_at = [], scratch.data_ptr(), 0
     for i, info in enumerate(infos):
         row = (p_coef[i], s_at, out.data_ptr() + o_at, p_results + 16 * i, capacity[i], info.hs, info.vs, info.mcus_x, info.mcus_y, 0)
+        if restart is not None:
+            row = row[:-1] + (int(restart[i]), 0)
         rows[i] = row + (p_results + records_at + _OPT_RECORD.itemsize * i,) if optimize else row
         o_out.append(o_at)
         s_at += shares[i]
         o_at += capacity[i]
-    return _EntropyJob(blk.ptr(desc), blk.device("results"), out, o_out, capacity, scratch, list(infos), blk, records_at)
+    return _EntropyJob(blk.ptr(desc), blk.device("results"), out, o_out, capacity, scratch, list(infos), blk, records_at,
+                       None if restart is None else [int(r) for r in restart])
 
 
 def _entropy_launch(job: _EntropyJob, stream) -> None:
-    global entropy_device_calls, entropy_opt_device_calls
-    name = "pp_jpeg_entropy_encode_batch" if job.records_at is None else "pp_jpeg_entropy_encode_opt_batch"
-    _lib.call(name, job.desc_ptr, len(job.infos), max(int(i.coef_count) // 64 for i in job.infos), stream.cuda_stream)
+    global entropy_device_calls, entropy_opt_device_calls, entropy_restart_device_calls
+    _lib.call(_entropy_call(job), job.desc_ptr, len(job.infos), max(int(i.coef_count) // 64 for i in job.infos), stream.cuda_stream)
     entropy_device_calls += 1
     entropy_opt_device_calls += job.records_at is not None
+    entropy_restart_device_calls += job.restart is not None
 
 
 def _entropy_collect(job: "_EntropyJob", qtables, stream, staging) -> List[bytes]:
     """The files of a coded batch: the result slots first (one copy, one synchronisation; with ``optimize`` the records, and
     in them every image's tables, come in the same copy), then the used bytes of every stream into the pinned buffer (one
     copy per image, one synchronisation), each between its headers and ``FF D9``."""
-    n, name = len(job.infos), ("pp_jpeg_entropy_encode_batch" if job.records_at is None else "pp_jpeg_entropy_encode_opt_batch")
+    n, name = len(job.infos), _entropy_call(job)
     back = job.results.cpu().numpy()  # (waits for the stream: the launches have run)
     res = back[:16 * n].view(_ENT_RESULT)
     records = None if job.records_at is None else back[job.records_at:job.records_at + _OPT_RECORD.itemsize * n].view(_OPT_RECORD)
@@ -787,10 +818,12 @@ def _entropy_collect(job: "_EntropyJob", qtables, stream, staging) -> List[bytes
         staging.buf[o:o + sz].copy_(job.out[oo:oo + sz], non_blocking=True)
     stream.synchronize()
     tables = [None] * n if records is None else [(r["bits"], r["vals"]) for r in records]
-    return [write_headers(qt, info, 0, t) + blk[o:o + sz].tobytes() + b"\xff\xd9" for qt, info, t, o, sz in zip(qtables, job.infos, tables, offs, sizes)]
+    restart = [0] * n if job.restart is None else job.restart
+    return [write_headers(qt, info, r, t) + blk[o:o + sz].tobytes() + b"\xff\xd9"
+            for qt, info, r, t, o, sz in zip(qtables, job.infos, restart, tables, offs, sizes)]
 
 
-def _stage_entropy(coefficients, dev, staging, optimize=False) -> _EntropyJob:
+def _stage_entropy(coefficients, dev, staging, optimize=False, restart=None) -> _EntropyJob:
     """Pack the descriptor table, the result slots and the coefficients of a batch into the pinned buffer and upload them
     with one copy."""
     n = len(coefficients)
@@ -798,18 +831,36 @@ def _stage_entropy(coefficients, dev, staging, optimize=False) -> _EntropyJob:
     blk = StagedBlock(_entropy_regions("desc", n, optimize), [("coef", [2 * int(c.info.coef_count) for c in coefficients])]).acquire(staging, dev)
     for view, c in zip(blk.hosts("coef", np.int16), coefficients):
         view[:] = np.asarray(c.coef).reshape(-1)
-    job = _entropy_job(blk, "desc", [c.info for c in coefficients], blk.ptrs("coef"), dev, optimize)
+    job = _entropy_job(blk, "desc", [c.info for c in coefficients], blk.ptrs("coef"), dev, optimize, restart)
     blk.upload()
     return job
 
 
-def entropy_encode_device(coefficients: Sequence[JpegCoefficients], device=None, staging=None, optimize: bool = False) -> List[bytes]:
+def _restart_value(name: str, value) -> int:
+    """``value`` as an int in 0..65535; booleans, floats and anything else are refused."""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 0 <= int(value) <= 65535:
+        raise ValueError(f"{name} must be an int in 0..65535, got {value!r}")
+    return int(value)
+
+
+def entropy_encode_device(coefficients: Sequence[JpegCoefficients], device=None, staging=None, optimize: bool = False,
+                          restart_interval=0) -> List[bytes]:
     """The files ``entropy_encode`` gives for a list of ``JpegCoefficients`` (three components, geometry of ``encode_plan``),
     coded on the device: the coefficient arrays are uploaded with the table in one copy, then ONE
     ``pp_jpeg_entropy_encode_batch`` call (seven launches) on the current stream. Invalid coefficients raise what
     ``entropy_encode`` raises for them (``ProbPoseLibraryError``, PP_ERR_INVALID_ARG). ``optimize``: the files of
-    ``entropy_encode(c, optimize=True)`` from ONE ``pp_jpeg_entropy_encode_opt_batch`` call (ten launches)."""
+    ``entropy_encode(c, optimize=True)`` from ONE ``pp_jpeg_entropy_encode_opt_batch`` call (ten launches).
+    ``restart_interval``: MCUs between restart markers, an int for all images or one int per image (0: none for that image):
+    the files of ``entropy_encode(c, R, optimize)`` from ONE ``pp_jpeg_entropy_encode_restart_batch`` resp.
+    ``pp_jpeg_entropy_encode_opt_restart_batch`` call (seven resp. ten launches again). With every interval 0 the call is the
+    one made without the keyword."""
     coefficients = list(coefficients)
+    if isinstance(restart_interval, (list, tuple, np.ndarray)):
+        if len(restart_interval) != len(coefficients):
+            raise ValueError(f"restart_interval holds {len(restart_interval)} values for {len(coefficients)} images")
+        restart = [_restart_value("restart_interval", r) for r in restart_interval]
+    else:
+        restart = [_restart_value("restart_interval", restart_interval)] * len(coefficients)
     if len(coefficients) == 0:
         return []
     dev = _cuda_device(device or "cuda", "entropy_encode_device")
@@ -821,13 +872,14 @@ def entropy_encode_device(coefficients: Sequence[JpegCoefficients], device=None,
             raise ValueError("the encoder takes three (64,) tables and info.coef_count int16 coefficients")
         write_headers(qt, c.info)  # (refuses an info that is no encode_plan result, and tables outside 1..255, before any GPU work)
         qts.append(qt)
-    job = _stage_entropy(coefficients, dev, staging, bool(optimize))
+    job = _stage_entropy(coefficients, dev, staging, bool(optimize), restart if any(restart) else None)
     stream = torch.cuda.current_stream(dev)
     _entropy_launch(job, stream)
     return _entropy_collect(job, qts, stream, staging)
 
 
-def _forward(images, quality, subsampling, channel_order, device, staging, entropy: bool, optimize: bool = False) -> Optional[_ForwardJob]:
+def _forward(images, quality, subsampling, channel_order, device, staging, entropy: bool, optimize: bool = False,
+             restart=None) -> Optional[_ForwardJob]:
     """What ``forward_batch`` and ``_encode_batch_device`` begin with: the options and images checked, the batch staged and
     ``pp_jpeg_forward_batch`` enqueued on the current stream. None for no images."""
     global forward_calls
@@ -839,7 +891,7 @@ def _forward(images, quality, subsampling, channel_order, device, staging, entro
     images, dev = _encoder_images(list(images), device)
     if len(images) == 0:
         return None
-    job = _stage_encode(images, qt, subsampling, channel_order, dev, staging if staging is not None else BatchStaging(), entropy, optimize)
+    job = _stage_encode(images, qt, subsampling, channel_order, dev, staging if staging is not None else BatchStaging(), entropy, optimize, restart)
     _lib.call("pp_jpeg_forward_batch", *job.args, torch.cuda.current_stream(dev).cuda_stream)
     forward_calls += 1
     return job
@@ -862,14 +914,20 @@ def forward_batch(images: Sequence, quality: int = 75, subsampling: str = "4:2:0
 
 
 def encode_batch(images: Sequence, quality: int = 75, subsampling: str = "4:2:0", channel_order: str = "bgr", restart_interval: int = 0,
-                 workers: int = 8, device=None, staging=None, entropy: str = "host", optimize: bool = False) -> List[bytes]:
+                 workers: int = 8, device=None, staging=None, entropy: str = "host", optimize: bool = False, restart_rows: int = 0) -> List[bytes]:
     """Baseline JPEG files of a batch of (H, W, 3) uint8 images (device tensors; a host array is uploaded first) of any mix
     of sizes: ``forward_batch`` on the device, then Huffman coding on a pool of ``workers`` host threads (at most
     ``runner.MAX_WORKERS``). ``quality`` 1..100, ``subsampling`` "4:4:4" / "4:2:2" / "4:2:0" and ``restart_interval`` (MCUs
     between restart markers, 0: none) mean what they mean to Pillow's ``Image.save``; ``channel_order``: "bgr" or "rgb"
     pixels. Each file decodes to the pixels Pillow's own file of that image decodes to.
 
-    ``entropy="device"`` codes on the device instead (restart interval 0 only): the forward launches, then
+    ``restart_rows`` (0: none) asks for a restart marker every ``restart_rows`` MCU rows of each image's OWN width - libjpeg's
+    ``restart_in_rows``, ``cjpeg -restart N`` - which is what a mixed-size batch needs: image i is coded at the interval
+    ``restart_rows * mcus_x[i]``. It excludes a non-zero ``restart_interval``; an interval above 65535 (the DRI segment holds
+    16 bits) raises ``ValueError`` naming the image.
+
+    ``entropy="device"`` codes on the device instead (``restart_interval`` must be 0 there; ``restart_rows`` is taken and runs
+    the ``*_restart_batch`` forms of the calls, launch for launch the same number): the forward launches, then
     ``pp_jpeg_entropy_encode_batch`` on the same stream; the coefficients stay on the device and ``workers`` is not used. A
     batch of n images then costs one upload (tables and descriptors), 1 + n downloads (the result slots, then the used
     bytes of each stream) and two synchronisations, one after each kind of download. The files are byte for byte those
@@ -886,24 +944,52 @@ def encode_batch(images: Sequence, quality: int = 75, subsampling: str = "4:2:0"
 
     if isinstance(restart_interval, bool) or not isinstance(restart_interval, (int, np.integer)) or not 0 <= int(restart_interval) <= 65535:
         raise ValueError(f"restart_interval must be an int in 0..65535, got {restart_interval!r}")
+    rows = _restart_value("restart_rows", restart_rows)
+    if rows and int(restart_interval):
+        raise ValueError("restart_rows and restart_interval exclude each other: one of them must be 0")
     if isinstance(images, (torch.Tensor, np.ndarray)):
         raise ValueError("encode_batch takes a sequence of (H, W, 3) images; imwrite_device takes one")
     _check_entropy(entropy)
+    if entropy == "device" and int(restart_interval) != 0:
+        raise ValueError("entropy='device' takes no restart_interval (one MCU count is no row of every width in a batch): ask for restart "
+                         "markers with restart_rows, or code coefficients with entropy_encode_device(..., restart_interval=...)")
+    restart = None
+    if rows:
+        images = list(images)
+        restart = _row_intervals(images, subsampling, rows)
     if entropy == "device":
-        if int(restart_interval) != 0:
-            raise ValueError("entropy='device' codes without restart intervals: restart_interval must be 0")
-        return _encode_batch_device(images, quality, subsampling, channel_order, device, staging, bool(optimize))
+        return _encode_batch_device(images, quality, subsampling, channel_order, device, staging, bool(optimize), restart)
     coefs = forward_batch(images, quality, subsampling, channel_order, device, staging, copy=False)  # (coded before staging is used again)
+    each = [int(restart_interval)] * len(coefs) if restart is None else restart
     if len(coefs) <= 1 or int(workers) <= 1:
-        return [entropy_encode(c, restart_interval, optimize) for c in coefs]
+        return [entropy_encode(c, r, optimize) for c, r in zip(coefs, each)]
     with ThreadPoolExecutor(max_workers=max(1, min(MAX_WORKERS, int(workers), len(coefs)))) as pool:
-        return list(pool.map(lambda c: entropy_encode(c, restart_interval, optimize), coefs))
+        return list(pool.map(lambda cr: entropy_encode(cr[0], cr[1], optimize), zip(coefs, each)))
 
 
-def _encode_batch_device(images, quality, subsampling, channel_order, device, staging, optimize=False) -> List[bytes]:
+def _row_intervals(images, subsampling, rows: int) -> list:
+    """Every image's restart interval for a marker each ``rows`` MCU rows: ``rows`` x the MCUs of a row of its own width.
+    ``ValueError`` for one that a DRI segment cannot hold. (What is no image is left to the encoder's own checks.)"""
+    if subsampling not in SUBSAMPLING:
+        raise ValueError(f"subsampling must be one of {sorted(SUBSAMPLING)}, got {subsampling!r}")
+    out = []
+    for i, im in enumerate(images):
+        shape = tuple(getattr(im, "shape", ()))
+        if len(shape) != 3 or not 1 <= shape[0] <= 65535 or not 1 <= shape[1] <= 65535:
+            out.append(0)
+            continue
+        mcus_x = int(encode_plan(int(shape[1]), int(shape[0]), subsampling).mcus_x)
+        if rows * mcus_x > 65535:
+            raise ValueError(f"image {i} ({shape[1]} x {shape[0]}): restart_rows={rows} x {mcus_x} MCUs a row is an interval of {rows * mcus_x}, "
+                             "above the 65535 a DRI segment holds")
+        out.append(rows * mcus_x)
+    return out
+
+
+def _encode_batch_device(images, quality, subsampling, channel_order, device, staging, optimize=False, restart=None) -> List[bytes]:
     """``encode_batch`` with both halves on the device: nine launches on the current stream (twelve with ``optimize``), no
-    coefficient copy."""
-    job = _forward(images, quality, subsampling, channel_order, device, staging, True, optimize)
+    coefficient copy. ``restart``: every image's interval (the ``*_restart_batch`` form of the entropy call), or None."""
+    job = _forward(images, quality, subsampling, channel_order, device, staging, True, optimize, restart)
     if job is None:
         return []
     stream = torch.cuda.current_stream(job.block.dev.device)
@@ -912,8 +998,8 @@ def _encode_batch_device(images, quality, subsampling, channel_order, device, st
 
 
 def imwrite_device(path: str, image, **kw) -> None:
-    """One picture written as a baseline JPEG file by ``encode_batch`` (its keyword arguments, ``entropy`` and ``optimize``
-    among them)."""
+    """One picture written as a baseline JPEG file by ``encode_batch`` (its keyword arguments, ``entropy``, ``optimize`` and
+    ``restart_rows`` among them)."""
     data = encode_batch([image], **kw)[0]
     with open(path, "wb") as f:
         f.write(data)

@@ -463,7 +463,7 @@ class PoseLocalVisualizer:
     canvas, stacked under the pose panel. Everything is drawn on the GPU; ``add_datasample`` copies the image back once."""
 
     def __init__(self, name="visualizer", radius=3, line_width=1, alpha=0.8, device="cuda:0", image_encoder="host", png_encoder="host", png_match="runs",
-                 jpeg_optimize=False, png_code="host"):
+                 jpeg_optimize=False, png_code="host", jpeg_restart_rows=0):
         if image_encoder not in ("host", "device"):
             raise ValueError(f"image_encoder must be 'host' or 'device', got {image_encoder!r}")
         if png_encoder not in ("host", "device"):
@@ -475,6 +475,9 @@ class PoseLocalVisualizer:
         self.image_encoder = image_encoder  # "device": a .jpg / .jpeg out_file is written by jpeg.imwrite_device
         self.png_encoder = png_encoder  # "device": a .png out_file is written by png.imwrite_device
         self.jpeg_optimize = bool(jpeg_optimize)  # that writer's optimize=: the picture's own Huffman tables (the same pixels, a smaller file)
+        if isinstance(jpeg_restart_rows, bool) or not isinstance(jpeg_restart_rows, (int, np.integer)) or not 0 <= int(jpeg_restart_rows) <= 65535:
+            raise ValueError(f"jpeg_restart_rows must be an int in 0..65535, got {jpeg_restart_rows!r}")
+        self.jpeg_restart_rows = int(jpeg_restart_rows)  # that writer's restart_rows=: a restart marker every so many MCU rows (0: none; the same pixels)
         self.png_match = png_match  # the match mode of that writer: "runs", or "lz" (pixel and row distances: smaller files of drawn frames)
         self.png_code = png_code  # where that writer builds its Huffman codes: "host" (a round trip between its halves), or "device" (one launch more)
         self.name = name
@@ -580,7 +583,8 @@ class PoseLocalVisualizer:
             if self.image_encoder == "device" and str(out_file).lower().endswith((".jpg", ".jpeg")):
                 from . import jpeg
 
-                jpeg.imwrite_device(out_file, out, quality=75, subsampling="4:2:0", channel_order="rgb", optimize=self.jpeg_optimize)
+                jpeg.imwrite_device(out_file, out, quality=75, subsampling="4:2:0", channel_order="rgb", optimize=self.jpeg_optimize,
+                                    restart_rows=self.jpeg_restart_rows)
             elif self.png_encoder == "device" and str(out_file).lower().endswith(".png"):
                 from . import png
 

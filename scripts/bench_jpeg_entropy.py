@@ -16,9 +16,16 @@ scripts/bench_png_encode.py. With ``--parent-lib PATH`` (an earlier build of the
 pp_jpeg_entropy_encode_batch is timed in the same alternation as this build's (``lib: "parent"``): the default path must lie
 within the spread two identical builds show.
 
+With ``--restart-rows N`` and / or ``--restart-interval R`` the coder with restart intervals
+(pp_jpeg_entropy_encode_restart_batch) is timed in the same alternations: entropy_call gains a line per kind (``restart``:
+"rows N" - a marker every N MCU rows - resp. "interval R" - R MCUs, 1 being the worst case) beside the interval-free call;
+with ``--restart-rows`` encode_batch gains device and host entropy at ``restart_rows=N``, and video_demo runs with
+``--restart-rows N`` on both sides.
+
 One JSON line per figure.
 
-    python scripts/bench_jpeg_entropy.py [--rounds 7] [--frames 64] [--demo-rounds 3] [--optimize off|both] [--parent-lib PATH]"""
+    python scripts/bench_jpeg_entropy.py [--rounds 7] [--frames 64] [--demo-rounds 3] [--optimize off|both] [--parent-lib PATH]
+                                         [--restart-rows N] [--restart-interval R]"""
 import argparse
 import ctypes
 import json
@@ -46,6 +53,8 @@ def main():
     ap.add_argument("--demo-rounds", type=int, default=3)
     ap.add_argument("--optimize", default="off", choices=["off", "both"], help="both: the optimised coder beside the default one")
     ap.add_argument("--parent-lib", default=None, help="an earlier build of libprobpose_mi355x.so: its entropy call is timed beside this build's")
+    ap.add_argument("--restart-rows", type=int, default=0, help="N > 0: the coder with a restart marker every N MCU rows beside the interval-free one")
+    ap.add_argument("--restart-interval", type=int, default=0, help="R > 0: the coder at a restart interval of R MCUs (1: the worst case) as well")
     args = ap.parse_args()
 
     import torch
@@ -92,13 +101,19 @@ def main():
             stream = torch.cuda.current_stream(dev)
             # name -> (the call, its staged job): this build's default coder, its optimised coder, the parent build's default coder
             calls = {}
-            for name in ("default",) + (("optimize",) if both else ()) + (("parent",) if parent is not None else ()):
-                forward = jpeg._stage_encode(frames[:n], qt, "4:2:0", "rgb", dev, staging, entropy=True, optimize=name == "optimize")
+            kinds = ("default",) + (("optimize",) if both else ()) + (("parent",) if parent is not None else ())
+            kinds += (("rows",) if args.restart_rows else ()) + (("interval",) if args.restart_interval else ())
+            mcus_x = int(jpeg.encode_plan(W, H, "4:2:0").mcus_x)
+            restart = {"rows": [args.restart_rows * mcus_x] * n, "interval": [args.restart_interval] * n}
+            for name in kinds:
+                forward = jpeg._stage_encode(frames[:n], qt, "4:2:0", "rgb", dev, staging, entropy=True, optimize=name == "optimize", restart=restart.get(name))
                 _lib.call("pp_jpeg_forward_batch", *forward.args, stream.cuda_stream)
                 job = forward.entropy
                 ent_args = (job.desc_ptr, n, max(int(i.coef_count) // 64 for i in job.infos), stream.cuda_stream)
                 if name == "parent":
                     fn = (lambda a=ent_args: parent.pp_jpeg_entropy_encode_batch(*a))
+                elif name in restart:
+                    fn = (lambda a=ent_args: _lib.call("pp_jpeg_entropy_encode_restart_batch", *a))
                 else:
                     fn = (lambda a=ent_args, f=("pp_jpeg_entropy_encode_opt_batch" if name == "optimize" else "pp_jpeg_entropy_encode_batch"): _lib.call(f, *a))
                 calls[name] = (fn, forward)
@@ -120,7 +135,8 @@ def main():
                 job = forward.entropy
                 res = job.results.cpu().numpy()[:16 * n].view(jpeg._ENT_RESULT)
                 assert (res["status"] == 0).all()
-                print(json.dumps(dict(figure="entropy_call", size=size, n=n, lib="parent" if name == "parent" else "this", optimize=name == "optimize",
+                kind = {"rows": f"rows {args.restart_rows}", "interval": f"interval {args.restart_interval}"}.get(name, "none")
+                print(json.dumps(dict(figure="entropy_call", size=size, n=n, lib="parent" if name == "parent" else "this", optimize=name == "optimize", restart=kind,
                                       device_event_us=round(statistics.median(us[name]), 1), min_us=round(min(us[name]), 1),
                                       max_us=round(max(us[name]), 1), rounds=args.rounds, stream_bytes=int(res["bytes"].sum()),
                                       coefficient_bytes=int(sum(2 * int(i.coef_count) for i in job.infos)), sclk_mhz=sclk)), flush=True)
@@ -128,8 +144,9 @@ def main():
 
         for n in (1, 16):
             for workers in (1, 8):
-                paths = {(e, o): (lambda e=e, o=o: jpeg.encode_batch(frames[:n], channel_order="rgb", workers=workers, staging=staging, entropy=e, optimize=o))
-                         for e in ("host", "device") for o in ((False, True) if both else (False,))}
+                paths = {(e, o, r): (lambda e=e, o=o, r=r: jpeg.encode_batch(frames[:n], channel_order="rgb", workers=workers, staging=staging, entropy=e,
+                                                                             optimize=o, restart_rows=r))
+                         for e in ("host", "device") for o in ((False, True) if both else (False,)) for r in sorted({0, args.restart_rows})}
                 times = {k: [] for k in paths}
                 for fn in paths.values():
                     fn()  # warm-up
@@ -140,8 +157,9 @@ def main():
                         fn()
                         torch.cuda.synchronize()
                         times[name].append(time.perf_counter() - t0)
-                for (name, o), ts in times.items():
-                    print(json.dumps(dict(figure="encode_batch", size=size, entropy=name, optimize=o, n=n, workers=workers, ms=round(statistics.median(ts) * 1e3, 3),
+                for (name, o, r), ts in times.items():
+                    print(json.dumps(dict(figure="encode_batch", size=size, entropy=name, optimize=o, restart_rows=r, n=n, workers=workers,
+                                          ms=round(statistics.median(ts) * 1e3, 3),
                                           min_ms=round(min(ts) * 1e3, 3), max_ms=round(max(ts) * 1e3, 3), rounds=args.rounds)), flush=True)
 
     if args.frames > 0:
@@ -156,11 +174,12 @@ def main():
             fps = {"host": [], "device": []}
             for _ in range(args.demo_rounds):
                 for e in fps:
-                    done = video_demo.main([src, CFG, "synthetic", "--out-video", os.path.join(td, f"out_{e}.avi"), "--decode", "device", "--entropy", e])
+                    done = video_demo.main([src, CFG, "synthetic", "--out-video", os.path.join(td, f"out_{e}.avi"), "--decode", "device", "--entropy", e] +
+                                           (["--restart-rows", str(args.restart_rows)] if args.restart_rows else []))
                     fps[e].append(done["frames"] / done["seconds"])
             same = open(os.path.join(td, "out_host.avi"), "rb").read() == open(os.path.join(td, "out_device.avi"), "rb").read()
             for e, v in fps.items():
-                print(json.dumps(dict(figure="video_demo", size="1920x1080", frames=args.frames, entropy=e, frames_per_s=round(statistics.median(v), 1),
+                print(json.dumps(dict(figure="video_demo", size="1920x1080", frames=args.frames, entropy=e, restart_rows=args.restart_rows, frames_per_s=round(statistics.median(v), 1),
                                       min=round(min(v), 1), max=round(max(v), 1), rounds=args.demo_rounds, outputs_equal=same, sclk_mhz=shader_clock())),
                       flush=True)
 
