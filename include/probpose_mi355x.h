@@ -1329,6 +1329,73 @@ int pp_oks_nms_batch(const double* kpts, const double* areas, const long long* i
                      long long n_instances, int n_images, int K, double thr, double guard, int area_f32, void* workspace,
                      long long workspace_bytes, unsigned char* keep, int* status, void* stream);
 
+/* ---- Loss mode: ProbMap targets and the OKS map loss (csrc/pp_probmap_encode.hip, csrc/pp_probmap_loss.hip; added under
+ * version 4: purely additive). Evaluation-mode forward losses only: no gradients.
+ *
+ * pp_probmap_encode: ProbMap.encode (mmpose/codecs/probmap.py:98-168, codecs/utils/oks_map.py) for a batch in one launch
+ * ("probmap_encode", one workgroup per map). keypoints (B, K, 2) float32 in input-pixel space, visible (B, K) float32. Per map:
+ * the coordinates are divided by (in_w - 1) / (W - 1) and (in_h - 1) / (H - 1) in float32, then every pixel gets
+ *   float32(exp(-(sqrt(dx^2 + dy^2))^2 / (2 s)))      in fp64, one rounding per operator,
+ * s = clip((2 sigma_k)^2 sqrt(H / 1.25 * W / 1.25) 2, 0.55, 3.0) with the 17 COCO sigmas, or `sigma` when that is > 0.
+ * visible < 0.5: a zero map, weight = visible. Otherwise weight = (some fp64 value of the map > 0) - decided before the rounding
+ * to float32, so a keypoint far outside the map gets weight 0. annotated = visible > 0; in_image = 0 <= x < in_w and
+ * 0 <= y < in_h on the unscaled coordinates. Outputs: heatmaps (B, K, H, W) float32, keypoint_weights (B, K) float32, annotated
+ * and in_image (B, K) uint8. Status instead of a launch: NULL pointers, B < 0, K/H/W <= 0, in_w/in_h <= 0 (INVALID_ARG);
+ * K != 17 with sigma <= 0 (INVALID_ARG: the sigma table is COCO's). A 1-pixel axis has scale factor (in - 1) / 0 = inf as in
+ * numpy: every finite coordinate lands on 0. B = 0 returns PP_OK untouched.
+ * pp_probmap_encode_s: the K values of s the launch would use, to a HOST array (the same checks; no device call). */
+int pp_probmap_encode(const float* keypoints, const float* visible, int B, int K, int H, int W, double in_w, double in_h,
+                      double sigma, float* heatmaps, float* keypoint_weights, unsigned char* annotated,
+                      unsigned char* in_image, void* stream);
+int pp_probmap_encode_s(int K, int H, int W, double sigma, double* s_host);
+
+/* pp_probmap_loss_maps: OKSHeatmapLoss.forward(per_pixel=True), oks_type "minus" (mmpose/models/losses/heatmap_loss.py:552-638),
+ * reduced to its mean, plus the argmax pixels pose_pck_accuracy(method="argmax") reads. pred, target (B, K, H, W) float32,
+ * weights (B, K) float32 (the mask of _get_mask: the keypoint's weight over its whole map). Launch one ("probmap_loss_maps"), one
+ * workgroup per map, the map staged once in LDS with a one-pixel zero halo: per map
+ *   map_sums[b, k] = w[b, k] * sum_pixels( smoothing_weight (Gx^2 + Gy^2) + (1 - smoothing_weight - gaussian_weight) p (1 - t)
+ *                                          + gaussian_weight (p - t)^2 )                                    in fp64,
+ * Gx, Gy the 3x3 Sobel responses of p with zero "same" padding; argmax (B, K, 2) int32 = row-major index of the maximum of p and
+ * of t (numpy's argmax: the first on ties, the first NaN if there is one) and maxval (B, K, 2) float32 those maxima. Launch two
+ * ("probmap_loss_mean", one workgroup, a fixed tree): loss[0] = float32(loss_weight * sum(map_sums) / (B K H W)). No atomics:
+ * the same bits launch after launch. map_sums (B, K) float64 is an output and the second launch's input.
+ * Status instead of a launch: NULL pointers, B < 0, K/H/W <= 0 (INVALID_ARG); (H + 2) (W + 2) > PP_PROBMAP_LOSS_MAX_TILE floats,
+ * the LDS stage (UNSUPPORTED). B = 0 returns PP_OK untouched. */
+#define PP_PROBMAP_LOSS_MAX_TILE 15360
+int pp_probmap_loss_maps(const float* pred, const float* target, const float* weights, int B, int K, int H, int W,
+                         double smoothing_weight, double gaussian_weight, double loss_weight, double* map_sums, int32_t* argmax,
+                         float* maxval, float* loss, void* stream);
+
+/* pp_probmap_loss_scalars: the scalar targets and the four scalar losses of ProbMapHead.loss (probmap_head.py:830-941) in ONE launch
+ * ("probmap_loss_scalars", one workgroup, fixed trees). Inputs on the device: scalars (4, B, K) float32 = the predicted probability,
+ * visibility, oks and error; in_image, annotated (keypoints_visible.astype(int)) and visibility (keypoints_visibility.astype(int))
+ * (B, K) uint8, each 0 or 1; kp_gt and kp_dt (B, K, 2) float64 = the target and the predicted maps decoded by pp_udp_heatmap_decode
+ * (ArgMaxProbMap.decode, the head's fast_decoder). loss_weights_host: four doubles on the HOST (probability, visibility, oks, error).
+ * Outputs on the device:
+ *   gt_oks (B, K) float32   _oks_from_heatmaps: NaN target coordinates -> 0, both coordinate sets times w = in_image & annotated,
+ *                           exp(-(dx^2 + dy^2) / (2 sigma_k)^2 / (64 * 48 * 0.53 + spacing(1)) / 2) (compute_oks, use_area=False,
+ *                           per_kpt=True, the sigmas / 10), 0 where w = 0; an instance without any w = 1 gets zeros and
+ *   oks_weight (B) float32  0, every other 1. PP_LOSS_FREEZE_OKS: all zeros.
+ *   gt_errs (B, K) float32  _error_from_heatmaps: ||gt - dt||, NaN target coordinates -> -1; PP_LOSS_FREEZE_ERROR: zeros.
+ *   vis_weights (B, K) float32  the class-balanced weights of :883-889 (1 / count of annotated invisible resp. visible keypoints,
+ *                           formed in float32, divided by the smallest positive one; 0 where not annotated).
+ *   out[6] float32          loss_probability = mean(BCE(p, in_image) * annotated), loss_visibility = mean(BCE(v, visibility) *
+ *                           vis_weights), loss_oks = mean((o w - gt_oks w)^2), loss_error = mean(smooth_l1(log(1 + e) w,
+ *                           log(1 + gt_errs) w)) - means over B K, times their loss weights -, mae_oks, mae_err = mean |.| over w = 1
+ *                           (NaN when no keypoint has w = 1). BCE is torch's binary_cross_entropy (logs clamped at -100), with
+ *                           PP_LOSS_PROB_LOGITS / PP_LOSS_VIS_LOGITS binary_cross_entropy_with_logits. Elementwise values and sums
+ *                           are fp64 from the float32 inputs. A batch without any annotated keypoint has loss_visibility 0 (the
+ *                           reference raises on the empty minimum).
+ * Status instead of a launch: NULL pointers, B < 0, K <= 0, unknown flags, K != 17 (INVALID_ARG). B = 0 returns PP_OK untouched. */
+#define PP_LOSS_FREEZE_OKS 1
+#define PP_LOSS_FREEZE_ERROR 2
+#define PP_LOSS_PROB_LOGITS 4
+#define PP_LOSS_VIS_LOGITS 8
+int pp_probmap_loss_scalars(const float* scalars, const unsigned char* in_image, const unsigned char* annotated,
+                            const unsigned char* visibility, const double* kp_gt, const double* kp_dt, int B, int K, int flags,
+                            const double* loss_weights_host, float* gt_oks, float* oks_weight, float* gt_errs, float* vis_weights,
+                            float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

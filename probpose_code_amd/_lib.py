@@ -217,6 +217,10 @@ SIGNATURES = {
     "pp_oks_nms_workspace_bytes": (c_longlong, [_P, c_longlong, c_int]),
     "pp_oks_nms_batch": (
         c_int, [_P, _P, _P, _P, c_longlong, c_int, c_int, c_double, c_double, c_int, _P, c_longlong, _P, _P, _P]),
+    "pp_probmap_encode": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_double, c_double, c_double, _P, _P, _P, _P, _P]),
+    "pp_probmap_encode_s": (c_int, [c_int, c_int, c_int, c_double, _P]),
+    "pp_probmap_loss_maps": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_double, c_double, c_double, _P, _P, _P, _P, _P]),
+    "pp_probmap_loss_scalars": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -115,12 +115,77 @@ class ProbMap(BaseKeypointCodec):
             )
         self._tables: Dict[Tuple[int, int, int, str], Tuple[torch.Tensor, torch.Tensor]] = {}
 
-    # -- encode is the training-side label generator (GenerateTarget); not on the inference path
-    def encode(self, keypoints, keypoints_visible=None, id_similarity=0.0, keypoints_visibility=None) -> dict:
-        raise NotImplementedError(
-            "ProbMap.encode (probmap.py:98-168) generates training targets and is outside the "
-            "MI355X inference hot path (SURVEY.md 2: 'decode only; encode is training')."
-        )
+    # -- encode: the label generator of GenerateTarget; what the loss mode (ProbMapHead.loss) scores the head's outputs against
+    def _check_encodable(self, K: int) -> None:
+        if self.heatmap_type != "gaussian":
+            raise NotImplementedError("only heatmap_type='gaussian' (the ProbPose setting) is encodable on MI355X")
+        if not (self.sigma is not None and self.sigma > 0) and K != len(_KPT_SIGMAS):
+            raise ValueError(f"{type(self).__name__}.encode with sigma <= 0 uses the {len(_KPT_SIGMAS)} COCO keypoint sigmas "
+                             f"(oks_map.py:39): got {K} keypoints")
+
+    def encode(self, keypoints: np.ndarray, keypoints_visible: Optional[np.ndarray] = None, id_similarity: Optional[float] = 0.0,
+               keypoints_visibility: Optional[np.ndarray] = None) -> dict:
+        """probmap.py:98-168 for ONE instance, on the host in numpy: ``keypoints`` (1, K, 2) in input-pixel space, ``keypoints_visible``
+        (1, K) -> the reference's dictionary: ``heatmaps`` (K, H, W) float32 - per labelled keypoint ``exp(-d^2 / 2s)`` in float64 around
+        ``keypoints / scale_factor``, ``s = clip((2 sigma_k)^2 sqrt(H / 1.25 * W / 1.25) 2, 0.55, 3.0)`` or a positive ``sigma`` -,
+        ``keypoint_weights`` (1, K) (``keypoints_visible`` with the labelled entries replaced by "the float64 map has a value above
+        zero": 0 for a keypoint far outside), ``annotated``, ``in_image`` (1, K) bool, ``keypoints_scaled``, ``heatmap_keypoints``,
+        ``identification_similarity``. The batched form on the device is ``encode_device``; this one is its restatement."""
+        assert keypoints.shape[0] == 1, f"{self.__class__.__name__} only support single-instance keypoint encoding"
+        N, K, _ = keypoints.shape
+        self._check_encodable(K)
+        if keypoints_visibility is None:
+            keypoints_visibility = np.zeros(keypoints.shape[:2], dtype=np.float32)
+        if keypoints_visible is None:
+            keypoints_visible = np.ones(keypoints.shape[:2], dtype=np.float32)
+        W, H = self.heatmap_size
+        scaled = keypoints / self.scale_factor
+        heatmaps = np.zeros((K, H, W), dtype=np.float32)
+        keypoint_weights = keypoints_visible.copy()
+        bbox_area = np.sqrt(H / 1.25 * W / 1.25)
+        y_idx, x_idx = np.indices((H, W))
+        for k in range(K):
+            if keypoints_visible[0, k] < 0.5:  # unlabelled: the zero map, the weight as it came
+                continue
+            dx = x_idx - scaled[0, k, 0]
+            dy = y_idx - scaled[0, k, 1]
+            dist = np.sqrt(dx**2 + dy**2)
+            s = np.clip((_KPT_SIGMAS[k] * 2) ** 2 * bbox_area * 2, 0.55, 3.0) if not (self.sigma is not None and self.sigma > 0) else self.sigma
+            oks_map = np.exp(-(dist**2 / (2 * s)))
+            keypoint_weights[0, k] = int(oks_map.max() > 0)
+            heatmaps[k] = oks_map
+        in_image = (keypoints[:, :, 0] >= 0) & (keypoints[:, :, 0] < self.input_size[0]) & (keypoints[:, :, 1] >= 0) & (
+            keypoints[:, :, 1] < self.input_size[1])
+        return dict(heatmaps=heatmaps, keypoint_weights=keypoint_weights, annotated=keypoints_visible > 0, in_image=in_image,
+                    keypoints_scaled=keypoints, heatmap_keypoints=keypoints / self.scale_factor,
+                    identification_similarity=id_similarity)
+
+    def encode_device(self, keypoints: torch.Tensor, keypoints_visible: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """``encode`` for a batch in ONE launch (``pp_probmap_encode``): ``keypoints`` (B, K, 2) in input-pixel space and
+        ``keypoints_visible`` (B, K) on the device (converted to float32: the division by ``scale_factor`` is float32, as for the float32
+        keypoints of the data pipeline) -> device tensors ``heatmaps`` (B, K, H, W) float32, ``keypoint_weights`` (B, K) float32,
+        ``annotated`` and ``in_image`` (B, K) bool. The maps are never built on the host."""
+        if not (isinstance(keypoints, torch.Tensor) and keypoints.is_cuda):
+            raise RuntimeError(f"{type(self).__name__}.encode_device needs tensors on the MI355X; there is no CPU fallback "
+                               "(the host form is `encode`)")
+        assert keypoints.dim() == 3 and keypoints.shape[-1] == 2, "keypoints should be a (B, K, 2) tensor"
+        B, K = int(keypoints.shape[0]), int(keypoints.shape[1])
+        assert tuple(keypoints_visible.shape) == (B, K), "keypoints_visible should be a (B, K) tensor"
+        self._check_encodable(K)
+        dev = keypoints.device
+        W, H = self.heatmap_size
+        kp = keypoints.to(torch.float32).contiguous()
+        vis = keypoints_visible.to(device=dev, dtype=torch.float32).contiguous()
+        out = dict(heatmaps=torch.empty((B, K, H, W), dtype=torch.float32, device=dev),
+                   keypoint_weights=torch.empty((B, K), dtype=torch.float32, device=dev),
+                   annotated=torch.empty((B, K), dtype=torch.uint8, device=dev),
+                   in_image=torch.empty((B, K), dtype=torch.uint8, device=dev))
+        with torch.cuda.device(dev):
+            _lib.call("pp_probmap_encode", _lib.ptr(kp), _lib.ptr(vis), B, K, H, W, float(self.input_size[0]), float(self.input_size[1]),
+                      float(self.sigma if self.sigma is not None else -1.0), _lib.ptr(out["heatmaps"]), _lib.ptr(out["keypoint_weights"]),
+                      _lib.ptr(out["annotated"]), _lib.ptr(out["in_image"]), _lib.stream_ptr(dev))
+        out["annotated"], out["in_image"] = out["annotated"].bool(), out["in_image"].bool()
+        return out
 
     # -- device-side tables, built once per (K, H, W, device) instead of on every call (post_processing.py:344)
     def _device_tables(self, K: int, H: int, W: int, device: torch.device):
@@ -342,9 +407,13 @@ class UDPExpMaxHeatmap(ProbMap):
 
     def encode(self, keypoints, keypoints_visible=None, id_similarity=0.0, keypoints_visibility=None) -> dict:
         raise NotImplementedError(
-            "UDPExpMaxHeatmap.encode (udp_expmax_heatmap.py:110-200) generates training targets and is outside the "
-            "MI355X inference hot path (SURVEY.md 2: 'decode only; encode is training')."
+            "UDPExpMaxHeatmap.encode (udp_expmax_heatmap.py:110-200) generates the Gaussian training targets of the ViTPose heads and is "
+            "not implemented on MI355X; the target generator that is, is ProbMap.encode / ProbMap.encode_device (the loss mode)."
         )
+
+    def encode_device(self, keypoints, keypoints_visible):
+        raise NotImplementedError("UDPExpMaxHeatmap.encode_device: this codec's training targets are Gaussians, not OKS maps; "
+                                  "ProbMap.encode_device is the target generator that runs")
 
     def _launch(self, hm, hmf, fi, taps, radius, avg, conv, out, shift_heatmap, dev) -> None:
         B, K, H, W = hm.shape
@@ -389,6 +458,6 @@ class ArgMaxProbMap(UDPHeatmap):
 
     def encode(self, keypoints, keypoints_visible=None, id_similarity=0.0, keypoints_visibility=None) -> dict:
         raise NotImplementedError(
-            "ArgMaxProbMap.encode (argmax_probmap.py:101-170) generates training targets and is outside the "
-            "MI355X inference hot path (SURVEY.md 2: 'decode only; encode is training')."
+            "ArgMaxProbMap.encode (argmax_probmap.py:101-170) generates training targets and is not implemented on MI355X: "
+            "it is a decoder here; the target generator that runs is ProbMap.encode / ProbMap.encode_device (the loss mode)."
         )

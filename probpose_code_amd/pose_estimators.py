@@ -13,8 +13,9 @@ Same registry names, constructor arguments, method names and outputs as
 but every ``forward`` / ``predict`` lands in ``ProbPoseEngine`` (hand-written HIP through the C ABI).
 The modules are ``torch.nn.Module`` parameter containers whose ``state_dict`` keys are exactly the
 reference's, so ``load_checkpoint`` / ``load_state_dict`` of ``ProbPose-s.pth`` work unchanged;
-torch never computes anything here. Training-side members (``loss``, the loss modules, ``encode``)
-are outside the hot path and raise ``NotImplementedError``.
+torch never computes anything here. ``ProbMapHead.loss`` / ``TopdownPoseEstimator.loss`` / ``forward(mode="loss")`` are the
+EVALUATION-mode loss - the reference's ``model.eval(); model(..., mode="loss")``: forward values only, no gradients, not a
+training step (losses.py). ``HeatmapHead.loss`` and the ``UDPHeatmap`` targets stay outside and raise ``NotImplementedError``.
 """
 from itertools import zip_longest
 from typing import Dict, List, Optional, Sequence, Tuple, Union
@@ -208,8 +209,9 @@ class FeatureMapProcessor(nn.Module):
 # =================================================================================================
 @register(MODELS, reference_name="ProbMapHead", mi355x_name="ProbMapHeadMI355X")
 class ProbMapHead(nn.Module):
-    """probmap_head.py:25-804, inference side. Constructor arguments are the reference's; loss configs are
-    accepted and ignored (training is out of scope)."""
+    """probmap_head.py:25-1012 without the backward side. Constructor arguments are the reference's. The five loss configs build the
+    modules of losses.py (a type or option outside the ProbPose config is refused by name when ``loss`` is first asked for - a
+    head built for inference with the reference's other loss types keeps loading); ``loss`` is the evaluation-mode forward loss."""
 
     _version = 2
 
@@ -230,6 +232,11 @@ class ProbMapHead(nn.Module):
         self.temperature = 0.5  # probmap_head.py:135
         self.normalize = normalize
         self.freeze_oks, self.freeze_error = freeze_oks, freeze_error
+        self.learn_heatmaps_from_zeros = bool(learn_heatmaps_from_zeros)
+        self._loss_cfgs = dict(keypoint_loss=keypoint_loss, probability_loss=probability_loss, visibility_loss=visibility_loss,
+                               oks_loss=oks_loss, error_loss=error_loss)
+        self._loss_modules = None  # built by the first `loss` call (losses.build_head_losses)
+        self._fast_decoder = None  # probmap_head.py:152-154, built with them
         self.decoder = KEYPOINT_CODECS.build(decoder) if decoder is not None else None
         if deconv_out_channels:
             if deconv_kernel_sizes is None or len(deconv_out_channels) != len(deconv_kernel_sizes):
@@ -391,8 +398,101 @@ class ProbMapHead(nn.Module):
             return preds, [PixelData(heatmaps=hm) for hm in heatmaps.detach().clone()]
         return preds
 
-    def loss(self, *a, **k):
-        raise NotImplementedError("training (probmap_head.py:806-) is outside the MI355X inference hot path")
+    # -- the evaluation-mode loss (probmap_head.py:806-1012): forward values, no gradients
+    def loss(self, feats: Tuple[Tensor], batch_data_samples: list, train_cfg: dict = {}) -> Dict[str, Tensor]:
+        """probmap_head.py:806-942 from the backbone's features: the reference's dictionary of device scalars ``loss_kpt``,
+        ``loss_probability``, ``loss_visibility``, ``loss_oks``, ``loss_error`` and, unless ``train_cfg['compute_acc']`` is False,
+        ``acc_pose``, ``acc_prob``, ``acc_vis``, ``mae_oks``, ``mae_err``. This is the EVALUATION-mode loss, the reference's
+        ``model.eval(); head.loss(...)``: the engine's one unflipped pass (no drop-path, the towers' normalisation layers as at test
+        time), no gradients - a number to report, not a training step."""
+        out = self._engine.run_head(self._to_nhwc(feats), flip_test=False, return_heatmaps=True)
+        return self.loss_from_outputs(out["heatmaps"], out["scalars"], batch_data_samples, train_cfg)
+
+    def _targets_of(self, batch_data_samples: list, dev) -> Dict[str, Tensor]:
+        """The ground truth ``loss`` reads (probmap_head.py:824-828), on the device. Samples packed the reference's way carry
+        ``gt_fields.heatmaps``, ``gt_instance_labels.keypoint_weights`` and ``gt_instances.in_image`` (``GenerateTarget`` +
+        ``PackPoseInputs``); samples of ``GenerateTarget(device=True)`` carry only ``gt_instances.keypoints_scaled`` - the keypoints in
+        input-pixel space - and the whole batch is encoded here in one ``pp_probmap_encode`` launch, the maps never exist on the host."""
+        gi = [d.gt_instances for d in batch_data_samples]
+        annotated = np.stack([np.asarray(g.keypoints_visible).astype(int) for g in gi]).reshape(len(gi), -1)
+        visibility = np.stack([np.asarray(g.keypoints_visibility).astype(int) for g in gi]).reshape(len(gi), -1)
+        for name, a in (("keypoints_visible", annotated), ("keypoints_visibility", visibility)):
+            if not np.isin(a, (0, 1)).all():
+                raise ValueError(f"ProbMapHead.loss: gt_instances.{name}.astype(int) must be 0 or 1 (got {np.unique(a).tolist()})")
+        if all("gt_fields" in d and "heatmaps" in d.gt_fields for d in batch_data_samples):
+            maps = torch.stack([torch.as_tensor(d.gt_fields.heatmaps) for d in batch_data_samples]).to(dev).float()
+            in_image = np.stack([np.asarray(g.in_image).astype(int) for g in gi]).reshape(len(gi), -1)
+            kw = torch.cat([torch.as_tensor(d.gt_instance_labels.keypoint_weights) for d in batch_data_samples]).to(dev).float()
+            flags = torch.from_numpy(np.stack([in_image, annotated, visibility]).astype(np.uint8)).to(dev)
+            return dict(heatmaps=maps, keypoint_weights=kw.reshape(len(gi), -1), in_image=flags[0], annotated=flags[1], visibility=flags[2])
+        if not all("keypoints_scaled" in g for g in gi):
+            raise ValueError("ProbMapHead.loss needs targets: gt_fields.heatmaps (GenerateTarget + PackPoseInputs) or "
+                             "gt_instances.keypoints_scaled (GenerateTarget(device=True)) in every data sample")
+        from .codecs import ProbMap
+
+        codec = self.decoder  # the targets are ProbMap's whatever decodes (the codec-swap configs keep ProbMap as the training codec)
+        if type(codec) is not ProbMap:
+            codec = ProbMap(input_size=tuple(codec.input_size), heatmap_size=tuple(codec.heatmap_size), sigma=codec.sigma)
+        kp = np.concatenate([np.asarray(g.keypoints_scaled, np.float32).reshape(1, -1, 2) for g in gi])
+        host = torch.from_numpy(np.concatenate([kp.reshape(len(gi), -1), annotated.astype(np.float32), visibility.astype(np.float32)], 1)).to(dev)
+        K = kp.shape[1]
+        enc = codec.encode_device(host[:, :2 * K].reshape(len(gi), K, 2), host[:, 2 * K:3 * K])
+        return dict(heatmaps=enc["heatmaps"], keypoint_weights=enc["keypoint_weights"], in_image=enc["in_image"].to(torch.uint8),
+                    annotated=enc["annotated"].to(torch.uint8), visibility=host[:, 3 * K:].to(torch.uint8))
+
+    def loss_from_outputs(self, heatmaps: Tensor, scalars: Tensor, batch_data_samples: list, train_cfg: dict = {},
+                          return_targets: bool = False):
+        """``loss`` behind ``forward``: ``heatmaps`` (B, K, H, W) - the normalised maps ``clamp(Sparsemax(x / temperature) * normalize, 0,
+        1)`` - and ``scalars`` (4, B, K) [probability, visibility, oks, error], on the device, as the engine leaves them. Launches: (one
+        ``pp_probmap_encode`` when the samples carry keypoints instead of maps,) two of ``pp_probmap_loss_maps``, two
+        ``pp_udp_heatmap_decode`` (the reference's hard-coded ``fast_decoder``, ArgMaxProbMap 192x256 / 48x64, on target and predicted
+        maps), one ``pp_probmap_loss_scalars``; ``acc_prob`` / ``acc_vis`` / ``acc_pose`` on the host in numpy from one (B, K, 10) copy.
+        ``return_targets``: also the dictionary of device targets (``gt_oks``, ``oks_weight``, ``gt_errs``, ``vis_weights``, ``argmax``, ...)."""
+        from . import losses as L
+
+        if self._loss_modules is None:
+            mods = L.build_head_losses(**self._loss_cfgs)
+            if mods is None:
+                raise RuntimeError("ProbMapHead.loss: the head was built without loss configs (keypoint_loss, probability_loss, visibility_loss, "
+                                   "oks_loss, error_loss)")
+            self._fast_decoder = KEYPOINT_CODECS.build(dict(type="ArgMaxProbMap", input_size=(192, 256), heatmap_size=(48, 64), sigma=-1))
+            self._loss_modules = mods
+        mods = self._loss_modules
+        if not (isinstance(heatmaps, Tensor) and heatmaps.is_cuda):
+            raise RuntimeError("ProbMapHead.loss needs the head's outputs on the MI355X; there is no CPU fallback")
+        dev = heatmaps.device
+        B, C, H, W = (int(v) for v in heatmaps.shape)
+        assert len(batch_data_samples) == B and tuple(scalars.shape) == (4, B, C), (len(batch_data_samples), tuple(scalars.shape), (B, C))
+        if (H, W) != (64, 48):
+            raise NotImplementedError(f"ProbMapHead.loss: the reference decodes gt_oks with a hard-coded ArgMaxProbMap of 64 x 48 maps "
+                                      f"(probmap_head.py:152-154); got {H} x {W}")
+        with torch.no_grad():
+            tg = self._targets_of(batch_data_samples, dev)
+            assert tuple(tg["heatmaps"].shape) == (B, C, H, W), f"target maps {tuple(tg['heatmaps'].shape)} v.s. predicted {(B, C, H, W)}"
+            heatmap_weights = tg["annotated"].float() if self.learn_heatmaps_from_zeros else tg["keypoint_weights"]
+            maps = mods["keypoint_loss"](heatmaps, tg["heatmaps"], heatmap_weights)
+            kp_gt = self._fast_decoder.decode_device(tg["heatmaps"])["keypoints"]
+            kp_dt = self._fast_decoder.decode_device(heatmaps)["keypoints"]
+            sc = L.probmap_loss_scalars(scalars, tg["in_image"], tg["annotated"], tg["visibility"], kp_gt, kp_dt, mods, self.freeze_oks,
+                                        self.freeze_error)
+            o = sc["out"]
+            losses = dict(loss_kpt=maps["loss"], loss_probability=o[0], loss_visibility=o[1], loss_oks=o[2], loss_error=o[3])
+            if train_cfg.get("compute_acc", True):
+                rec = torch.cat([maps["argmax"].double(), maps["maxval"].double(), tg["keypoint_weights"].double()[..., None],
+                                 scalars[0].double()[..., None], scalars[1].double()[..., None], tg["in_image"].double()[..., None],
+                                 tg["annotated"].double()[..., None], tg["visibility"].double()[..., None]], -1).cpu().numpy()  # (B, K, 10)
+                acc_pose = L.pose_accuracy(rec[..., 0:2].astype(np.int64), rec[..., 2:4].astype(np.float32), rec[..., 4] > 0.5, H, W)
+                gt_probs, ann, gt_vis = rec[..., 7].astype(np.float32), rec[..., 8] > 0.5, rec[..., 9].astype(np.float32)
+                acc_prob = L.binary_accuracy(rec[..., 5].astype(np.float32), gt_probs, ann)  # the reference's order: probability first
+                acc_vis = L.binary_accuracy(rec[..., 6].astype(np.float32), gt_vis, ann & (gt_probs > 0.5))
+                zero = lambda: torch.tensor([0.0], device=dev)  # noqa: E731  (get_binary_accuracy without both classes, :972-973)
+                losses.update(acc_pose=torch.tensor(acc_pose, device=dev),
+                              acc_prob=torch.tensor(acc_prob, device=dev) if acc_prob is not None else zero(),
+                              acc_vis=torch.tensor(acc_vis, device=dev) if acc_vis is not None else zero(), mae_oks=o[4], mae_err=o[5])
+        if return_targets:
+            return losses, dict(tg, gt_oks=sc["gt_oks"], oks_weight=sc["oks_weight"], gt_errs=sc["gt_errs"], vis_weights=sc["vis_weights"],
+                                argmax=maps["argmax"], maxval=maps["maxval"], map_sums=maps["map_sums"], kp_gt=kp_gt, kp_dt=kp_dt)
+        return losses
 
 
 @register(MODELS, reference_name="HeatmapHead", mi355x_name="HeatmapHeadMI355X")
@@ -724,8 +824,20 @@ class TopdownPoseEstimator(nn.Module):
         else:
             raise RuntimeError(f'Invalid mode "{mode}". Only supports loss, predict and tensor mode.')
 
-    def loss(self, inputs, data_samples):
-        raise NotImplementedError("training is outside the MI355X inference hot path")
+    def loss(self, inputs: Tensor, data_samples: list, train_cfg: Optional[dict] = None, slot: int = 0) -> Dict[str, Tensor]:
+        """topdown.py:55-70 in EVALUATION mode - the reference's ``model.eval(); model(inputs, data_samples, mode="loss")``: the engine's
+        single unflipped pass (the one ``predict`` runs without the flip test: no drop-path, the towers' normalisation layers as at test
+        time) leaves the normalised maps and the four tower outputs on the device, and ``ProbMapHead.loss_from_outputs`` scores them
+        against the samples' targets. Forward values only: there are no gradients, this is not a training step. The precision mode is the
+        engine's. Heads other than ``ProbMapHead`` refuse. ``slot``: the engine workspace the pass runs in (the dataset loop gives it one
+        beside those of its batches in flight)."""
+        assert self.with_head, "The model must have head to compute the loss."
+        if not isinstance(self.head, ProbMapHead):
+            return self.head.loss(inputs, data_samples)  # (HeatmapHead: its pinned refusal)
+        if isinstance(inputs, list):
+            inputs = torch.stack(inputs)
+        out = self.engine.forward(inputs, False, None, return_heatmaps=True, slot=slot)
+        return self.head.loss_from_outputs(out["heatmaps"], out["scalars"], data_samples, self.train_cfg if train_cfg is None else train_cfg)
 
     def extract_feat(self, inputs: Tensor) -> Tuple[Tensor]:
         """The backbone's maps - with a neck too (deviation from topdown.py:72-84): the x4 upsampled map of the ``-simple``

@@ -228,9 +228,29 @@ def _pipeline_of(model, dataset):
     return pipe
 
 
+LOSS_NOTE = ("loss/*: instance-weighted means of the batches' evaluation-mode loss dictionaries (no gradients). loss/loss_visibility is not "
+             "exactly the whole-set value: its class-balancing weights are normalised per batch. A batch without annotated keypoints "
+             "inside the image has no mae_oks / mae_err and is left out of their means.")
+
+
+def _with_targets(pipeline, model):
+    """``pipeline`` with ``GenerateTarget(encoder=<the head's ProbMap codec>, device=True)`` in front of ``PackPoseInputs`` - a new
+    Compose, the dataset's own is left as it is."""
+    from .transforms import Compose, GenerateTarget, PackPoseInputs
+
+    codec = model.head.decoder
+    gen = GenerateTarget(encoder=dict(type="ProbMap", input_size=tuple(codec.input_size), heatmap_size=tuple(codec.heatmap_size),
+                                      sigma=codec.sigma), device=True)
+    ts = list(pipeline.transforms)
+    if any(isinstance(t, GenerateTarget) for t in ts):
+        return pipeline
+    at = next((i for i, t in enumerate(ts) if isinstance(t, PackPoseInputs)), len(ts))
+    return Compose(ts[:at] + [gen] + ts[at:])
+
+
 def test_dataset(model, dataset, evaluator=None, batch_size: int = 64, workers: int = 8, depth: int = 2,
                  sink: Optional[Callable[[list], None]] = None, decode: str = "host", decode_entropy: str = "host",
-                 show_dir: Optional[str] = None, show_kpt_thr: float = 0.3) -> dict:
+                 show_dir: Optional[str] = None, show_kpt_thr: float = 0.3, loss: bool = False) -> dict:
     """Run ``model`` over every instance of ``dataset`` (``get_data_info(i)``, i in order) and return the evaluator's metrics
     (``{}`` without one). ``sink``, when given, receives every batch's list of PoseDataSample, in order. ``decode``: "host"
     (``apis.load_image_bgr`` on the threads) or "device" (the split JPEG decoder of ``jpeg``: the same pixels; a file outside
@@ -244,7 +264,13 @@ def test_dataset(model, dataset, evaluator=None, batch_size: int = 64, workers: 
     ``model.test_cfg.output_heatmaps`` is on. An image's pixels are then kept until the batches that read it have been DRAWN.
     ``.jpg`` / ``.jpeg`` names are coded by ``jpeg.encode_batch(entropy="device", quality=75, subsampling="4:2:0")``, ``.png`` names
     by ``png.encode_batch``, any other suffix by Pillow from a host copy; the files are written on the loop's thread pool.
-    The samples given to ``sink`` and the evaluator are the same with and without it."""
+    The samples given to ``sink`` and the evaluator are the same with and without it.
+
+    ``loss`` (off by default; ``ProbMapHead`` models on annotated keypoints): ``GenerateTarget(device=True)`` joins the pipeline and
+    every batch is also scored by ``model.loss`` - the evaluation-mode loss, one extra unflipped pass in a workspace of its own, the
+    batch's targets encoded by one ``pp_probmap_encode`` launch. The result then also holds ``loss/<key>`` for every key of the loss
+    dictionary: the instance-weighted mean over the batches (``LOSS_NOTE`` says what that is not). The samples and the metrics are
+    the same with and without it."""
     from . import jpeg
     from .apis import load_image_bgr
     from .transforms import BatchStaging, pseudo_collate
@@ -263,6 +289,10 @@ def test_dataset(model, dataset, evaluator=None, batch_size: int = 64, workers: 
     plan = plan_batches([d["img_path"] for d in infos], batch_size)
     last = last_use(plan)
     pipeline = _pipeline_of(model, dataset)
+    if loss:
+        pipeline = _with_targets(pipeline, model)
+    held: List[dict] = []  # loss: the collated batches whose samples have not come back yet, in order
+    loss_sum: Dict[str, torch.Tensor] = {}  # key -> (2,) float64 on the device: sum of value * n, sum of n, over the batches with a finite value
     device = next(model.parameters()).device
     ahead = max(2, depth)
     pool = ThreadPoolExecutor(max_workers=max(1, min(MAX_WORKERS, int(workers))))
@@ -350,7 +380,22 @@ def test_dataset(model, dataset, evaluator=None, batch_size: int = 64, workers: 
                 if isinstance(p["inputs"], torch.Tensor) and p["inputs"].is_cuda:
                     p["inputs"].record_stream(consumer)
             if packed:
-                yield pseudo_collate(packed)
+                data = pseudo_collate(packed)
+                if loss:
+                    held.append(data)
+                yield data
+
+    def score(samples):
+        """The loss dictionary of the batch whose samples have just come back, added to the running sums on the device (no host wait)."""
+        data = model.data_preprocessor(held.pop(0), False)
+        assert len(data["data_samples"]) == len(samples)
+        values = model.loss(data["inputs"], data["data_samples"], slot=depth)
+        n = float(len(samples))
+        for key, v in values.items():
+            v = v.reshape(-1)[0].double()
+            ok = torch.isfinite(v)
+            term = torch.stack([torch.where(ok, v * n, torch.zeros_like(v)), ok.double() * n])
+            loss_sum[key] = term if key not in loss_sum else loss_sum[key] + term
 
     if show_dir is not None:
         from .visualization import PoseLocalVisualizer
@@ -369,8 +414,15 @@ def test_dataset(model, dataset, evaluator=None, batch_size: int = 64, workers: 
                     sink(samples)
                 if evaluator is not None:
                     evaluator.process(samples)
+                if loss:
+                    score(samples)
         for w in writes:
             w.result()  # (a failed write is this call's failure)
     finally:
         pool.shutdown(wait=True, cancel_futures=True)
-    return evaluator.evaluate() if evaluator is not None else {}
+    metrics = evaluator.evaluate() if evaluator is not None else {}
+    if loss and loss_sum:
+        totals = torch.stack(list(loss_sum.values())).cpu().numpy()  # one copy
+        for key, (s, c) in zip(loss_sum, totals):
+            metrics["loss/" + key] = float(s / c) if c > 0 else float("nan")
+    return metrics

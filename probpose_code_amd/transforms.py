@@ -441,12 +441,74 @@ class TopdownAffine(BaseTransform):
         return f"{self.__class__.__name__}(input_size={self.input_size}, use_udp={self.use_udp})"
 
 
+@_register("GenerateTarget")
+class GenerateTarget(BaseTransform):
+    """mmpose/datasets/transforms/common_transforms.py:1270-1457 restricted to ONE ``ProbMap`` encoder (no encoder lists, no
+    ``multilevel``, no ``use_dataset_keypoint_weights``): encodes ``transformed_keypoints`` (else ``keypoints``) with
+    ``keypoints_visible`` / ``keypoints_visibility`` and updates the results with the codec's dictionary - ``heatmaps``,
+    ``keypoint_weights``, ``annotated``, ``in_image``, ``keypoints_scaled``, ``heatmap_keypoints``, ``identification_similarity`` -
+    plus the codec's non-empty mapping tables, which ``PackPoseInputs`` follows.
+
+    ``device=True`` (MI355X only, the dataset loop's setting): nothing is encoded per sample. The results get ``keypoints_scaled``
+    alone - the keypoints in input-pixel space, float32 - and ``ProbMapHead.loss`` encodes the whole batch in one ``pp_probmap_encode``
+    launch; the maps never exist on the host."""
+
+    def __init__(self, encoder: dict, target_type: Optional[str] = None, multilevel: bool = False,
+                 use_dataset_keypoint_weights: bool = False, device: bool = False) -> None:
+        from .codecs import ProbMap
+        from .registry import KEYPOINT_CODECS
+
+        if isinstance(encoder, (list, tuple)) or multilevel:
+            raise NotImplementedError("GenerateTarget on MI355X takes a single ProbMap encoder (encoder lists / multilevel=True are not implemented)")
+        if use_dataset_keypoint_weights:
+            raise NotImplementedError("GenerateTarget(use_dataset_keypoint_weights=True) is not implemented on MI355X")
+        self.encoder_cfg = dict(encoder)
+        self.encoder = KEYPOINT_CODECS.build(dict(encoder))
+        if type(self.encoder) is not ProbMap:
+            raise NotImplementedError(f"GenerateTarget on MI355X encodes with ProbMap only; {type(self.encoder).__name__}.encode is not implemented")
+        self.device = bool(device)
+
+    def transform(self, results: Dict) -> Optional[dict]:
+        if results.get("transformed_keypoints", None) is not None:
+            keypoints = results["transformed_keypoints"]
+        elif results.get("keypoints", None) is not None:
+            keypoints = results["keypoints"]
+        else:
+            raise ValueError("GenerateTarget requires 'transformed_keypoints' or 'keypoints' in the results.")
+        keypoints_visible = results["keypoints_visible"]
+        if keypoints_visible.ndim == 3 and keypoints_visible.shape[2] == 2:
+            keypoints_visible, results["keypoints_visible_weights"] = keypoints_visible[..., 0], keypoints_visible[..., 1]
+            results["keypoints_visible"] = keypoints_visible
+        if self.device:
+            assert keypoints.shape[0] == 1, "GenerateTarget only supports single-instance keypoint encoding"
+            results["keypoints_scaled"] = np.ascontiguousarray(keypoints[..., :2], dtype=np.float32)
+            return results
+        encoded = self.encoder.encode(keypoints=keypoints, keypoints_visible=keypoints_visible,
+                                      keypoints_visibility=results.get("keypoints_visibility", None))
+        for name in ("field_mapping_table", "instance_mapping_table", "label_mapping_table"):
+            if getattr(self.encoder, name):
+                encoded[name] = getattr(self.encoder, name)
+        results.update(encoded)
+        return results
+
+    def __repr__(self) -> str:
+        return f"{self.__class__.__name__}(encoder={self.encoder_cfg}, device={self.device})"
+
+
 @_register("PackPoseInputs")
 class PackPoseInputs(BaseTransform):
     """mmpose/datasets/transforms/formatting.py:61-285 for the keys the test path carries: ``inputs`` = the crop as a
     (C, h, w) tensor (already on the device after TopdownAffine), ``data_samples`` = PoseDataSample with ``gt_instances``
     (bbox -> bboxes, bbox_score -> bbox_scores, bbox_scale -> bbox_scales, keypoints ... as the reference's mapping table)
-    and the ``meta_keys`` present in the results."""
+    and the ``meta_keys`` present in the results. Behind ``GenerateTarget`` also what the loss reads (formatting.py:204-265):
+    ``keypoints_in_image`` (``in_image``, and-ed with a given one), ``gt_instance_labels`` (``keypoint_weights``, ... as tensors) and
+    ``gt_fields`` (``heatmaps``, ... as tensors) - each set only when the results hold one of its keys."""
+
+    label_mapping_table = dict(keypoint_labels="keypoint_labels", keypoint_weights="keypoint_weights",
+                               keypoints_visible_weights="keypoints_visible_weights")
+    field_mapping_table = dict(heatmaps="heatmaps", instance_heatmaps="instance_heatmaps", heatmap_mask="heatmap_mask",
+                               heatmap_weights="heatmap_weights", displacements="displacements",
+                               displacement_weights="displacement_weights")
 
     instance_mapping_table = dict(bbox="bboxes", bbox_score="bbox_scores", keypoints="keypoints", keypoints_cam="keypoints_cam",
                                   keypoints_visible="keypoints_visible", keypoints_visibility="keypoints_visibility",
@@ -460,12 +522,23 @@ class PackPoseInputs(BaseTransform):
         self.meta_keys, self.pack_transformed = tuple(meta_keys), pack_transformed
 
     def transform(self, results: dict) -> dict:
-        from .structures import InstanceData, PoseDataSample
+        from .structures import InstanceData, PixelData, PoseDataSample
 
         img = results["img"]
         if isinstance(img, np.ndarray):  # image_to_tensor: HWC -> CHW
             img = torch.from_numpy(np.ascontiguousarray(img.transpose(2, 0, 1) if img.ndim == 3 else img[None]))
+        if "in_image" in results:  # formatting.py:204-209
+            if "keypoints_in_image" not in results:
+                results["keypoints_in_image"] = results["in_image"]
+            results["keypoints_in_image"] = results["keypoints_in_image"] & results["in_image"]
         ds = PoseDataSample()
+        for table, kind, attr in ((results.get("label_mapping_table", self.label_mapping_table), InstanceData, "gt_instance_labels"),
+                                  (results.get("field_mapping_table", self.field_mapping_table), PixelData, "gt_fields")):
+            packed = {p: results[k] for k, p in table.items() if k in results}
+            if packed:
+                if any(isinstance(v, list) for v in packed.values()):
+                    raise NotImplementedError(f"PackPoseInputs: lists of {attr} (several encoders) are not implemented on MI355X")
+                setattr(ds, attr, kind(**{p: torch.from_numpy(v) if isinstance(v, np.ndarray) else v for p, v in packed.items()}))
         gt = InstanceData()
         for key, packed in results.get("instance_mapping_table", self.instance_mapping_table).items():
             if key in results:

@@ -15,6 +15,9 @@ duplicates removed by OKS-NMS per image), for a single-dataset config:
         --cfg-options test_dataloader.dataset.data_root=/data/coco/ \
         --bbox-file /data/coco/person_detection_results/COCO_val2017_detections_AP_H_56_person.json --nms device
 
+``--loss`` adds the head's evaluation-mode loss dictionary (``model.eval(); model(..., mode="loss")`` of the reference: forward
+values, no gradients) as ``loss/<key>`` lines beside the metrics.
+
 ``--show-dir DIR`` dumps one picture per evaluated instance (the reference's PoseVisualizationHook); add
 ``--cfg-options model.test_cfg.output_heatmaps=True`` for the probability-area panel under the pose."""
 import ast
@@ -42,7 +45,7 @@ def parse_cfg_options(items):
     return opts
 
 
-def main(argv=None):
+def build_parser():
     ap = ArgumentParser(description="Evaluate a config's test set (COCO-style datasets, ground-truth boxes)")
     ap.add_argument("config")
     ap.add_argument("checkpoint", help='a checkpoint file, or "synthetic" for seeded random weights')
@@ -68,7 +71,17 @@ def main(argv=None):
     ap.add_argument("--show-dir", default=None, metavar="DIR",
                     help="write one picture per evaluated instance into DIR, named <image stem>_<index>.<suffix>: the pose on the image and, with "
                          "model.test_cfg.output_heatmaps=True, the probability areas under it; drawn and coded (.jpg, .png) on the GPU")
+    ap.add_argument("--loss", action="store_true",
+                    help="also report the evaluation-mode loss dictionary of the head (ProbMapHead.loss: no gradients, not a training step) as "
+                         "loss/<key>, the instance-weighted mean over the batches; targets are encoded on the GPU, one launch per batch")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
+    if args.loss and args.bbox_file:
+        ap.error("--loss needs the ground-truth keypoints of the annotation file: not with --bbox-file")
     if args.bbox_score_thr is not None and not args.bbox_file:
         ap.error("--bbox-score-thr needs --bbox-file")
     if args.decode_entropy == "device" and args.decode != "device":
@@ -102,10 +115,12 @@ def main(argv=None):
     batch_size = args.batch_size or int(loader.get("batch_size", 64))
     t0 = time.perf_counter()
     metrics = runner.test_dataset(model, dataset, evaluator, batch_size=batch_size, workers=args.workers, decode=args.decode,
-                                  decode_entropy=args.decode_entropy, show_dir=args.show_dir)
+                                  decode_entropy=args.decode_entropy, show_dir=args.show_dir, loss=args.loss)
     dt = time.perf_counter() - t0
     for k, v in metrics.items():
         print(f"{k}: {v:.4f}")
+    if args.loss:
+        print(runner.LOSS_NOTE)
     print(f"{len(dataset)} instances in {dt:.2f} s ({len(dataset) / dt:.1f} instances/s)", file=sys.stderr)
     if args.out:
         with open(args.out, "w") as f:
