@@ -8,6 +8,9 @@ a Motion-JPEG AVI - no cv2, no frame ever stored as pixels on the host with ``--
 Frames go through ``apis.inference_topdown_stream`` (``--depth`` frames in flight), are drawn with
 ``PoseLocalVisualizer.draw_datasample`` (the frame stays a device tensor) and encoded ``--encode-batch`` at a time with
 ``jpeg.encode_batch``. The box of every frame is the whole image, or ``--bboxes x0,y0,x1,y1;...`` for all frames.
+With ``--track`` the boxes follow the persons instead: ``--bboxes`` (default: the whole image) are the FIRST frame's boxes, every later frame
+is cropped with the boxes the device derived from the poses of the frame before it (``apis.inference_topdown_track``,
+``probpose_code_amd/tracking.py``; the defaults of its rule are not validated on real footage), and the ``--out-file`` records gain ``track_id``.
 CHECKPOINT may be "synthetic" (seeded random weights: plumbing check)."""
 import json
 import os
@@ -67,6 +70,12 @@ def main(argv=None):
     ap.add_argument("--depth", type=int, default=2, help="frames in flight on the device")
     ap.add_argument("--encode-batch", type=int, default=8, help="drawn frames encoded per jpeg.encode_batch call")
     ap.add_argument("--bboxes", default=None, help="x0,y0,x1,y1;x0,y0,x1,y1;... for every frame (default: the whole image)")
+    ap.add_argument("--track", action="store_true",
+                    help="--bboxes are the first frame's boxes; later frames are cropped with boxes derived on the GPU from the frame before")
+    ap.add_argument("--track-kpt-thr", type=float, default=None, help="with --track: a keypoint counts for the next box from this presence probability on (0.3)")
+    ap.add_argument("--track-expand", type=float, default=None, help="with --track: the keypoints' box is grown by this factor (1.25)")
+    ap.add_argument("--track-max-lost", type=int, default=None, help="with --track: a track dies after more than this many frames without a box update (10)")
+    ap.add_argument("--track-dup-thr", type=float, default=None, help="with --track: two tracks whose poses have an OKS above this are one person (0.9)")
     ap.add_argument("--precision", default=None, choices=[None, "f16x3", "bf16", "f32"], help="overrides model.precision of the config")
     ap.add_argument("--cfg-options", nargs="+", default=None, metavar="KEY=VALUE", help="override config keys as tools/test.py does")
     ap.add_argument("--draw-heatmap", action="store_true", help="the probability areas of the keypoints under the poses")
@@ -119,6 +128,24 @@ def main(argv=None):
             shown.append(img)
             yield img, boxes
 
+    def tracked():
+        """--track: the first frame's boxes are --bboxes (or the whole image), the tracker makes the others."""
+        it = decoded()
+        try:
+            first = next(it)[0]
+        except StopIteration:
+            return
+        first_boxes = boxes if boxes is not None else np.array([[0, 0, first.shape[1], first.shape[0]]], np.float32)
+        params = {k: v for k, v in dict(kpt_thr=args.track_kpt_thr, expand=args.track_expand, max_lost=args.track_max_lost,
+                                        dup_oks_thr=args.track_dup_thr).items() if v is not None}
+
+        def images():
+            yield first
+            for img, _ in it:
+                yield img
+
+        yield from apis.inference_topdown_track(model, images(), first_boxes, depth=args.depth, **params)
+
     records, pending, written = [], [], 0
     t0 = time.perf_counter()
     with MjpegAviWriter(args.out_video, fps) as out:
@@ -131,10 +158,18 @@ def main(argv=None):
                 written += 1
             pending.clear()
 
-        for samples in apis.inference_topdown_stream(model, decoded(), depth=args.depth):
+        for samples in (tracked() if args.track else apis.inference_topdown_stream(model, decoded(), depth=args.depth)):
             img = shown.popleft()
-            merged = merge_data_samples(samples)
             rgb = img.flip(-1) if hasattr(img, "flip") else img[:, :, ::-1]
+            if not samples:  # --track: every track has died - the frame is written as it came
+                import torch
+
+                pending.append(rgb.contiguous() if hasattr(rgb, "contiguous") else torch.from_numpy(np.ascontiguousarray(rgb)).to(args.device))
+                records.append([])
+                if len(pending) >= args.encode_batch:
+                    flush()
+                continue
+            merged = merge_data_samples(samples)
             pending.append(vis.draw_datasample(rgb, merged, draw_heatmap=args.draw_heatmap, kpt_thr=args.kpt_thr))
             if len(pending) >= args.encode_batch:
                 flush()
@@ -142,7 +177,8 @@ def main(argv=None):
                 pi = merged.pred_instances
                 records.append([dict(bbox=pi.bboxes[i].tolist(), keypoints=pi.keypoints[i].tolist(), keypoint_scores=pi.keypoint_scores[i].tolist(),
                                      keypoints_visible=pi.keypoints_visible[i].tolist(),
-                                     **(dict(keypoints_probs=pi.keypoints_probs[i].tolist()) if "keypoints_probs" in pi else {}))
+                                     **(dict(keypoints_probs=pi.keypoints_probs[i].tolist()) if "keypoints_probs" in pi else {}),
+                                     **(dict(track_id=int(samples[i].metainfo["track_id"])) if args.track else {}))
                                 for i in range(len(pi.keypoints))])
         if pending:
             flush()

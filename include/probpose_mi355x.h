@@ -1396,6 +1396,44 @@ int pp_probmap_loss_scalars(const float* scalars, const unsigned char* in_image,
                             const double* loss_weights_host, float* gt_oks, float* oks_weight, float* gt_errs, float* vis_weights,
                             float* out, void* stream);
 
+/* ---- following persons through a video (csrc/pp_track.hip, csrc/pp_track_core.h; probpose_code_amd/tracking.py) ------------------------
+ * pp_track_update: the person boxes of the next frame from this frame's poses, in ONE launch ("track_update") of one 64-lane
+ * workgroup, lane i = track i. Inputs on the device: records (n, K, 7) float64 = x, y, conf, prob, vis, oks, err in crop space as
+ * pp_pack_records leaves them; centers, scales (n, 2) float32 the crops were cut with; sigmas (K) float64 of the dataset; the track
+ * state boxes_in (n, 4) float32 xyxy, alive_in, lost_in (n) int32. Per alive track: keypoints to image space as
+ * TopdownPoseEstimator.add_pred_to_datasample maps them, x / input_w * scale + centre - 0.5 * scale in float64 (0.5 * scale a float32
+ * product); a keypoint is selected when its gate - the prob column (PP_TRACK_GATE_PROB) or the conf column (PP_TRACK_GATE_CONF) - is
+ * finite and >= kpt_thr and its coordinates are finite. With at least min_keypoints selected: the min/max box of the selected
+ * keypoints, grown about its centre by expand with each side at least min_side, smooth * old + (1 - smooth) * new (smooth = 0: the
+ * new box itself), rounded to float32; lost = 0. Otherwise the box is kept, lost + 1, and beyond max_lost alive = 0 for good.
+ * Duplicates: every two tracks updated in this frame whose image-space poses have an OKS (mmpose/evaluation/functional/nms.py
+ * oks_iou, all K keypoints, the mean area of the two new boxes) above dup_oks_thr, visited in the order (0,1) (0,2) .. (1,2) ..: of
+ * two tracks still alive the one with the lower mean gate over its selected keypoints dies, the higher index on a tie. Dead and free
+ * slots keep box and lost count. Outputs boxes_out, alive_out, lost_out may be the inputs (a lane touches its own rows only).
+ * next_centers, next_scales (n, 2) float32 and next_maps (n, 2, 3) float64, given together or all NULL: pp_track_affine_params of
+ * boxes_out, fused into the launch; they may be centers / scales.
+ * Float64 throughout, one rounding per operator, sums over K through one fixed tree, no atomics: the same bits launch after launch,
+ * and the host form's bits up to exp() (an OKS within a few ulp of dup_oks_thr may be decided either way).
+ * Status instead of a launch (PP_ERR_INVALID_ARG): NULL pointers, n outside 1..PP_TRACK_MAX_TRACKS, K outside
+ * 1..PP_TRACK_MAX_KEYPOINTS, an input side outside 2..32767, an unknown gate, NaN thresholds, min_keypoints < 1, expand or min_side or
+ * input_padding not positive and finite, smooth outside [0, 1), max_lost < 0.
+ *
+ * pp_track_affine_params ("track_affine_params", the same kernel without the update): for boxes (n, 4) float32 xyxy the centres and
+ * scales (n, 2) float32 of bbox_xyxy2cs(padding = input_padding) + TopdownAffine._fix_aspect_ratio(w / h) and the dst -> src maps
+ * (n, 2, 3) float64 pp_warp_affine_u8 reads: get_udp_warp_matrix at rot = 0 in float32 as numpy promotes it, inverted in float64 as
+ * cv2.warpAffine does - bit for bit transforms.topdown_affine_params + transforms.invert_affine. use_udp = True pipelines only. */
+#define PP_TRACK_MAX_TRACKS 64
+#define PP_TRACK_MAX_KEYPOINTS 256
+#define PP_TRACK_GATE_PROB 0
+#define PP_TRACK_GATE_CONF 1
+int pp_track_update(const double* records, const float* centers, const float* scales, int n, int K, int input_w, int input_h,
+                    int gate, const double* sigmas, const float* boxes_in, const int32_t* alive_in, const int32_t* lost_in,
+                    double kpt_thr, int min_keypoints, double expand, double min_side, double smooth, int max_lost,
+                    double dup_oks_thr, float* boxes_out, int32_t* alive_out, int32_t* lost_out, double input_padding,
+                    float* next_centers, float* next_scales, double* next_maps, void* stream);
+int pp_track_affine_params(const float* boxes, int n, int input_w, int input_h, double input_padding, float* centers, float* scales,
+                           double* maps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

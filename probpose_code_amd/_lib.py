@@ -221,6 +221,10 @@ SIGNATURES = {
     "pp_probmap_encode_s": (c_int, [c_int, c_int, c_int, c_double, _P]),
     "pp_probmap_loss_maps": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_double, c_double, c_double, _P, _P, _P, _P, _P]),
     "pp_probmap_loss_scalars": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "pp_track_update": (
+        c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_double, c_int, c_double, c_double, c_double, c_int, c_double,
+                _P, _P, _P, c_double, _P, _P, _P, _P]),
+    "pp_track_affine_params": (c_int, [_P, c_int, c_int, c_int, c_double, _P, _P, _P, _P]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -16,6 +16,7 @@ from .pose_estimators import build_pose_estimator
 from .structures import InstanceData, PoseDataSample
 from .synthetic import COCO_FLIP_INDICES
 from . import transforms as T
+from .tracking import inference_topdown_track  # noqa: F401  (the video loop whose boxes follow the persons: only the first frame needs boxes)
 
 
 def coco_dataset_meta() -> dict:
